@@ -2,6 +2,8 @@
 """Throughput of the attention hot path on MI355X: windows/sec, forward+backward.
 
     python bench.py --gpus N --steps K --warmup W          (N>1 without a launcher: starts its own N ranks through torch.distributed.run)
+    python bench.py ... --full                             (+ every figure beside the headline, listed below)
+    python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, as DIR/<name>.npy)
 
 One step = one TRAIN-MODE (dropout 0.1) forward + MSE loss + backward pass (all input, weight and
 LayerNorm gradients) over one synthetic batch already resident in HBM; with N>1 each rank holds its own
@@ -9,7 +11,11 @@ B sequences (weak scaling) and the step ends with the RCCL SUM all-reduce of the
 A window is one time-step of one sequence: windows/step = N*B*T.
 
 Primary workload (`value`): the encoder-stack hot path of the SFT configuration the metric is quoted on
-(C4: T=500, d_model=128, heads=8, N=6, d_ff=128, 32 sequences per GPU).  Rank 0 prints ONE JSON line with
+(C4: T=500, d_model=128, heads=8, N=6, d_ff=128, 32 sequences per GPU).  Rank 0 prints ONE JSON line.  A plain run sets up, warms
+up, times the K steps (`value`, `ms_per_step`), writes the outputs if asked and prints the line; nothing else runs.
+--dump-outputs DIR writes, after the timed steps, the loss, the encoder output, the input gradient and every parameter gradient of
+the last timed step (float32; inputs, weights and dropout seeds are the same in every run with the same arguments; an output over its
+share of 64 MB keeps a fixed, seeded sample of its sequences).  With --full the line also holds
   roofline     — the dominant kernel of the step (by HIP-event time measured here, on the stream the
                  kernels run on): algorithmic FLOPs per launch / average duration vs the dense bf16 MFMA peak;
   cpu_baseline — the CPU oracle (a port of the reference path, fp32 torch CPU) timed on this box's host
@@ -23,7 +29,8 @@ Primary workload (`value`): the encoder-stack hot path of the SFT configuration 
   mft_model    — (N=1) the whole MFT model of configs[2] (3 modality encoders + MFN gate, T=300).
   config_full_batch — (N=1) configs[3] at its full batch of 256 sequences on ONE GPU (the 32-sequence slice above is the
                  weak-scaling anchor; the batch also fits one GPU);
-  mft_configs4 — (N=1) the whole MFT model at the configs[4] per-GPU slice (3 modalities, T=1000, 64 sequences, d=256).
+  mft_configs4 — (N=1) the whole MFT model at the configs[4] per-GPU slice (3 modalities, T=1000, 64 sequences, d=256);
+  two_streams, step_hbm, kernel_ms_per_step, and (N>1) allreduce_ms.
 `roofline.traffic` comes from profiles/r*_pmc_per_kernel.json (separate rocprofv3 --pmc passes of this workload) and only if
 that summary was collected on the kernel sources now running (sha of csrc/); otherwise it is null with the reason.
 """
@@ -228,6 +235,34 @@ def make_encoder(cfg):
                                       MT.PositionwiseFeedForward(cfg["d"], cfg["f"], DROPOUT), DROPOUT), cfg["N"])
 
 
+DUMP_BYTES = 60 * 10**6       # --dump-outputs: all arrays together (under 64 MB, headers included)
+DUMP_WHOLE_BYTES = 1 << 20     # arrays up to this size are always written whole
+DUMP_SEED = 20241016           # which sequences a sampled array keeps
+
+
+def dump_outputs(path, arrays):
+    """{name: device tensor} -> <path>/<name>.npy in float32.  If the arrays exceed DUMP_BYTES, each one above DUMP_WHOLE_BYTES keeps the
+    same fraction of its leading-axis rows (sequences), chosen by a fixed seed: the same rows in every run, and in every array of
+    that leading size."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    big = {k for k, v in arrays.items() if v.numel() * 4 > DUMP_WHOLE_BYTES}
+    room = DUMP_BYTES - sum(v.numel() * 4 for k, v in arrays.items() if k not in big)
+    frac = min(1.0, room / max(1, sum(arrays[k].numel() * 4 for k in big)))
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if name in big and frac < 1.0:
+            rows = t.shape[0]
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, max(1, int(rows * frac)), replace=False))
+            t = t[torch.as_tensor(idx, device=t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    print("bench.py: wrote %d arrays (%.1f MB%s) to %s" % (len(arrays), total / 1e6, ", sampled" if frac < 1.0 else "", path),
+          file=sys.stderr)
+
+
 def cpu_baseline(cfg, seconds_budget=15.0):
     """Oracle (port of the reference path) fwd+bwd on host cores, bounded sample of the same workload."""
     import oracle
@@ -399,14 +434,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="C4", choices=sorted(WORKLOADS))
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-full-model", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="only the headline step (profiling runs: every dispatch of a kernel is then one of "
-                    "the headline shape, so per-dispatch counter averages and dispatch counts belong to it alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float32, 64 MB at most)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (Adam, two streams, per-kernel "
+                    "roofline, whole models, full batch, MFT, CPU baseline, all-reduce time); a plain run times the headline step only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-full-model", action="store_true", help="with --full: skip the whole-model / full-batch / MFT blocks")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: only the headline step (profiling runs: every dispatch of a "
+                    "kernel is then one of the headline shape, so per-dispatch counter averages and dispatch counts belong to it alone)")
     ap.add_argument("--eval-mode", action="store_true", help="dropout as identity (parity-test arithmetic) instead of train mode")
     ap.add_argument("--batch", type=int, default=0, help="override the per-GPU number of sequences (experiments only)")
-    ap.add_argument("--profile-steps", type=int, default=5, help="extra eager steps with per-kernel HIP-event timing")
+    ap.add_argument("--profile-steps", type=int, default=5, help="with --full: extra eager steps with per-kernel HIP-event timing")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.headline_only:
         args.no_full_model = True
 
@@ -457,24 +498,32 @@ def main():
     nvalid = float(world * B * T)
 
     calls = [0]                                             # every execution of the headline step in this process (eager or while capturing)
+    last = {}                                               # the step's loss and encoder output (detached: no autograd graph survives the step)
 
     def fwd_bwd():
         calls[0] += 1
         for p in params:
             p.grad = None
         x.grad = None
-        mse_sum_loss_backward(enc(x, mask), tgt, nvalid)
+        y = enc(x, mask)
+        last["loss"] = mse_sum_loss_backward(y, tgt, nvalid)
+        last["y"] = y.detach()
 
     run = Runner(fwd_bwd, params, world, not args.no_graph, args.warmup)
     elapsed = run.timed(args.steps, dist, dev)
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * M * args.steps / elapsed
-    ar_ms = run.allreduce_ms(max(5, args.steps // 2))
+    if args.dump_outputs and rank == 0:
+        # a replayed graph refills the tensors it captured: `last`, x.grad and every p.grad hold the last timed step's values
+        outs = {"loss": last["loss"], "y": last["y"], "x_grad": x.grad}
+        outs.update(("grad." + n, p.grad) for n, p in enc.named_parameters() if p.grad is not None)
+        dump_outputs(args.dump_outputs, outs)
+    ar_ms = run.allreduce_ms(max(5, args.steps // 2)) if args.full else None
 
     # ---- the same step followed by the reference's optimiser (Adam lr 1e-4, weight decay 1e-4: transformer/SFT/train.py:621);
     #      reported beside the headline, never as it ("with and without Adam + all-reduce")
     adam = None
-    if (rank == 0 or world > 1) and not args.headline_only:
+    if args.full and (rank == 0 or world > 1) and not args.headline_only:
         from multimodal_transformer_amd.optim import FlatAdam
         opt = FlatAdam(params, lr=1e-4, weight_decay=1e-4)       # torch.optim.Adam's update as one launch over the flat parameter buffer
         def step_adam():
@@ -496,7 +545,7 @@ def main():
     # ---- the same step as two half-batches on two HIP streams inside one graph (Encoder.sub_batch_streams = 2): reported beside the
     #      headline, never as it — the headline's kernels have the GPU to themselves, which is what the roofline line prices
     two_streams = None
-    if rank == 0 and world == 1 and B >= 2 and not args.headline_only:
+    if args.full and rank == 0 and world == 1 and B >= 2 and not args.headline_only:
         enc.sub_batch_streams = 2
         try:
             trun = Runner(fwd_bwd, params, 1, not args.no_graph, 3)
@@ -511,7 +560,7 @@ def main():
 
     # ---- per-kernel timing (HIP events on the launch stream), eager, outside the timed region
     roofline, kernel_ms = None, {}
-    if rank == 0 and args.profile_steps > 0:
+    if args.full and rank == 0 and args.profile_steps > 0:
         _lib.profile(True)
         for _ in range(args.profile_steps):
             fwd_bwd()
@@ -522,7 +571,7 @@ def main():
 
     # ---- whole SFT sequence model, same batch shape (N=1 only)
     full = None
-    if rank == 0 and world == 1 and not args.no_full_model and args.workload in ("C4", "C2"):
+    if args.full and rank == 0 and world == 1 and not args.no_full_model and args.workload in ("C4", "C2"):
         from multimodal_transformer_amd import multiTransformer as MT
         torch.manual_seed(1)
         model = MT.NLPTransformer(512, embed_dim=d, h=h, N=N, d_ff=f, dropout=DROPOUT, device=dev)
@@ -553,7 +602,7 @@ def main():
     # ---- raw windows -> valence: the 3-modality SFT pipeline of transformer/SFT/models.py (CNN k=2 + max-pool + Highway per
     #      modality, fusion, NLPTransformer) at the configs[3] per-GPU slice, N=1 only.  d_model = 128 as in configs[3].
     pipeline = None
-    if rank == 0 and world == 1 and not args.no_full_model and args.workload == "C4":
+    if args.full and rank == 0 and world == 1 and not args.no_full_model and args.workload == "C4":
         from multimodal_transformer_amd import models as MM, multiTransformer as MT
         torch.manual_seed(1)
         pm = ["acoustic", "image", "linguistic"]
@@ -597,7 +646,7 @@ def main():
 
     # ---- whole MFT model at configs[2] (3 modalities, T=300, 32 sequences), N=1 only
     mft = None
-    if rank == 0 and world == 1 and not args.no_full_model and args.workload == "C4":
+    if args.full and rank == 0 and world == 1 and not args.no_full_model and args.workload == "C4":
         from multimodal_transformer_amd import multiTransformer as MT
         torch.manual_seed(1)
         mods = ["acoustic", "image", "linguistic"]                       # transformer/MFT/train.py default modality set order
@@ -636,7 +685,7 @@ def main():
 
     # ---- configs[3] at its full batch (256 sequences) on one GPU
     full_batch = None
-    if rank == 0 and world == 1 and not args.no_full_model and args.workload == "C4" and args.batch == 0:
+    if args.full and rank == 0 and world == 1 and not args.no_full_model and args.workload == "C4" and args.batch == 0:
         Bf = 256
         xf = torch.randn(Bf, T, d, generator=g).to(dev).requires_grad_()
         tgtf = torch.rand(Bf, T, d, generator=g).to(dev)
@@ -668,7 +717,7 @@ def main():
 
     # ---- whole MFT model at the configs[4] per-GPU slice (3 modalities, T=1000, 64 sequences, d=256), N=1 only
     mft4 = None
-    if rank == 0 and world == 1 and not args.no_full_model and args.workload == "C4":
+    if args.full and rank == 0 and world == 1 and not args.no_full_model and args.workload == "C4":
         from multimodal_transformer_amd import multiTransformer as MT
         torch.manual_seed(1)
         mods = ["acoustic", "image", "linguistic"]
@@ -722,11 +771,10 @@ def main():
             "launch": run.launch,
             "algorithmic_mflop_per_window": round(fpw / 1e6, 3),
             "step_mfma_frac": round(value * fpw / (world * MFMA_BF16_PEAK_TFLOPS * 1e12), 5),
-            "roofline": roofline,
-            "step_hbm": step_hbm(train, cfg, ms_per_step),
             "fwd_bwd_calls": calls[0],
-            "kernel_ms_per_step": kernel_ms,
         }
+        if args.full:
+            out.update(roofline=roofline, step_hbm=step_hbm(train, cfg, ms_per_step), kernel_ms_per_step=kernel_ms)
         if ar_ms is not None:
             out["allreduce_ms"] = round(ar_ms, 4)
             out["allreduce"] = run.exchange
@@ -745,7 +793,7 @@ def main():
             out["raw_pipeline"] = pipeline
         if mft is not None:
             out["mft_model"] = mft
-        if not args.no_cpu_baseline and world == 1:        # N = 1 only: the other ranks must not wait on 15 s of CPU work
+        if args.full and not args.no_cpu_baseline and world == 1:        # N = 1 only: the other ranks must not wait on 15 s of CPU work
             out["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -19,7 +19,7 @@ def test_two_rank_bench_line():
     env = dict(os.environ, MMT_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     # called the way the driver calls it: plain `python bench.py --gpus 2 ...`, no launcher around it — bench.py starts its own ranks
     cmd = [sys.executable, os.path.join(conftest.ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-full-model", "--profile-steps", "0"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-full-model", "--profile-steps", "0"]
     res = conftest.run_in_fresh_process(cmd, env, timeout=900)
     if res is None:
         pytest.skip("no launcher process (tests were not started through pytest_configure with GPU tests selected)")

@@ -11,10 +11,10 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_${TAG}_$WL
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="$REPO/bench.py --workload $WL"
+BENCH="$REPO/bench.py --full --workload $WL"
 # the headline workload only (--no-full-model drops the whole-model / full-batch / MFT blocks, which launch the same kernels at other
 # sizes and would blur the per-kernel averages the roofline line is checked against)
-echo "== kernel-trace + stats of: python3 bench.py --no-full-model --no-cpu-baseline"
+echo "== kernel-trace + stats of: python3 bench.py --full --no-full-model --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python3 $BENCH --no-full-model --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log || exit 1
 SHORT="--steps 3 --warmup 1 --profile-steps 0 --no-graph --headline-only --no-cpu-baseline"
 # (the last three groups answer "how much does a kernel pull from L2 into the CUs" and "how scalar is it"; a counter name this rocprofv3
@@ -31,6 +31,6 @@ if [ "$WL" = "C4" ]; then cp $OUT/summary/pmc_per_kernel.json profiles/${TAG}_pm
 tail -1 $OUT/bench_under_rocprof.json > profiles/${TAG}_bench_${WL}_under_rocprofv3.json
 if [ "$WL" = "C4" ]; then
   echo "== default bench"
-  python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
+  python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
   tail -1 $OUT/bench_default.json > $OUT/summary/bench_C4.json
 fi

@@ -59,7 +59,7 @@ for f in glob.glob(os.path.join(out, "pmc_FETCH_SIZE.json")):
         import bench
         res["_meta"] = {"workload": cfg["workload"].split("; fwd")[0], "train": cfg["dropout"].startswith("train"),
                         "csrc_sha": bench.kernel_source_sha(), "steps_profiled": ncalls,
-                        "command": "rocprofv3 --kernel-trace --pmc <one counter group per run> -- python3 bench.py --steps 3 --warmup 1 "
+                        "command": "rocprofv3 --kernel-trace --pmc <one counter group per run> -- python3 bench.py --full --steps 3 --warmup 1 "
                                    "--profile-steps 0 --no-graph --headline-only --no-cpu-baseline",
                         "units": "averages per dispatch; FETCH_SIZE/WRITE_SIZE in KiB as reported; hbm_* bytes = 2*1024*FETCH_SIZE + "
                                  "1024*WRITE_SIZE (gfx950 correction, MI355X_MICROARCH.md 'HBM'); SQ_* cycle counters in quad-cycles "
