@@ -200,6 +200,23 @@ int mmt_lstm_scan_backward(const float* dh_all, const float* dc_all, const float
                            const float* c_all, const float* acts, float* dgx, float* dh0, float* dc0,
                            void* workspace, size_t workspace_bytes, int T, int B, int H, mmt_stream_t stream);
 
+/* ---- Local attention of the LSTM baselines: the softmax of the attention MLP's logits and the convolution of the LSTM outputs
+ * with them.  Replaces `attn = self.attn(embed)`'s nn.Softmax(dim=1), pad_packed_sequence's zeroing and convolve / pad_shift
+ *                                                             transformer/B1-LSTM/models.py:10-25,186-207
+ *                                                             (the shared MultiLSTM copy: transformer/SFT/models.py:10-25,195-216)
+ * z (B,T,L) logits; h (T,B,H) the LSTM outputs, time-major as mmt_lstm_scan_forward writes them; valid (B,T) the prefix mask {0,1}.
+ * Outputs ctx (B,T,H) = sum_{i<L, t-i>=0} a[b,t,i] valid[b,t-i] h[t-i,b,:] and attn = a (B,T,L), kept for the backward, where
+ * a[b,t,i] = softmax over t of z[b,:,i]: the reference's dim=1 is the TIME axis of the 3-D logits, so each of the L columns is
+ * normalised over all T steps of the padded batch, padded steps included.  1 <= L <= 16; any B >= 1, T >= 1 (taps before step 0
+ * are zero), H >= 1 (four-float accesses when H % 4 == 0 and h / ctx are 16-byte aligned).  No workspace. */
+int mmt_local_attn_forward(const float* z, const float* h, const float* valid, float* ctx, float* attn,
+                           int B, int T, int H, int L, mmt_stream_t stream);
+/* dctx (B,T,H) -> dz (B,T,L), dh (T,B,H) (zero at steps where valid == 0).  Two launches; deterministic (no atomics).
+ * workspace: mmt_local_attn_workspace_bytes(B,T,H,L) bytes, any contents (every word used is written first); 0 = bad arguments. */
+size_t mmt_local_attn_workspace_bytes(int B, int T, int H, int L);
+int mmt_local_attn_backward(const float* dctx, const float* attn, const float* h, const float* valid, float* dz, float* dh,
+                            void* workspace, size_t workspace_bytes, int B, int T, int H, int L, mmt_stream_t stream);
+
 /* ---- MFN delta-memory recurrence.  Replaces the memory update inside MFN.forward's time loop
  *                                                             transformer/MFT/multiTransformer.py:221-224
  * apre (T,B,128): gamma{1,2}_fc1 applied to the `attended` part of `both` (+bias), rows [gamma1(64); gamma2(64)];

@@ -53,6 +53,9 @@ SIGNATURES = {
     "mmt_lstm_scan_workspace_bytes": (_SZ, [_I]),
     "mmt_lstm_scan_forward": (_I, [_P] * 8 + [_SZ] + [_I] * 3 + [_P]),
     "mmt_lstm_scan_backward": (_I, [_P] * 10 + [_SZ] + [_I] * 3 + [_P]),
+    "mmt_local_attn_forward": (_I, [_P] * 5 + [_I] * 4 + [_P]),
+    "mmt_local_attn_workspace_bytes": (_SZ, [_I] * 4),
+    "mmt_local_attn_backward": (_I, [_P] * 7 + [_SZ] + [_I] * 4 + [_P]),
     "mmt_mfn_mem_scan_workspace_bytes": (_SZ, []),
     "mmt_mfn_mem_scan_forward": (_I, [_P] * 9 + [_SZ] + [_I] * 4 + [_F, _U64, _P]),
     "mmt_mfn_mem_scan_forward_devseed": (_I, [_P] * 9 + [_SZ] + [_I] * 4 + [_F, _P, _P]),
@@ -389,7 +392,8 @@ def next_dropout_seed(device, site, holder=None, index=0):
 
 def device_seed(holder, site=None, index=0):
     """The ``DeviceSeed`` of one dropout site of a module (sites: 1 encoder stack, 2 / 4 the MFN's gamma and output dropouts, 5 the SFT
-    embedding's input dropout, 6 the window encoder's Dropout(0.3)).  ``site=None`` is accepted only where the module has ONE site."""
+    embedding's input dropout, 6 the window encoder's Dropout(0.3), 7 / 8 the LSTM baselines' embed input dropout and decoder dropout).
+    ``site=None`` is accepted only where the module has ONE site."""
     seeds = holder.__dict__.get("_dev_seeds", {})
     if site is None:
         sites = sorted({s for (s, _) in seeds})

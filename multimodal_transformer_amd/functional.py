@@ -5,6 +5,7 @@ Each Function is the forward/backward pair of one reference class:
   layer_norm     <- LayerNorm.forward                :88-91
   sdpa           <- attention()                      :22-34
   linear         <- nn.Linear (+ReLU) call sites     :15-20,43,55,65
+  local_attention <- softmax(dim=1) + convolve of the LSTM baselines   transformer/B1-LSTM/models.py:10-25,186-207
 All tensors must live on a HIP device; there is no CPU path.
 """
 import torch
@@ -348,6 +349,52 @@ def linear(x, weight, bias=None, act=0, rowscale=None, in_dropout=0.0, out_dropo
                            seed if isinstance(seed, _lib.DeviceSeed) else int(seed))
 
 
+class _LinearPairFn(torch.autograd.Function):
+    """(act1(x W1^T + b1), act2(x W2^T + b2)): two affine maps of ONE input as one autograd node, so that the two gradients into x are
+    summed by a copy2d launch instead of by autograd's library add (the LSTM baselines feed their time-major embedding to the attention
+    MLP and to the LSTM's input projection)."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2, act1, act2):
+        _lib.require_hip(x, W1, b1, W2, b2)
+        x_, W1_, b1_, W2_, b2_ = _f32c(x), _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
+        y1, ws1, nb1 = _raw_linear_fwd(x_, W1_, b1_, act1)
+        y2, ws2, nb2 = _raw_linear_fwd(x_, W2_, b2_, act2)
+        ctx.cfg = (act1, act2, b1 is not None, b2 is not None)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(x_, W1_, W2_, y1 if act1 else None, y2 if act2 else None)
+            ctx.ws = (ws1, nb1, ws2, nb2)
+        else:
+            _lib.POOL.put(ws1); _lib.POOL.put(ws2)
+        return y1, y2
+
+    @staticmethod
+    def backward(ctx, dy1, dy2):
+        x_, W1_, W2_, y1, y2 = ctx.saved_tensors
+        act1, act2, has_b1, has_b2 = ctx.cfg
+        ws1, nb1, ws2, nb2 = ctx.ws
+        ctx.ws = None
+        need_x = ctx.needs_input_grad[0]
+        g = ctx.needs_input_grad
+        dy1 = _f32c(dy1) if dy1 is not None else torch.zeros(x_.shape[:-1] + (W1_.shape[0],), dtype=torch.float32, device=x_.device)
+        dy2 = _f32c(dy2) if dy2 is not None else torch.zeros(x_.shape[:-1] + (W2_.shape[0],), dtype=torch.float32, device=x_.device)
+        dx1, dW1, db1 = _raw_linear_bwd(dy1, x_, W1_, y1, None, ws1, nb1, need_x, g[1], has_b1 and g[2], act1)
+        dx2, dW2, db2 = _raw_linear_bwd(dy2, x_, W2_, y2, None, ws2, nb2, need_x, g[3], has_b2 and g[4], act2)
+        dx = None
+        if need_x:
+            K = x_.shape[-1]
+            dx = torch.empty_like(x_)
+            copy2d([_seg(dx, K, x_.numel() // K, K, src=dx1, src_ld=K, src2=dx2, src2_ld=K)])        # dx = dx1 + dx2
+        return dx, dW1, db1, dW2, db2, None, None
+
+
+def linear_pair(x, W1, b1, W2, b2, act1=0, act2=0):
+    """(act1(x W1^T + b1), act2(x W2^T + b2)) with one gradient node for x; x's width must be a multiple of 4."""
+    if x.shape[-1] % 4:
+        raise ValueError("linear_pair: input width %d is no multiple of 4" % x.shape[-1])
+    return _LinearPairFn.apply(x, W1, b1, W2, b2, int(act1), int(act2))
+
+
 class _HighwayFn(torch.autograd.Function):
     """The Highway layer of the window encoder with the front-end's Dropout(0.3) behind it, as ONE autograd node:
         out = drop(gate * proj + (1 - gate) * x),  proj = x Wp^T + bp,  gate = sigmoid(x Wg^T + bg)
@@ -355,11 +402,11 @@ class _HighwayFn(torch.autograd.Function):
     summed by a copy2d launch instead of by autograd's library adds."""
 
     @staticmethod
-    def forward(ctx, x, Wp, bp, Wg, bg, p, seed):
+    def forward(ctx, x, Wp, bp, Wg, bg, p, seed, proj_act):
         lib = _lib.load()
         _lib.require_hip(x, Wp, bp, Wg, bg)
         x_, Wp_, bp_, Wg_, bg_ = _f32c(x), _f32c(Wp), _f32c(bp), _f32c(Wg), _f32c(bg)
-        proj, wsp, nbp = _raw_linear_fwd(x_, Wp_, bp_)
+        proj, wsp, nbp = _raw_linear_fwd(x_, Wp_, bp_, act=proj_act)
         gate, wsg, nbg = _raw_linear_fwd(x_, Wg_, bg_, act=3)
         out = torch.empty_like(x_)
         dev_seed = isinstance(seed, _lib.DeviceSeed) and p > 0.0
@@ -371,14 +418,14 @@ class _HighwayFn(torch.autograd.Function):
             ctx.ws = (wsp, nbp, wsg, nbg)
         else:
             _lib.POOL.put(wsp); _lib.POOL.put(wsg)
-        ctx.cfg = (p, 0 if dev_seed else int(seed))
+        ctx.cfg = (p, 0 if dev_seed else int(seed), proj_act)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         lib = _lib.load()
         x_, Wp_, Wg_, proj, gate, block = ctx.saved_tensors
-        p, seed = ctx.cfg
+        p, seed, proj_act = ctx.cfg
         wsp, nbp, wsg, nbg = ctx.ws
         ctx.ws = None
         d_ = _f32c(dout)
@@ -386,18 +433,66 @@ class _HighwayFn(torch.autograd.Function):
         _lib.check(lib.mmt_highway_backward(_lib.ptr(d_), _lib.ptr(x_), _lib.ptr(proj), _lib.ptr(gate), _lib.ptr(dx), _lib.ptr(dproj), _lib.ptr(dgate),
                                             x_.numel(), p, seed, _lib.ptr(block), _lib.stream_ptr()))
         need_x = ctx.needs_input_grad[0]
-        dx1, dWp, dbp = _raw_linear_bwd(dproj, x_, Wp_, None, None, wsp, nbp, need_x, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        dx1, dWp, dbp = _raw_linear_bwd(dproj, x_, Wp_, proj if proj_act else None, None, wsp, nbp, need_x, ctx.needs_input_grad[1],
+                                        ctx.needs_input_grad[2], act=proj_act)
         dx2, dWg, dbg = _raw_linear_bwd(dgate, x_, Wg_, gate, None, wsg, nbg, need_x, ctx.needs_input_grad[3], ctx.needs_input_grad[4], act=3)
         if need_x:
             K = x_.shape[-1]
             copy2d([_seg(dx, K, x_.numel() // K, K, src=dx1, src_ld=K, src2=dx2, src2_ld=K, acc=True)])        # dx += dx1 + dx2
-        return (dx if need_x else None), dWp, dbp, dWg, dbg, None, None
+        return (dx if need_x else None), dWp, dbp, dWg, dbg, None, None, None
 
 
-def highway(x, Wp, bp, Wg, bg, dropout_p=0.0, seed=0):
+def highway(x, Wp, bp, Wg, bg, dropout_p=0.0, seed=0, proj_act=0):
     """drop(gate * proj + (1 - gate) * x) with proj = x Wp^T + bp, gate = sigmoid(x Wg^T + bg); seed: python int or ``_lib.DeviceSeed``
-    (train-mode dropout: stream 3000 of dropout_mask, index = element)."""
-    return _HighwayFn.apply(x, Wp, bp, Wg, bg, float(dropout_p), seed if isinstance(seed, _lib.DeviceSeed) else int(seed))
+    (train-mode dropout: stream 3000 of dropout_mask, index = element).  proj_act = 1: proj = ReLU(x Wp^T + bp), the Highway of the
+    B1-LSTM variant (transformer/B1-LSTM/models.py:52), the ReLU riding in the projection GEMM's epilogue."""
+    return _HighwayFn.apply(x, Wp, bp, Wg, bg, float(dropout_p), seed if isinstance(seed, _lib.DeviceSeed) else int(seed), int(proj_act))
+
+
+class _LocalAttnFn(torch.autograd.Function):
+    """ctx = convolve(h * valid, softmax_t(z)): the local attention of the LSTM baselines (transformer/B1-LSTM/models.py:10-25,186-207).
+    z (B,T,L) logits, h (T,B,H) LSTM outputs (time-major, as lstm_scan returns them), valid (B,T[,1]) prefix mask -> ctx (B,T,H).
+    The softmax runs over the TIME axis, padded steps included (the reference's nn.Softmax(dim=1) on 3-D logits); steps with
+    valid == 0 contribute no h (pad_packed_sequence's zeros).  Gradients flow to z and h."""
+
+    @staticmethod
+    def forward(ctx, z, h, valid):
+        lib = _lib.load()
+        _lib.require_hip(z, h, valid)
+        z_, h_, v_ = _f32c(z), _f32c16(h), _f32c(valid)
+        B, T, L = z_.shape
+        if h_.dim() != 3 or h_.shape[0] != T or h_.shape[1] != B:
+            raise ValueError("local_attention: h must be (T,B,H) = (%d,%d,H), got %s" % (T, B, tuple(h_.shape)))
+        if v_.numel() != B * T:
+            raise ValueError("local_attention: valid must have B*T = %d entries, got %d" % (B * T, v_.numel()))
+        H = h_.shape[2]
+        out = torch.empty(B, T, H, dtype=torch.float32, device=z_.device)
+        a = torch.empty(B, T, L, dtype=torch.float32, device=z_.device)
+        _lib.check(lib.mmt_local_attn_forward(_lib.ptr(z_), _lib.ptr(h_), _lib.ptr(v_), _lib.ptr(out), _lib.ptr(a), B, T, H, L,
+                                              _lib.stream_ptr()))
+        ctx.save_for_backward(a, h_, v_)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        a, h_, v_ = ctx.saved_tensors
+        B, T, L = a.shape
+        H = h_.shape[2]
+        g = _f32c16(dout)
+        nbytes = lib.mmt_local_attn_workspace_bytes(B, T, H, L)
+        ws = _lib.POOL.get(nbytes, g.device, tag=("local_attn", B, T, H, L))
+        dz = torch.empty_like(a)
+        dh = torch.empty_like(h_)
+        _lib.check(lib.mmt_local_attn_backward(_lib.ptr(g), _lib.ptr(a), _lib.ptr(h_), _lib.ptr(v_), _lib.ptr(dz), _lib.ptr(dh),
+                                               _lib.ptr(ws), nbytes, B, T, H, L, _lib.stream_ptr()))
+        _lib.POOL.put(ws)
+        return dz, dh, None
+
+
+def local_attention(z, h, valid):
+    """(B,T,L) logits, (T,B,H) LSTM outputs, (B,T[,1]) mask -> (B,T,H) context; see _LocalAttnFn."""
+    return _LocalAttnFn.apply(z, h, valid)
 
 
 class _LstmScanFn(torch.autograd.Function):

@@ -5,6 +5,11 @@
     transformer/SFT/models.py:27-142      early fusion: concat -> tanh(fusionLayer) -> NLPTransformer   (``MultiCNNTransformer``)
     transformer/MFT/models.py:27-138      per-modality dict -> MultiTransformer (MFN gate)               (``MultiCNNTransformerMFT``)
     transformer/B2-Trans/models.py:27-134 single modality -> UniFullTransformer                           (``MultiCNNTransformerB2``)
+    transformer/B3-MFN/models.py:81-138   per-modality dict -> MultiTransformerB3 (Linear embed, MFN gate) (``MultiCNNTransformerB3``)
+    transformer/B1-LSTM/models.py:79-133  ReLU Highway, concat -> MultiLSTM with local attention           (``MultiCNNLSTM``)
+
+and the two copies of the LSTM baseline's sequence model: ``MultiLSTM`` (transformer/SFT/models.py:144-225, byte-identical in MFT,
+B2-Trans, B3-MFN and Performance-Eval) and ``MultiLSTMB1`` (transformer/B1-LSTM/models.py:135-216).
 
 The reference walks the batch in a Python loop (SFT/models.py:123) and runs Conv1d + MaxPool1d per sequence; windows are
 independent, so here all B*T windows of a modality go through ONE fused conv-GEMM + max-pool HIP kernel
@@ -15,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, functional as F_hip
-from .multiTransformer import (MultiTransformer, NLPTransformer, UniFullTransformer, UniTransformer, _MOD_STREAMS,
+from .multiTransformer import (MultiTransformer, MultiTransformerB3, NLPTransformer, UniFullTransformer, UniTransformer, _MOD_STREAMS,
                                _hip_device)
 
 
@@ -32,6 +37,15 @@ class Highway(nn.Module):
         """``dropout_p`` / ``seed``: the front-end's Dropout(0.3) on the Highway output (SFT/models.py:132-134), fused into the combine"""
         return F_hip.highway(x_conv_out, self.linear_projection.weight, self.linear_projection.bias,
                              self.linear_gate.weight, self.linear_gate.bias, dropout_p, seed)       # drop(gate*proj + (1-gate)*x)
+
+
+class HighwayB1(Highway):
+    """The B1-LSTM variant's Highway: x_gate * ReLU(proj(x)) + (1 - x_gate) * x — transformer/B1-LSTM/models.py:27-55 (:52 applies the
+    ReLU the other variants' Highway omits).  Same keys as ``Highway``; the ReLU rides in the projection GEMM's epilogue."""
+
+    def forward(self, x_conv_out, dropout_p=0.0, seed=0):
+        return F_hip.highway(x_conv_out, self.linear_projection.weight, self.linear_projection.bias,
+                             self.linear_gate.weight, self.linear_gate.bias, dropout_p, seed, proj_act=1)
 
 
 class CNN(nn.Module):
@@ -59,6 +73,7 @@ class CNN(nn.Module):
 
 class _FrontEnd(nn.Module):
     window_embed_size = {"linguistic": 300, "emotient": 20, "acoustic": 256, "image": 256}     # SFT/models.py:90
+    _highway_cls = Highway
 
     def _build(self, mods, dims, k):
         self.mods = mods
@@ -67,7 +82,7 @@ class _FrontEnd(nn.Module):
         total = 0
         for mod in mods:
             self.CNN[mod] = CNN(dims[mod], self.window_embed_size[mod], k)
-            self.Highway[mod] = Highway(self.window_embed_size[mod])
+            self.Highway[mod] = self._highway_cls(self.window_embed_size[mod])
             self.add_module("cnn_{}".format(mod), self.CNN[mod])
             self.add_module("highway_{}".format(mod), self.Highway[mod])
             total += self.window_embed_size[mod]
@@ -152,3 +167,133 @@ class MultiCNNTransformerB2(_FrontEnd):
         if len(outs) > 1:
             return self.Transformer(F_hip.cat_cols([outs[m] for m in self.mods]), mask, length)
         return self.Transformer(outs[self.mods[0]], mask, length)
+
+
+class MultiCNNTransformerB3(_FrontEnd):
+    """B3-MFN: transformer/B3-MFN/models.py:81-138 — the MFT front-end with the fixed window embed sizes of SFT and the B3 sequence model
+    (Linear embed -> MFN gate, no encoder stacks)."""
+
+    def __init__(self, mods, dims, fuse_embed_size=256, k=2, device=torch.device("cuda:0")):
+        super().__init__()
+        total = self._build(mods, dims, k)
+        if len(mods) > 1:
+            self.Transformer = MultiTransformerB3(mods=mods, window_embed_size=self.window_embed_size, device=device)
+        else:
+            self.Transformer = UniTransformer(total, device=device)
+        self.dropout = nn.Dropout(p=0.3)
+        self.device = _hip_device(device)
+        self.to(self.device)
+
+    def forward(self, inputs, length, mask=None):
+        outs = self._encode(inputs)
+        if len(self.mods) > 1:
+            return self.Transformer(outs, mask, length)
+        return self.Transformer(outs[self.mods[0]], mask, length)
+
+
+class _LocalAttnLSTM(nn.Module):
+    """The LSTM baseline's sequence model, shared by both copies:
+
+        embed   = ReLU(Linear(Dropout(p_in)(x)))                                  (B,T,E)    one row-GEMM, input dropout in its staging
+        z       = Linear(E->L)(ReLU(Linear(E->E)(embed)))                         (B,T,L)    the attention MLP  } one node on the
+        gx      = embed W_ih^T + (b_ih + b_hh)                                    (T,B,4H)   time-major for the scan } time-major embed
+        h       = LSTM scan of gx with zero h0 / c0                               (T,B,H)
+        context = convolve(h * mask, softmax over TIME of z)                      (B,T,H)    functional.local_attention
+        out     = Linear(E->1)(ReLU(Linear(H->E)(context)) [Dropout]) * mask      (B,T,1)
+
+    pack_padded_sequence / pad_packed_sequence are not needed: the LSTM is causal, so the scan over all T steps gives the same h at
+    real steps, and local_attention zeroes it at padded ones (outputs and gradients are those of the packed run).  The attention
+    softmax normalises each of the L columns over all T steps of the padded batch (nn.Softmax(dim=1) on (B,T,L) logits), so outputs
+    at real steps depend on the padded length, as in the reference."""
+
+    _embed_p = 0.1
+    _dec_dropout = None
+
+    def __init__(self, window_embed_size, embed_dim, h_dim=256, n_layers=1, attn_len=5, device=torch.device("cuda:0")):
+        super().__init__()
+        self.embed_dim = embed_dim
+        self.h_dim = h_dim
+        self.n_layers = n_layers
+        self.attn_len = attn_len
+        self.embed = nn.Sequential(nn.Dropout(self._embed_p), nn.Linear(window_embed_size, embed_dim), nn.ReLU())
+        self.attn = nn.Sequential(nn.Linear(embed_dim, embed_dim), nn.ReLU(), nn.Linear(embed_dim, attn_len), nn.Softmax(dim=1))
+        self.lstm = nn.LSTM(embed_dim, h_dim, n_layers, batch_first=True)
+        if self._dec_dropout is None:
+            self.decoder = nn.Sequential(nn.Linear(h_dim, embed_dim), nn.ReLU(), nn.Linear(embed_dim, 1))
+        else:
+            self.decoder = nn.Sequential(nn.Linear(h_dim, embed_dim), nn.ReLU(), nn.Dropout(self._dec_dropout), nn.Linear(embed_dim, 1))
+        self.device = _hip_device(device)
+        self.to(self.device)
+
+    def forward(self, inputs, mask, lengths, target=None, output_feats=False):
+        B, T = inputs.shape[0], inputs.shape[1]
+        if len(lengths) != B or int(max(lengths)) != T:
+            raise ValueError("%s: the input's time axis (%d) must equal max(lengths) and len(lengths) the batch (%d); got lengths %s"
+                             % (type(self).__name__, T, B, list(lengths)))
+        if self.n_layers != 1:
+            raise NotImplementedError("%s: only the reference's single-layer LSTM (n_layers=1) is implemented" % type(self).__name__)
+        if mask is None:
+            raise ValueError("%s: the (B,T,1) mask is required (the reference multiplies the output by it)" % type(self).__name__)
+        p_in = float(self.embed[0].p) if self.training else 0.0
+        seed = _lib.next_dropout_seed(inputs.device, 7, holder=self) if p_in > 0.0 else 0
+        embed = F_hip.linear(inputs, self.embed[1].weight, self.embed[1].bias, act=1, in_dropout=p_in, seed=seed)
+        lstm = self.lstm
+        # both consumers of the embedding read it time-major (one gradient node for it: no library add in the backward); the attention
+        # MLP's (T,B,L) logits go back to batch-major, a copy of B*T*L floats
+        hid, gx = F_hip.linear_pair(F_hip.time_major(embed), self.attn[0].weight, self.attn[0].bias,
+                                    lstm.weight_ih_l0, F_hip.add2(lstm.bias_ih_l0, lstm.bias_hh_l0), act1=1)
+        z = F_hip.batch_major(F_hip.linear(hid, self.attn[2].weight, self.attn[2].bias))
+        h_all, _ = F_hip.lstm_scan(gx, lstm.weight_hh_l0)
+        context = F_hip.local_attention(z, h_all, mask)
+        dec0, last = self.decoder[0], self.decoder[-1]
+        p_dec = float(self.decoder[2].p) if (self.training and self._dec_dropout is not None) else 0.0
+        seed_dec = _lib.next_dropout_seed(inputs.device, 8, holder=self) if p_dec > 0.0 else 0
+        hid = F_hip.linear(context, dec0.weight, dec0.bias, act=1, out_dropout=p_dec, seed=seed_dec)
+        return F_hip.linear(hid, last.weight, last.bias, rowscale=mask.float().reshape(-1))
+
+
+class MultiLSTM(_LocalAttnLSTM):
+    """The shared copy: transformer/SFT/models.py:144-225 (MFT, B2-Trans, B3-MFN, Performance-Eval identical) — embed dropout 0.1,
+    decoder Linear, ReLU, Linear (keys decoder.0 / decoder.2).  The configuration of the shipped B1-LSTM-L.pth checkpoint."""
+
+    def __init__(self, window_embed_size, embed_dim=128, h_dim=256, n_layers=1, attn_len=5, device=torch.device("cuda:0")):
+        super().__init__(window_embed_size, embed_dim, h_dim, n_layers, attn_len, device)
+
+
+class MultiLSTMB1(_LocalAttnLSTM):
+    """The B1-LSTM copy: transformer/B1-LSTM/models.py:135-216 — embed_dim 512, embed dropout 0.4, decoder Linear, ReLU,
+    Dropout(0.4), Linear (keys decoder.0 / decoder.3).  The reference calls this class ``MultiLSTM`` too."""
+    _embed_p = 0.4
+    _dec_dropout = 0.4
+
+    def __init__(self, window_embed_size, embed_dim=512, h_dim=256, n_layers=1, attn_len=5, device=torch.device("cuda:0")):
+        super().__init__(window_embed_size, embed_dim, h_dim, n_layers, attn_len, device)
+
+
+class MultiCNNLSTM(_FrontEnd):
+    """B1-LSTM: transformer/B1-LSTM/models.py:79-133 — per modality CNN(k=2) + max-pool -> ReLU Highway (``HighwayB1``) -> Dropout(0.3),
+    modalities concatenated (no fusion layer), then the LSTM baseline's sequence model.
+
+    Keyword-only extensions (the reference's positional signature is kept): ``window_embed_size`` replaces B1's fixed window embed sizes
+    (linguistic 1024, :91) and ``lstm_cls`` chooses the copy of the sequence model (B1's own by default).  The shipped checkpoint
+    transformer/ModelSave/B1-LSTM/B1-LSTM-L.pth was saved from an older models.py: linguistic window_embed_size 300 and the shared
+    MultiLSTM (E = 128, H = 256, L = 5, decoder keys .0 / .2), i.e.
+        MultiCNNLSTM(["linguistic"], {"linguistic": 300}, window_embed_size={"linguistic": 300}, lstm_cls=MultiLSTM).
+    Whether that file's Highway had the ReLU cannot be read from its weights; ``MultiCNNLSTM`` exists only in B1, so B1's Highway is used."""
+    _highway_cls = HighwayB1
+
+    def __init__(self, mods, dims, fuse_embed_size=256, k=2, device=torch.device("cuda:0"), *, window_embed_size=None,
+                 lstm_cls=MultiLSTMB1):
+        super().__init__()
+        self.window_embed_size = dict(window_embed_size) if window_embed_size is not None else \
+            {"linguistic": 1024, "emotient": 20, "acoustic": 256, "image": 256}          # B1-LSTM/models.py:91
+        total = self._build(mods, dims, k)
+        self.LSTM = lstm_cls(total, device=device)
+        self.dropout = nn.Dropout(p=0.3)
+        self.device = _hip_device(device)
+        self.to(self.device)
+
+    def forward(self, inputs, length, mask=None):
+        outs = self._encode(inputs)
+        x = F_hip.cat_cols([outs[m] for m in self.mods]) if len(self.mods) > 1 else outs[self.mods[0]]
+        return self.LSTM(x, mask, length)

@@ -366,6 +366,34 @@ class MultiTransformer(nn.Module):
         return self.mfn._gate(gate_in, mask)                         # ... * mask (:310) in the gate's last pass
 
 
+class MultiTransformerB3(nn.Module):
+    """B3-MFN sequence model (transformer/B3-MFN/multiTransformer.py:250-307): the MFT model without its encoder stacks — per-modality
+    Linear embed -> MFN gate -> mask.  Keys ``embed_{mod}.*`` and ``mfn.*`` only."""
+
+    def __init__(self, mods, window_embed_size, N=6, d_ff=128, h=8, dropout=0.1, n_layers=1, device=torch.device("cuda:0")):
+        super().__init__()
+        self.mods = list(mods)
+        self.window_embed_size = window_embed_size
+        self.embed_dim = {"linguistic": 256, "emotient": 16, "acoustic": 256, "image": 256}
+        self.embed = {}
+        for mod in self.mods:
+            self.embed[mod] = nn.Linear(window_embed_size[mod], self.embed_dim[mod])
+            self.add_module("embed_%s" % mod, self.embed[mod])
+        self.mfn = MFN(self.mods, self.embed_dim, 1, device=device)
+        self.device = _hip_device(device)
+        self.to(self.device)
+
+    def forward(self, inputs, mask, lengths, tgt_init=0.5, target=None):
+        gate_in = {}
+        main, streams = _MOD_STREAMS.begin(self.device, len(self.mods))
+        for mod, st in zip(self.mods, streams):
+            with torch.cuda.stream(st):
+                e = F_hip.linear(inputs[mod], self.embed[mod].weight, self.embed[mod].bias)
+                gate_in[mod] = F_hip.time_major(e)                    # the reference's permute(1,0,2), :294
+        _MOD_STREAMS.end(main, streams, list(gate_in.values()))
+        return self.mfn._gate(gate_in, mask)                         # ... * mask (:304) in the gate's last pass
+
+
 class _DecoderMixin:
     """Autoregressive 1-layer LSTM decoder + MLP shared by UniTransformer and NLPTransformer
     (transformer/SFT/multiTransformer.py:463-483).  Step t feeds [o_{t-1}; enc_t] with o = h, so
