@@ -72,7 +72,6 @@ SIGNATURES = {
 }
 
 
-
 class CopySeg(ctypes.Structure):
     """mmt_copy_seg of include/mmt_hip.h"""
     _fields_ = [("src", _P), ("src2", _P), ("dst", _P), ("rowscale", _P), ("rows", _I), ("cols", _I), ("src_ld", _I), ("src2_ld", _I),
@@ -122,12 +121,11 @@ def require_hip(*tensors):
                                "(move the module and its inputs to a HIP device)" % t.device)
 
 
-def ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def stream_ptr():
-    return torch.cuda.current_stream().cuda_stream
+def launch(name, *args):
+    """Call the C entry point ``name`` on the current stream (read now: StreamFork's ``torch.cuda.stream`` blocks rely on it).  A tensor
+    goes as its data_ptr(), None as a null pointer, every other argument unchanged; a non-zero return code raises."""
+    fn = getattr(load(), name)
+    check(fn(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], torch.cuda.current_stream().cuda_stream))
 
 
 SIDE_LANES = {}       # raw stream handle -> lane id (>= 1); filled by StreamFork
@@ -247,7 +245,7 @@ class DeviceErrorWatch:
             acc = self._accum.get(str(dev_word.device))
             if acc is None:
                 return              # nothing ran eagerly before the capture: this launch stays unwatched
-            check(load().mmt_error_accumulate(ptr(dev_word), ptr(acc), stream_ptr()))
+            launch("mmt_error_accumulate", dev_word, acc)
             with self._mutex:
                 if what not in self._captured:
                     self._captured.append(what)
@@ -322,9 +320,6 @@ class DeviceSeed:
 
     def peek(self):
         return int(self.state.item()) & 0xFFFFFFFFFFFFFFFF
-
-    def ptr(self):
-        return self.state.data_ptr()
 
 
 def canonical_device(device):

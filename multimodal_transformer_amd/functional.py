@@ -6,8 +6,11 @@ Each Function is the forward/backward pair of one reference class:
   sdpa           <- attention()                      :22-34
   linear         <- nn.Linear (+ReLU) call sites     :15-20,43,55,65
   local_attention <- softmax(dim=1) + convolve of the LSTM baselines   transformer/B1-LSTM/models.py:10-25,186-207
-All tensors must live on a HIP device; there is no CPU path.
+All tensors must live on a HIP device; there is no CPU path.  Every C call goes through ``_lib.launch``.
 """
+import ctypes
+import math
+
 import torch
 
 from . import _lib
@@ -21,6 +24,49 @@ def _f32c16(t):
     """contiguous fp32 AND 16-byte aligned (a contiguous view at an odd storage offset is not): for kernels that move four floats per lane"""
     t = _f32c(t)
     return t.clone() if t is not None and t.data_ptr() % 16 else t
+
+
+# Dropout seeds: a python int (by value) or a ``_lib.DeviceSeed`` (device-resident: fresh masks at every hipGraph replay).
+def _seed_arg(seed):
+    """The one normalisation of a seed argument: a DeviceSeed stays one, anything else becomes a python int (a list: item by item)."""
+    if isinstance(seed, (list, tuple)):
+        return [_seed_arg(v) for v in seed]
+    return seed if isinstance(seed, _lib.DeviceSeed) else int(seed)
+
+
+def _seed_pair(seed):
+    """(value, state word) of the entry points that take a seed either way: (seed, None) by value, (0, state) for a DeviceSeed."""
+    return (0, seed.state) if isinstance(seed, _lib.DeviceSeed) else (int(seed), None)
+
+
+def _launch_seeded(name, seed, *args, state_arg=True):
+    """``name`` with the seed by value behind ``args``, or its twin ``name``_devseed with the DeviceSeed's state word there, which the
+    launch reads and advances.  ``state_arg=False``: the twin takes no seed (the encoder backward finds it in its forward's workspace)."""
+    if not isinstance(seed, _lib.DeviceSeed):
+        _lib.launch(name, *args, seed)
+    elif state_arg:
+        _lib.launch(name + "_devseed", *args, seed.state)
+    else:
+        _lib.launch(name + "_devseed", *args)
+
+
+# Pool workspaces held from forward to backward (_lib.WorkspacePool): the Functions that keep one use these two.
+def _hold(ctx, *ws):
+    """Forward: keep the workspaces for the backward if an input needs a gradient (-> True), else hand them back to the pool at once."""
+    if any(ctx.needs_input_grad):
+        ctx.ws = ws
+        return True
+    for w in ws:
+        _lib.POOL.put(w)
+    return False
+
+
+def _take_ws(ctx, op):
+    """Backward: the workspaces the forward kept, exactly once; a second backward of the same forward raises before any launch."""
+    ws, ctx.ws = getattr(ctx, "ws", None), None
+    if ws is None:
+        raise RuntimeError("%s: backward called twice on the same forward (its workspace went back to the pool)" % op)
+    return ws
 
 
 # Sub-batch streams.  Sequences are independent, so one stack call may run as k sub-batches on k HIP streams (forked and joined by event,
@@ -52,95 +98,81 @@ def _chunk_seed(seed, i, nsplit=1):
     return seed if i == 0 else _lib.mix64(seed, i)
 
 
+def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit):
+    """The fused stack's forward, one launch per sub-batch on a stream of its own; keeps on ``ctx`` what _encoder_bwd needs."""
+    lib = _lib.load()
+    _lib.require_hip(x, mask, flat_params)
+    x_, m_, p_ = _f32c(x), _f32c(mask), _f32c(flat_params)
+    B, T, d = x_.shape
+    if m_.numel() != B * T:
+        raise ValueError("mask must have B*T = %d elements (shape (B,T,1)), got %s" % (B * T, tuple(mask.shape)))
+    m_ = m_.view(B, T)
+    need = lib.mmt_encoder_param_count(d, d_ff, n_layers)
+    if p_.numel() != need:
+        raise ValueError("flat parameter buffer has %d elements, expected %d" % (p_.numel(), need))
+    train = dropout_p > 0.0                    # eval-mode workspaces carry no dropout bit masks
+    if isinstance(seed, (list, tuple)) and len(seed) < nsplit:
+        raise ValueError("encoder_stack: one seed per sub-batch stream")
+    y = torch.empty_like(x_)
+    chunks = _row_chunks(B, nsplit)
+    main, streams = _SPLIT_STREAMS.begin(x_.device, len(chunks))
+    parts = []
+    for i, ((b0, b1), st) in enumerate(zip(chunks, streams)):
+        with torch.cuda.stream(st):
+            dims = (b1 - b0, T, d, h, d_ff, n_layers)
+            nbytes = (lib.mmt_encoder_workspace_bytes if train else lib.mmt_encoder_workspace_bytes_eval)(*dims)
+            if nbytes == 0:
+                _lib.launch("mmt_encoder_forward", None, None, None, None, None, 0, *dims, eps, 0.0, 0)
+            ws = _lib.POOL.get(nbytes, x_.device, tag=("encoder",) + dims + (train,))
+            sd = _chunk_seed(seed, i, len(chunks))
+            _launch_seeded("mmt_encoder_forward", sd, x_[b0:b1], m_[b0:b1], p_, y[b0:b1], ws, nbytes, *dims, eps, dropout_p)
+            parts.append((b0, b1, ws, sd))
+    _SPLIT_STREAMS.end(main, streams)
+    if _hold(ctx, *[ws for _, _, ws, _ in parts]):
+        ctx.save_for_backward(x_, m_, p_)
+        ctx.parts = [(b0, b1, sd) for b0, b1, _, sd in parts]
+        ctx.cfg = (T, d, h, d_ff, n_layers, eps, dropout_p)
+    return y
+
+
+def _encoder_bwd(ctx, dy):
+    """-> (dx, gradient of the flat parameter buffer) of _encoder_fwd's call."""
+    wss = _take_ws(ctx, "encoder_stack")
+    x_, m_, p_ = ctx.saved_tensors
+    T, d, h, d_ff, n_layers, eps, dropout_p = ctx.cfg
+    dy_ = _f32c(dy)
+    dx = torch.empty_like(x_)
+    dps = [torch.empty_like(p_) for _ in wss]       # fresh buffers per call: returned gradient views never alias later calls
+    main, streams = _SPLIT_STREAMS.begin(x_.device, len(wss))
+    for (b0, b1, sd), ws, dp, st in zip(ctx.parts, wss, dps, streams):
+        with torch.cuda.stream(st):
+            _launch_seeded("mmt_encoder_backward", sd, dy_[b0:b1], x_[b0:b1], m_[b0:b1], p_, dx[b0:b1], dp, ws, ws.numel(),
+                           b1 - b0, T, d, h, d_ff, n_layers, eps, dropout_p, state_arg=False)
+            _lib.POOL.put(ws)
+    _SPLIT_STREAMS.end(main, streams)
+    if len(dps) > 1:                                # the sub-batches' parameter gradients, summed into the first buffer
+        n = p_.numel()
+        for other in dps[1:]:
+            copy2d([_seg(dps[0], n, 1, n, src=other, src_ld=n, acc=True)])
+    return dx, dps[0]
+
+
 class _EncoderStackFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, _needs=False, nsplit=1):
-        lib = _lib.load()
-        _lib.require_hip(x, mask, flat_params)
-        x_, m_, p_ = _f32c(x), _f32c(mask), _f32c(flat_params)
-        B, T, d = x_.shape
-        if m_.numel() != B * T:
-            raise ValueError("mask must have B*T = %d elements (shape (B,T,1)), got %s" % (B * T, tuple(mask.shape)))
-        need = lib.mmt_encoder_param_count(d, d_ff, n_layers)
-        if p_.numel() != need:
-            raise ValueError("flat parameter buffer has %d elements, expected %d" % (p_.numel(), need))
-        train = dropout_p > 0.0                    # eval-mode workspaces carry no dropout bit masks
-        if isinstance(seed, (list, tuple)) and len(seed) < nsplit:
-            raise ValueError("encoder_stack: one seed per sub-batch stream")
-        y = torch.empty_like(x_)
-        chunks = _row_chunks(B, nsplit)
-        main, streams = _SPLIT_STREAMS.begin(x_.device, len(chunks))
-        parts = []
-        for i, ((b0, b1), st) in enumerate(zip(chunks, streams)):
-            with torch.cuda.stream(st):
-                Bi = b1 - b0
-                nbytes = (lib.mmt_encoder_workspace_bytes if train else lib.mmt_encoder_workspace_bytes_eval)(Bi, T, d, h, d_ff, n_layers)
-                if nbytes == 0:
-                    _lib.check(lib.mmt_encoder_forward(None, None, None, None, None, 0, Bi, T, d, h, d_ff, n_layers, eps, 0.0, 0, None))
-                ws = _lib.POOL.get(nbytes, x_.device, tag=("encoder", Bi, T, d, h, d_ff, n_layers, train))
-                sd = _chunk_seed(seed, i, len(chunks))
-                xp, mp, yp = _lib.ptr(x_) + 4 * b0 * T * d, _lib.ptr(m_) + 4 * b0 * T, _lib.ptr(y) + 4 * b0 * T * d
-                if isinstance(sd, _lib.DeviceSeed):  # device-resident seed: read and advanced by the launch itself (hipGraph replays)
-                    _lib.check(lib.mmt_encoder_forward_devseed(xp, mp, _lib.ptr(p_), yp, _lib.ptr(ws), nbytes,
-                                                               Bi, T, d, h, d_ff, n_layers, eps, dropout_p, sd.ptr(), _lib.stream_ptr()))
-                else:
-                    _lib.check(lib.mmt_encoder_forward(xp, mp, _lib.ptr(p_), yp, _lib.ptr(ws), nbytes,
-                                                       Bi, T, d, h, d_ff, n_layers, eps, dropout_p, sd, _lib.stream_ptr()))
-                parts.append((b0, b1, ws, nbytes, sd))
-        _SPLIT_STREAMS.end(main, streams)
-        needs_bwd = _needs or any(ctx.needs_input_grad)
-        if needs_bwd:
-            ctx.save_for_backward(x_, m_, p_)
-            ctx.parts = parts
-            ctx.cfg = (B, T, d, h, d_ff, n_layers, eps, dropout_p)
-        else:
-            for part in parts:
-                _lib.POOL.put(part[2])
-        return y
+    def forward(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit):
+        return _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit)
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
-        x_, m_, p_ = ctx.saved_tensors
-        B, T, d, h, d_ff, n_layers, eps, dropout_p = ctx.cfg
-        if ctx.parts is None:
-            raise RuntimeError("encoder_stack: backward called twice on the same forward (workspace already released)")
-        parts, ctx.parts = ctx.parts, None
-        dy_ = _f32c(dy)
-        dx = torch.empty_like(x_)
-        dps = [torch.empty_like(p_) for _ in parts]     # fresh buffers per call: returned gradient views never alias later calls
-        main, streams = _SPLIT_STREAMS.begin(x_.device, len(parts))
-        for (b0, b1, ws, nbytes, sd), dp, st in zip(parts, dps, streams):
-            with torch.cuda.stream(st):
-                Bi = b1 - b0
-                gp, xp, mp, dxp = (_lib.ptr(dy_) + 4 * b0 * T * d, _lib.ptr(x_) + 4 * b0 * T * d, _lib.ptr(m_) + 4 * b0 * T,
-                                   _lib.ptr(dx) + 4 * b0 * T * d)
-                if isinstance(sd, _lib.DeviceSeed):  # the forward left its seed in the workspace
-                    _lib.check(lib.mmt_encoder_backward_devseed(gp, xp, mp, _lib.ptr(p_), dxp, _lib.ptr(dp), _lib.ptr(ws), nbytes,
-                                                                Bi, T, d, h, d_ff, n_layers, eps, dropout_p, _lib.stream_ptr()))
-                else:
-                    _lib.check(lib.mmt_encoder_backward(gp, xp, mp, _lib.ptr(p_), dxp, _lib.ptr(dp), _lib.ptr(ws), nbytes,
-                                                        Bi, T, d, h, d_ff, n_layers, eps, dropout_p, sd, _lib.stream_ptr()))
-                _lib.POOL.put(ws)
-        _SPLIT_STREAMS.end(main, streams)
-        if len(dps) > 1:                                # the sub-batches' parameter gradients, summed into the first buffer
-            n = p_.numel()
-            for other in dps[1:]:
-                copy2d([_seg(dps[0], n, 1, n, src=other, src_ld=n, acc=True)])
-        return dx, None, dps[0], None, None, None, None, None, None, None, None
-
-
-def _seed_arg(seed):
-    if isinstance(seed, (list, tuple)):
-        return [_seed_arg(v) for v in seed]
-    return seed if isinstance(seed, _lib.DeviceSeed) else int(seed)
+        dx, dflat = _encoder_bwd(ctx, dy)
+        return dx, None, dflat, None, None, None, None, None, None, None
 
 
 def encoder_stack(x, mask, flat_params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, nsplit=1):
     """``seed``: a python int (by value) or a ``_lib.DeviceSeed`` (device-resident: fresh masks at every hipGraph replay), or one
     of either per sub-batch stream; ``nsplit``: run the batch as that many sub-batches on HIP streams of their own (see _SPLIT_STREAMS)."""
     return _EncoderStackFn.apply(x, mask, flat_params, int(h), int(d_ff), int(n_layers), float(eps), float(dropout_p), _seed_arg(seed),
-                                 False, int(nsplit))
+                                 int(nsplit))
 
 
 class _EncoderStackParamsFn(torch.autograd.Function):
@@ -156,30 +188,13 @@ class _EncoderStackParamsFn(torch.autograd.Function):
         if flat is None:
             flat = torch.cat([q.detach().reshape(-1) for q in params]).float()
         ctx.shapes = [tuple(q.shape) for q in params]
-        ctx.inner = _Ctx()
-        y = _EncoderStackFn.forward(ctx.inner, x, mask, flat, h, d_ff, n_layers, eps, dropout_p, seed, _needs=any(ctx.needs_input_grad),
-                                    nsplit=nsplit)
-        return y
+        return _encoder_fwd(ctx, x, mask, flat, h, d_ff, n_layers, eps, dropout_p, seed, nsplit)
 
     @staticmethod
     def backward(ctx, dy):
-        dx, _, dflat = _EncoderStackFn.backward(ctx.inner, dy)[:3]
-        grads, off = [], 0
-        for shp in ctx.shapes:
-            n = 1
-            for v in shp:
-                n *= v
-            grads.append(dflat[off:off + n].view(shp))
-            off += n
+        dx, dflat = _encoder_bwd(ctx, dy)
+        grads = [g.view(shp) for g, shp in zip(dflat.split([math.prod(shp) for shp in ctx.shapes]), ctx.shapes)]
         return (dx, None, None, None, None, None, None, None, None, None) + tuple(grads)
-
-
-class _Ctx:
-    """Minimal stand-in for the autograd context when one Function drives another's static methods."""
-    needs_input_grad = (False, False, False)
-
-    def save_for_backward(self, *t):
-        self.saved_tensors = t
 
 
 def encoder_stack_params(x, mask, params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, flat=None, nsplit=1):
@@ -190,32 +205,26 @@ def encoder_stack_params(x, mask, params, h, d_ff, n_layers, eps=1e-6, dropout_p
 class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, a_2, b_2, eps):
-        lib = _lib.load()
         _lib.require_hip(x, a_2, b_2)
         x_, a_, b_ = _f32c(x), _f32c(a_2), _f32c(b_2)
         d = x_.shape[-1]
         M = x_.numel() // d
         y = torch.empty_like(x_)
         stats = torch.empty(M, 2, dtype=torch.float32, device=x_.device)
-        _lib.check(lib.mmt_layernorm_forward(_lib.ptr(x_), _lib.ptr(a_), _lib.ptr(b_), _lib.ptr(y), _lib.ptr(stats), M, d, eps,
-                                             _lib.stream_ptr()))
+        _lib.launch("mmt_layernorm_forward", x_, a_, b_, y, stats, M, d, eps)
         ctx.save_for_backward(x_, a_, stats)
         ctx.eps = eps
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
         x_, a_, stats = ctx.saved_tensors
         d = x_.shape[-1]
         M = x_.numel() // d
         dy_ = _f32c(dy)
-        dx = torch.empty_like(x_)
-        da = torch.empty_like(a_)
-        db = torch.empty_like(a_)
-        scratch = torch.empty(lib.mmt_layernorm_scratch_floats(M, d), dtype=torch.float32, device=x_.device)
-        _lib.check(lib.mmt_layernorm_backward(_lib.ptr(dy_), _lib.ptr(x_), _lib.ptr(a_), _lib.ptr(stats), _lib.ptr(dx),
-                                              _lib.ptr(da), _lib.ptr(db), _lib.ptr(scratch), M, d, ctx.eps, _lib.stream_ptr()))
+        dx, da, db = torch.empty_like(x_), torch.empty_like(a_), torch.empty_like(a_)
+        scratch = torch.empty(_lib.load().mmt_layernorm_scratch_floats(M, d), dtype=torch.float32, device=x_.device)
+        _lib.launch("mmt_layernorm_backward", dy_, x_, a_, stats, dx, da, db, scratch, M, d, ctx.eps)
         return dx, da, db, None
 
 
@@ -237,27 +246,22 @@ class _SdpaFn(torch.autograd.Function):
         train = dropout_p > 0.0
         nbytes = (lib.mmt_sdpa_workspace_bytes if train else lib.mmt_sdpa_workspace_bytes_eval)(B, T, d, h)
         if nbytes == 0:
-            _lib.check(lib.mmt_sdpa_forward(None, None, None, None, None, None, 0, B, T, d, h, 0.0, 0, None))
+            _lib.launch("mmt_sdpa_forward", None, None, None, None, None, None, 0, B, T, d, h, 0.0, 0)
         ws = _lib.POOL.get(nbytes, q_.device, tag=("sdpa", B, T, d, h, train))
         out = torch.empty_like(q_)
-        _lib.check(lib.mmt_sdpa_forward(_lib.ptr(q_), _lib.ptr(k_), _lib.ptr(v_), _lib.ptr(m_), _lib.ptr(out), _lib.ptr(ws), nbytes,
-                                        B, T, d, h, dropout_p, seed, _lib.stream_ptr()))
-        if any(ctx.needs_input_grad):
-            ctx.ws, ctx.cfg, ctx.mask = ws, (B, T, d, h, nbytes, dropout_p, seed), m_
-        else:
-            _lib.POOL.put(ws)
+        _lib.launch("mmt_sdpa_forward", q_, k_, v_, m_, out, ws, nbytes, B, T, d, h, dropout_p, seed)
+        if _hold(ctx, ws):
+            ctx.cfg, ctx.mask = (B, T, d, h, dropout_p, seed), m_
         return out
 
     @staticmethod
     def backward(ctx, dctx):
-        lib = _lib.load()
-        B, T, d, h, nbytes, dropout_p, seed = ctx.cfg
+        (ws,) = _take_ws(ctx, "sdpa")
+        B, T, d, h, dropout_p, seed = ctx.cfg
         g = _f32c(dctx)
         dq, dk, dv = (torch.empty_like(g) for _ in range(3))
-        _lib.check(lib.mmt_sdpa_backward(_lib.ptr(g), _lib.ptr(ctx.mask), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(ctx.ws),
-                                         nbytes, B, T, d, h, dropout_p, seed, _lib.stream_ptr()))
-        _lib.POOL.put(ctx.ws)
-        ctx.ws = None
+        _lib.launch("mmt_sdpa_backward", g, ctx.mask, dq, dk, dv, ws, ws.numel(), B, T, d, h, dropout_p, seed)
+        _lib.POOL.put(ws)
         return dq, dk, dv, None, None, None, None
 
 
@@ -267,45 +271,50 @@ def sdpa(q, k, v, mask, h, dropout_p=0.0, seed=0):
     return _SdpaFn.apply(q, k, v, mask, int(h), float(dropout_p), int(seed))
 
 
+def _linear_ws(x_, N):
+    """The pool workspace of an affine map of x_ to N features (zero pads survive reuse: the kernels never write them)."""
+    K = x_.shape[-1]
+    M = x_.numel() // K
+    return _lib.POOL.get(_lib.load().mmt_linear_workspace_bytes(M, K, N), x_.device, tag=("linear", M, K, N))
+
+
 def _raw_linear_fwd(x_, W_, b_, act=0, r_=None, in_p=0.0, out_p=0.0, seed=0):
-    """y = rowscale * drop_out(act(drop_in(x) W^T + b)) on contiguous fp32 device tensors, outside autograd -> (y, workspace, bytes)."""
-    lib = _lib.load()
+    """y = rowscale * drop_out(act(drop_in(x) W^T + b)) on contiguous fp32 device tensors, outside autograd -> (y, workspace)."""
     K, N = x_.shape[-1], W_.shape[0]
     M = x_.numel() // K
     if W_.shape[1] != K:
         raise ValueError("linear: weight %s does not match input features %d" % (tuple(W_.shape), K))
-    nbytes = lib.mmt_linear_workspace_bytes(M, K, N)
-    ws = _lib.POOL.get(nbytes, x_.device, tag=("linear", M, K, N))     # zero pads survive reuse: the kernels never write them
+    ws = _linear_ws(x_, N)
     y = torch.empty(x_.shape[:-1] + (N,), dtype=torch.float32, device=x_.device)
     if in_p > 0.0 or out_p > 0.0:
-        dev_seed = isinstance(seed, _lib.DeviceSeed)
-        _lib.check(lib.mmt_linear_dropout_forward(_lib.ptr(x_), _lib.ptr(W_), _lib.ptr(b_), _lib.ptr(r_), _lib.ptr(y), _lib.ptr(ws), nbytes,
-                                                  M, K, N, act, in_p, out_p, 0 if dev_seed else int(seed),
-                                                  seed.ptr() if dev_seed else None, _lib.stream_ptr()))
+        _lib.launch("mmt_linear_dropout_forward", x_, W_, b_, r_, y, ws, ws.numel(), M, K, N, act, in_p, out_p, *_seed_pair(seed))
     else:
-        _lib.check(lib.mmt_linear_forward(_lib.ptr(x_), _lib.ptr(W_), _lib.ptr(b_), _lib.ptr(r_), _lib.ptr(y), _lib.ptr(ws), nbytes,
-                                          M, K, N, act, _lib.stream_ptr()))
-    return y, ws, nbytes
+        _lib.launch("mmt_linear_forward", x_, W_, b_, r_, y, ws, ws.numel(), M, K, N, act)
+    return y, ws
 
 
-def _raw_linear_bwd(g, x_, W_, y_, r_, ws, nbytes, need_x, need_w, need_b, act=0, in_p=0.0, out_p=0.0, seed=0):
-    """-> (dx, dW, db) of the affine map above (each None unless asked for); hands the workspace back to the pool."""
-    lib = _lib.load()
+def _raw_linear_bwd(g, x_, W_, y_, r_, ws, need_x, need_w, need_b, act=0, in_p=0.0, out_p=0.0, seed=0, dW=None, db=None):
+    """-> (dx, dW, db) of the affine map above, each None unless asked for (or, for dW and db, handed in to be written); hands the
+    workspace back to the pool."""
     K, N = x_.shape[-1], W_.shape[0]
     M = x_.numel() // K
     dx = torch.empty_like(x_) if need_x else None
-    dW = torch.empty_like(W_) if need_w else None
-    db = torch.empty(N, dtype=torch.float32, device=x_.device) if need_b else None
+    dW = torch.empty_like(W_) if need_w else dW
+    db = torch.empty(N, dtype=torch.float32, device=x_.device) if need_b else db
     if in_p > 0.0 or out_p > 0.0:
-        dev_seed = isinstance(seed, _lib.DeviceSeed)
-        _lib.check(lib.mmt_linear_dropout_backward(_lib.ptr(g), _lib.ptr(x_), _lib.ptr(W_), _lib.ptr(y_), _lib.ptr(r_), _lib.ptr(dx),
-                                                   _lib.ptr(dW), _lib.ptr(db), _lib.ptr(ws), nbytes, M, K, N, act, in_p, out_p,
-                                                   0 if dev_seed else int(seed), 1 if dev_seed else 0, _lib.stream_ptr()))
+        value, state = _seed_pair(seed)
+        _lib.launch("mmt_linear_dropout_backward", g, x_, W_, y_, r_, dx, dW, db, ws, ws.numel(), M, K, N, act, in_p, out_p, value,
+                    int(state is not None))
     else:
-        _lib.check(lib.mmt_linear_backward(_lib.ptr(g), _lib.ptr(x_), _lib.ptr(W_), _lib.ptr(y_), _lib.ptr(r_), _lib.ptr(dx),
-                                           _lib.ptr(dW), _lib.ptr(db), _lib.ptr(ws), nbytes, M, K, N, act, _lib.stream_ptr()))
+        _lib.launch("mmt_linear_backward", g, x_, W_, y_, r_, dx, dW, db, ws, ws.numel(), M, K, N, act)
     _lib.POOL.put(ws)
     return dx, dW, db
+
+
+def _wgrad(g, x, W, dW, db=None):
+    """dW = g^T x (and db = the column sums of g) into the given tensors: the weight-gradient half of the affine map's backward, used
+    for the window contractions of the scans."""
+    _raw_linear_bwd(g, x, W, None, None, _linear_ws(x, W.shape[0]), False, False, False, dW=dW, db=db)
 
 
 class _LinearFn(torch.autograd.Function):
@@ -315,22 +324,19 @@ class _LinearFn(torch.autograd.Function):
         x_, W_, b_, r_ = _f32c(x), _f32c(W), _f32c(b), _f32c(rowscale)
         if r_ is not None and r_.numel() != x_.numel() // x_.shape[-1]:
             raise ValueError("linear: rowscale must have one entry per row")
-        y, ws, nbytes = _raw_linear_fwd(x_, W_, b_, act, r_, in_p, out_p, seed)
-        ctx.cfg = (act, nbytes, b is not None, in_p, out_p, seed)
-        if any(ctx.needs_input_grad):
+        y, ws = _raw_linear_fwd(x_, W_, b_, act, r_, in_p, out_p, seed)
+        ctx.cfg = (act, b is not None, in_p, out_p, seed)
+        if _hold(ctx, ws):
             ctx.save_for_backward(x_, W_, y if act != 0 else None, r_)
-            ctx.ws = ws
-        else:
-            _lib.POOL.put(ws)
         return y
 
     @staticmethod
     def backward(ctx, dy):
+        (ws,) = _take_ws(ctx, "linear")
         x_, W_, y_, r_ = ctx.saved_tensors
-        act, nbytes, has_b, in_p, out_p, seed = ctx.cfg
-        dx, dW, db = _raw_linear_bwd(_f32c(dy), x_, W_, y_, r_, ctx.ws, nbytes, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
-                                     has_b and ctx.needs_input_grad[2], act, in_p, out_p, seed)
-        ctx.ws = None
+        act, has_b, in_p, out_p, seed = ctx.cfg
+        need = ctx.needs_input_grad
+        dx, dW, db = _raw_linear_bwd(_f32c(dy), x_, W_, y_, r_, ws, need[0], need[1], has_b and need[2], act, in_p, out_p, seed)
         return dx, dW, db, None, None, None, None, None
 
 
@@ -345,8 +351,7 @@ def linear(x, weight, bias=None, act=0, rowscale=None, in_dropout=0.0, out_dropo
         pad = 4 - K % 4
         x = cat_cols([x, torch.zeros(*x.shape[:-1], pad, dtype=x.dtype, device=x.device)])
         weight = cat_cols([weight, torch.zeros(weight.shape[0], pad, dtype=weight.dtype, device=weight.device)])
-    return _LinearFn.apply(x, weight, bias, rowscale, int(act), float(in_dropout), float(out_dropout),
-                           seed if isinstance(seed, _lib.DeviceSeed) else int(seed))
+    return _LinearFn.apply(x, weight, bias, rowscale, int(act), float(in_dropout), float(out_dropout), _seed_arg(seed))
 
 
 class _LinearPairFn(torch.autograd.Function):
@@ -358,32 +363,26 @@ class _LinearPairFn(torch.autograd.Function):
     def forward(ctx, x, W1, b1, W2, b2, act1, act2):
         _lib.require_hip(x, W1, b1, W2, b2)
         x_, W1_, b1_, W2_, b2_ = _f32c(x), _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
-        y1, ws1, nb1 = _raw_linear_fwd(x_, W1_, b1_, act1)
-        y2, ws2, nb2 = _raw_linear_fwd(x_, W2_, b2_, act2)
+        y1, ws1 = _raw_linear_fwd(x_, W1_, b1_, act1)
+        y2, ws2 = _raw_linear_fwd(x_, W2_, b2_, act2)
         ctx.cfg = (act1, act2, b1 is not None, b2 is not None)
-        if any(ctx.needs_input_grad):
+        if _hold(ctx, ws1, ws2):
             ctx.save_for_backward(x_, W1_, W2_, y1 if act1 else None, y2 if act2 else None)
-            ctx.ws = (ws1, nb1, ws2, nb2)
-        else:
-            _lib.POOL.put(ws1); _lib.POOL.put(ws2)
         return y1, y2
 
     @staticmethod
     def backward(ctx, dy1, dy2):
+        ws1, ws2 = _take_ws(ctx, "linear_pair")
         x_, W1_, W2_, y1, y2 = ctx.saved_tensors
         act1, act2, has_b1, has_b2 = ctx.cfg
-        ws1, nb1, ws2, nb2 = ctx.ws
-        ctx.ws = None
-        need_x = ctx.needs_input_grad[0]
-        g = ctx.needs_input_grad
+        need_x, g = ctx.needs_input_grad[0], ctx.needs_input_grad
         dy1 = _f32c(dy1) if dy1 is not None else torch.zeros(x_.shape[:-1] + (W1_.shape[0],), dtype=torch.float32, device=x_.device)
         dy2 = _f32c(dy2) if dy2 is not None else torch.zeros(x_.shape[:-1] + (W2_.shape[0],), dtype=torch.float32, device=x_.device)
-        dx1, dW1, db1 = _raw_linear_bwd(dy1, x_, W1_, y1, None, ws1, nb1, need_x, g[1], has_b1 and g[2], act1)
-        dx2, dW2, db2 = _raw_linear_bwd(dy2, x_, W2_, y2, None, ws2, nb2, need_x, g[3], has_b2 and g[4], act2)
-        dx = None
+        dx1, dW1, db1 = _raw_linear_bwd(dy1, x_, W1_, y1, None, ws1, need_x, g[1], has_b1 and g[2], act1)
+        dx2, dW2, db2 = _raw_linear_bwd(dy2, x_, W2_, y2, None, ws2, need_x, g[3], has_b2 and g[4], act2)
+        dx = torch.empty_like(x_) if need_x else None
         if need_x:
             K = x_.shape[-1]
-            dx = torch.empty_like(x_)
             copy2d([_seg(dx, K, x_.numel() // K, K, src=dx1, src_ld=K, src2=dx2, src2_ld=K)])        # dx = dx1 + dx2
         return dx, dW1, db1, dW2, db2, None, None
 
@@ -403,39 +402,30 @@ class _HighwayFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, Wp, bp, Wg, bg, p, seed, proj_act):
-        lib = _lib.load()
         _lib.require_hip(x, Wp, bp, Wg, bg)
         x_, Wp_, bp_, Wg_, bg_ = _f32c(x), _f32c(Wp), _f32c(bp), _f32c(Wg), _f32c(bg)
-        proj, wsp, nbp = _raw_linear_fwd(x_, Wp_, bp_, act=proj_act)
-        gate, wsg, nbg = _raw_linear_fwd(x_, Wg_, bg_, act=3)
+        proj, wsp = _raw_linear_fwd(x_, Wp_, bp_, act=proj_act)
+        gate, wsg = _raw_linear_fwd(x_, Wg_, bg_, act=3)
         out = torch.empty_like(x_)
-        dev_seed = isinstance(seed, _lib.DeviceSeed) and p > 0.0
-        block = torch.empty(2, dtype=torch.int64, device=x_.device) if dev_seed else None       # seed + stream keys of this call, for the backward
-        _lib.check(lib.mmt_highway_forward(_lib.ptr(x_), _lib.ptr(proj), _lib.ptr(gate), _lib.ptr(out), x_.numel(), p,
-                                           0 if dev_seed else int(seed), seed.ptr() if dev_seed else None, _lib.ptr(block), _lib.stream_ptr()))
-        if any(ctx.needs_input_grad):
+        value, state = _seed_pair(seed)
+        block = None if state is None else torch.empty(2, dtype=torch.int64, device=x_.device)     # this call's seed + stream keys
+        _lib.launch("mmt_highway_forward", x_, proj, gate, out, x_.numel(), p, value, state, block)
+        if _hold(ctx, wsp, wsg):
             ctx.save_for_backward(x_, Wp_, Wg_, proj, gate, block)
-            ctx.ws = (wsp, nbp, wsg, nbg)
-        else:
-            _lib.POOL.put(wsp); _lib.POOL.put(wsg)
-        ctx.cfg = (p, 0 if dev_seed else int(seed), proj_act)
+        ctx.cfg = (p, value, proj_act)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
+        wsp, wsg = _take_ws(ctx, "highway")
         x_, Wp_, Wg_, proj, gate, block = ctx.saved_tensors
         p, seed, proj_act = ctx.cfg
-        wsp, nbp, wsg, nbg = ctx.ws
-        ctx.ws = None
         d_ = _f32c(dout)
         dx, dproj, dgate = torch.empty_like(x_), torch.empty_like(x_), torch.empty_like(x_)
-        _lib.check(lib.mmt_highway_backward(_lib.ptr(d_), _lib.ptr(x_), _lib.ptr(proj), _lib.ptr(gate), _lib.ptr(dx), _lib.ptr(dproj), _lib.ptr(dgate),
-                                            x_.numel(), p, seed, _lib.ptr(block), _lib.stream_ptr()))
-        need_x = ctx.needs_input_grad[0]
-        dx1, dWp, dbp = _raw_linear_bwd(dproj, x_, Wp_, proj if proj_act else None, None, wsp, nbp, need_x, ctx.needs_input_grad[1],
-                                        ctx.needs_input_grad[2], act=proj_act)
-        dx2, dWg, dbg = _raw_linear_bwd(dgate, x_, Wg_, gate, None, wsg, nbg, need_x, ctx.needs_input_grad[3], ctx.needs_input_grad[4], act=3)
+        _lib.launch("mmt_highway_backward", d_, x_, proj, gate, dx, dproj, dgate, x_.numel(), p, seed, block)
+        need_x, g = ctx.needs_input_grad[0], ctx.needs_input_grad
+        dx1, dWp, dbp = _raw_linear_bwd(dproj, x_, Wp_, proj if proj_act else None, None, wsp, need_x, g[1], g[2], act=proj_act)
+        dx2, dWg, dbg = _raw_linear_bwd(dgate, x_, Wg_, gate, None, wsg, need_x, g[3], g[4], act=3)
         if need_x:
             K = x_.shape[-1]
             copy2d([_seg(dx, K, x_.numel() // K, K, src=dx1, src_ld=K, src2=dx2, src2_ld=K, acc=True)])        # dx += dx1 + dx2
@@ -446,7 +436,7 @@ def highway(x, Wp, bp, Wg, bg, dropout_p=0.0, seed=0, proj_act=0):
     """drop(gate * proj + (1 - gate) * x) with proj = x Wp^T + bp, gate = sigmoid(x Wg^T + bg); seed: python int or ``_lib.DeviceSeed``
     (train-mode dropout: stream 3000 of dropout_mask, index = element).  proj_act = 1: proj = ReLU(x Wp^T + bp), the Highway of the
     B1-LSTM variant (transformer/B1-LSTM/models.py:52), the ReLU riding in the projection GEMM's epilogue."""
-    return _HighwayFn.apply(x, Wp, bp, Wg, bg, float(dropout_p), seed if isinstance(seed, _lib.DeviceSeed) else int(seed), int(proj_act))
+    return _HighwayFn.apply(x, Wp, bp, Wg, bg, float(dropout_p), _seed_arg(seed), int(proj_act))
 
 
 class _LocalAttnFn(torch.autograd.Function):
@@ -457,7 +447,6 @@ class _LocalAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, h, valid):
-        lib = _lib.load()
         _lib.require_hip(z, h, valid)
         z_, h_, v_ = _f32c(z), _f32c16(h), _f32c(valid)
         B, T, L = z_.shape
@@ -468,24 +457,20 @@ class _LocalAttnFn(torch.autograd.Function):
         H = h_.shape[2]
         out = torch.empty(B, T, H, dtype=torch.float32, device=z_.device)
         a = torch.empty(B, T, L, dtype=torch.float32, device=z_.device)
-        _lib.check(lib.mmt_local_attn_forward(_lib.ptr(z_), _lib.ptr(h_), _lib.ptr(v_), _lib.ptr(out), _lib.ptr(a), B, T, H, L,
-                                              _lib.stream_ptr()))
+        _lib.launch("mmt_local_attn_forward", z_, h_, v_, out, a, B, T, H, L)
         ctx.save_for_backward(a, h_, v_)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
         a, h_, v_ = ctx.saved_tensors
         B, T, L = a.shape
         H = h_.shape[2]
         g = _f32c16(dout)
-        nbytes = lib.mmt_local_attn_workspace_bytes(B, T, H, L)
+        nbytes = _lib.load().mmt_local_attn_workspace_bytes(B, T, H, L)
         ws = _lib.POOL.get(nbytes, g.device, tag=("local_attn", B, T, H, L))
-        dz = torch.empty_like(a)
-        dh = torch.empty_like(h_)
-        _lib.check(lib.mmt_local_attn_backward(_lib.ptr(g), _lib.ptr(a), _lib.ptr(h_), _lib.ptr(v_), _lib.ptr(dz), _lib.ptr(dh),
-                                               _lib.ptr(ws), nbytes, B, T, H, L, _lib.stream_ptr()))
+        dz, dh = torch.empty_like(a), torch.empty_like(h_)
+        _lib.launch("mmt_local_attn_backward", g, a, h_, v_, dz, dh, ws, nbytes, B, T, H, L)
         _lib.POOL.put(ws)
         return dz, dh, None
 
@@ -504,7 +489,6 @@ class _LstmScanFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gx, W_rec, h0, c0):
-        lib = _lib.load()
         ctx.set_materialize_grads(False)            # an unused output (the decoder never reads c_all) arrives as None, not as a zero fill
         _lib.require_hip(gx, W_rec, h0, c0)
         gx_, W_, h0_, c0_ = _f32c(gx), _f32c(W_rec), _f32c(h0), _f32c(c0)
@@ -512,13 +496,12 @@ class _LstmScanFn(torch.autograd.Function):
         H = H4 // 4
         if W_.shape != (4 * H, H):
             raise ValueError("lstm_scan: W_rec must be (4H,H) = (%d,%d), got %s" % (4 * H, H, tuple(W_.shape)))
-        nbytes = lib.mmt_lstm_scan_workspace_bytes(H)
+        nbytes = _lib.load().mmt_lstm_scan_workspace_bytes(H)
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=gx_.device)
         h_all = torch.empty(T, B, H, dtype=torch.float32, device=gx_.device)
         c_all = torch.empty_like(h_all)
         acts = torch.empty(T, B, 4 * H, dtype=torch.float32, device=gx_.device)
-        _lib.check(lib.mmt_lstm_scan_forward(_lib.ptr(gx_), _lib.ptr(W_), _lib.ptr(h0_), _lib.ptr(c0_), _lib.ptr(h_all), _lib.ptr(c_all),
-                                             _lib.ptr(acts), _lib.ptr(ws), nbytes, T, B, H, _lib.stream_ptr()))
+        _lib.launch("mmt_lstm_scan_forward", gx_, W_, h0_, c0_, h_all, c_all, acts, ws, nbytes, T, B, H)
         if H > 128:                                 # four-CU scan: its exchange waits are bounded and report through this word
             _lib.ERRORS.watch(ws[:4].view(torch.int32), "lstm_scan forward (T=%d, B=%d, H=%d)" % (T, B, H))
         ctx.save_for_backward(W_, h0_, c0_, h_all, c_all, acts)
@@ -527,17 +510,14 @@ class _LstmScanFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dh_all, dc_all):
-        lib = _lib.load()
         W_, h0_, c0_, h_all, c_all, acts = ctx.saved_tensors
         T, B, H, nbytes = ctx.dims
         dev = h_all.device
         dh_, dc_ = _f32c(dh_all), _f32c(dc_all)
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         dgx = torch.empty(T, B, 4 * H, dtype=torch.float32, device=dev)
-        dh0 = torch.empty(B, H, dtype=torch.float32, device=dev)
-        dc0 = torch.empty(B, H, dtype=torch.float32, device=dev)
-        _lib.check(lib.mmt_lstm_scan_backward(_lib.ptr(dh_), _lib.ptr(dc_), _lib.ptr(W_), _lib.ptr(c0_), _lib.ptr(c_all), _lib.ptr(acts),
-                                              _lib.ptr(dgx), _lib.ptr(dh0), _lib.ptr(dc0), _lib.ptr(ws), nbytes, T, B, H, _lib.stream_ptr()))
+        dh0, dc0 = (torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(2))
+        _lib.launch("mmt_lstm_scan_backward", dh_, dc_, W_, c0_, c_all, acts, dgx, dh0, dc0, ws, nbytes, T, B, H)
         if H > 128:
             _lib.ERRORS.watch(ws[:4].view(torch.int32), "lstm_scan backward (T=%d, B=%d, H=%d)" % (T, B, H))
         dW = None
@@ -545,13 +525,8 @@ class _LstmScanFn(torch.autograd.Function):
             # dW_rec = sum_{t,b} dG[t,b,:]^T h_{t-1}[b,:]  — a window-contraction: the weight-gradient GEMM
             hprev = torch.empty_like(h_all)          # h_{t-1}: h0 (or zeros), then h_all shifted by one step
             copy2d([_seg(hprev, H, B, H, src=h0_, src_ld=H), _seg(hprev, H, (T - 1) * B, H, src=h_all, src_ld=H, dst_off=B * H)])
-            M = T * B
-            lb = lib.mmt_linear_workspace_bytes(M, H, 4 * H)
-            lws = _lib.POOL.get(lb, dev, tag=("linear", M, H, 4 * H))
             dW = torch.empty_like(W_)
-            _lib.check(lib.mmt_linear_backward(_lib.ptr(dgx), _lib.ptr(hprev), _lib.ptr(W_), None, None, None, _lib.ptr(dW), None,
-                                               _lib.ptr(lws), lb, M, H, 4 * H, 0, _lib.stream_ptr()))
-            _lib.POOL.put(lws)
+            _wgrad(dgx, hprev, W_, dW)
         return (dgx, dW, dh0 if (h0_ is not None and ctx.needs_input_grad[2]) else None,
                 dc0 if (c0_ is not None and ctx.needs_input_grad[3]) else None)
 
@@ -566,7 +541,6 @@ class _ConvPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        lib = _lib.load()
         _lib.require_hip(x, weight, bias)
         if x.requires_grad:
             raise NotImplementedError("conv_maxpool: the windows are input data; a gradient w.r.t. them is not implemented "
@@ -577,14 +551,13 @@ class _ConvPoolFn(torch.autograd.Function):
         if w_.shape != (F_, D, 2):
             raise NotImplementedError("conv_maxpool: weight must be (F, D, 2) = nn.Conv1d(D, F, kernel_size=2).weight, got %s"
                                       % (tuple(w_.shape),))
-        nbytes = lib.mmt_convpool_workspace_bytes(N, W, D, F_)
+        nbytes = _lib.load().mmt_convpool_workspace_bytes(N, W, D, F_)
         if nbytes == 0:
-            _lib.check(lib.mmt_convpool_forward(None, None, None, None, None, None, 0, N, W, D, F_, None))
+            _lib.launch("mmt_convpool_forward", None, None, None, None, None, None, 0, N, W, D, F_)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x_.device)
         out = torch.empty(N, F_, dtype=torch.float32, device=x_.device)
         arg = torch.empty(N, F_, dtype=torch.int32, device=x_.device)
-        _lib.check(lib.mmt_convpool_forward(_lib.ptr(x_), _lib.ptr(w_), _lib.ptr(b_), _lib.ptr(out), _lib.ptr(arg), _lib.ptr(ws), nbytes,
-                                            N, W, D, F_, _lib.stream_ptr()))
+        _lib.launch("mmt_convpool_forward", x_, w_, b_, out, arg, ws, nbytes, N, W, D, F_)
         ctx.save_for_backward(x_, arg)
         ctx.dims = (N, W, D, F_, nbytes)
         ctx.mark_non_differentiable(arg)
@@ -593,17 +566,14 @@ class _ConvPoolFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, _darg):
-        lib = _lib.load()
         x_, arg = ctx.saved_tensors
         N, W, D, F_, nbytes = ctx.dims
         if dout is None:
             return None, None, None
         g = _f32c(dout)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
-        dw = torch.empty(F_, D, 2, dtype=torch.float32, device=g.device)
-        db = torch.empty(F_, dtype=torch.float32, device=g.device)
-        _lib.check(lib.mmt_convpool_backward(_lib.ptr(x_), _lib.ptr(g), _lib.ptr(arg), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), nbytes,
-                                             N, W, D, F_, _lib.stream_ptr()))
+        dw, db = torch.empty(F_, D, 2, dtype=torch.float32, device=g.device), torch.empty(F_, dtype=torch.float32, device=g.device)
+        _lib.launch("mmt_convpool_backward", x_, g, arg, dw, db, ws, nbytes, N, W, D, F_)
         return None, dw, db
 
 
@@ -612,82 +582,82 @@ def conv_maxpool(x, weight, bias):
     return _ConvPoolFn.apply(x, weight, bias)
 
 
+def _mem_scan_fwd(apre, chat, Wm, W2, b2, T, B, dropout_p, seed):
+    """The MFN memory recurrence on contiguous fp32 tensors with rows t*B + b -> (mem_all, u_all, g_all), shaped like apre's rows."""
+    MD, HG = W2.shape[1], W2.shape[2]
+    nbytes = _lib.load().mmt_mfn_mem_scan_workspace_bytes()
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=apre.device)
+    rows = apre.shape[:-1]
+    mem_all, u_all, g_all = _new(*rows, MD, like=apre), _new(*rows, 2 * HG, like=apre), _new(*rows, 2 * MD, like=apre)
+    _launch_seeded("mmt_mfn_mem_scan_forward", seed, apre, chat, Wm, W2, b2, mem_all, u_all, g_all, ws, nbytes, T, B, MD, HG, dropout_p)
+    return mem_all, u_all, g_all
+
+
+def _mem_scan_bwd(dmem, chat, Wm, W2, mem_all, u_all, g_all, T, B, dropout_p):
+    """-> (dapre, dchat, dWm, dW2, db2) of _mem_scan_fwd: the scan backward, then its batched weight gradients (window contractions)
+    dWm = dapre^T mem_prev, dW2_g = dz_g^T u_g, db2_g = sum dz_g."""
+    MD, HG = W2.shape[1], W2.shape[2]
+    M = T * B
+    nbytes = _lib.load().mmt_mfn_mem_scan_workspace_bytes()
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dmem.device)
+    dchat, dapre, dz = torch.empty_like(chat), torch.empty_like(u_all), torch.empty_like(g_all)
+    _lib.launch("mmt_mfn_mem_scan_backward", dmem, chat, mem_all, u_all, g_all, Wm, W2, dchat, dapre, dz, ws, nbytes, T, B, MD, HG,
+                dropout_p)
+    mem_prev = torch.empty_like(mem_all)
+    dzs, us = [_new(M, MD, like=dz) for _ in range(2)], [_new(M, HG, like=dz) for _ in range(2)]
+    segs = [_seg(mem_prev, MD, B, MD), _seg(mem_prev, MD, M - B, MD, src=mem_all, src_ld=MD, dst_off=B * MD)]
+    for g in range(2):
+        segs += [_seg(dzs[g], MD, M, MD, src=dz, src_ld=2 * MD, src_off=g * MD),
+                 _seg(us[g], HG, M, HG, src=u_all, src_ld=2 * HG, src_off=g * HG)]
+    copy2d(segs)
+    dWm, dW2, db2 = torch.empty_like(Wm), torch.empty_like(W2), _new(2, MD, like=dz)
+    _wgrad(dapre, mem_prev, Wm, dWm)
+    for g in range(2):
+        _wgrad(dzs[g], us[g], W2[g], dW2[g], db2[g])
+    return dapre, dchat, dWm, dW2, db2
+
+
 class _MfnMemScanFn(torch.autograd.Function):
     """mem_all = scan(apre, chat, Wm, W2, b2): the MFN memory recurrence
     (transformer/MFT/multiTransformer.py:221-224) with everything that does not depend on mem batched before."""
 
     @staticmethod
     def forward(ctx, apre, chat, Wm, W2, b2, dropout_p, seed):
-        lib = _lib.load()
         _lib.require_hip(apre, chat, Wm, W2, b2)
         a_, c_, Wm_, W2_, b2_ = _f32c(apre), _f32c(chat), _f32c(Wm), _f32c(W2), _f32c(b2)
         T, B, U = a_.shape
         MD, HG = c_.shape[-1], W2_.shape[-1]
         if U != 2 * HG or Wm_.shape != (U, MD) or W2_.shape != (2, MD, HG) or b2_.shape != (2, MD):
             raise ValueError("mfn_mem_scan: inconsistent shapes")
-        dev = a_.device
-        nbytes = lib.mmt_mfn_mem_scan_workspace_bytes()
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        mem_all = torch.empty(T, B, MD, dtype=torch.float32, device=dev)
-        u_all = torch.empty(T, B, U, dtype=torch.float32, device=dev)
-        g_all = torch.empty(T, B, 2 * MD, dtype=torch.float32, device=dev)
-        if isinstance(seed, _lib.DeviceSeed):
-            _lib.check(lib.mmt_mfn_mem_scan_forward_devseed(_lib.ptr(a_), _lib.ptr(c_), _lib.ptr(Wm_), _lib.ptr(W2_), _lib.ptr(b2_), _lib.ptr(mem_all),
-                                                            _lib.ptr(u_all), _lib.ptr(g_all), _lib.ptr(ws), nbytes, T, B, MD, HG,
-                                                            dropout_p, seed.ptr(), _lib.stream_ptr()))
-        else:
-            _lib.check(lib.mmt_mfn_mem_scan_forward(_lib.ptr(a_), _lib.ptr(c_), _lib.ptr(Wm_), _lib.ptr(W2_), _lib.ptr(b2_), _lib.ptr(mem_all),
-                                                    _lib.ptr(u_all), _lib.ptr(g_all), _lib.ptr(ws), nbytes, T, B, MD, HG,
-                                                    dropout_p, seed, _lib.stream_ptr()))
+        mem_all, u_all, g_all = _mem_scan_fwd(a_, c_, Wm_, W2_, b2_, T, B, dropout_p, seed)
         ctx.save_for_backward(c_, Wm_, W2_, mem_all, u_all, g_all)
-        ctx.dims = (T, B, U, MD, HG, nbytes)
         ctx.dropout_p = dropout_p
         return mem_all
 
     @staticmethod
     def backward(ctx, dmem):
-        lib = _lib.load()
         c_, Wm_, W2_, mem_all, u_all, g_all = ctx.saved_tensors
-        T, B, U, MD, HG, nbytes = ctx.dims
-        dev = c_.device
-        dm = _f32c(dmem)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        dchat = torch.empty_like(c_)
-        dapre = torch.empty_like(u_all)
-        dz = torch.empty_like(g_all)
-        _lib.check(lib.mmt_mfn_mem_scan_backward(_lib.ptr(dm), _lib.ptr(c_), _lib.ptr(mem_all), _lib.ptr(u_all), _lib.ptr(g_all), _lib.ptr(Wm_),
-                                                 _lib.ptr(W2_), _lib.ptr(dchat), _lib.ptr(dapre), _lib.ptr(dz), _lib.ptr(ws), nbytes,
-                                                 T, B, MD, HG, ctx.dropout_p, _lib.stream_ptr()))
-        M = T * B
-        st = _lib.stream_ptr()
-        # batched weight gradients (window contractions): dWm = dapre^T mem_prev ; dW2_g = dz_g^T u_g ; db2 = sum dz
-        mem_prev = torch.empty_like(mem_all)
-        dzs = [torch.empty(T, B, MD, dtype=torch.float32, device=dev) for _ in range(2)]
-        us = [torch.empty(T, B, HG, dtype=torch.float32, device=dev) for _ in range(2)]
-        segs = [_seg(mem_prev, MD, B, MD), _seg(mem_prev, MD, (T - 1) * B, MD, src=mem_all, src_ld=MD, dst_off=B * MD)]
-        for g in range(2):
-            segs += [_seg(dzs[g], MD, M, MD, src=dz, src_ld=2 * MD, src_off=g * MD), _seg(us[g], HG, M, HG, src=u_all, src_ld=2 * HG, src_off=g * HG)]
-        copy2d(segs)
-        dWm = torch.empty_like(Wm_)
-        lb = lib.mmt_linear_workspace_bytes(M, MD, U)
-        lws = _lib.POOL.get(lb, dev, tag=("linear", M, MD, U))
-        _lib.check(lib.mmt_linear_backward(_lib.ptr(dapre), _lib.ptr(mem_prev), _lib.ptr(Wm_), None, None, None, _lib.ptr(dWm), None,
-                                           _lib.ptr(lws), lb, M, MD, U, 0, st))
-        _lib.POOL.put(lws)
-        dW2 = torch.empty_like(W2_)
-        db2 = torch.empty(2, MD, dtype=torch.float32, device=dev)
-        lb2 = lib.mmt_linear_workspace_bytes(M, HG, MD)
-        for g in range(2):
-            dzg, ug = dzs[g], us[g]
-            lws2 = _lib.POOL.get(lb2, dev, tag=("linear", M, HG, MD))
-            _lib.check(lib.mmt_linear_backward(_lib.ptr(dzg), _lib.ptr(ug), _lib.ptr(W2_[g]), None, None, None, _lib.ptr(dW2[g]),
-                                               _lib.ptr(db2[g]), _lib.ptr(lws2), lb2, M, HG, MD, 0, st))
-            _lib.POOL.put(lws2)
+        T, B = mem_all.shape[:2]
+        dapre, dchat, dWm, dW2, db2 = _mem_scan_bwd(_f32c(dmem), c_, Wm_, W2_, mem_all, u_all, g_all, T, B, ctx.dropout_p)
         return dapre, dchat, dWm, dW2, db2, None, None
 
 
 def mfn_mem_scan(apre, chat, Wm, W2, b2, dropout_p=0.0, seed=0):
     return _MfnMemScanFn.apply(apre, chat, Wm, W2, b2, float(dropout_p), _seed_arg(seed))
+
+
+def _mse_sum(pred, target, denom):
+    """-> (loss, dpred): sum((pred - target)^2) / denom and its gradient 2 (pred - target) / denom, in one launch."""
+    _lib.require_hip(pred, target)
+    p_, t_ = _f32c16(pred), _f32c16(target)
+    if p_.shape != t_.shape:
+        raise ValueError("mse_sum_loss: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
+    n = p_.numel()
+    loss = torch.empty((), dtype=torch.float32, device=p_.device)
+    dpred = torch.empty_like(p_)
+    scratch = torch.empty(_lib.load().mmt_mse_sum_scratch_doubles(n), dtype=torch.float64, device=p_.device)
+    _lib.launch("mmt_mse_sum_forward", p_, t_, 1.0 / float(denom), loss, dpred, scratch, n)
+    return loss, dpred
 
 
 class _MseSumLossFn(torch.autograd.Function):
@@ -696,17 +666,7 @@ class _MseSumLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, denom):
-        lib = _lib.load()
-        _lib.require_hip(pred, target)
-        p_, t_ = _f32c16(pred), _f32c16(target)
-        if p_.shape != t_.shape:
-            raise ValueError("mse_sum_loss: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
-        n = p_.numel()
-        loss = torch.empty((), dtype=torch.float32, device=p_.device)
-        dpred = torch.empty_like(p_)
-        scratch = torch.empty(lib.mmt_mse_sum_scratch_doubles(n), dtype=torch.float64, device=p_.device)
-        _lib.check(lib.mmt_mse_sum_forward(_lib.ptr(p_), _lib.ptr(t_), 1.0 / float(denom), _lib.ptr(loss), _lib.ptr(dpred), _lib.ptr(scratch),
-                                           n, _lib.stream_ptr()))
+        loss, dpred = _mse_sum(pred, target, denom)
         ctx.save_for_backward(dpred)
         return loss
 
@@ -725,17 +685,7 @@ def mse_sum_loss_backward(pred, target, denom):
     """``loss = mse_sum_loss(pred, target, denom); loss.backward()`` (transformer/SFT/train.py:133-139) without the two kernels autograd
     spends on the seed gradient (a fill with 1.0 and a multiplication by it): the loss kernel's gradient 2 (pred - target) / denom is
     handed straight to ``pred.backward``.  Returns the detached loss."""
-    lib = _lib.load()
-    _lib.require_hip(pred, target)
-    p_, t_ = _f32c16(pred), _f32c16(target)
-    if p_.shape != t_.shape:
-        raise ValueError("mse_sum_loss: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
-    n = p_.numel()
-    loss = torch.empty((), dtype=torch.float32, device=p_.device)
-    dpred = torch.empty_like(p_)
-    scratch = torch.empty(lib.mmt_mse_sum_scratch_doubles(n), dtype=torch.float64, device=p_.device)
-    _lib.check(lib.mmt_mse_sum_forward(_lib.ptr(p_), _lib.ptr(t_), 1.0 / float(denom), _lib.ptr(loss), _lib.ptr(dpred), _lib.ptr(scratch),
-                                       n, _lib.stream_ptr()))
+    loss, dpred = _mse_sum(pred, target, denom)
     pred.backward(dpred.view(pred.shape))
     return loss
 
@@ -755,12 +705,11 @@ def _seg(dst, dst_ld, rows, cols, src=None, src_ld=0, src2=None, src2_ld=0, rows
 
 def copy2d(segs):
     """Run a list of ``_seg`` copies (destinations must not overlap) — 24 per kernel launch."""
-    import ctypes
     segs = [g for g in segs if g.rows > 0 and g.cols > 0]
     if not segs:
         return
     arr = (_lib.CopySeg * len(segs))(*segs)
-    _lib.check(_lib.load().mmt_copy2d(ctypes.cast(arr, ctypes.c_void_p), len(segs), _lib.stream_ptr()))
+    _lib.launch("mmt_copy2d", ctypes.cast(arr, ctypes.c_void_p), len(segs))
 
 
 def _new(*shape, like):
@@ -898,7 +847,7 @@ class _AddRow0Fn(torch.autograd.Function):
         B, n, rshape = ctx.dims
         g = _f32c(dy)
         drow = _new(n, like=g)
-        _lib.check(_lib.load().mmt_colsum(_lib.ptr(g), _lib.ptr(drow), B, n, n, _lib.stream_ptr()))
+        _lib.launch("mmt_colsum", g, drow, B, n, n)
         return dy, drow.view(rshape)
 
 
@@ -924,7 +873,7 @@ class _BroadcastRowsFn(torch.autograd.Function):
         B, n, rshape = ctx.dims
         g = _f32c(dy)
         drow = _new(n, like=g)
-        _lib.check(_lib.load().mmt_colsum(_lib.ptr(g), _lib.ptr(drow), B, n, n, _lib.stream_ptr()))
+        _lib.launch("mmt_colsum", g, drow, B, n, n)
         return drow.view(rshape), None
 
 
@@ -982,7 +931,6 @@ class _MfnGateFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, nm, pg, seed_g, p_out, seed_out, *ts):
-        lib = _lib.load()
         _lib.require_hip(*ts)
         hs = [_f32c(t) for t in ts[:nm]]
         cs = [_f32c(t) for t in ts[nm:2 * nm]]
@@ -1004,12 +952,12 @@ class _MfnGateFn(torch.autograd.Function):
             segs.append(_seg(c_star, A, M, H, src=c, src_ld=H, dst_off=col))
             col += H
         copy2d(segs)
-        a1, ws_a11, nb_a11 = _raw_linear_fwd(c_star, a11w, a11b, 1)
-        logits, ws_a12, nb_a12 = _raw_linear_fwd(a1, a12w, a12b, 0)
+        a1, ws_a11 = _raw_linear_fwd(c_star, a11w, a11b, 1)
+        logits, ws_a12 = _raw_linear_fwd(a1, a12w, a12b, 0)
         att, attended = torch.empty_like(logits), torch.empty_like(logits)
-        _lib.check(lib.mmt_softmax_mul_forward(_lib.ptr(logits), _lib.ptr(c_star), _lib.ptr(att), _lib.ptr(attended), M, A, _lib.stream_ptr()))
-        a2, ws_a21, nb_a21 = _raw_linear_fwd(attended, a21w, a21b, 1)
-        c_hat, ws_a22, nb_a22 = _raw_linear_fwd(a2, a22w, a22b, 2)
+        _lib.launch("mmt_softmax_mul_forward", logits, c_star, att, attended, M, A)
+        a2, ws_a21 = _raw_linear_fwd(attended, a21w, a21b, 1)
+        c_hat, ws_a22 = _raw_linear_fwd(a2, a22w, a22b, 2)
         # gamma fc1 = [attended part | memory part] of `both` (:221-223), gamma1 rows above gamma2 rows
         Wa, Wm, b1 = _new(2 * HG, A, like=like), _new(2 * HG, MD, like=like), _new(2 * HG, like=like)
         W2, b2 = _new(2, MD, HG, like=like), _new(2, MD, like=like)
@@ -1021,16 +969,8 @@ class _MfnGateFn(torch.autograd.Function):
                      _seg(W2, HG, MD, HG, src=w2, src_ld=HG, dst_off=i * MD * HG),
                      _seg(b2, MD, 1, MD, src=bb2, src_ld=MD, dst_off=i * MD)]
         copy2d(segs)
-        apre, ws_ap, nb_ap = _raw_linear_fwd(attended, Wa, b1, 0)
-        nbm = lib.mmt_mfn_mem_scan_workspace_bytes()
-        wsm = torch.empty(nbm, dtype=torch.uint8, device=like.device)
-        mem_all, u_all, g_all = _new(M, MD, like=like), _new(M, 2 * HG, like=like), _new(M, 2 * MD, like=like)
-        args = (_lib.ptr(apre), _lib.ptr(c_hat), _lib.ptr(Wm), _lib.ptr(W2), _lib.ptr(b2), _lib.ptr(mem_all), _lib.ptr(u_all), _lib.ptr(g_all),
-                _lib.ptr(wsm), nbm, T, B, MD, HG, pg)
-        if isinstance(seed_g, _lib.DeviceSeed):
-            _lib.check(lib.mmt_mfn_mem_scan_forward_devseed(*args, seed_g.ptr(), _lib.stream_ptr()))
-        else:
-            _lib.check(lib.mmt_mfn_mem_scan_forward(*args, int(seed_g), _lib.stream_ptr()))
+        apre, ws_ap = _raw_linear_fwd(attended, Wa, b1, 0)
+        mem_all, u_all, g_all = _mem_scan_fwd(apre, c_hat, Wm, W2, b2, T, B, pg, seed_g)
         # [h of every modality ; mem]  (:241-243) and the read-out MLP (:244-246)
         last = _new(M, SH + MD, like=like)
         segs, col = [], 0
@@ -1039,35 +979,26 @@ class _MfnGateFn(torch.autograd.Function):
             col += H
         segs.append(_seg(last, SH + MD, M, MD, src=mem_all, src_ld=MD, dst_off=col))
         copy2d(segs)
-        hid, ws_o1, nb_o1 = _raw_linear_fwd(last, o1w, o1b, 1, None, 0.0, p_out, seed_out)
-        out, ws_o2, nb_o2 = _raw_linear_fwd(hid, o2w, o2b, 0)
-        if not any(ctx.needs_input_grad):               # inference: nothing is kept, the workspaces go straight back to the pool
-            for w in (ws_a11, ws_a12, ws_a21, ws_a22, ws_ap, ws_o1, ws_o2):
-                _lib.POOL.put(w)
-            ctx.k = None
-            return out.view(T, B, o2w.shape[0])
-        ctx.k = dict(nm=nm, T=T, B=B, Hs=Hs, SH=SH, MD=MD, HG=HG, A=A, pg=pg, p_out=p_out, seed_out=seed_out,
-                     P=P, c_star=c_star, a1=a1, att=att, attended=attended, a2=a2, c_hat=c_hat, Wa=Wa, Wm=Wm, W2=W2,
-                     mem_all=mem_all, u_all=u_all, g_all=g_all, last=last, hid=hid,
-                     ws=dict(a11=(ws_a11, nb_a11), a12=(ws_a12, nb_a12), a21=(ws_a21, nb_a21), a22=(ws_a22, nb_a22), ap=(ws_ap, nb_ap),
-                             o1=(ws_o1, nb_o1), o2=(ws_o2, nb_o2)))
+        hid, ws_o1 = _raw_linear_fwd(last, o1w, o1b, 1, None, 0.0, p_out, seed_out)
+        out, ws_o2 = _raw_linear_fwd(hid, o2w, o2b, 0)
+        if _hold(ctx, ws_a11, ws_a12, ws_a21, ws_a22, ws_ap, ws_o1, ws_o2):        # inference keeps nothing
+            ctx.k = dict(nm=nm, T=T, B=B, Hs=Hs, SH=SH, MD=MD, HG=HG, A=A, pg=pg, p_out=p_out, seed_out=seed_out,
+                         P=P, c_star=c_star, a1=a1, att=att, attended=attended, a2=a2, c_hat=c_hat, Wa=Wa, Wm=Wm, W2=W2,
+                         mem_all=mem_all, u_all=u_all, g_all=g_all, last=last, hid=hid)
         return out.view(T, B, o2w.shape[0])
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
-        k = ctx.k
-        if k is None:
-            raise RuntimeError("mfn_gate: backward called twice on the same forward (workspaces already released)")
-        ctx.k = None
+        ws_a11, ws_a12, ws_a21, ws_a22, ws_ap, ws_o1, ws_o2 = _take_ws(ctx, "mfn_gate")
+        k, ctx.k = ctx.k, None
         nm, T, B, Hs, SH, MD, HG, A = k["nm"], k["T"], k["B"], k["Hs"], k["SH"], k["MD"], k["HG"], k["A"]
         (a11w, a11b, a12w, a12b, a21w, a21b, a22w, a22b, g11w, g11b, g12w, g12b, g21w, g21b, g22w, g22b, o1w, o1b, o2w, o2b) = k["P"]
         M = T * B
-        st = _lib.stream_ptr()
         g = _f32c(dout).reshape(M, -1)
         like = g
-        d_hid, dWo2, dbo2 = _raw_linear_bwd(g, k["hid"], o2w, None, None, *k["ws"]["o2"], True, True, True)
-        d_last, dWo1, dbo1 = _raw_linear_bwd(d_hid, k["last"], o1w, k["hid"], None, *k["ws"]["o1"], True, True, True, 1, 0.0, k["p_out"], k["seed_out"])
+        d_hid, dWo2, dbo2 = _raw_linear_bwd(g, k["hid"], o2w, None, None, ws_o2, True, True, True)
+        d_last, dWo1, dbo1 = _raw_linear_bwd(d_hid, k["last"], o1w, k["hid"], None, ws_o1, True, True, True, 1, 0.0, k["p_out"],
+                                             k["seed_out"])
         d_hs = [_new(T, B, H, like=like) for H in Hs]
         d_mem = _new(M, MD, like=like)
         segs, col = [], 0
@@ -1076,41 +1007,16 @@ class _MfnGateFn(torch.autograd.Function):
             col += H
         segs.append(_seg(d_mem, MD, M, MD, src=d_last, src_ld=SH + MD, src_off=col))
         copy2d(segs)
-        # memory scan backward, then its batched weight gradients (window contractions)
-        nbm = lib.mmt_mfn_mem_scan_workspace_bytes()
-        wsm = torch.empty(nbm, dtype=torch.uint8, device=like.device)
-        d_chat, d_apre, dz = _new(M, MD, like=like), _new(M, 2 * HG, like=like), _new(M, 2 * MD, like=like)
-        _lib.check(lib.mmt_mfn_mem_scan_backward(_lib.ptr(d_mem), _lib.ptr(k["c_hat"]), _lib.ptr(k["mem_all"]), _lib.ptr(k["u_all"]), _lib.ptr(k["g_all"]),
-                                                 _lib.ptr(k["Wm"]), _lib.ptr(k["W2"]), _lib.ptr(d_chat), _lib.ptr(d_apre), _lib.ptr(dz), _lib.ptr(wsm), nbm,
-                                                 T, B, MD, HG, k["pg"], st))
-        mem_prev = _new(M, MD, like=like)
-        dzs, us = [_new(M, MD, like=like) for _ in range(2)], [_new(M, HG, like=like) for _ in range(2)]
-        segs = [_seg(mem_prev, MD, B, MD), _seg(mem_prev, MD, M - B, MD, src=k["mem_all"], src_ld=MD, dst_off=B * MD)]
-        for i in range(2):
-            segs += [_seg(dzs[i], MD, M, MD, src=dz, src_ld=2 * MD, src_off=i * MD), _seg(us[i], HG, M, HG, src=k["u_all"], src_ld=2 * HG, src_off=i * HG)]
-        copy2d(segs)
-
-        def wgrad(gg, xx, Wt, want_b):
-            """dW = gg^T xx (and db = column sums of gg) through the weight-gradient path of the affine map"""
-            Mm, Kk, Nn = xx.shape[0], xx.shape[1], gg.shape[1]
-            lb = lib.mmt_linear_workspace_bytes(Mm, Kk, Nn)
-            lws = _lib.POOL.get(lb, like.device, tag=("linear", Mm, Kk, Nn))
-            dW = _new(Nn, Kk, like=like)
-            db = _new(Nn, like=like) if want_b else None
-            _lib.check(lib.mmt_linear_backward(_lib.ptr(gg), _lib.ptr(xx), _lib.ptr(Wt), None, None, None, _lib.ptr(dW), _lib.ptr(db),
-                                               _lib.ptr(lws), lb, Mm, Kk, Nn, 0, st))
-            _lib.POOL.put(lws)
-            return dW, db
-        dWm, _ = wgrad(d_apre, mem_prev, k["Wm"], False)
-        dW2b2 = [wgrad(dzs[i], us[i], k["W2"][i], True) for i in range(2)]
-        d_att, dWa, db1 = _raw_linear_bwd(d_apre, k["attended"], k["Wa"], None, None, *k["ws"]["ap"], True, True, True)
-        d_a2, dWa22, dba22 = _raw_linear_bwd(d_chat, k["a2"], a22w, k["c_hat"], None, *k["ws"]["a22"], True, True, True, 2)
-        d_att2, dWa21, dba21 = _raw_linear_bwd(d_a2, k["attended"], a21w, k["a2"], None, *k["ws"]["a21"], True, True, True, 1)
+        d_apre, d_chat, dWm, dW2, db2s = _mem_scan_bwd(d_mem, k["c_hat"], k["Wm"], k["W2"], k["mem_all"], k["u_all"], k["g_all"], T, B,
+                                                      k["pg"])
+        d_att, dWa, db1 = _raw_linear_bwd(d_apre, k["attended"], k["Wa"], None, None, ws_ap, True, True, True)
+        d_a2, dWa22, dba22 = _raw_linear_bwd(d_chat, k["a2"], a22w, k["c_hat"], None, ws_a22, True, True, True, 2)
+        d_att2, dWa21, dba21 = _raw_linear_bwd(d_a2, k["attended"], a21w, k["a2"], None, ws_a21, True, True, True, 1)
         copy2d([_seg(d_att, A, M, A, src=d_att2, src_ld=A, acc=True)])                 # `attended` feeds att2_fc1 and both gamma fc1
         d_logits, d_cstar = torch.empty_like(d_att), torch.empty_like(d_att)
-        _lib.check(lib.mmt_softmax_mul_backward(_lib.ptr(d_att), _lib.ptr(k["att"]), _lib.ptr(k["c_star"]), _lib.ptr(d_logits), _lib.ptr(d_cstar), M, A, st))
-        d_a1, dWa12, dba12 = _raw_linear_bwd(d_logits, k["a1"], a12w, None, None, *k["ws"]["a12"], True, True, True)
-        d_cs2, dWa11, dba11 = _raw_linear_bwd(d_a1, k["c_star"], a11w, k["a1"], None, *k["ws"]["a11"], True, True, True, 1)
+        _lib.launch("mmt_softmax_mul_backward", d_att, k["att"], k["c_star"], d_logits, d_cstar, M, A)
+        d_a1, dWa12, dba12 = _raw_linear_bwd(d_logits, k["a1"], a12w, None, None, ws_a12, True, True, True)
+        d_cs2, dWa11, dba11 = _raw_linear_bwd(d_a1, k["c_star"], a11w, k["a1"], None, ws_a11, True, True, True, 1)
         # dc_t = d cStar[new part]_t + d cStar[prev part]_{t+1}; both cStar paths (att1 MLP input, the product) summed on the way
         d_cs = [_new(T, B, H, like=like) for H in Hs]
         segs, col = [], 0
@@ -1131,8 +1037,8 @@ class _MfnGateFn(torch.autograd.Function):
             segs += [_seg(dw, A + MD, HG, A, src=dWa, src_ld=A, src_off=i * HG * A),
                      _seg(dw, A + MD, HG, MD, src=dWm, src_ld=MD, src_off=i * HG * MD, dst_off=A),
                      _seg(db, HG, 1, HG, src=db1, src_ld=HG, src_off=i * HG),
-                     _seg(dw2, HG, MD, HG, src=dW2b2[i][0], src_ld=HG),
-                     _seg(db2, MD, 1, MD, src=dW2b2[i][1], src_ld=MD)]
+                     _seg(dw2, HG, MD, HG, src=dW2[i], src_ld=HG),
+                     _seg(db2, MD, 1, MD, src=db2s[i], src_ld=MD)]
         copy2d(segs)
         gp = (dWa11, dba11, dWa12, dba12, dWa21, dba21, dWa22, dba22, dg[0][0], dg[0][1], dg[0][2], dg[0][3],
               dg[1][0], dg[1][1], dg[1][2], dg[1][3], dWo1, dbo1, dWo2, dbo2)
@@ -1141,9 +1047,8 @@ class _MfnGateFn(torch.autograd.Function):
 
 def mfn_gate(hs, cs, params, gamma_dropout=0.0, gamma_seed=0, out_dropout=0.0, out_seed=0):
     """hs, cs: per-modality (T,B,H_m) LSTM states; params: the 20 gate tensors (see _MfnGateFn.NP) -> (T,B,output_dim)."""
-    def sd(v):
-        return v if isinstance(v, _lib.DeviceSeed) else int(v)
-    return _MfnGateFn.apply(len(hs), float(gamma_dropout), sd(gamma_seed), float(out_dropout), sd(out_seed), *hs, *cs, *params)
+    return _MfnGateFn.apply(len(hs), float(gamma_dropout), _seed_arg(gamma_seed), float(out_dropout), _seed_arg(out_seed),
+                            *hs, *cs, *params)
 
 
 def check_device_errors():
@@ -1153,17 +1058,14 @@ def check_device_errors():
 
 def poison_lds(device, pattern=0x7FC00000):
     """Test hook: leave `pattern` in every LDS word of every CU (see include/mmt_hip.h)."""
-    lib = _lib.load()
     sink = torch.zeros(1, dtype=torch.int32, device=device)
-    _lib.check(lib.mmt_debug_poison_lds(int(pattern), _lib.ptr(sink), _lib.stream_ptr()))
+    _lib.launch("mmt_debug_poison_lds", int(pattern), sink)
 
 
 def dropout_mask(p, seed, stream_id, n, device, attn_Tp=0):
     """Test hook: (keep mask as a bool tensor of n entries, scale of kept values) of one dropout stream."""
-    import ctypes
-    lib = _lib.load()
     keep = torch.empty(n, dtype=torch.uint8, device=device)
     sc = ctypes.c_float(0.0)
-    _lib.check(lib.mmt_debug_dropout_mask(float(p), int(seed), int(stream_id), int(n), int(attn_Tp), _lib.ptr(keep),
-                                          ctypes.cast(ctypes.pointer(sc), ctypes.c_void_p), _lib.stream_ptr()))
+    _lib.launch("mmt_debug_dropout_mask", float(p), int(seed), int(stream_id), int(n), int(attn_Tp), keep,
+                ctypes.cast(ctypes.pointer(sc), ctypes.c_void_p))
     return keep.bool(), float(sc.value)

@@ -18,7 +18,6 @@ def batched_ccc(pred, target, lengths):
     (transformer/SFT/train.py:236-238)."""
     import torch
     from . import _lib
-    lib = _lib.load()
     _lib.require_hip(pred, target)
     p_ = pred.detach().reshape(pred.shape[0], -1).contiguous().float()
     t_ = target.detach().reshape(target.shape[0], -1).contiguous().float()
@@ -29,5 +28,5 @@ def batched_ccc(pred, target, lengths):
         raise ValueError("batched_ccc: a length is outside [0, T]")
     ln = torch.as_tensor([int(L) for L in lengths], dtype=torch.int32).to(p_.device)
     out = torch.empty(B, dtype=torch.float64, device=p_.device)
-    _lib.check(lib.mmt_ccc_forward(_lib.ptr(p_), _lib.ptr(t_), _lib.ptr(ln), _lib.ptr(out), B, T, _lib.stream_ptr()))
+    _lib.launch("mmt_ccc_forward", p_, t_, ln, out, B, T)
     return out

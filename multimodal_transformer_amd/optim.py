@@ -94,7 +94,6 @@ class FlatAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib.load()
         for gi, group in enumerate(self.param_groups):
             live = [p for p in group["params"] if p.grad is not None]
             if not live:
@@ -116,6 +115,6 @@ class FlatAdam(torch.optim.Optimizer):
                 ms = arr(*[mb + 4 * plan["off"][id(q)] for q, _ in ranges])
                 vs = arr(*[vb + 4 * plan["off"][id(q)] for q, _ in ranges])
                 ns = (ctypes.c_size_t * nch)(*[n for _, n in ranges])
-                _lib.check(lib.mmt_adam_step(ps, gs, ms, vs, ns, nch, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                             float(group["weight_decay"]), s, _lib.stream_ptr()))
+                _lib.launch("mmt_adam_step", ps, gs, ms, vs, ns, nch, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                            float(group["weight_decay"]), s)
         return loss

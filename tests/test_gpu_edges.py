@@ -292,3 +292,38 @@ def test_results_do_not_depend_on_unwritten_lds(dev, d, h, B, T, p):
         for name, a, b in zip(("y", "dx", "dparams"), ref, cur):
             assert torch.isfinite(b).all(), "%s not finite after LDS was filled with %08x" % (name, pattern)
             assert torch.equal(a, b), "%s changed after LDS was filled with %08x" % (name, pattern)
+
+
+@pytest.mark.parametrize("op", ["sdpa", "linear", "linear_dropout", "linear_pair", "highway", "encoder_stack", "mfn_gate"])
+def test_second_backward_of_one_forward_raises(dev, op):
+    """a Function that keeps a pool workspace from its forward hands it back in its backward: a second backward of the same forward
+    (retain_graph=True) must raise a clear error before any launch instead of running on a workspace the pool may have reused"""
+    from multimodal_transformer_amd import multiTransformer as MT, functional as F
+    torch.manual_seed(5)
+    B, T, d, h = 2, 16, 128, 8
+
+    def leaf(*shape):
+        return (0.1 * torch.randn(*shape, device=dev)).requires_grad_()
+
+    x, mask = leaf(B, T, d), torch.ones(B, T, 1, device=dev)
+    if op == "sdpa":
+        y = F.sdpa(x, leaf(B, T, d), leaf(B, T, d), mask, h, dropout_p=0.1, seed=3)
+    elif op in ("linear", "linear_dropout"):
+        p = 0.1 if op == "linear_dropout" else 0.0
+        y = F.linear(x, leaf(64, d), leaf(64), act=1, in_dropout=p, out_dropout=p, seed=3)
+    elif op == "linear_pair":
+        y1, y2 = F.linear_pair(x, leaf(64, d), leaf(64), leaf(32, d), leaf(32), 1, 0)
+        y = y1.sum() + y2.sum()
+    elif op == "highway":
+        y = F.highway(x, leaf(d, d), leaf(d), leaf(d, d), leaf(d), dropout_p=0.3, seed=3)
+    elif op == "encoder_stack":
+        enc, _ = _encoder(d, h, 2, dev)
+        flat = torch.cat([q.reshape(-1) for q in enc.flat_parameters()]).detach().requires_grad_()
+        y = F.encoder_stack(x, mask, flat, h, R.D_FF, 2, dropout_p=0.1, seed=3)
+    else:
+        mfn = MT.MFN(R.MODS_AVL, {m: 256 for m in R.MODS_AVL}, 1, device=dev).to(dev).eval()
+        y = mfn({m: leaf(T, B, 256) for m in R.MODS_AVL})
+    y.sum().backward(retain_graph=True)
+    with pytest.raises(RuntimeError, match="backward called twice"):
+        y.sum().backward(retain_graph=True)
+    torch.cuda.synchronize()
