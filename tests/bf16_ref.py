@@ -1,0 +1,297 @@
+"""A bf16-faithful fp64 reference of the hot kernels (TEST INFRASTRUCTURE, a plain helper module).
+
+The plain references (``oracle.scaled_dot_attention``, ``oracle.encoder_stack`` and the fp64 affine map of the linear tests) carry no
+bf16, so a test against them has to absorb the whole error of the bf16 design.  The functions here take the same arguments plus
+``rounding``: with ``rounding=True`` they round to bf16 at every point where the kernels form a bf16 operand, with everything else in
+fp64 on the CPU; gradients come from torch autograd.  What is left between a kernel and this reference is fp32-vs-fp64 accumulation
+order, the hardware exp2 / log2 / reciprocal, and a few sites noted below that are not emulated.  With ``rounding=False`` every
+function is the plain reference again (tests/test_bf16_ref.py holds them to 1e-12).
+
+Two primitives place the roundings:
+  * ``round_fwd(t)``: bf16 round-to-nearest-even in the forward, straight-through in the backward;
+  * ``round_bwd(t)``: identity in the forward, rounds the incoming gradient to bf16 in the backward.
+
+Sites, read from the kernel sources (csrc/):
+  * weights: every prepared weight is bf16 (pad_cast_kernel);
+  * affine map (api.hip linear_*): A = bf16(drop_in(x)) (rowgemm staging, cast_rows_kernel), y = rowscale * drop_out(act(A W^T + b))
+    in fp32; the backward operand g = bf16(dy * rowscale * act' * 1/(1-p_out)) (grad_prep_kernel) -> dx = (g W) * drop_in' in fp32,
+    dW = g^T A, db = colsum(g);
+  * encoder layer: xn1 = bf16(LN1(x)), Q' = bf16((xn1 Wq^T + bq) log2(e)/sqrt(d_k)) with blanked query rows Q' = 0, K = bf16(.),
+    V = bf16(.) (rowgemm.h EPI_FRAG); ctx = bf16(.) (attn.h); x1 = x + drop(ctx Wo^T + bo) in fp32; xn2 = bf16(LN2(x1));
+    hid = bf16(drop(ReLU(xn2 W1^T + b1))) (EPI_PLAIN, KEEP_A2); x2 = x1 + drop(hid W2^T + b2); LayerNorm statistics, the residual
+    stream and the final LayerNorm in fp32;
+  * backward of a layer: the MFMA operands dx2 (into W2), dh (into W1), dx1 (into Wo), dO (= dctx, rowgemm.h EPI_FRAG with delta)
+    and dQKV are bf16; dQKV is formed by the attention kernels as bf16(dQ / sqrt(d_k)), bf16(ln2 dK'), bf16(dV);
+  * attention forward (attn_fwd_kernel): scores in the log2 domain, P = 2^(S' - m) relative to a LAZILY rescaled running maximum m
+    (MMT_RESCALE_THR: m moves only at the first key tile and when some query of the 32-query tile exceeds it by more than 8), P rounded
+    to bf16 (dropped entries zeroed) before P V, the normaliser l summing the fp32 P — except at d_k <= 16 in eval mode, where it sums
+    the bf16 P through the ones-row of the MFMA; ctx = bf16(O * (1/(1-p)) / l).  This is emulated tile by tile (``_attn_forward_value``);
+  * attention backward (attn.h dkv / dq kernels, attn_bwd_pair.h): P is recomputed from the stored L = m + log2 l, delta = rowsum(dO . ctx)
+    from the bf16 dO and the bf16 ctx (not sum_j P_j dP_j: the difference is coherent along a row, ~1e-2 of a dQ row), the recomputed P
+    (with the drop multiplier) is bf16 in dV = P^T dO, dS = P (dP - delta) is bf16 in dK and dQ (``_AttnCore``, an explicit backward).
+
+  * the one-kernel backward in train mode (attn_bwd_pair.h) rounds P m / c and dS / c, c = 1/(1-p), and scales the sums by c: a
+    different rounding of the same operands, but dQ = sum_j dS_j K_j cancels (sum_j dS_j = 0), so it moves dQ by ~3.5e-3 rel-L2.
+
+Not emulated: the fp32 hardware exp2 / log2, and the kernels' fp32 accumulation order.  The latter cannot be: fp32 noise (~1e-7) tips a
+few bf16 roundings to the other neighbour, a whole bf16 ulp of that element, and a tipped hidden pre-activation near 0 flips a ReLU mask.
+``jitter`` reproduces the effect on the reference itself (tests/test_bf16_ref.py test_fp32_noise_tips_bf16_roundings): at d = 256 it
+moves the stack's output by ~7e-4, dx by ~6e-3 and the FFN gradients by ~3e-2, the size of what remains between kernels and reference.
+"""
+import math
+
+import torch
+
+import oracle
+
+LOG2E = 1.4426950408889634
+LN2 = 0.6931471805599453
+RESCALE_THR = 8.0           # attn.h MMT_RESCALE_THR
+
+
+_JITTER = None      # (generator, relative size): see jitter()
+
+
+def bf16(t):
+    """bf16 round-to-nearest-even of an fp64 tensor, back in fp64 (no autograd)."""
+    if _JITTER is not None:
+        g, eps = _JITTER
+        t = t * (1 + eps * torch.randn(t.shape, generator=g, dtype=t.dtype))
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+class jitter:
+    """Within this context every value is perturbed by a relative `eps` (normal) just before it is rounded to bf16: what a different
+    fp32 accumulation order does to the kernels' values.  Two runs of the reference, with and without, measure how far apart two
+    equally correct implementations land when fp32 noise tips bf16 roundings (tests/test_bf16_ref.py)."""
+    def __init__(self, eps, seed=0):
+        self.eps, self.seed = eps, seed
+
+    def __enter__(self):
+        global _JITTER
+        _JITTER = (torch.Generator().manual_seed(self.seed), self.eps)
+
+    def __exit__(self, *a):
+        global _JITTER
+        _JITTER = None
+
+
+class _RoundFwd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t):
+        return bf16(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+class _RoundBwd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t):
+        return t.view_as(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return bf16(g)
+
+
+def round_fwd(t):
+    return _RoundFwd.apply(t)
+
+
+def round_bwd(t):
+    return _RoundBwd.apply(t)
+
+
+def _sites(rounding):
+    ident = (lambda t: t)
+    return (round_fwd, round_bwd) if rounding else (ident, ident)
+
+
+# ------------------------------------------------------------------------------------------------ affine map
+def linear(x, W, b=None, act=0, rowscale=None, in_drop=None, out_drop=None, rounding=True):
+    """y = rowscale * out_drop * act(in_drop * x W^T + b), act 0 (none) or 1 (ReLU); in_drop / out_drop are dropout multipliers
+    shaped like x / y.  The plain form is the one of test_linear and test_linear_fused_dropout_replay."""
+    rf, rb = _sites(rounding)
+    xa = x * in_drop if in_drop is not None else x
+    y = rf(xa) @ rf(W).t()
+    if b is not None:
+        y = y + b
+    y = rb(y)
+    if act == 1:
+        y = torch.relu(y)
+    elif act != 0:
+        raise NotImplementedError("bf16_ref.linear: act %d" % act)
+    if out_drop is not None:
+        y = y * out_drop
+    if rowscale is not None:
+        y = y * rowscale.reshape(-1, *([1] * (y.dim() - 1)))
+    return y
+
+
+# ------------------------------------------------------------------------------------------------ attention core
+def _attn_forward_value(Qp, K, V, prob_drop, ones_rowsum):
+    """The forward value of attn_fwd_kernel from the bf16 operands Q' (log2 domain), K, V: (B, h, T, d_k) fp64 -> ctx before its final
+    rounding.  Query tiles of 32 rows share one rescale decision (one wave); key tiles of 32 are swept in order."""
+    with torch.no_grad():
+        B, h, T, dk = Qp.shape
+        nt = -(-T // 32)
+        Tp = nt * 32
+        Qpad = torch.zeros(B, h, Tp, dk, dtype=Qp.dtype)
+        Qpad[:, :, :T] = Qp                                    # query rows >= T exist in the last tile, as Q' = 0
+        S = Qpad @ K.transpose(-2, -1)                         # (B, h, Tp, T), log2 domain
+        St = S.reshape(B, h, nt, 32, T)
+        ms = []
+        for kt in range(nt):
+            tile = St[..., 32 * kt: min(T, 32 * kt + 32)]
+            tmax = tile.amax(dim=-1)                           # (B, h, nt, 32)
+            if kt == 0:
+                m = tmax
+            else:
+                rel = tmax - m
+                move = (rel > RESCALE_THR).any(dim=-1, keepdim=True)      # __any over the wave's 32 queries
+                m = torch.where(move, m + rel.clamp(min=0.0), m)
+            ms.append(m)
+        keep = None
+        if prob_drop is not None:
+            keep = torch.zeros(B, h, Tp, T, dtype=Qp.dtype)
+            keep[:, :, :T] = (prob_drop != 0).to(Qp.dtype).expand(B, h, T, T)
+            keep = keep.reshape(B, h, nt, 32, T)
+        P, Pb = torch.empty_like(St), torch.empty_like(St)
+        for kt in range(nt):
+            c0, c1 = 32 * kt, min(T, 32 * kt + 32)
+            p = torch.exp2(St[..., c0:c1] - ms[kt].unsqueeze(-1))          # what the tile rounds, relative to the maximum of its time
+            pk = p if keep is None else p * keep[..., c0:c1]
+            alpha = torch.exp2(ms[kt] - ms[-1]).unsqueeze(-1)              # the later rescales of o and l (fp32, after the rounding)
+            P[..., c0:c1] = p * alpha
+            Pb[..., c0:c1] = bf16(pk) * alpha
+        P = P.reshape(B, h, Tp, T)[:, :, :T]
+        Pb = Pb.reshape(B, h, Tp, T)[:, :, :T]
+        l = (Pb if ones_rowsum else P).sum(dim=-1, keepdim=True)
+        L = ms[-1].reshape(B, h, Tp)[:, :, :T].unsqueeze(-1) + torch.log2(l)        # the row constant the backward recomputes P from
+        if prob_drop is None:
+            return (Pb @ V) / l, L
+        scale = float(prob_drop.max())
+        return (Pb @ V) * (scale / l), L
+
+
+class _AttnCore(torch.autograd.Function):
+    """ctx = attention(Q', K, V) on the bf16 operands: the forward kernel's value (rounded), the backward kernels' gradients.
+    Backward (attn.h attn_bwd_dkv_kernel / attn_bwd_dq_kernel): dO = bf16(dctx); P = 2^(S' - L) recomputed; dP = dO V^T;
+    delta = rowsum(dO . ctx) from the bf16 ctx; dS = P (dP m - delta) with m the drop multiplier; dV = bf16(P m)^T dO;
+    dK' = ln2 bf16(dS)^T Q'; dQ' = ln2 bf16(dS) K."""
+    @staticmethod
+    def forward(ctx, Qp, K, V, prob_drop, ones_rowsum, fold_drop):
+        val, L = _attn_forward_value(Qp, K, V, prob_drop, ones_rowsum)
+        out = bf16(val)
+        ctx.save_for_backward(Qp, K, V, out, L)
+        ctx.prob_drop, ctx.fold_drop = prob_drop, fold_drop
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        Qp, K, V, out, L = ctx.saved_tensors
+        dO = bf16(dout)
+        P = torch.exp2(Qp @ K.transpose(-2, -1) - L)
+        dP = dO @ V.transpose(-2, -1)
+        delta = (dO * out).sum(dim=-1, keepdim=True)
+        md = ctx.prob_drop
+        dS = P * ((dP if md is None else dP * md) - delta)
+        Pd = P if md is None else P * md
+        if ctx.fold_drop:           # attn_bwd_pair.h in train mode rounds P m / c and dS / c (c = 1/(1-p)), and scales the sums by c
+            c = float(md.max())
+            Pdr, dSr = bf16(Pd / c) * c, bf16(dS / c) * c
+        else:
+            Pdr, dSr = bf16(Pd), bf16(dS)
+        dV = Pdr.transpose(-2, -1) @ dO
+        return LN2 * (dSr @ K), LN2 * (dSr.transpose(-2, -1) @ Qp), dV, None, None, None
+
+
+def one_kernel_bwd(dk, T):
+    """Whether the attention backward runs as ONE kernel (attn_bwd_pair.h attn_bwd_fused_ok: d_k <= 16, 9..16 key tiles)."""
+    return -(-dk // 16) * 16 == 16 and 8 < -(-T // 32) <= 16
+
+
+def _attention(q_lin, k_lin, v_lin, row_keep, prob_drop, rounding, fused_attn_bwd=True):
+    """q_lin, k_lin, v_lin: (B, h, T, d_k) as their producers form them (before Q's softmax scale); row_keep (B, 1, T, 1) or None.
+    -> ctx (B, h, T, d_k).  With rounding=False this is oracle.scaled_dot_attention (a blanked row as Q' = 0 soft-maxes to the same
+    uniform row as the reference's -1e9 and passes no gradient to q)."""
+    rf, rb = _sites(rounding)
+    dk = q_lin.shape[-1]
+    Qs = rb(q_lin) * (LOG2E / math.sqrt(dk))
+    if row_keep is not None:
+        Qs = Qs * row_keep
+    Qp, K, V = rf(Qs), rf(rb(k_lin)), rf(rb(v_lin))
+    if rounding:
+        fold = prob_drop is not None and fused_attn_bwd and one_kernel_bwd(dk, Qp.shape[-2])
+        return _AttnCore.apply(Qp, K, V, prob_drop, -(-dk // 16) * 16 == 16 and prob_drop is None, fold)
+    P = torch.softmax((Qp @ K.transpose(-2, -1)) * LN2, dim=-1)
+    if prob_drop is not None:
+        P = P * prob_drop
+    return P @ V
+
+
+def sdpa(q, k, v, row_mask=None, prob_drop=None, rounding=True, fused_attn_bwd=True):
+    """Same arguments as oracle.scaled_dot_attention (q, k, v: (B, h, T, d_k); row_mask (B, 1, T, 1)) -> (ctx, None).
+    Emulates the stand-alone attention (mmt_sdpa_*): Q' = bf16(q log2(e)/sqrt(d_k)), K, V, dq, dk, dv all bf16.
+    fused_attn_bwd=False: the two-kernel backward (MMT_NO_FUSED_ATTN_BWD=1) where the one-kernel backward would run."""
+    keep = None if row_mask is None else (row_mask != 0).to(q.dtype)
+    return _attention(q, k, v, keep, prob_drop, rounding, fused_attn_bwd), None
+
+
+# ------------------------------------------------------------------------------------------------ encoder stack
+def _affine(p, name, x, rf):
+    return x @ rf(p[name + ".weight"]).transpose(0, 1) + p[name + ".bias"]
+
+
+def encoder_layer(p, prefix, x, mask, h, drops=None, rounding=True, fused_attn_bwd=True):
+    rf, rb = _sites(rounding)
+    dr = drops or {}
+    B, T, d = x.shape
+    dk = d // h
+    row_keep = None if mask is None else (mask.unsqueeze(1) != 0).to(x.dtype)
+
+    def split(z):
+        return z.reshape(B, T, h, dk).permute(0, 2, 1, 3)
+
+    n0 = rf(oracle.layer_norm(x, p[prefix + "sublayer.0.norm.a_2"], p[prefix + "sublayer.0.norm.b_2"]))
+    a = prefix + "self_attn.linears."
+    q, k, v = (split(_affine(p, a + str(i), n0, rf)) for i in range(3))
+    ctx = _attention(q, k, v, row_keep, dr.get("attn"), rounding, fused_attn_bwd)
+    merged = ctx.permute(0, 2, 1, 3).reshape(B, T, d)
+    o = _affine(p, a + "3", merged, rf)
+    o = rb(o * dr["sub0"] if "sub0" in dr else o)               # dx1 (into Wo) is a bf16 operand
+    x = x + o
+    n1 = rf(oracle.layer_norm(x, p[prefix + "sublayer.1.norm.a_2"], p[prefix + "sublayer.1.norm.b_2"]))
+    f = prefix + "feed_forward."
+    hid = torch.relu(rb(_affine(p, f + "w_1", n1, rf)))         # dh (into W1) is a bf16 operand
+    if "ffn" in dr:
+        hid = hid * dr["ffn"]
+    y = _affine(p, f + "w_2", rf(hid), rf)
+    y = rb(y * dr["sub1"] if "sub1" in dr else y)               # dx2 (into W2) is a bf16 operand
+    return x + y
+
+
+def encoder_stack(p, prefix, x, mask, h, drops=None, rounding=True, fused_attn_bwd=True):
+    """Same arguments as oracle.encoder_stack."""
+    for i in range(oracle.count_layers(p, prefix)):
+        x = encoder_layer(p, "%slayers.%d." % (prefix, i), x, mask, h, None if drops is None else drops[i], rounding, fused_attn_bwd)
+    return oracle.layer_norm(x, p[prefix + "norm.a_2"], p[prefix + "norm.b_2"])
+
+
+def encoder_param_shapes(d, d_ff, n):
+    """{state_dict name: shape} of an n-layer encoder, in the order of Encoder.flat_parameters() (the fused stack's flat buffer)."""
+    s = {}
+    for i in range(n):
+        L = "layers.%d." % i
+        for j in range(4):
+            s[L + "self_attn.linears.%d.weight" % j] = (d, d)
+            s[L + "self_attn.linears.%d.bias" % j] = (d,)
+        s[L + "feed_forward.w_1.weight"], s[L + "feed_forward.w_1.bias"] = (d_ff, d), (d_ff,)
+        s[L + "feed_forward.w_2.weight"], s[L + "feed_forward.w_2.bias"] = (d, d_ff), (d,)
+        for j in range(2):
+            s[L + "sublayer.%d.norm.a_2" % j] = (d,)
+            s[L + "sublayer.%d.norm.b_2" % j] = (d,)
+    s["norm.a_2"], s["norm.b_2"] = (d,), (d,)
+    return s

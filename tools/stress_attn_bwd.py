@@ -2,7 +2,9 @@
 """Developer tool: the one-kernel attention backward (attn_bwd_pair.h) against the two-kernel path (MMT_NO_FUSED_ATTN_BWD=1) over many
 sequence lengths of its range (257..512: every tile count 9..16, ragged and full last tiles), ragged batches, d_k = 16 and a padded
 head (d_k = 10), with and without dropout.  Two child processes (the switch is read once per process); the same seeds give the same
-masks, so the two paths compute the same gradients up to bf16 rounding of differently ordered sums."""
+masks, so the two paths compute the same gradients up to bf16 rounding of differently ordered sums.
+The suite's check of the same pair is tests/test_gpu_bf16_faithful.py::test_sdpa (both paths against the bf16-faithful reference and
+against each other); this tool sweeps many more lengths."""
 import os
 import subprocess
 import sys
