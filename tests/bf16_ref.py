@@ -33,7 +33,19 @@ Sites, read from the kernel sources (csrc/):
   * the one-kernel backward in train mode (attn_bwd_pair.h) rounds P m / c and dS / c, c = 1/(1-p), and scales the sums by c: a
     different rounding of the same operands, but dQ = sum_j dS_j K_j cancels (sum_j dS_j = 0), so it moves dQ by ~3.5e-3 rel-L2.
 
-Not emulated: the fp32 hardware exp2 / log2, and the kernels' fp32 accumulation order.  The latter cannot be: fp32 noise (~1e-7) tips a
+  * LSTM scan forward (scan_units.h:58,125, scan256.h:61,122, scan_cluster.h:89,140, scan.h:80,137): the MFMA operands bf16(h_{t-1})
+    (h0 included) and bf16(W_rec); gx, the gate pre-activations and activations, c and the stored h are fp32.  Backward
+    (scan_units.h:249, scan256.h:227, scan_cluster.h:252, scan.h:227): the recurrent product dh_{t-1} = bf16(dG_t) W_rec; dgx = dG in
+    fp32; dW_rec = bf16(dG)^T bf16(h_prev) (functional._wgrad).  One line places all of it (``lstm_scan``):
+        pre_t = gx_t + round_bwd(round_fwd(h_{t-1}) @ round_fwd(W_rec)^T);
+  * MFN memory scan forward (scan.h:302-387 and the _sw twins): u = drop(ReLU(apre + bf16(mem) bf16(Wm)^T)), z_g = bf16(u_g) bf16(W2_g)^T
+    + b2_g, mem = sigmoid(z_1) mem + sigmoid(z_2) chat; mem and everything written stays fp32.  Backward: du = bf16(dz) W2, dmem
+    from bf16(dapre) Wm; dapre, dchat and dz are fp32; dWm, dW2 and db2 go through _wgrad, which rounds its operand, so
+    db2 = colsum(bf16(dz)) (``mfn_mem_scan``: the bias sits inside round_bwd).
+
+Not emulated: the fp32 hardware exp2 / log2 / reciprocal (the scans' sigmoid_f / tanh_f, scan.h:15-16; tanh_f(x) = 2 sigmoid(2x) - 1 loses
+relative accuracy near 0, about 6e-8 absolute, so every measure of the scans is per row, never per element), and the kernels' fp32
+accumulation order.  The latter cannot be: fp32 noise (~1e-7) tips a
 few bf16 roundings to the other neighbour, a whole bf16 ulp of that element, and a tipped hidden pre-activation near 0 flips a ReLU mask.
 ``jitter`` reproduces the effect on the reference itself (tests/test_bf16_ref.py test_fp32_noise_tips_bf16_roundings): at d = 256 it
 moves the stack's output by ~7e-4, dx by ~6e-3 and the FFN gradients by ~3e-2, the size of what remains between kernels and reference.
@@ -295,3 +307,58 @@ def encoder_param_shapes(d, d_ff, n):
             s[L + "sublayer.%d.norm.b_2" % j] = (d,)
     s["norm.a_2"], s["norm.b_2"] = (d,), (d,)
     return s
+
+
+# ------------------------------------------------------------------------------------------------ scans
+def lstm_scan(gx, W, h0=None, c0=None, rounding=True, mutate=None):
+    """Same arguments as functional.lstm_scan: gx (T, B, 4H) = x W_ih^T + b_ih + b_hh, W (4H, H), h0 / c0 (B, H) or None (zeros), gate
+    order i, f, g, o -> (h_all, c_all), each (T, B, H).  With rounding=False it is the oracle.lstm_cell loop.
+    mutate (tests only): {"h": f(t, h_{t-1}) -> what step t multiplies, "c": f(t, c_{t-1}) -> what step t carries}."""
+    rf, rb = _sites(rounding)
+    m = mutate or {}
+    T, B, H4 = gx.shape
+    H = H4 // 4
+    h = h0 if h0 is not None else gx.new_zeros(B, H)
+    c = c0 if c0 is not None else gx.new_zeros(B, H)
+    Wr = rf(W).t()
+    hs, cs = [], []
+    for t in range(T):
+        hin = m["h"](t, h) if "h" in m else h
+        cin = m["c"](t, c) if "c" in m else c
+        pre = gx[t] + rb(rf(hin) @ Wr)
+        i, f = torch.sigmoid(pre[:, :H]), torch.sigmoid(pre[:, H:2 * H])
+        g, o = torch.tanh(pre[:, 2 * H:3 * H]), torch.sigmoid(pre[:, 3 * H:])
+        c = f * cin + i * g
+        h = o * torch.tanh(c)
+        hs.append(h)
+        cs.append(c)
+    return torch.stack(hs), torch.stack(cs)
+
+
+def mfn_mem_scan(apre, chat, Wm, W2, b2, drop=None, rounding=True, mutate=None):
+    """Same arguments as functional.mfn_mem_scan, the dropout given as its multiplier: apre (T, B, 2HG) = the batched part of both gamma
+    fc1 layers, chat (T, B, MD), Wm (2HG, MD), W2 (2, MD, HG), b2 (2, MD), drop (T, B, 2HG) or None -> mem_all (T, B, MD).  With
+    rounding=False it is the plain memory recurrence (test_gpu_models._oracle_mem_scan).
+    mutate (tests only): {"u": f(t, relu(pre), drop_t) -> u, "z": f(t, g, product, b2_g) -> z_g}."""
+    rf, rb = _sites(rounding)
+    m = mutate or {}
+    T, B, U = apre.shape
+    HG = W2.shape[-1]
+    mem = apre.new_zeros(B, chat.shape[-1])
+    Wmr, W2r = rf(Wm).t(), [rf(W2[g]).t() for g in range(2)]
+    out = []
+    for t in range(T):
+        r = torch.relu(apre[t] + rb(rf(mem) @ Wmr))
+        dt = None if drop is None else drop[t]
+        if "u" in m:
+            u = m["u"](t, r, dt)
+        else:
+            u = r if dt is None else r * dt
+        ur = rf(u)
+        z = []
+        for g in range(2):
+            prod = ur[:, g * HG:(g + 1) * HG] @ W2r[g]
+            z.append(m["z"](t, g, prod, b2[g]) if "z" in m else rb(prod + b2[g]))
+        mem = torch.sigmoid(z[0]) * mem + torch.sigmoid(z[1]) * chat[t]
+        out.append(mem)
+    return torch.stack(out)

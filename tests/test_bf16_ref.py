@@ -196,3 +196,215 @@ def test_fp32_noise_tips_bf16_roundings():
     with E.jitter(0.0, 1):                                      # the hook itself changes nothing
         yc, _, _ = _run_enc(E.encoder_stack, p32, x, g, mask, h, None)
     assert torch.equal(yc, ya)
+
+
+# ------------------------------------------------------------------------------------------ scans
+def _lstm_inputs(T, B, H, init, tag):
+    gx = R.gen_normal(tag + "gx", (T, B, 4 * H), 3)
+    W = R.gen_normal(tag + "w", (4 * H, H), 3) / np.sqrt(H)
+    h0 = 0.5 * R.gen_normal(tag + "h0", (B, H), 3) if init else None
+    c0 = 0.5 * R.gen_normal(tag + "c0", (B, H), 3) if init else None
+    gh, gc = R.gen_normal(tag + "gh", (T, B, H), 3), R.gen_normal(tag + "gc", (T, B, H), 3)
+    return gx, W, h0, c0, gh, gc
+
+
+def _run_lstm(fn, inputs, **kw):
+    gx, W, h0, c0, gh, gc = inputs
+    leaves = [None if t is None else t.double().clone().requires_grad_() for t in (gx, W, h0, c0)]
+    h, c = fn(*leaves, **kw)
+    ((h * gh.double()).sum() + (c * gc.double()).sum()).backward()
+    out = {"h": h.detach(), "c": c.detach(), "dgx": leaves[0].grad, "dW": leaves[1].grad}
+    if h0 is not None:
+        out["dh0"], out["dc0"] = leaves[2].grad, leaves[3].grad
+    return out
+
+
+def _mfn_inputs(T, B, tag):
+    apre = R.gen_normal(tag + "a", (T, B, 128), 3)
+    chat = torch.tanh(R.gen_normal(tag + "c", (T, B, 128), 3))
+    Wm = R.gen_normal(tag + "wm", (128, 128), 3) / np.sqrt(128)
+    W2 = R.gen_normal(tag + "w2", (2, 128, 64), 3) / 8
+    b2 = 0.1 * R.gen_normal(tag + "b2", (2, 128), 3)
+    return apre, chat, Wm, W2, b2, R.gen_normal(tag + "g", (T, B, 128), 3)
+
+
+def _run_mfn(fn, inputs, **kw):
+    *args, g = inputs
+    leaves = [t.double().clone().requires_grad_() for t in args]
+    mem = fn(*leaves, **kw)
+    (mem * g.double()).sum().backward()
+    return dict(zip(("mem", "dapre", "dchat", "dWm", "dW2", "db2"), [mem.detach()] + [t.grad for t in leaves]))
+
+
+def _mfn_drop(T, B, p, tag):
+    return (R.gen_uniform(tag + "drop", (T, B, 128), 3) > p).double() / (1 - p)
+
+
+@pytest.mark.parametrize("init", [False, True])
+def test_lstm_scan_without_rounding_is_the_oracle_loop(init):
+    from test_gpu_models import _oracle_lstm
+    inputs = _lstm_inputs(7, 5, 20, init, "e_lstm")
+    a = _run_lstm(E.lstm_scan, inputs, rounding=False)
+    b = _run_lstm(_oracle_lstm, inputs)
+    for k in b:
+        assert _rel(a[k], b[k]) <= 1e-12, k
+
+
+@pytest.mark.parametrize("drop", [False, True])
+def test_mfn_mem_scan_without_rounding_is_the_plain_recurrence(drop):
+    from test_gpu_models import _oracle_mem_scan
+    T, B = 6, 3
+    inputs = _mfn_inputs(T, B, "e_mfn")
+    d = _mfn_drop(T, B, 0.2, "e_mfn") if drop else None
+    a = _run_mfn(E.mfn_mem_scan, inputs, drop=d, rounding=False)
+    b = _run_mfn(_oracle_mem_scan, inputs, drop=d)
+    for k in b:
+        assert _rel(a[k], b[k]) <= 1e-12, k
+
+
+def _lstm_case(cid):
+    import test_gpu_bf16_scans as S
+    return next(c for c in S.LSTM_CASES if c["id"] == cid)
+
+
+def test_scan_jitter_floor():
+    """The floor of the scan bounds in test_gpu_bf16_scans.py: how far fp32-level noise (half an fp32 ulp before every bf16 rounding)
+    moves the reference from itself at the long shapes of that file.  Tipped bf16(h) roundings feed back through the recurrence, so the
+    distance is also reported per time step.  Every bound there must sit at or above this floor."""
+    import test_gpu_bf16_scans as S
+    from test_gpu_bf16_faithful import measures
+    lstm_b = {"h": S.LSTM_OUT, "c": S.LSTM_OUT, "dgx": S.LSTM_DGX, "dW": S.LSTM_DW, "dh0": S.LSTM_D0, "dc0": S.LSTM_D0}
+    t0 = time.time()
+    for cid in ("l_T1000_B3_H48_i_hc", "l_T1000_B2_H88_n_hc", "l_T1000_B2_H256_i_hc"):
+        c = _lstm_case(cid)
+        a = S.lstm_ref(c)
+        S._LSTM_REFS.pop(cid)
+        with E.jitter(6e-8, 1):
+            b = S.lstm_ref(c)
+        S._LSTM_REFS.pop(cid)
+        for k in a:
+            rel, row = measures(b[k], a[k])
+            seq = S.seq_max(b[k], a[k]) if a[k].ndim == 3 else 0.0
+            print("jitter floor %s %-4s rel-L2 %.2e  row-max %.2e  seq-max %.2e" % (cid, k, rel, row, seq))
+            bd = lstm_b[k]
+            assert rel <= bd[0] and row <= bd[1] and (a[k].ndim != 3 or seq <= bd[2]), (cid, k)
+        if "dW" in a:
+            assert abs(S.ls_scale(b["dW"], a["dW"])) <= S.LSTM_W_SCALE
+        d = np.linalg.norm((b["h"] - a["h"]).reshape(c["T"], -1), axis=1) / np.linalg.norm(a["h"].reshape(c["T"], -1), axis=1)
+        print("jitter floor %s h per step: t < 10 %.1e, t < 100 %.1e, t < 1000 %.1e" % (cid, d[:10].max(), d[:100].max(), d.max()))
+    for cid in ("m_T1000_B2_p0", "m_T300_B33_p0"):
+        c = next(x for x in S.MFN_CASES if x["id"] == cid)
+        inputs = S.mfn_inputs(c)
+        a = _run_mfn(E.mfn_mem_scan, inputs)
+        with E.jitter(6e-8, 1):
+            b = _run_mfn(E.mfn_mem_scan, inputs)
+        bds = S.mfn_bounds(c)
+        for k in a:
+            ga, gb = a[k].numpy(), b[k].numpy()
+            if k == "db2":
+                ga, gb = ga.ravel(), gb.ravel()
+            rel, row = measures(gb, ga)
+            seq = S.seq_max(gb, ga) if k in ("mem", "dapre", "dchat") else 0.0
+            print("jitter floor %s %-5s rel-L2 %.2e  row-max %.2e  seq-max %.2e" % (cid, k, rel, row, seq))
+            bd = bds[k]
+            assert rel <= bd[0] and (bd[1] is None or row <= bd[1]) and (len(bd) < 3 or seq <= bd[2]), (cid, k)
+        d = np.linalg.norm((b["mem"] - a["mem"]).numpy().reshape(c["T"], -1), axis=1)
+        d /= np.linalg.norm(a["mem"].numpy().reshape(c["T"], -1), axis=1)
+        print("jitter floor %s mem per step: t < 10 %.1e, t < 100 %.1e, t < %d %.1e" % (cid, d[:10].max(), d[:100].max(), c["T"], d.max()))
+    print("%.1f s" % (time.time() - t0))
+
+
+# Mutations of the reference itself, each a subtle kernel bug: each must exceed the bound test_gpu_bf16_scans.py applies, on the
+# measure meant to catch it, so those bounds see such a bug without a broken kernel ever running.
+def _mut_stale(inputs):
+    hist = {}
+
+    def h(t, x):                    # sequence 3 multiplies h_{t-2} instead of h_{t-1} at step 10: a one-step-stale exchange
+        hist[t] = x
+        if t != 10:
+            return x
+        x = x.clone()
+        x[3] = hist[9][3]
+        return x
+    return _run_lstm(E.lstm_scan, inputs, mutate={"h": h})
+
+
+def _mut_ragged_tile(inputs):
+    gx, W, h0, c0, gh, gc = inputs
+    H = W.shape[1]
+    last = (H - 1) // 16 * 16        # the last, ragged 16-unit tile: rows q H + u of every gate q, u >= last
+    Wt = W.clone()
+    for q in range(4):
+        Wt[q * H + last:(q + 1) * H] *= 1.01
+    return _run_lstm(E.lstm_scan, (gx, Wt, h0, c0, gh, gc))
+
+
+def _mut_dc_carry(inputs):           # the dc carry from step 10 back to c_9 dropped
+    return _run_lstm(E.lstm_scan, inputs, mutate={"c": lambda t, c: c.detach() if t == 10 else c})
+
+
+def _mut_dh0(inputs):
+    """dh0 without the contribution of step 0: the recurrent gradient of step 1 (the loop stops one step early)"""
+    kept = {}
+
+    def h(t, x):
+        if t == 1:
+            kept["h"] = x + 0.0
+            kept["h"].retain_grad()
+            return kept["h"]
+        return x
+    out = _run_lstm(E.lstm_scan, inputs, mutate={"h": h})
+    out["dh0"] = kept["h"].grad
+    return out
+
+
+def _mut_relu_mask(T, B, p, tag):
+    drop = _mfn_drop(T, B, p, tag)
+    sc = 1 / (1 - p)
+
+    def u(t, r, d):                  # relu' taken from the pre-dropout value: dropped units pass their gradient (scaled) on
+        return r * sc - (r * (sc - d)).detach()
+    return _run_mfn(E.mfn_mem_scan, _mfn_inputs(T, B, tag), drop=drop, mutate={"u": u}), drop
+
+
+def _mut_db2(T, B, tag):             # db2 summed from the unrounded dz
+    return _run_mfn(E.mfn_mem_scan, _mfn_inputs(T, B, tag), mutate={"z": lambda t, g, prod, b: E.round_bwd(prod) + b})
+
+
+_LSTM_MUTANTS = [("stale_exchange", _mut_stale, (20, 5, 256), "h", 1), ("stale_exchange_seq", _mut_stale, (20, 5, 256), "h", 2),
+                 ("ragged_tile", _mut_ragged_tile, (13, 5, 20), "h", 1), ("ragged_tile_rel", _mut_ragged_tile, (13, 5, 20), "h", 0),
+                 ("dc_carry", _mut_dc_carry, (20, 5, 48), "dgx", 1), ("dh0_step0", _mut_dh0, (20, 5, 88), "dh0", 1)]
+
+
+@pytest.mark.parametrize("name,mut,shape,tensor,measure", _LSTM_MUTANTS, ids=[m[0] for m in _LSTM_MUTANTS])
+def test_lstm_scan_bounds_see_a_mutant(name, mut, shape, tensor, measure):
+    """measure: 0 rel-L2, 1 per-row maximum, 2 per-sequence maximum, against the bound of test_gpu_bf16_scans.py"""
+    import test_gpu_bf16_scans as S
+    from test_gpu_bf16_faithful import measures
+    inputs = _lstm_inputs(*shape, True, "e_mut_" + name)
+    ref = _run_lstm(E.lstm_scan, inputs)
+    got = mut(inputs)
+    g, r = got[tensor].numpy(), ref[tensor].numpy()
+    m = (measures(g, r) + (S.seq_max(g, r) if r.ndim == 3 else None,))[measure]
+    bound = {"h": S.LSTM_OUT, "dgx": S.LSTM_DGX, "dh0": S.LSTM_D0}[tensor][measure]
+    print("mutant %s: %s %s %.3e (bound %.1e)" % (name, tensor, ("rel-L2", "row-max", "seq-max")[measure], m, bound))
+    assert m > bound
+
+
+def test_mfn_mem_scan_bounds_see_a_mutant():
+    import test_gpu_bf16_scans as S
+    from test_gpu_bf16_faithful import measures
+    T, B, p = 5, 17, 0.2                                   # a short-tier case of test_gpu_bf16_scans.py
+    got, drop = _mut_relu_mask(T, B, p, "e_mut_relu")
+    ref = _run_mfn(E.mfn_mem_scan, _mfn_inputs(T, B, "e_mut_relu"), drop=drop)
+    row = measures(got["dapre"].numpy(), ref["dapre"].numpy())[1]
+    print("mutant relu' before dropout: dapre row-max %.3e (bound %.1e)" % (row, S.MFN_SHORT["dapre"][1]))
+    assert row > S.MFN_SHORT["dapre"][1]
+    T, B = 3, 1                                            # an exact-tier case
+    got = _mut_db2(T, B, "e_mut_db2")
+    ref = _run_mfn(E.mfn_mem_scan, _mfn_inputs(T, B, "e_mut_db2"))
+    row = measures(got["db2"].numpy().ravel(), ref["db2"].numpy().ravel())[1]
+    print("mutant db2 from the unrounded dz: db2 row-max %.3e (bound %.1e)" % (row, S.MFN_EXACT["db2"][1]))
+    assert row > S.MFN_EXACT["db2"][1]
+    for k in ("mem", "dapre", "dchat", "dWm", "dW2"):     # nothing else moves: only the bias's own gradient is summed differently
+        assert torch.equal(got[k], ref[k]), k
