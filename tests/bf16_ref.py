@@ -43,8 +43,23 @@ Sites, read from the kernel sources (csrc/):
     from bf16(dapre) Wm; dapre, dchat and dz are fp32; dWm, dW2 and db2 go through _wgrad, which rounds its operand, so
     db2 = colsum(bf16(dz)) (``mfn_mem_scan``: the bias sits inside round_bwd).
 
+  * window encoder forward (convpool.h): weights bf16 (convpool_prep_kernel, :43), the raw rows bf16 while staging (:103-107); the sums
+    S[n, p, f] = bf16(x)[n, p] . bf16(w)[f, :, 0] + bf16(x)[n, p+1] . bf16(w)[f, :, 1] in fp32; the pool takes the FIRST maximum (:169
+    inside a lane, :173 across the two lane halves, :175 across row tiles: strictly greater replaces) over positions < W - 1 (:168);
+    the bias is added after the pool, in fp32 (:188).  Backward (convpool_bwd_kernel): dW[f, d, j] = sum_n bf16(dy[n, f])
+    bf16(x[n, arg + j, d]) (:312 the one-hot A operand, :264-272 the transposed rows), db[f] = sum_n dy[n, f] from the UNROUNDED dy
+    (:299).  ``conv_maxpool`` places it in one line: out = round_bwd(gather(S, arg)) + b;
+  * tanh / sigmoid epilogues of the affine map (rowgemm.h:387-392): on the fp32 sum + bias, output fp32.  The backward takes act' from
+    the SAVED fp32 OUTPUT (api.hip grad_prep_kernel :1000-1001: 1 - y^2, y (1 - y)), multiplies in fp32 and rounds once:
+    g = bf16(dy * rowscale * act'(y)), the same place as the ReLU's, so ``linear`` keeps its one round_bwd in front of the activation;
+  * Highway (functional._HighwayFn, glue.h:97-125): proj = linear(x, act 0 or 1), gate = linear(x, act 3), both fp32;
+    out = drop * (x + gate * (proj - x)) in fp32 from the UNROUNDED x (:105); backward g = drop * dout, dx = g (1 - gate), dproj = g gate,
+    dgate = g (proj - x) in fp32 (:122); dproj and dgate become bf16 operands inside the two affine backwards (grad_prep_kernel),
+    dx sums the three fp32 paths (copy2d).  ``linear_pair`` is two affine maps of one input, dx their fp32 sum.
+
 Not emulated: the fp32 hardware exp2 / log2 / reciprocal (the scans' sigmoid_f / tanh_f, scan.h:15-16; tanh_f(x) = 2 sigmoid(2x) - 1 loses
-relative accuracy near 0, about 6e-8 absolute, so every measure of the scans is per row, never per element), and the kernels' fp32
+relative accuracy near 0, about 6e-8 absolute, so every measure of the scans is per row, never per element; the affine map's tanh and
+sigmoid epilogues are the same two formulas), and the kernels' fp32
 accumulation order.  The latter cannot be: fp32 noise (~1e-7) tips a
 few bf16 roundings to the other neighbour, a whole bf16 ulp of that element, and a tipped hidden pre-activation near 0 flips a ReLU mask.
 ``jitter`` reproduces the effect on the reference itself (tests/test_bf16_ref.py test_fp32_noise_tips_bf16_roundings): at d = 256 it
@@ -62,6 +77,7 @@ RESCALE_THR = 8.0           # attn.h MMT_RESCALE_THR
 
 
 _JITTER = None      # (generator, relative size): see jitter()
+_JITTER_INPUTS = True
 
 
 def bf16(t):
@@ -75,17 +91,19 @@ def bf16(t):
 class jitter:
     """Within this context every value is perturbed by a relative `eps` (normal) just before it is rounded to bf16: what a different
     fp32 accumulation order does to the kernels' values.  Two runs of the reference, with and without, measure how far apart two
-    equally correct implementations land when fp32 noise tips bf16 roundings (tests/test_bf16_ref.py)."""
-    def __init__(self, eps, seed=0):
-        self.eps, self.seed = eps, seed
+    equally correct implementations land when fp32 noise tips bf16 roundings (tests/test_bf16_ref.py).
+    inputs=False: ``linear`` rounds its x and W unperturbed, as for a stand-alone affine map or Highway, whose x and W are given fp32
+    data with the same bf16 value in every implementation; only computed values (the backward's operands) are perturbed."""
+    def __init__(self, eps, seed=0, inputs=True):
+        self.eps, self.seed, self.inputs = eps, seed, inputs
 
     def __enter__(self):
-        global _JITTER
-        _JITTER = (torch.Generator().manual_seed(self.seed), self.eps)
+        global _JITTER, _JITTER_INPUTS
+        _JITTER, _JITTER_INPUTS = (torch.Generator().manual_seed(self.seed), self.eps), self.inputs
 
     def __exit__(self, *a):
-        global _JITTER
-        _JITTER = None
+        global _JITTER, _JITTER_INPUTS
+        _JITTER, _JITTER_INPUTS = None, True
 
 
 class _RoundFwd(torch.autograd.Function):
@@ -122,17 +140,26 @@ def _sites(rounding):
 
 
 # ------------------------------------------------------------------------------------------------ affine map
-def linear(x, W, b=None, act=0, rowscale=None, in_drop=None, out_drop=None, rounding=True):
-    """y = rowscale * out_drop * act(in_drop * x W^T + b), act 0 (none) or 1 (ReLU); in_drop / out_drop are dropout multipliers
-    shaped like x / y.  The plain form is the one of test_linear and test_linear_fused_dropout_replay."""
+def linear(x, W, b=None, act=0, rowscale=None, in_drop=None, out_drop=None, rounding=True, mutate=None):
+    """y = rowscale * out_drop * act(in_drop * x W^T + b), act 0 (none), 1 (ReLU), 2 (tanh) or 3 (sigmoid); in_drop / out_drop are
+    dropout multipliers shaped like x / y.  The plain form is the one of test_linear and test_linear_fused_dropout_replay.
+    mutate (tests only): {"act": f(pre) -> y in place of the activation}."""
     rf, rb = _sites(rounding)
     xa = x * in_drop if in_drop is not None else x
+    if rounding and not _JITTER_INPUTS:
+        rf = _RoundInput.apply
     y = rf(xa) @ rf(W).t()
     if b is not None:
         y = y + b
-    y = rb(y)
-    if act == 1:
+    y = rb(y)                                                   # g = bf16(dy * rowscale * act'): one rounding, in front of the activation
+    if mutate and "act" in mutate:
+        y = mutate["act"](y)
+    elif act == 1:
         y = torch.relu(y)
+    elif act == 2:
+        y = torch.tanh(y)
+    elif act == 3:
+        y = torch.sigmoid(y)
     elif act != 0:
         raise NotImplementedError("bf16_ref.linear: act %d" % act)
     if out_drop is not None:
@@ -362,3 +389,125 @@ def mfn_mem_scan(apre, chat, Wm, W2, b2, drop=None, rounding=True, mutate=None):
         mem = torch.sigmoid(z[0]) * mem + torch.sigmoid(z[1]) * chat[t]
         out.append(mem)
     return torch.stack(out)
+
+
+# ------------------------------------------------------------------------------------------------ window encoder
+def conv_plan(N, W, D, F):
+    """What mmt_convpool_forward / _backward launch for (N, W, D, F): a mirror of carve_conv and of the forward's channel dispatch
+    (csrc/api.hip).  nsplit window splits of `wins` windows (the last one `last` windows), npairs window pairs in the fullest split,
+    nrt row tiles per window, one_rt the backward instance, fwd the forward launches as (CT, channel blocks, c_first)."""
+    up = lambda a, m: -(-a // m) * m  # noqa: E731
+    FPAD, DPB = up(F, 256), up(D, 128)
+    blocks = (DPB // 128) * (FPAD // 256)
+    ns = max(1, min(-(-512 // blocks), (N + 1) // 2))
+    wins = up(-(-N // ns), 2)
+    nsplit = -(-N // wins)
+    last = N - (nsplit - 1) * wins
+    nmain, rem = F // 256, F % 256
+    fwd = [(4, nmain, 0)] if nmain else []
+    if rem > 128:
+        fwd.append((4, 1, nmain * 256))
+    elif rem > 64:
+        fwd.append((2, 1, nmain * 256))
+    elif rem > 0:
+        fwd.append((1, 1, nmain * 256))
+    return {"nsplit": nsplit, "wins": wins, "last": last, "npairs": (min(wins, N) + 1) // 2, "nrt": -(-(W - 1) // 32), "one_rt": W <= 33,
+            "fwd": fwd, "fwd_wgs": -(-N // 8)}
+
+
+class _MapBwd(torch.autograd.Function):
+    """identity in the forward, fn(gradient) in the backward"""
+    @staticmethod
+    def forward(ctx, t, fn):
+        ctx.fn = fn
+        return t.view_as(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.fn(g), None
+
+
+def _exact_bf16(t):
+    """bf16 of an INPUT (no jitter: the rounding of given fp32 data is the same in every implementation)"""
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+class _RoundInput(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t):
+        return _exact_bf16(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+def conv_sums(x, w, rounding=True):
+    """S (N, W-1, F) without the bias, and per (n, p, f) the sum of |terms| (for the fp32 dot-product bound), no autograd"""
+    with torch.no_grad():
+        xr, wr = (_exact_bf16(x), _exact_bf16(w)) if rounding else (x, w)
+        S = xr[:, :-1] @ wr[:, :, 0].t() + xr[:, 1:] @ wr[:, :, 1].t()
+        A = xr[:, :-1].abs() @ wr[:, :, 0].abs().t() + xr[:, 1:].abs() @ wr[:, :, 1].abs().t()
+    return S, A
+
+
+def conv_maxpool(x, w, b, arg=None, rounding=True, mutate=None):
+    """Same arguments as functional.conv_maxpool (x (N, W, D), w (F, D, 2), b (F,)) -> (out (N, F), arg (N, F), S (N, W-1, F) without
+    the bias).  arg given: the pool gathers at those positions, so autograd yields the exact gradient for that choice (the kernel's own).
+    With rounding=False: oracle.cnn_maxpool.  Under ``jitter`` the operands are NOT perturbed (x and w are inputs: their bf16 values are
+    the same in every implementation); the sums are, by eps * sqrt(2D) * sqrt(sum of the squared terms) (normal): the random-walk size
+    of an fp32 accumulation of 2D terms, 3-4x what an fp32 matmul in another order shows against fp64 on the CPU.
+    mutate (tests only): {"tap": f(j, rows (N, W-1, D), w_j (F, D)) -> the tap's product, "S": f(S, xr, wr) -> S (may add positions),
+    "pool": f(S) -> arg, "gathered": f(pooled sums) -> the same, "b": f(b) -> b, "round_dy": f(dy) -> the backward's dy operand}."""
+    m = mutate or {}
+    rin = _RoundInput.apply if rounding else (lambda t: t)
+    xr, wr = rin(x), rin(w)
+    S = 0
+    for j in range(2):
+        rows, wj = xr[:, j:j + x.shape[1] - 1], wr[:, :, j]
+        S = S + (m["tap"](j, rows, wj) if "tap" in m else rows @ wj.t())
+    if "S" in m:
+        S = m["S"](S, xr, wr)
+    if _JITTER is not None:
+        g, eps = _JITTER
+        with torch.no_grad():
+            sq = (xr[:, :-1] ** 2) @ (wr[:, :, 0] ** 2).t() + (xr[:, 1:] ** 2) @ (wr[:, :, 1] ** 2).t()
+            noise = eps * math.sqrt(2 * x.shape[2]) * sq.sqrt() * torch.randn(sq.shape, generator=g, dtype=sq.dtype)
+        S = S + noise
+    if arg is None:
+        arg = m["pool"](S.detach()) if "pool" in m else S.detach().argmax(dim=1)      # argmax: the first position of the maximum
+    pooled = S.gather(1, arg.long().unsqueeze(1)).squeeze(1)
+    if "gathered" in m:
+        pooled = m["gathered"](pooled)
+    if rounding:
+        pooled = _MapBwd.apply(pooled, m["round_dy"]) if "round_dy" in m else round_bwd(pooled)      # dW from bf16(dy), db from dy
+    out = pooled + (m["b"](b) if "b" in m else b)
+    return out, arg, S.detach()
+
+
+def highway(x, Wp, bp, Wg, bg, drop=None, proj_act=0, rounding=True, mutate=None):
+    """Same arguments as functional.highway, the dropout given as its multiplier (shaped like x): drop * (x + gate * (proj - x)),
+    proj = act(x Wp^T + bp) (proj_act 0, or 1: the B1 variant's ReLU), gate = sigmoid(x Wg^T + bg).  With rounding=False: oracle.highway.
+    mutate (tests only): {"combine": f(x, proj, gate) -> the combine before the dropout, "gate_act": f(pre) -> gate}."""
+    m = mutate or {}
+    proj = linear(x, Wp, bp, act=proj_act, rounding=rounding)
+    gate = linear(x, Wg, bg, act=3, rounding=rounding, mutate={"act": m["gate_act"]} if "gate_act" in m else None)
+    y = m["combine"](x, proj, gate) if "combine" in m else x + gate * (proj - x)
+    return y if drop is None else y * drop
+
+
+def linear_pair(x, W1, b1, W2, b2, act1=0, act2=0, rounding=True):
+    """Same arguments as functional.linear_pair: two affine maps of one input; autograd sums the two fp32 gradients into x."""
+    return linear(x, W1, b1, act=act1, rounding=rounding), linear(x, W2, b2, act=act2, rounding=rounding)
+
+
+def window_encoder(p, mod, x, drop=None, arg=None, proj_act=0, rounding=True):
+    """Same arguments as oracle.window_encoder (p: {state_dict name: tensor}, x (B, T, W, D), drop (B*T, F) or None) -> ((B, T, F), arg):
+    conv + pool, Highway, dropout multiplier, as models._FrontEnd._encode chains them for one modality.  The Highway's fp32 dx is the
+    conv's dy."""
+    B, T, W, D = x.shape
+    e, arg, _ = conv_maxpool(x.reshape(B * T, W, D), p["cnn_%s.conv1d.weight" % mod], p["cnn_%s.conv1d.bias" % mod], arg, rounding)
+    h = "highway_%s." % mod
+    y = highway(e, p[h + "linear_projection.weight"], p[h + "linear_projection.bias"], p[h + "linear_gate.weight"],
+                p[h + "linear_gate.bias"], drop, proj_act, rounding)
+    return y.reshape(B, T, -1), arg

@@ -408,3 +408,401 @@ def test_mfn_mem_scan_bounds_see_a_mutant():
     assert row > S.MFN_EXACT["db2"][1]
     for k in ("mem", "dapre", "dchat", "dWm", "dW2"):     # nothing else moves: only the bias's own gradient is summed differently
         assert torch.equal(got[k], ref[k]), k
+
+
+# ------------------------------------------------------------------------------------------ window encoder (front end)
+def _conv_small(N=23, W=9, D=20, F=37, tag="e_conv"):
+    x = R.gen_normal(tag + "x", (N, W, D), 4)
+    w = R.gen_normal(tag + "w", (F, D, 2), 4) / np.sqrt(2 * D)
+    b = 0.1 * R.gen_normal(tag + "b", (F,), 4)
+    return x, w, b, R.gen_normal(tag + "g", (N, F), 4)
+
+
+def _run_conv(x, w, b, g, **kw):
+    wl, bl = w.double().clone().requires_grad_(), b.double().clone().requires_grad_()
+    out, arg, S = E.conv_maxpool(x.double(), wl, bl, **kw)
+    out.backward(g.double())
+    return {"out": out.detach(), "arg": arg, "S": S, "dW": wl.grad, "db": bl.grad}
+
+
+def test_conv_maxpool_without_rounding_is_the_oracle():
+    from test_gpu_frontend import _conv_fp64
+    x, w, b, g = _conv_small()
+    a = _run_conv(x, w, b, g, rounding=False)
+    wl, bl = w.double().requires_grad_(), b.double().requires_grad_()
+    out, arg = oracle.cnn_maxpool(x.double(), wl, bl)
+    out.backward(g.double())
+    assert _rel(a["out"], out) <= 1e-12 and torch.equal(a["arg"], arg)
+    assert _rel(a["dW"], wl.grad) <= 1e-12 and _rel(a["db"], bl.grad) <= 1e-12
+    y = _conv_fp64(x, w, b)
+    assert _rel(a["out"], y.max(dim=1).values) <= 1e-12 and _rel(a["S"] + b.double(), y) <= 1e-12
+    # a given argmax is gathered, whatever it is: the gradient of that choice
+    other = (arg + 1) % (x.shape[1] - 1)
+    c = _run_conv(x, w, b, g, arg=other, rounding=False)
+    assert _rel(c["out"], y.gather(1, other.unsqueeze(1)).squeeze(1)) <= 1e-12
+    # with rounding on: dW from bf16(dy) and bf16(x) rows at the argmax, db from the unrounded dy
+    r = _run_conv(x, w, b, g)
+    xr, gr = E.bf16(x.double()), E.bf16(g.double())
+    n_idx = torch.arange(x.shape[0]).unsqueeze(1).expand_as(r["arg"])
+    for j in range(2):
+        assert _rel(r["dW"][:, :, j], (gr.unsqueeze(2) * xr[n_idx, r["arg"] + j]).sum(dim=0)) <= 1e-12
+    assert _rel(r["db"], g.double().sum(0)) <= 1e-12 and not torch.equal(gr, g.double())
+
+
+@pytest.mark.parametrize("act", [2, 3])
+def test_linear_tanh_sigmoid_without_rounding_is_the_plain_map(act):
+    M, K, N = 37, 43, 29
+    x, W, b, g = (R.gen_normal("e_lin" + n, s, 2) for n, s in (("x", (M, K)), ("W", (N, K)), ("b", (N,)), ("g", (M, N))))
+    r = (R.gen_uniform("e_lin_r", (M,), 2) > 0.3).double()
+    la = [t.double().requires_grad_() for t in (x, W, b)]
+    E.linear(*la, act=act, rowscale=r, rounding=False).backward(g.double())
+    lb = [t.double().requires_grad_() for t in (x, W, b)]
+    pre = lb[0] @ lb[1].t() + lb[2]
+    ((torch.tanh(pre) if act == 2 else torch.sigmoid(pre)) * r[:, None]).backward(g.double())
+    for a, c in zip(_grads(la), _grads(lb)):
+        assert _rel(a, c) <= 1e-12
+    # with rounding on, the backward's operand is ONE rounding of dy * rowscale * act'(y): db is its column sum
+    lc = [t.double().requires_grad_() for t in (x, W, b)]
+    y = E.linear(*lc, act=act, rowscale=r)
+    y.backward(g.double())
+    yy = (y.detach() / r[:, None]).nan_to_num()
+    dact = 1 - yy * yy if act == 2 else yy * (1 - yy)
+    assert _rel(lc[2].grad, E.bf16(g.double() * r[:, None] * dact).sum(0)) <= 1e-12
+
+
+def _hw_params(n, tag):
+    names = ("linear_projection.weight", "linear_projection.bias", "linear_gate.weight", "linear_gate.bias")
+    return R.gen_params({k: ((n, n) if k.endswith("weight") else (n,)) for k in names}, 4), names
+
+
+@pytest.mark.parametrize("drop", [False, True])
+@pytest.mark.parametrize("proj_act", [0, 1])
+def test_highway_without_rounding_is_the_oracle(proj_act, drop):
+    rows, n = 11, 44
+    p32, names = _hw_params(n, "e_hw")
+    x, g = R.gen_normal("e_hw:x", (rows, n), 4), R.gen_normal("e_hw:g", (rows, n), 4)
+    d = (R.gen_uniform("e_hw:d", (rows, n), 4) > 0.3).double() / 0.7 if drop else None
+    la = [x.double().requires_grad_()] + [p32[k].double().requires_grad_() for k in names]
+    E.highway(*la, drop=d, proj_act=proj_act, rounding=False).backward(g.double())
+    pd = {k: v.double().requires_grad_() for k, v in p32.items()}
+    xd = x.double().requires_grad_()
+    if proj_act == 0:
+        ref = oracle.highway(pd, "", xd)
+    else:                                                       # the B1 variant: ReLU on the projection
+        gate = torch.sigmoid(xd @ pd[names[2]].t() + pd[names[3]])
+        ref = gate * torch.relu(xd @ pd[names[0]].t() + pd[names[1]]) + (1 - gate) * xd
+    ref = ref if d is None else ref * d
+    ref.backward(g.double())
+    for a, c in zip(_grads(la), [xd.grad] + [pd[k].grad for k in names]):
+        assert _rel(a, c) <= 1e-12
+
+
+def test_linear_pair_without_rounding_is_two_plain_maps():
+    M, K = 13, 20
+    x, W1, b1, W2, b2, g1, g2 = (R.gen_normal("e_pair" + n, s, 4) for n, s in (("x", (M, K)), ("w1", (9, K)), ("b1", (9,)), ("w2", (31, K)),
+                                                                                  ("b2", (31,)), ("g1", (M, 9)), ("g2", (M, 31))))
+    la = [t.double().requires_grad_() for t in (x, W1, b1, W2, b2)]
+    y1, y2 = E.linear_pair(*la, act1=1, act2=0, rounding=False)
+    ((y1 * g1.double()).sum() + (y2 * g2.double()).sum()).backward()
+    lb = [t.double().requires_grad_() for t in (x, W1, b1, W2, b2)]
+    r1, r2 = torch.relu(lb[0] @ lb[1].t() + lb[2]), lb[0] @ lb[3].t() + lb[4]
+    ((r1 * g1.double()).sum() + (r2 * g2.double()).sum()).backward()
+    assert _rel(y1, r1) <= 1e-12 and _rel(y2, r2) <= 1e-12
+    for a, c in zip(_grads(la), _grads(lb)):
+        assert _rel(a, c) <= 1e-12
+
+
+def _chain_params(mod, Fo, D, seed=4):
+    h = "highway_%s." % mod
+    return R.gen_params({"cnn_%s.conv1d.weight" % mod: (Fo, D, 2), "cnn_%s.conv1d.bias" % mod: (Fo,), h + "linear_projection.weight": (Fo, Fo),
+                         h + "linear_projection.bias": (Fo,), h + "linear_gate.weight": (Fo, Fo), h + "linear_gate.bias": (Fo,)}, seed)
+
+
+@pytest.mark.parametrize("drop", [False, True])
+def test_window_encoder_without_rounding_is_the_oracle(drop):
+    mod, Fo, D, B, T, W = "acoustic", 44, 24, 2, 7, 6
+    p32 = _chain_params(mod, Fo, D)
+    x, g = R.gen_normal("e_we:x", (B, T, W, D), 4), R.gen_normal("e_we:g", (B, T, Fo), 4)
+    d = (R.gen_uniform("e_we:d", (B * T, Fo), 4) > 0.3).double() / 0.7 if drop else None
+    pa = {k: v.double().requires_grad_() for k, v in p32.items()}
+    ya, _ = E.window_encoder(pa, mod, x.double(), d, rounding=False)
+    ya.backward(g.double())
+    pb = {k: v.double().requires_grad_() for k, v in p32.items()}
+    yb = oracle.window_encoder(pb, mod, x.double(), d)
+    yb.backward(g.double())
+    assert _rel(ya, yb) <= 1e-12
+    for k in pb:
+        assert _rel(pa[k].grad, pb[k].grad) <= 1e-12, k
+
+
+# The plan of every conv case of tests/test_gpu_bf16_frontend.py, from reading carve_conv and mmt_convpool_forward (csrc/api.hip):
+# (wins, pairs in the fullest split, splits, windows of the last split, ONE_RT, row tiles, forward launches (CT, blocks, c_first))
+_PLANS = {
+    (3001, 10, 88, 256): (6, 3, 501, 1, True, 1, [(4, 1, 0)]),
+    (331, 30, 1000, 256): (6, 3, 56, 1, True, 1, [(4, 1, 0)]),
+    (600, 33, 300, 300): (8, 4, 75, 8, True, 1, [(4, 1, 0), (1, 1, 256)]),
+    (4000, 9, 20, 20): (8, 4, 500, 8, True, 1, [(1, 1, 0)]),
+    (2100, 70, 24, 32): (6, 3, 350, 6, False, 3, [(1, 1, 0)]),
+    (2565, 10, 88, 256): (6, 3, 428, 3, True, 1, [(4, 1, 0)]),
+    (2565, 12, 88, 256): (6, 3, 428, 3, True, 1, [(4, 1, 0)]),
+    (21, 12, 88, 256): (2, 1, 11, 1, True, 1, [(4, 1, 0)]),
+    (21, 40, 40, 64): (2, 1, 11, 1, False, 2, [(1, 1, 0)]),
+    (40, 40, 40, 64): (2, 1, 20, 2, False, 2, [(1, 1, 0)]),
+    (24, 3, 40, 64): (2, 1, 12, 2, True, 1, [(1, 1, 0)]),
+    (24, 34, 40, 64): (2, 1, 12, 2, False, 2, [(1, 1, 0)]),
+}
+for _W, _nrt in ((2, 1), (33, 1), (34, 2), (65, 2), (66, 3)):
+    _PLANS[(9, _W, 40, 64)] = (2, 1, 5, 1, _W <= 33, _nrt, [(1, 1, 0)])
+    _PLANS[(2565, _W, 40, 64)] = (6, 3, 428, 3, _W <= 33, _nrt, [(1, 1, 0)])
+for _N, _ns in ((1, 1), (7, 4), (8, 4), (9, 5)):
+    _PLANS[(_N, 10, 88, 256)] = (2, 1, _ns, 2 - _N % 2, True, 1, [(4, 1, 0)])
+for _F, _fwd in ((20, [(1, 1, 0)]), (64, [(1, 1, 0)]), (65, [(2, 1, 0)]), (128, [(2, 1, 0)]), (129, [(4, 1, 0)]), (200, [(4, 1, 0)]),
+                 (256, [(4, 1, 0)]), (300, [(4, 1, 0), (1, 1, 256)]), (330, [(4, 1, 0), (2, 1, 256)]), (450, [(4, 1, 0), (4, 1, 256)]),
+                 (600, [(4, 2, 0), (2, 1, 512)])):
+    _PLANS[(37, 7, 52, _F)] = (2, 1, 19, 1, True, 1, _fwd)
+for _D in (4, 20, 28, 32, 36, 128, 132, 260):
+    _PLANS[(37, 7, _D, 70)] = (2, 1, 19, 1, True, 1, [(2, 1, 0)])
+
+
+def test_conv_plan_of_every_gpu_case():
+    import test_gpu_bf16_frontend as FE
+    seen = set()
+    for c in FE.CONV_CASES:
+        key = (c["N"], c["W"], c["D"], c["F"])
+        pl = E.conv_plan(*key)
+        assert key in _PLANS, "no pinned plan for %s" % c["id"]
+        want = _PLANS[key]
+        got = (pl["wins"], pl["npairs"], pl["nsplit"], pl["last"], pl["one_rt"], pl["nrt"], pl["fwd"])
+        assert got == want, (c["id"], got, want)
+        seen.add(key)
+    assert seen == set(_PLANS)
+    plans = [E.conv_plan(c["N"], c["W"], c["D"], c["F"]) for c in FE.CONV_CASES]
+    # what the file is for: ONE_RT with >= 3 pairs, several row tiles with >= 3 pairs, <4> at a non-zero c_first, <2>, <1>, an odd last split
+    assert any(p["one_rt"] and p["npairs"] >= 3 for p in plans) and any(not p["one_rt"] and p["npairs"] >= 3 for p in plans)
+    assert any((4, 1, 256) in p["fwd"] for p in plans) and any(p["fwd"] == [(4, 1, 0)] for p in plans)
+    assert any(ct == 2 for p in plans for ct, _, _ in p["fwd"]) and any(ct == 1 for p in plans for ct, _, _ in p["fwd"])
+    assert any(p["last"] == 1 and p["wins"] > 2 for p in plans) and any(p["last"] == 3 for p in plans)
+    for mod, Fo, B, T in FE.CHAIN_CASES:
+        pl = E.conv_plan(B * T, R.FE_WINDOW[mod], R.FE_DIMS[mod], Fo)
+        assert pl["one_rt"] and pl["npairs"] >= 3, (mod, Fo, pl)
+
+
+def test_conv_tie_cases_tie_in_the_reference():
+    """The constructed ties of test_gpu_bf16_frontend.py are exact in the reference too: bit-identical sums at the tied positions, the
+    first of them the argmax, and the tied pair the maximum of a useful number of (window, channel) pairs."""
+    import test_gpu_bf16_frontend as FE
+    for c in FE.CONV_CASES:
+        if not c["kind"].startswith("tie"):
+            continue
+        x, w, b, g = FE.conv_inputs(c)
+        S, _ = E.conv_sums(x.double(), w.double())
+        arg = S.argmax(dim=1)
+        if c["kind"] == "tie_const":
+            assert bool((S == S[:, :1]).all()) and int(arg.max()) == 0
+        elif c["kind"] == "tie_pad":
+            W = c["W"]
+            assert bool((S[:, W - 2] == 0).all())
+            n = int((arg == W - 2).sum())
+            print("%s: the zero sum of the last position is the maximum of %d pairs" % (c["id"], n))
+            assert n == arg.numel()
+        else:
+            for res, (p, q) in FE.tie_positions(c).items():
+                assert torch.equal(S[res::2, p], S[res::2, q])
+                n = int((arg[res::2] == p).sum())
+                print("%s: windows %d mod 2, positions %d = %d are the maximum of %d pairs" % (c["id"], res, p, q, n))
+                assert n > 100 and int((arg[res::2] == q).sum()) == 0
+
+
+def _hw_run(rows, n, tag, proj_act=0, drop=None, **kw):
+    import test_gpu_bf16_frontend as FE
+    *args, g = FE.hw_inputs(rows, n, tag)
+    ld = [t.double().requires_grad_() for t in args]
+    y = E.highway(*ld, drop=drop, proj_act=proj_act, **kw)
+    y.backward(g.double())
+    return [y.detach()] + [t.grad for t in ld]
+
+
+def test_frontend_jitter_floor():
+    """The floor of the bounds in test_gpu_bf16_frontend.py: what fp32-level noise (half an fp32 ulp before every bf16 rounding; on the
+    conv's sums the random-walk size of a 2D-term fp32 accumulation, see bf16_ref.conv_maxpool) does to the reference itself.
+    The conv's argmax must change in at most ARG_SHARE of the pairs for the file's own inputs (per case and over the file): that is the
+    condition under which the cap holds.  The Highway's, the tanh / sigmoid map's and the chain's measures must stay within the bounds."""
+    import test_gpu_bf16_frontend as FE
+    from test_gpu_bf16_faithful import measures
+    t0 = time.time()
+    nd = tot = 0
+    for c in FE.CONV_CASES:
+        if c["kind"].startswith("tie"):
+            continue
+        x, w, b, g = FE.conv_inputs(c)
+        _, a0, _ = E.conv_maxpool(x.double(), w.double(), b.double())
+        with E.jitter(6e-8, 1):
+            _, a1, _ = E.conv_maxpool(x.double(), w.double(), b.double())
+        d = int((a0 != a1).sum())
+        print("jitter floor conv %-34s argmax changes in %d of %d pairs (%.1e)" % (c["id"], d, a0.numel(), d / a0.numel()))
+        assert d <= max(FE.ARG_SHARE * a0.numel(), 0 if a0.numel() >= 10000 else 1), c["id"]
+        nd, tot = nd + d, tot + a0.numel()
+    print("jitter floor conv: %d of %d pairs over the file (%.1e)" % (nd, tot, nd / tot))
+    assert nd <= FE.ARG_SHARE * tot
+    for rows, n in ((3001, 256), (600, 300), (500, 20)):
+        for proj_act in (0, 1):
+            a = _hw_run(rows, n, "bffe_hw%dx%d" % (rows, n), proj_act)
+            with E.jitter(6e-8, 1, inputs=False):              # stand-alone: x and the weights are given data
+                b_ = _hw_run(rows, n, "bffe_hw%dx%d" % (rows, n), proj_act)
+            for k, u, v in zip(("y",) + FE.HW_NAMES, b_, a):
+                rel, row = measures(u.numpy(), v.numpy())
+                print("jitter floor highway %dx%d a%d %-4s rel-L2 %.2e  row-max %.2e" % (rows, n, proj_act, k, rel, row))
+                bd = FE.HW_OUT if k == "y" else FE.HW_GRAD
+                assert rel <= bd[0] and row <= bd[1], (rows, n, k)
+            for i in (2, 4):
+                assert abs(FE.ls_scale(b_[i].numpy(), a[i].numpy())) <= FE.HW_W_SCALE
+    M, K, N = 200, 576, 129
+    x, W, b, g = FE._lin_inputs(M, K, N, "bffe_lin%dx%dx%d" % (M, K, N))
+    for act in (2, 3):
+        res = []
+        for jit in (False, True):
+            ld = [t.double().requires_grad_() for t in (x, W, b)]
+            if jit:
+                with E.jitter(6e-8, 1, inputs=False):
+                    y = E.linear(*ld, act=act)
+                    y.backward(g.double())
+            else:
+                y = E.linear(*ld, act=act)
+                y.backward(g.double())
+            res.append([y.detach()] + [t.grad for t in ld])
+        for k, u, v in zip(("y", "dx", "dW", "db"), res[1], res[0]):
+            rel, row = measures(u.numpy(), v.numpy())
+            print("jitter floor linear act %d %-3s rel-L2 %.2e  row-max %.2e" % (act, k, rel, row))
+            bd = FE.LIN_ACT_OUT if k == "y" else FE.LIN_ACT_GRAD
+            assert rel <= bd[0] and row <= bd[1], (act, k)
+    mod, Fo, B, T = "acoustic", 88, 5, 513
+    p32 = _chain_params(mod, Fo, R.FE_DIMS[mod], 37)
+    x = R.gen_normal("bffe_chain:%s%d:x" % (mod, Fo), (B, T, R.FE_WINDOW[mod], R.FE_DIMS[mod]), 37)
+    g = R.gen_normal("bffe_chain:%s%d:g" % (mod, Fo), (B, T, Fo), 37)
+    res = []
+    for jit in (False, True):
+        pd = {k: v.double().requires_grad_() for k, v in p32.items()}
+        if jit:
+            with E.jitter(6e-8, 1):
+                y, arg = E.window_encoder(pd, mod, x.double(), arg=res[0][1])
+                y.backward(g.double())
+        else:
+            y, arg = E.window_encoder(pd, mod, x.double())
+            y.backward(g.double())
+        res.append((y.detach(), arg, {k: v.grad.reshape(v.shape[0], -1) if v.dim() == 3 else v.grad for k, v in pd.items()}))
+    rel, row = measures(res[1][0].numpy(), res[0][0].numpy())
+    print("jitter floor chain %s%d y rel-L2 %.2e  row-max %.2e" % (mod, Fo, rel, row))
+    assert rel <= FE.CHAIN_OUT[0] and row <= FE.CHAIN_OUT[1]
+    for k in res[0][2]:
+        rel, row = measures(res[1][2][k].numpy(), res[0][2][k].numpy())
+        print("jitter floor chain %s%d %-40s rel-L2 %.2e  row-max %.2e" % (mod, Fo, k, rel, row))
+        assert rel <= FE.CHAIN_GRAD[0] and row <= FE.CHAIN_GRAD[1], k
+    print("%.1f s" % (time.time() - t0))
+
+
+# Mutations of the front-end reference, each a subtle kernel bug: each must fail what test_gpu_bf16_frontend.py asserts.
+def _keep_value(value, grad_path):
+    """the value of `value` with the gradient of `grad_path`"""
+    return value.detach() + (grad_path - grad_path.detach())
+
+
+def _conv_mutant_inputs(N, W, D, F, tag):
+    return _conv_small(N, W, D, F, "e_cmut_" + tag)
+
+
+def test_conv_bounds_see_the_pool_mutants():
+    import test_gpu_bf16_frontend as FE
+    from test_gpu_bf16_faithful import measures
+    # the LAST instead of the first maximum: invisible to the near-tie rule (the gap is exactly 0), seen by the exact-tie cases
+    c = dict(next(x for x in FE.CONV_CASES if x["kind"] == "tie_d4d8"), N=64)
+    x, w, b, g = FE.conv_inputs(c)
+    last = lambda S: S.shape[1] - 1 - S.flip(1).argmax(dim=1)  # noqa: E731
+    ref = _run_conv(x, w, b, g)
+    mut = _run_conv(x, w, b, g, mutate={"pool": last})
+    run = {"S": ref["S"], "A": E.conv_sums(x.double(), w.double())[1], "arg": mut["arg"]}
+    nd, worst = FE.arg_differences(c, run)
+    print("mutant last maximum: argmax differs in %d pairs, gap / slack %.1e" % (nd, worst))
+    assert nd > 100 and worst == 0.0                       # a tie case fails on any difference
+    # one position too many in the last row tile (row <= plim): the padding row's sum x[W-1] . w[:, :, 0] takes part in the pool
+    for key in ((2565, 10, 88, 256), (9, 34, 40, 64)):
+        c = next(x for x in FE.CONV_CASES if (x["N"], x["W"], x["D"], x["F"]) == key and x["kind"] in ("neg", "rt"))
+        x, w, b, g = FE.conv_inputs(c)
+        x, g = x[:300], g[:300]
+        wl = w.double()
+        S = torch.cat([E.conv_sums(x.double(), wl)[0], (E.bf16(x.double())[:, -1] @ E.bf16(wl)[:, :, 0].t()).unsqueeze(1)], dim=1)
+        arg = S.argmax(dim=1)
+        rel, row = measures((S.amax(dim=1)).numpy(), S[:, :-1].amax(dim=1).numpy())
+        print("mutant row <= plim %s: argmax = W - 1 in %d pairs, out rel-L2 %.2e row-max %.2e" % (c["id"], int((arg == c["W"] - 1).sum()), rel, row))
+        assert int(arg.max()) == c["W"] - 1 and rel > FE.CONV_OUT[0] and row > FE.CONV_OUT[1]
+
+
+def test_conv_bounds_see_the_backward_mutants():
+    import test_gpu_bf16_frontend as FE
+    from test_gpu_bf16_faithful import measures
+    N, W, D, F = 3001, 10, 88, 256
+    pl = E.conv_plan(N, W, D, F)
+    x, w, b, g = _conv_mutant_inputs(N, W, D, F, "bwd")
+    ref = _run_conv(x, w, b, g)
+
+    def dist(mut, name):
+        a, r = mut[name], ref[name]
+        if a.dim() == 3:
+            a, r = a.reshape(F, -1), r.reshape(F, -1)
+        return measures(a.numpy(), r.numpy()) + (FE.ls_scale(a.numpy(), r.numpy()),)
+    # npairs = (nend - nbeg) / 2: the last window of an odd split is left out of dW (its dy still reaches db)
+    keep = torch.ones(N, 1, dtype=torch.float64)
+    assert pl["last"] % 2 == 1
+    keep[N - 1] = 0.0
+    m = _run_conv(x, w, b, g, arg=ref["arg"], mutate={"gathered": lambda s: _keep_value(s, s * keep)})
+    rel, row, sc = dist(m, "dW")
+    print("mutant odd last window dropped: dW rel-L2 %.2e row-max %.2e" % (rel, row))
+    assert rel > FE.CONV_DW[0] and row > FE.CONV_DW[1] and torch.equal(m["db"], ref["db"])
+    # the previous pair's rows as the B operand of tap 1 (a stale LDS buffer): the forward is untouched
+    def stale(j, rows, wj):
+        prod = rows @ wj.t()
+        return prod if j == 0 else _keep_value(prod, rows.roll(2, dims=0) @ wj.t())
+    m = _run_conv(x, w, b, g, arg=ref["arg"], mutate={"tap": stale})
+    rel, row, sc = dist(m, "dW")
+    print("mutant stale rows for tap 1: dW rel-L2 %.2e row-max %.2e" % (rel, row))
+    assert torch.equal(m["out"], ref["out"]) and rel > FE.CONV_DW[0] and row > FE.CONV_DW[1]
+    # dy truncated instead of rounded to bf16: a coherent -2^-9-ish scale of dW
+    def trunc(t):
+        bits = t.float().view(torch.int32) & -65536
+        return bits.view(torch.float32).double()
+    m = _run_conv(x, w, b, g, arg=ref["arg"], mutate={"round_dy": trunc})
+    rel, row, sc = dist(m, "dW")
+    print("mutant dy truncated: dW rel-L2 %.2e row-max %.2e scale %.2e" % (rel, row, sc))
+    assert rel > FE.CONV_DW[0] and row > FE.CONV_DW[1] and abs(sc) > FE.CONV_W_SCALE
+    # db counted once per row tile instead of once per window (first_rt always 1), at three row tiles
+    N, W, D, F = 300, 70, 24, 32
+    nrt = E.conv_plan(N, W, D, F)["nrt"]
+    x, w, b, g = _conv_mutant_inputs(N, W, D, F, "db")
+    ref = _run_conv(x, w, b, g)
+    m = _run_conv(x, w, b, g, mutate={"b": lambda t: _keep_value(t, nrt * t)})
+    rel, row = measures(m["db"].numpy(), ref["db"].numpy())
+    print("mutant db once per row tile: db rel-L2 %.2e row-max %.2e" % (rel, row))
+    assert nrt == 3 and rel > FE.CONV_DB[0] and row > FE.CONV_DB[1] and torch.equal(m["dW"], ref["dW"])
+
+
+def test_highway_bounds_see_a_mutant():
+    import test_gpu_bf16_frontend as FE
+    from test_gpu_bf16_faithful import measures
+    rows, n = 600, 300
+    ref = _hw_run(rows, n, "bffe_hw%dx%d" % (rows, n))
+    # dgate = g * proj: the "- x" lost
+    m = _hw_run(rows, n, "bffe_hw%dx%d" % (rows, n),
+                mutate={"combine": lambda x, proj, gate: _keep_value(x + gate * (proj - x), x + gate.detach() * (proj - x) + gate * proj.detach())})
+    assert torch.equal(m[0], ref[0])
+    for i, k in ((4, "dWg"), (5, "dbg"), (1, "dx")):
+        rel, row = measures(m[i].numpy(), ref[i].numpy())
+        print("mutant dgate without - x: %s rel-L2 %.2e row-max %.2e" % (k, rel, row))
+        assert rel > FE.HW_GRAD[0] and row > FE.HW_GRAD[1]
+    # the sigmoid's derivative from the pre-activation rounded to bf16 instead of from the saved fp32 output
+    def gate_act(pre):
+        s = torch.sigmoid(E.bf16(pre.detach()))
+        return _keep_value(torch.sigmoid(pre), pre * (s * (1 - s)))
+    m = _hw_run(rows, n, "bffe_hw%dx%d" % (rows, n), mutate={"gate_act": gate_act})
+    assert torch.equal(m[0], ref[0])
+    rel, row = measures(m[4].numpy(), ref[4].numpy())
+    print("mutant sigmoid' from bf16(pre): dWg rel-L2 %.2e row-max %.2e" % (rel, row))
+    assert rel > FE.HW_GRAD[0] or row > FE.HW_GRAD[1]
