@@ -92,6 +92,36 @@ __host__ __device__ __forceinline__ size_t fragR_elems(int Tp, int DKP) { return
 
 __host__ __device__ __forceinline__ int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// pack (B,T,d) fp32 head-major-column tensors into fragment layouts; unpack head-padded bf16 back.
+__global__ void pack_frag_kernel(const float* __restrict__ src, bf16* __restrict__ fr,
+                                 const float* __restrict__ rowmask, float scale, int use_mask,
+                                 const bf16* __restrict__ ctx, int ldctx, float* __restrict__ delta,
+                                 int M, int T, int Tp, int h, int dk, int DKP, int d) {
+    const size_t total = (size_t)M * h;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int m = (int)(idx / h), head = (int)(idx % h), b = m / T, t = m - b * T;
+        const size_t bh = (size_t)b * h + head;
+        float sc = scale;
+        if (use_mask && rowmask && rowmask[m] == 0.0f) sc = 0.f;
+        float part = 0.f;
+        for (int e = 0; e < dk; ++e) {
+            const bf16 v = (bf16)(src[(size_t)m * d + head * dk + e] * sc);
+            fr[bh * fragR_elems(Tp, DKP) + fragR_index(t, e, DKP)] = v;
+            if (delta) part += (float)v * (float)ctx[(size_t)m * ldctx + head * DKP + e];
+        }
+        if (delta) delta[bh * Tp + t] = -part;       // stored negated, like the fused path
+    }
+}
+
+__global__ void unpad_heads_kernel(const bf16* __restrict__ src, int ld, int col0, float* __restrict__ dst,
+                                   int M, int h, int dk, int DKP, int d) {
+    const size_t total = (size_t)M * d;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int m = (int)(idx / d), c = (int)(idx % d), head = c / dk, e = c - head * dk;
+        dst[idx] = (float)src[(size_t)m * ld + col0 + head * DKP + e];
+    }
+}
+
 // ---- dropout: counter-based generator.  One 32-bit hash word serves the index pair (2i, 2i+1); each
 // element compares its 16-bit half with thr16 = round(p * 65536): P(drop) = thr16/65536 (exact to 1.5e-5),
 // kept values are scaled by 65536/(65536 - thr16).  A mask is a pure function of (seed, stream, index), so the

@@ -146,3 +146,36 @@ __global__ void error_accumulate_kernel(const unsigned* __restrict__ word, unsig
 __global__ void zero_fill_kernel(unsigned* __restrict__ p, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
 }
+
+// ---- test hooks (mmt_debug_dropout_mask, mmt_debug_poison_lds) ----
+// keep[i] = 1 if index i of dropout stream `stream` is kept under (p, seed): lets a test rebuild the exact masks the
+// kernels used and replay the reference arithmetic with them.
+// attn_Tp == 0: flat stream (index i).  attn_Tp > 0: attention-probability stream, i = (bh*Tp + q)*Tp + key, which the
+// attention kernels evaluate as a per-(batch,head) stream with the 32-bit index q*Tp + key.
+__global__ void dropout_mask_kernel(DropCfg c, uint64_t n, uint8_t* __restrict__ keep) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        keep[i] = drop_keep(c, i) ? 1 : 0;
+}
+// Test hook: leave a chosen bit pattern in every LDS word (and a spread of VGPRs) of every CU.  A kernel whose result depends on LDS
+// it never wrote (what a freshly powered GPU hands it: the first process on a box) then produces a different answer after this call.
+__global__ __launch_bounds__(1024) void poison_lds_kernel(uint32_t pattern, int words, uint32_t* sink) {
+    extern __shared__ uint32_t poison_smem[];
+    for (int i = threadIdx.x; i < words; i += blockDim.x) poison_smem[i] = pattern;
+    __syncthreads();
+    // keep the stores alive and hold the CU for a moment so that the grid spreads over all CUs
+    uint32_t acc = 0;
+    for (int i = threadIdx.x; i < words; i += blockDim.x * 7) acc ^= poison_smem[i];
+    if (acc == 0x12345u) sink[0] = acc;
+}
+// ... and in the vector registers: a wave starts with whatever the previous wave on its SIMD slot left there.
+__global__ __launch_bounds__(256, 2) void poison_vgpr_kernel(uint32_t pattern, uint32_t* sink) {
+    constexpr int NR = 232;
+    uint32_t r[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) { r[i] = pattern; asm volatile("" : "+v"(r[i])); }
+    __builtin_amdgcn_s_sleep(64);
+    uint32_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) { asm volatile("" : "+v"(r[i])); acc += r[i] ^ (uint32_t)i; }
+    if (acc == 0x12345u) sink[0] = acc;
+}

@@ -140,6 +140,60 @@ __global__ void pad_cast_kernel(const float* __restrict__ src, bf16* __restrict_
     }
 }
 
+__global__ void pad_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, int n, int np) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < np) dst[i] = (i < n && src) ? src[i] : 0.f;
+}
+
+// g = dy * rowscale * act'(y) -> bf16 row-major [M][NP] (pad columns written as zeros): the A operand of the input-gradient GEMM and
+// of the weight-gradient kernel
+__global__ void grad_prep_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ rowscale,
+                                 int act, bf16* __restrict__ g, int M, int N, int NP, float gscale) {      // gscale: 1/(1-p) of an output dropout (y > 0 <=> kept)
+    const size_t total = (size_t)M * (NP >> 2);
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int m = (int)(idx / (NP >> 2)), n = (int)(idx % (NP >> 2)) * 4;
+        bf16x4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float v = 0.f;
+            if (n + i < N) {
+                v = dy[(size_t)m * N + n + i];
+                if (rowscale) v *= rowscale[m];
+                if (act == 1) { v = (y[(size_t)m * N + n + i] > 0.f) ? v * gscale : 0.f; }
+                else if (act == 2) { const float yy = y[(size_t)m * N + n + i]; v *= 1.f - yy * yy; }
+                else if (act == 3) { const float yy = y[(size_t)m * N + n + i]; v *= yy * (1.f - yy); }
+            }
+            o[i] = (bf16)v;
+        }
+        *reinterpret_cast<bf16x4*>(g + (size_t)m * NP + n) = o;
+    }
+}
+
+// fp32 [M][K] -> bf16 row-major [M][KP] (pad columns written as zeros): the B operand of the weight-gradient kernel
+// (`drop_in`: the input dropout of the forward, index m*KP + k, regenerated here)
+__global__ void cast_rows_kernel(const float* __restrict__ src, bf16* __restrict__ dst, int M, int K, int KP, DropCfg drop_in,
+                                 const uint64_t* __restrict__ seedword) {
+    const DropCfg drop = drop_resolve(drop_in, seedword);
+    const size_t total = (size_t)M * (KP >> 2);
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int m = (int)(idx / (KP >> 2)), k = (int)(idx % (KP >> 2)) * 4;
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = (k + i < K) ? src[(size_t)m * K + k + i] : 0.f;
+        if (drop.thr16) {
+#pragma unroll
+            for (int i = 0; i < 4; i += 2) {
+                const uint32_t w = drop_pair(drop, (uint64_t)m * KP + k + i);
+                v[i] = drop_lo(drop, w, v[i]); v[i + 1] = drop_hi(drop, w, v[i + 1]);
+            }
+        }
+        bf16x4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = (bf16)v[i];
+        *reinterpret_cast<bf16x4*>(dst + (size_t)m * KP + k) = o;
+    }
+}
+
 // ---- LayerNorm alone (reference variant).  8 threads per row, 32 rows per workgroup. -------------
 __global__ __launch_bounds__(MMT_THREADS) void layernorm_fwd_kernel(
         const float* __restrict__ x, const float* __restrict__ a, const float* __restrict__ b, float eps,

@@ -799,7 +799,7 @@ __device__ __forceinline__ void ln_tile_out(const float* Xs, int ldx, const LnOu
 }
 
 // Stage roles of the chained kernels.  rowgemm_stage() serves every affine map of the library and decides most of its options at run
-// time; in a chain each stage's role is fixed, and what mmt_encoder_forward / _backward (api.hip) leave unset for that role is pinned
+// time; in a chain each stage's role is fixed, and what encoder_forward_impl / encoder_backward_impl (api.hip) leave unset for that role is pinned
 // here in a local copy of the stage's parameters: the copies are constants to the compiler, so the options' code — the tanh / sigmoid
 // epilogues, the ReLU-mask, row-scale and second-output paths, K-chunked staging — and their scalar branch / exec-mask bookkeeping
 // (40 % of the static instruction stream of these kernels was scalar) drop out of the kernel.
@@ -891,7 +891,7 @@ __device__ __forceinline__ RowSmem carve_fixed(char* smem) {
     sm.lda2 = LDA2;
     return sm;
 }
-// the geometry launch_rowchain (api.hip) computes for SHAPE 128; it refuses the fixed instance when its own numbers differ
+// the geometry chain_geom (api.hip) gives launch_rowchain for SHAPE 128; it refuses the fixed instance when its own numbers differ
 #define MMT_FIX128_LDF 132
 #define MMT_FIX128_LDA2 136
 #define MMT_FIX128_LDA_FWD 136

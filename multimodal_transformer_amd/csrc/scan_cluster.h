@@ -11,7 +11,7 @@
 //
 // Residency: the 4 workgroups of a sequence must run at the same time.  The host only takes this path for
 // 4*B <= 128 workgroups and only when the occupancy query says that twice that many fit the device at once (api.hip:
-// cl4_resident), launched as ONE kernel whose block index is decoded so that the four parts of a sequence sit on the same
+// plan_lstm_scan, cl4_resident), launched as ONE kernel whose block index is decoded so that the four parts of a sequence sit on the same
 // XCD.  Nothing can guarantee residency against other streams or processes holding CUs: every wait is bounded and a
 // time-out raises a device error word (cl_wait_granule) instead of silently consuming a stale granule.
 #pragma once

@@ -13,7 +13,7 @@ Two primitives place the roundings:
 
 Sites, read from the kernel sources (csrc/):
   * weights: every prepared weight is bf16 (pad_cast_kernel);
-  * affine map (api.hip linear_*): A = bf16(drop_in(x)) (rowgemm staging, cast_rows_kernel), y = rowscale * drop_out(act(A W^T + b))
+  * affine map (api.hip linear_*): A = bf16(drop_in(x)) (rowgemm staging; misc_kernels.h cast_rows_kernel), y = rowscale * drop_out(act(A W^T + b))
     in fp32; the backward operand g = bf16(dy * rowscale * act' * 1/(1-p_out)) (grad_prep_kernel) -> dx = (g W) * drop_in' in fp32,
     dW = g^T A, db = colsum(g);
   * encoder layer: xn1 = bf16(LN1(x)), Q' = bf16((xn1 Wq^T + bq) log2(e)/sqrt(d_k)) with blanked query rows Q' = 0, K = bf16(.),
@@ -50,7 +50,7 @@ Sites, read from the kernel sources (csrc/):
     bf16(x[n, arg + j, d]) (:312 the one-hot A operand, :264-272 the transposed rows), db[f] = sum_n dy[n, f] from the UNROUNDED dy
     (:299).  ``conv_maxpool`` places it in one line: out = round_bwd(gather(S, arg)) + b;
   * tanh / sigmoid epilogues of the affine map (rowgemm.h:387-392): on the fp32 sum + bias, output fp32.  The backward takes act' from
-    the SAVED fp32 OUTPUT (api.hip grad_prep_kernel :1000-1001: 1 - y^2, y (1 - y)), multiplies in fp32 and rounds once:
+    the SAVED fp32 OUTPUT (misc_kernels.h grad_prep_kernel, act 2 and 3: 1 - y^2, y (1 - y)), multiplies in fp32 and rounds once:
     g = bf16(dy * rowscale * act'(y)), the same place as the ReLU's, so ``linear`` keeps its one round_bwd in front of the activation;
   * Highway (functional._HighwayFn, glue.h:97-125): proj = linear(x, act 0 or 1), gate = linear(x, act 3), both fp32;
     out = drop * (x + gate * (proj - x)) in fp32 from the UNROUNDED x (:105); backward g = drop * dout, dx = g (1 - gate), dproj = g gate,

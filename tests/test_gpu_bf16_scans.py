@@ -9,7 +9,8 @@ where the kernels round, so the bounds sit one to two orders of magnitude lower,
   * the per-sequence maximum  max_b ||got[:, b] - ref[:, b]|| / rms_b ||ref[:, b]||  of the (T, B, .) tensors;
   * the least-squares scale <got - ref, ref> / <ref, ref> of the weight gradients.
 
-Every dispatch branch of mmt_lstm_scan_forward / _backward and mmt_mfn_mem_scan_forward / _backward (csrc/api.hip) has cases, and each
+Every dispatch branch of plan_lstm_scan (one plan for mmt_lstm_scan_forward and _backward) and of mmt_mfn_mem_scan_forward / _backward
+(csrc/api.hip) has cases, and each
 case asserts through torch.profiler that the kernel it is labelled for ran.  The four-CU scans (scan_cluster.h) run once more under
 MMT_NO_CLUSTER_SCAN=1, where the same shapes go to scan256.h; those results are checked against the reference and against the four-CU
 ones.  The switch is read once per process, so all GPU work happens in child processes (conftest.run_in_fresh_process) that hand their
@@ -107,8 +108,8 @@ def scan_bt(B):
 
 
 def lstm_family(B, H, no_cluster=False):
-    """the LSTM scan variant mmt_lstm_scan_forward / _backward choose on an MI355X: cl4 (scan_cluster.h), s256 (scan256.h), u1 / u2
-    (scan_units.h, one / two sequences per workgroup) or gen (scan.h)"""
+    """the LSTM scan variant plan_lstm_scan (csrc/api.hip: the one decision both scans dispatch from) chooses on an MI355X: cl4
+    (scan_cluster.h), s256 (scan256.h), u1 / u2 (scan_units.h, one / two sequences per workgroup) or gen (scan.h)"""
     hp16 = -(-H // 16) * 16
     hpad = 64 if hp16 <= 64 else 128 if hp16 <= 128 else 256
     bt = scan_bt(B)
