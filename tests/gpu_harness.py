@@ -1,0 +1,195 @@
+"""What the GPU test files share: the old-style tolerances, the `dev` fixture, the measures of the bf16-faithful tier (tests/bf16_ref.py),
+the child-process runner for tests whose environment switches are read once per process, and the harvest of device kernel names.
+
+A plain module, not a conftest: it defines no pytest hooks, and a test file imports what it uses by name, the fixtures included.  The
+test files keep their cases, their bounds and their comparisons.  Importing this module must not initialise the GPU: the children of
+run_child import it before they set anything up.
+"""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+from torch.autograd import DeviceType
+from torch.profiler import ProfilerActivity, profile
+
+import conftest
+import recipe as R
+from conftest import rel_l2
+
+# bf16 MFMA operands against an all-fp32 / fp64 reference (test_gpu_parity.py's docstring states where each applies)
+OUT_RTOL = 2e-2
+GRAD_RTOL = 4e-2
+RELU_GRAD_RTOL = 9e-2          # measured worst over the suite 6.5e-2 (ffn_d128 dw_1.bias), x 1.3
+CCC_MIN = 1 - 1e-3
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def tmp_dir(request, tmp_path_factory):
+    return tmp_path_factory.mktemp(request.module.__name__)
+
+
+def mta():
+    import multimodal_transformer_amd as m
+    return m
+
+
+def _report(tag, got, ref):
+    got = np.asarray(got, dtype=np.float64)
+    ref = np.asarray(ref, dtype=np.float64)
+    r = rel_l2(got, ref)
+    print("%-44s rel_l2 %.3e  max_abs %.3e  ref_rms %.3e" % (tag, r, np.abs(got - ref).max(), np.sqrt((ref ** 2).mean())))
+    return r
+
+
+def load_named(model, seed=R.SEED):
+    """the recipe's parameters for the model's state_dict, loaded into it -> the fp32 parameters"""
+    p32 = R.gen_params(R.shapes_of(model.state_dict()), seed)
+    model.load_state_dict(p32)
+    return p32
+
+
+def seeded_encoder(d, h, n, dev, seed):
+    """an n-layer Encoder with the recipe's parameters, on the device in eval mode -> (encoder, the fp32 parameters)"""
+    MT = mta().multiTransformer
+    enc = MT.Encoder(MT.EncoderLayer(d, MT.MultiHeadedAttention(h, d), MT.PositionwiseFeedForward(d, R.D_FF, 0.1), 0.1), n)
+    p32 = load_named(enc, seed)
+    return enc.to(dev).eval(), p32
+
+
+# ------------------------------------------------------------------------------------------------ measures of the bf16-faithful tier
+def _rows(a):
+    a = np.asarray(a, dtype=np.float64)
+    return a.reshape(-1, 1) if a.ndim == 1 else a.reshape(-1, a.shape[-1]) if a.ndim > 2 else a
+
+
+def measures(got, ref):
+    """(rel-L2, per-row maximum) of got against ref."""
+    g, r = _rows(got), _rows(ref)
+    diff = np.linalg.norm(g - r, axis=1)
+    rms = np.sqrt(np.mean(np.sum(r * r, axis=1)))
+    return float(np.linalg.norm(g - r) / max(np.linalg.norm(r), 1e-300)), float(diff.max() / max(rms, 1e-300))
+
+
+def check(tag, got, ref, rel_bound, row_bound=None, scale_ref=None, failures=None):
+    """scale_ref: measure against another tensor's magnitude (for an analytically zero reference, e.g. the key bias's gradient).
+    failures: a list to append a failure message to instead of raising (every tensor of a case is then reported)."""
+    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    rel, row = measures(got, ref)
+    if scale_ref is not None:
+        s = np.asarray(scale_ref, dtype=np.float64)
+        rel = float(np.linalg.norm(got - ref) / np.linalg.norm(s))
+        row = float(np.abs(got - ref).max() / np.sqrt(np.mean(s * s)))
+    print("%-52s rel-L2 %.2e  row-max %.2e" % (tag, rel, row))
+    msg = None
+    if not np.isfinite(got).all():
+        msg = "%s: not finite" % tag
+    elif rel > rel_bound:
+        msg = "%s: rel-L2 %.3e > %.1e" % (tag, rel, rel_bound)
+    elif row_bound is not None and row > row_bound:
+        msg = "%s: per-row maximum %.3e > %.1e" % (tag, row, row_bound)
+    if msg and failures is None:
+        raise AssertionError(msg)
+    if msg:
+        failures.append(msg)
+
+
+def seq_max(got, ref):
+    """max_b ||got[:, b] - ref[:, b]|| / rms_b ||ref[:, b]|| of (T, B, ...) tensors: the worst single sequence across all t."""
+    g = np.asarray(got, dtype=np.float64)
+    r = np.asarray(ref, dtype=np.float64)
+    g, r = g.reshape(g.shape[0], g.shape[1], -1), r.reshape(r.shape[0], r.shape[1], -1)
+    diff = np.sqrt(((g - r) ** 2).sum(axis=(0, 2)))
+    return float(diff.max() / max(np.sqrt((r * r).sum(axis=(0, 2)).mean()), 1e-300))
+
+
+def ls_scale(got, ref):
+    """<got - ref, ref> / <ref, ref>: a wrongly scaled term moves it, noise hardly does."""
+    r = np.asarray(ref, dtype=np.float64).ravel()
+    return float(np.dot(np.asarray(got, dtype=np.float64).ravel() - r, r) / np.dot(r, r))
+
+
+def check_scan(tag, got, ref, bounds, failures, seq=False, scale=None):
+    """rel-L2 and per-row maximum through check(); with seq the per-sequence maximum, with scale (its bound) the least-squares scale."""
+    check(tag, got, ref, bounds[0], bounds[1], failures=failures)
+    if seq:
+        s = seq_max(got, ref)
+        print("%-52s seq-max %.2e" % (tag, s))
+        if s > bounds[2]:
+            failures.append("%s: per-sequence maximum %.3e > %.1e" % (tag, s, bounds[2]))
+    if scale is not None:
+        s = ls_scale(got, ref)
+        print("%-52s scale %.2e" % (tag, s))
+        if abs(s) > scale:
+            failures.append("%s: least-squares scale %.3e > %.1e" % (tag, s, scale))
+
+
+# the affine map's shapes (M, K, N, act, rowscale), inputs and bound: test_gpu_bf16_faithful.py and test_gpu_bf16_frontend.py run them
+LIN_REL = 3e-6                       # 1.6e-7 / 7.2e-7 (fp32 accumulation only), rel-L2 and per row
+_LIN = [(1, 4, 1, 0, False), (31, 5, 5, 1, False), (32, 43, 129, 0, True), (33, 301, 256, 1, True), (200, 576, 129, 1, False),
+        (200, 43, 256, 0, False), (33, 576, 1, 0, True), (1, 301, 129, 1, False), (32, 4, 256, 1, True), (200, 5, 5, 0, True),
+        (31, 576, 256, 0, False), (200, 301, 1, 1, True)]
+
+
+def _lin_inputs(M, K, N, tag):
+    x = R.gen_normal(tag + "x", (M, K), 5)
+    W = R.gen_normal(tag + "w", (N, K), 5) / np.sqrt(K)
+    b = 0.1 * R.gen_normal(tag + "b", (N,), 5)
+    g = R.gen_normal(tag + "g", (M, N), 5)
+    return x, W, b, g
+
+
+# ------------------------------------------------------------------------------------------------ child processes
+_RUNS = {}
+
+
+def run_child(module, kind, switch, payload, tmp_dir, switches, timeout):
+    """child_main(kind, out_path, json of payload) of the test module `module`, in a fresh process (conftest.run_in_fresh_process) with
+    the variables of every set in `switches` removed from the environment and those of switches[switch] set -> the arrays of the .npz
+    it wrote, as a dict.  One run per (module, kind, switch): later calls get the first one's arrays."""
+    key = (module, kind, switch)
+    if key not in _RUNS:
+        env = dict(os.environ)
+        for s in switches.values():
+            for k in s:
+                env.pop(k, None)
+        env.update(switches[switch])
+        env["PYTHONPATH"] = os.pathsep.join([conftest.ROOT, os.path.join(conftest.ROOT, "tests"), conftest.GOLDEN,
+                                             env.get("PYTHONPATH", "")])
+        out = os.path.join(str(tmp_dir), "%s_%s.npz" % (kind, switch))
+        stub = "import sys, %s as m; m.child_main(*sys.argv[1:])" % module
+        res = conftest.run_in_fresh_process([sys.executable, "-c", stub, kind, out, json.dumps(payload)], env, timeout=timeout)
+        if res is None:
+            pytest.skip("no launcher process (tests were collected with the GPU already initialised)")
+        assert res["rc"] == 0, res["stderr"][-3000:]
+        with np.load(out) as z:
+            _RUNS[key] = {k: z[k] for k in z.files}
+    return _RUNS[key]
+
+
+# ------------------------------------------------------------------------------------------------ device kernel names
+def device_kernel_names(fn, warm=False):
+    """fn() under torch.profiler -> (its result, the names of the device kernels it launched).  The names are None where the profiler
+    reports no device activity: a caller then skips only its assertion on the names.  warm: one unprofiled call of fn first."""
+    if warm:
+        fn()
+        torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        res = fn()
+        torch.cuda.synchronize()
+    names = [e.name for e in prof.events() if e.device_type == DeviceType.CUDA]
+    return res, (names or None)
+
+
+def library_kernels(names):
+    """kernels that are not ours: ATen element-wise / reduction / copy / cat kernels, rocBLAS / hipBLASLt / MIOpen GEMMs"""
+    bad = ("at::", "at_cuda", "elementwise", "Cijk_", "rocblas", "hipblas", "miopen", "MIOpen", "CatArray", "reduce_kernel", "vectorized_")
+    return sorted(set(n for n in names if any(b in n for b in bad)))

@@ -11,6 +11,7 @@ import bf16_ref as E
 import oracle
 import recipe as R
 from conftest import rel_l2
+from gpu_harness import ls_scale, measures, seq_max
 
 
 def _rel(a, b):
@@ -272,7 +273,6 @@ def test_scan_jitter_floor():
     moves the reference from itself at the long shapes of that file.  Tipped bf16(h) roundings feed back through the recurrence, so the
     distance is also reported per time step.  Every bound there must sit at or above this floor."""
     import test_gpu_bf16_scans as S
-    from test_gpu_bf16_faithful import measures
     lstm_b = {"h": S.LSTM_OUT, "c": S.LSTM_OUT, "dgx": S.LSTM_DGX, "dW": S.LSTM_DW, "dh0": S.LSTM_D0, "dc0": S.LSTM_D0}
     t0 = time.time()
     for cid in ("l_T1000_B3_H48_i_hc", "l_T1000_B2_H88_n_hc", "l_T1000_B2_H256_i_hc"):
@@ -284,12 +284,12 @@ def test_scan_jitter_floor():
         S._LSTM_REFS.pop(cid)
         for k in a:
             rel, row = measures(b[k], a[k])
-            seq = S.seq_max(b[k], a[k]) if a[k].ndim == 3 else 0.0
+            seq = seq_max(b[k], a[k]) if a[k].ndim == 3 else 0.0
             print("jitter floor %s %-4s rel-L2 %.2e  row-max %.2e  seq-max %.2e" % (cid, k, rel, row, seq))
             bd = lstm_b[k]
             assert rel <= bd[0] and row <= bd[1] and (a[k].ndim != 3 or seq <= bd[2]), (cid, k)
         if "dW" in a:
-            assert abs(S.ls_scale(b["dW"], a["dW"])) <= S.LSTM_W_SCALE
+            assert abs(ls_scale(b["dW"], a["dW"])) <= S.LSTM_W_SCALE
         d = np.linalg.norm((b["h"] - a["h"]).reshape(c["T"], -1), axis=1) / np.linalg.norm(a["h"].reshape(c["T"], -1), axis=1)
         print("jitter floor %s h per step: t < 10 %.1e, t < 100 %.1e, t < 1000 %.1e" % (cid, d[:10].max(), d[:100].max(), d.max()))
     for cid in ("m_T1000_B2_p0", "m_T300_B33_p0"):
@@ -304,7 +304,7 @@ def test_scan_jitter_floor():
             if k == "db2":
                 ga, gb = ga.ravel(), gb.ravel()
             rel, row = measures(gb, ga)
-            seq = S.seq_max(gb, ga) if k in ("mem", "dapre", "dchat") else 0.0
+            seq = seq_max(gb, ga) if k in ("mem", "dapre", "dchat") else 0.0
             print("jitter floor %s %-5s rel-L2 %.2e  row-max %.2e  seq-max %.2e" % (cid, k, rel, row, seq))
             bd = bds[k]
             assert rel <= bd[0] and (bd[1] is None or row <= bd[1]) and (len(bd) < 3 or seq <= bd[2]), (cid, k)
@@ -380,12 +380,11 @@ _LSTM_MUTANTS = [("stale_exchange", _mut_stale, (20, 5, 256), "h", 1), ("stale_e
 def test_lstm_scan_bounds_see_a_mutant(name, mut, shape, tensor, measure):
     """measure: 0 rel-L2, 1 per-row maximum, 2 per-sequence maximum, against the bound of test_gpu_bf16_scans.py"""
     import test_gpu_bf16_scans as S
-    from test_gpu_bf16_faithful import measures
     inputs = _lstm_inputs(*shape, True, "e_mut_" + name)
     ref = _run_lstm(E.lstm_scan, inputs)
     got = mut(inputs)
     g, r = got[tensor].numpy(), ref[tensor].numpy()
-    m = (measures(g, r) + (S.seq_max(g, r) if r.ndim == 3 else None,))[measure]
+    m = (measures(g, r) + (seq_max(g, r) if r.ndim == 3 else None,))[measure]
     bound = {"h": S.LSTM_OUT, "dgx": S.LSTM_DGX, "dh0": S.LSTM_D0}[tensor][measure]
     print("mutant %s: %s %s %.3e (bound %.1e)" % (name, tensor, ("rel-L2", "row-max", "seq-max")[measure], m, bound))
     assert m > bound
@@ -393,7 +392,6 @@ def test_lstm_scan_bounds_see_a_mutant(name, mut, shape, tensor, measure):
 
 def test_mfn_mem_scan_bounds_see_a_mutant():
     import test_gpu_bf16_scans as S
-    from test_gpu_bf16_faithful import measures
     T, B, p = 5, 17, 0.2                                   # a short-tier case of test_gpu_bf16_scans.py
     got, drop = _mut_relu_mask(T, B, p, "e_mut_relu")
     ref = _run_mfn(E.mfn_mem_scan, _mfn_inputs(T, B, "e_mut_relu"), drop=drop)
@@ -628,7 +626,6 @@ def test_frontend_jitter_floor():
     The conv's argmax must change in at most ARG_SHARE of the pairs for the file's own inputs (per case and over the file): that is the
     condition under which the cap holds.  The Highway's, the tanh / sigmoid map's and the chain's measures must stay within the bounds."""
     import test_gpu_bf16_frontend as FE
-    from test_gpu_bf16_faithful import measures
     t0 = time.time()
     nd = tot = 0
     for c in FE.CONV_CASES:
@@ -655,7 +652,7 @@ def test_frontend_jitter_floor():
                 bd = FE.HW_OUT if k == "y" else FE.HW_GRAD
                 assert rel <= bd[0] and row <= bd[1], (rows, n, k)
             for i in (2, 4):
-                assert abs(FE.ls_scale(b_[i].numpy(), a[i].numpy())) <= FE.HW_W_SCALE
+                assert abs(ls_scale(b_[i].numpy(), a[i].numpy())) <= FE.HW_W_SCALE
     M, K, N = 200, 576, 129
     x, W, b, g = FE._lin_inputs(M, K, N, "bffe_lin%dx%dx%d" % (M, K, N))
     for act in (2, 3):
@@ -712,7 +709,6 @@ def _conv_mutant_inputs(N, W, D, F, tag):
 
 def test_conv_bounds_see_the_pool_mutants():
     import test_gpu_bf16_frontend as FE
-    from test_gpu_bf16_faithful import measures
     # the LAST instead of the first maximum: invisible to the near-tie rule (the gap is exactly 0), seen by the exact-tie cases
     c = dict(next(x for x in FE.CONV_CASES if x["kind"] == "tie_d4d8"), N=64)
     x, w, b, g = FE.conv_inputs(c)
@@ -738,7 +734,6 @@ def test_conv_bounds_see_the_pool_mutants():
 
 def test_conv_bounds_see_the_backward_mutants():
     import test_gpu_bf16_frontend as FE
-    from test_gpu_bf16_faithful import measures
     N, W, D, F = 3001, 10, 88, 256
     pl = E.conv_plan(N, W, D, F)
     x, w, b, g = _conv_mutant_inputs(N, W, D, F, "bwd")
@@ -748,7 +743,7 @@ def test_conv_bounds_see_the_backward_mutants():
         a, r = mut[name], ref[name]
         if a.dim() == 3:
             a, r = a.reshape(F, -1), r.reshape(F, -1)
-        return measures(a.numpy(), r.numpy()) + (FE.ls_scale(a.numpy(), r.numpy()),)
+        return measures(a.numpy(), r.numpy()) + (ls_scale(a.numpy(), r.numpy()),)
     # npairs = (nend - nbeg) / 2: the last window of an odd split is left out of dW (its dy still reaches db)
     keep = torch.ones(N, 1, dtype=torch.float64)
     assert pl["last"] % 2 == 1
@@ -786,7 +781,6 @@ def test_conv_bounds_see_the_backward_mutants():
 
 def test_highway_bounds_see_a_mutant():
     import test_gpu_bf16_frontend as FE
-    from test_gpu_bf16_faithful import measures
     rows, n = 600, 300
     ref = _hw_run(rows, n, "bffe_hw%dx%d" % (rows, n))
     # dgate = g * proj: the "- x" lost

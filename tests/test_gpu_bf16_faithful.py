@@ -14,24 +14,22 @@ weight-gradient matrix of the stack also has its least-squares scale bounded: no
 
 The stack runs under the default paths, under MMT_NO_FIXED_SHAPES=1 and under MMT_NO_CHAIN4=1 MMT_NO_BWD_BOUNDARY=1; the stand-alone
 attention's one-kernel backward also under MMT_NO_FUSED_ATTN_BWD=1.  The switches are read once per process, so every GPU run of sdpa
-and of the stack happens in a child process (conftest.run_in_fresh_process) that hands its arrays back through an .npz file.
+and of the stack happens in a child process (gpu_harness.run_child, which calls child_main below) that hands its arrays back through an
+.npz file.  The measures (measures, check) are gpu_harness's.
 """
 import json
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import bf16_ref as E
-import conftest
 import recipe as R
+from gpu_harness import _LIN, LIN_REL, _lin_inputs, check, dev, run_child, tmp_dir  # noqa: F401 (dev, tmp_dir: fixtures)
 
 pytestmark = pytest.mark.gpu
 
-# bounds: measured worst on the MI355X in the comments (rel-L2 / per-row maximum)
-LIN_REL = 3e-6                       # 1.6e-7 / 7.2e-7 (fp32 accumulation only), rel-L2 and per row
+# bounds: measured worst on the MI355X in the comments (rel-L2 / per-row maximum); the affine map's LIN_REL is gpu_harness's
 SDPA_OUT, SDPA_OUT_ROW = 4e-4, 1e-2  # 9.9e-5 / 2.6e-3
 SDPA_GRAD = 2e-3                     # 4.5e-4
 # Per row the attention gradients reach 1.4e-2 (dv at T = 511, d_k = 16, eval), the same on the one- and the two-kernel backward.  The
@@ -56,149 +54,67 @@ ENC_CLEAN = {"bfe_d40_n2_T33_p0": (1.5e-3, 7e-3)}
 ENC_W_SCALE = 2e-3
 
 
-def _rows(a):
-    a = np.asarray(a, dtype=np.float64)
-    return a.reshape(-1, 1) if a.ndim == 1 else a.reshape(-1, a.shape[-1]) if a.ndim > 2 else a
-
-
-def measures(got, ref):
-    """(rel-L2, per-row maximum) of got against ref."""
-    g, r = _rows(got), _rows(ref)
-    diff = np.linalg.norm(g - r, axis=1)
-    rms = np.sqrt(np.mean(np.sum(r * r, axis=1)))
-    return float(np.linalg.norm(g - r) / max(np.linalg.norm(r), 1e-300)), float(diff.max() / max(rms, 1e-300))
-
-
-def check(tag, got, ref, rel_bound, row_bound=None, scale_ref=None, failures=None):
-    """scale_ref: measure against another tensor's magnitude (for an analytically zero reference, e.g. the key bias's gradient).
-    failures: a list to append a failure message to instead of raising (every tensor of a case is then reported)."""
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    rel, row = measures(got, ref)
-    if scale_ref is not None:
-        s = np.asarray(scale_ref, dtype=np.float64)
-        rel = float(np.linalg.norm(got - ref) / np.linalg.norm(s))
-        row = float(np.abs(got - ref).max() / np.sqrt(np.mean(s * s)))
-    print("%-52s rel-L2 %.2e  row-max %.2e" % (tag, rel, row))
-    msg = None
-    if not np.isfinite(got).all():
-        msg = "%s: not finite" % tag
-    elif rel > rel_bound:
-        msg = "%s: rel-L2 %.3e > %.1e" % (tag, rel, rel_bound)
-    elif row_bound is not None and row > row_bound:
-        msg = "%s: per-row maximum %.3e > %.1e" % (tag, row, row_bound)
-    if msg and failures is None:
-        raise AssertionError(msg)
-    if msg:
-        failures.append(msg)
-
-
 # ------------------------------------------------------------------------------------------------ child process
-_CHILD = r"""
-import json, sys
-import numpy as np
-import torch
-import bf16_ref as E
-import recipe as R
-from multimodal_transformer_amd import functional as F
-kind, out_path = sys.argv[1], sys.argv[2]
-cases = json.loads(sys.argv[3])
-dev = torch.device("cuda:0")
-out = {}
-for c in cases:
-    cid = c["id"]
-    if kind == "sdpa":
-        B, T, d, h, lengths, p = c["B"], c["T"], c["d"], c["h"], c["lengths"], c["p"]
-        q, k, v, g = (R.gen_normal(cid + n, (B, T, d), 13) for n in "qkvg")
-        mask = R.prefix_mask(lengths, T).to(dev)
-        leaves = [(2 * q).to(dev).requires_grad_(), k.to(dev).requires_grad_(), v.to(dev).requires_grad_()]
-        seed = 1000 + T + d
-        y = F.sdpa(*leaves, mask, h, dropout_p=p, seed=seed)
-        y.backward(g.to(dev))
-        for n, t in zip(("y", "dq", "dk", "dv"), [y.detach()] + [t.grad for t in leaves]):
-            out[cid + ":" + n] = t.cpu().numpy()
-        if p > 0:
-            Tp = -(-T // 32) * 32
-            keep, sc = F.dropout_mask(p, seed, 0, B * h * Tp * Tp, dev, attn_Tp=Tp)
-            out[cid + ":keep"] = keep.reshape(B, h, Tp, Tp)[:, :, :T, :T].cpu().numpy()
-            out[cid + ":scale"] = np.array(sc)
-    else:
-        d, h, n, B, T, lengths, p = c["d"], c["h"], c["n"], c["B"], c["T"], c["lengths"], c["p"]
-        p32 = R.gen_params(E.encoder_param_shapes(d, R.D_FF, n), 17)
-        flat = torch.cat([t.reshape(-1) for t in p32.values()]).to(dev).requires_grad_()
-        x = R.gen_normal(cid + ":x", (B, T, d), 17).to(dev).requires_grad_()
-        g = R.gen_normal(cid + ":g", (B, T, d), 17).to(dev)
-        mask = R.prefix_mask(lengths, T).to(dev)
-        seed = 4242 + d + T
-        y = F.encoder_stack(x, mask, flat, h, R.D_FF, n, dropout_p=p, seed=seed)
-        y.backward(g)
-        out[cid + ":y"], out[cid + ":dx"], out[cid + ":dflat"] = y.detach().cpu().numpy(), x.grad.cpu().numpy(), flat.grad.cpu().numpy()
-        if p > 0:
-            Tp, DP, FP, M = -(-T // 32) * 32, -(-d // 64) * 64, -(-R.D_FF // 64) * 64, B * T
-            for l in range(n):
-                ka, sa = F.dropout_mask(p, seed, 4 * l + 0, B * h * Tp * Tp, dev, attn_Tp=Tp)
-                k0, s0 = F.dropout_mask(p, seed, 4 * l + 1, M * DP, dev)
-                kf, sf = F.dropout_mask(p, seed, 4 * l + 2, M * FP, dev)
-                k1, s1 = F.dropout_mask(p, seed, 4 * l + 3, M * DP, dev)
-                out["%s:attn%d" % (cid, l)] = ka.reshape(B, h, Tp, Tp)[:, :, :T, :T].cpu().numpy()
-                out["%s:sub0%d" % (cid, l)] = k0.reshape(B, T, DP)[:, :, :d].cpu().numpy()
-                out["%s:ffn%d" % (cid, l)] = kf.reshape(B, T, FP)[:, :, :R.D_FF].cpu().numpy()
-                out["%s:sub1%d" % (cid, l)] = k1.reshape(B, T, DP)[:, :, :d].cpu().numpy()
-                out["%s:scales%d" % (cid, l)] = np.array([sa, s0, sf, s1])
-torch.cuda.synchronize()
-F.check_device_errors()
-np.savez(out_path, **out)
-"""
+def child_main(kind, out_path, payload_json):
+    """The GPU runs of every case in the payload, in a process of their own: kind "sdpa" or "enc"."""
+    from multimodal_transformer_amd import functional as F
+    cases = json.loads(payload_json)
+    dev = torch.device("cuda:0")
+    out = {}
+    for c in cases:
+        cid = c["id"]
+        if kind == "sdpa":
+            B, T, d, h, lengths, p = c["B"], c["T"], c["d"], c["h"], c["lengths"], c["p"]
+            q, k, v, g = (R.gen_normal(cid + n, (B, T, d), 13) for n in "qkvg")
+            mask = R.prefix_mask(lengths, T).to(dev)
+            leaves = [(2 * q).to(dev).requires_grad_(), k.to(dev).requires_grad_(), v.to(dev).requires_grad_()]
+            seed = 1000 + T + d
+            y = F.sdpa(*leaves, mask, h, dropout_p=p, seed=seed)
+            y.backward(g.to(dev))
+            for n, t in zip(("y", "dq", "dk", "dv"), [y.detach()] + [t.grad for t in leaves]):
+                out[cid + ":" + n] = t.cpu().numpy()
+            if p > 0:
+                Tp = -(-T // 32) * 32
+                keep, sc = F.dropout_mask(p, seed, 0, B * h * Tp * Tp, dev, attn_Tp=Tp)
+                out[cid + ":keep"] = keep.reshape(B, h, Tp, Tp)[:, :, :T, :T].cpu().numpy()
+                out[cid + ":scale"] = np.array(sc)
+        else:
+            d, h, n, B, T, lengths, p = c["d"], c["h"], c["n"], c["B"], c["T"], c["lengths"], c["p"]
+            p32 = R.gen_params(E.encoder_param_shapes(d, R.D_FF, n), 17)
+            flat = torch.cat([t.reshape(-1) for t in p32.values()]).to(dev).requires_grad_()
+            x = R.gen_normal(cid + ":x", (B, T, d), 17).to(dev).requires_grad_()
+            g = R.gen_normal(cid + ":g", (B, T, d), 17).to(dev)
+            mask = R.prefix_mask(lengths, T).to(dev)
+            seed = 4242 + d + T
+            y = F.encoder_stack(x, mask, flat, h, R.D_FF, n, dropout_p=p, seed=seed)
+            y.backward(g)
+            out[cid + ":y"], out[cid + ":dx"], out[cid + ":dflat"] = y.detach().cpu().numpy(), x.grad.cpu().numpy(), flat.grad.cpu().numpy()
+            if p > 0:
+                Tp, DP, FP, M = -(-T // 32) * 32, -(-d // 64) * 64, -(-R.D_FF // 64) * 64, B * T
+                for l in range(n):
+                    ka, sa = F.dropout_mask(p, seed, 4 * l + 0, B * h * Tp * Tp, dev, attn_Tp=Tp)
+                    k0, s0 = F.dropout_mask(p, seed, 4 * l + 1, M * DP, dev)
+                    kf, sf = F.dropout_mask(p, seed, 4 * l + 2, M * FP, dev)
+                    k1, s1 = F.dropout_mask(p, seed, 4 * l + 3, M * DP, dev)
+                    out["%s:attn%d" % (cid, l)] = ka.reshape(B, h, Tp, Tp)[:, :, :T, :T].cpu().numpy()
+                    out["%s:sub0%d" % (cid, l)] = k0.reshape(B, T, DP)[:, :, :d].cpu().numpy()
+                    out["%s:ffn%d" % (cid, l)] = kf.reshape(B, T, FP)[:, :, :R.D_FF].cpu().numpy()
+                    out["%s:sub1%d" % (cid, l)] = k1.reshape(B, T, DP)[:, :, :d].cpu().numpy()
+                    out["%s:scales%d" % (cid, l)] = np.array([sa, s0, sf, s1])
+    torch.cuda.synchronize()
+    F.check_device_errors()
+    np.savez(out_path, **out)
+
 
 _SWITCHES = {"default": {}, "no_fused_attn_bwd": {"MMT_NO_FUSED_ATTN_BWD": "1"}, "no_fixed_shapes": {"MMT_NO_FIXED_SHAPES": "1"},
              "no_chain4_boundary": {"MMT_NO_CHAIN4": "1", "MMT_NO_BWD_BOUNDARY": "1"}}
-_RUNS = {}
 
 
 def _child(kind, switch, cases, tmp_dir):
-    key = (kind, switch)
-    if key not in _RUNS:
-        env = dict(os.environ)
-        for s in _SWITCHES.values():
-            for k in s:
-                env.pop(k, None)
-        env.update(_SWITCHES[switch])
-        env["PYTHONPATH"] = os.pathsep.join([conftest.ROOT, os.path.join(conftest.ROOT, "tests"), conftest.GOLDEN,
-                                             env.get("PYTHONPATH", "")])
-        out = os.path.join(str(tmp_dir), "%s_%s.npz" % key)
-        res = conftest.run_in_fresh_process([sys.executable, "-c", _CHILD, kind, out, json.dumps(cases)], env, timeout=300)
-        if res is None:
-            pytest.skip("no launcher process (tests were collected with the GPU already initialised)")
-        assert res["rc"] == 0, res["stderr"][-3000:]
-        with np.load(out) as z:
-            _RUNS[key] = {k: z[k] for k in z.files}
-    return _RUNS[key]
-
-
-@pytest.fixture(scope="module")
-def tmp_dir(tmp_path_factory):
-    return tmp_path_factory.mktemp("bf16_faithful")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
+    return run_child(__name__, kind, switch, cases, tmp_dir, _SWITCHES, timeout=300)
 
 
 # ------------------------------------------------------------------------------------------------ linear
-_LIN = [(1, 4, 1, 0, False), (31, 5, 5, 1, False), (32, 43, 129, 0, True), (33, 301, 256, 1, True), (200, 576, 129, 1, False),
-        (200, 43, 256, 0, False), (33, 576, 1, 0, True), (1, 301, 129, 1, False), (32, 4, 256, 1, True), (200, 5, 5, 0, True),
-        (31, 576, 256, 0, False), (200, 301, 1, 1, True)]
-
-
-def _lin_inputs(M, K, N, tag):
-    x = R.gen_normal(tag + "x", (M, K), 5)
-    W = R.gen_normal(tag + "w", (N, K), 5) / np.sqrt(K)
-    b = 0.1 * R.gen_normal(tag + "b", (N,), 5)
-    g = R.gen_normal(tag + "g", (M, N), 5)
-    return x, W, b, g
-
-
 def _lin_compare(tag, y, leaves, x, W, b, g, **kw):
     ld = [t.double().requires_grad_() for t in (x, W, b)]
     ref = E.linear(*ld, **kw)

@@ -33,8 +33,7 @@ import torch
 
 import bf16_ref as E
 import recipe as R
-from test_gpu_bf16_faithful import _LIN, LIN_REL, _lin_inputs, check, measures
-from test_gpu_bf16_scans import ls_scale
+from gpu_harness import _LIN, LIN_REL, _lin_inputs, check, dev, device_kernel_names, ls_scale, measures  # noqa: F401 (dev: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -60,12 +59,6 @@ HW_W_SCALE = 1.5e-5                    # 3.6e-6
 # Highway's dx
 CHAIN_OUT = (6.5e-5, 2.1e-3)           # 1.6e-5 / 5.2e-4
 CHAIN_GRAD = (4.6e-4, 3.4e-3)          # 1.2e-4 / 8.4e-4
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------------------------ conv cases
@@ -141,17 +134,6 @@ _FWD = re.compile(r"convpool_fwd_kernel<\s*(\d+)\s*>")
 _BWD = re.compile(r"convpool_bwd_kernel<\s*(\w+)\s*>")
 
 
-def profiled(fn):
-    """fn() under torch.profiler -> (result, names of the device kernels, or None where the profiler reports none)"""
-    from torch.autograd import DeviceType
-    from torch.profiler import profile, ProfilerActivity
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        res = fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events() if e.device_type == DeviceType.CUDA]
-    return res, (names or None)
-
-
 def check_conv_ran(tag, names, plan):
     if names is None:
         return                               # the profiler reports no device kernels on this box: only this assertion is skipped
@@ -178,7 +160,7 @@ def conv_run(c, dev):
         out, arg = F.conv_maxpool(xg, wd, bd)
         out.backward(gg)
         return out.detach(), arg
-    (out, arg), names = profiled(step)
+    (out, arg), names = device_kernel_names(step)
     F.check_device_errors()
     S, A = E.conv_sums(x.double(), w.double())
     _CONV_RUNS[c["id"]] = {"out": out.cpu(), "arg": arg.cpu().long(), "dW": wd.grad.cpu(), "db": bd.grad.cpu(), "names": names, "S": S,
@@ -382,7 +364,7 @@ def test_linear_pair(dev, M, K, N1, N2, absent):
     r1, r2 = E.linear_pair(*ld, act1=1, act2=0)
     loss(r1, r2, g1.double(), g2.double()).backward()
     failures = []
-    # ReLU and no activation: test_gpu_bf16_faithful's bound for the single affine map (measured here 8.8e-8 / 1.2e-7, dx 1.8e-7 / 3.1e-7)
+    # ReLU and no activation: the single affine map's bound LIN_REL (measured here 8.8e-8 / 1.2e-7, dx 1.8e-7 / 3.1e-7)
     check(tag + " y1", y1.detach().cpu(), r1.detach(), LIN_REL, LIN_REL, failures=failures)
     check(tag + " y2", y2.detach().cpu(), r2.detach(), LIN_REL, LIN_REL, failures=failures)
     for i, n in enumerate(("dx", "dW1", "db1", "dW2", "db2")):
@@ -429,7 +411,7 @@ def test_window_encoder_chain(dev, mod, Fo, B, T, train):
         y = F.highway(e, *(pg[n] for n in names[2:]), dropout_p=p, seed=seed).reshape(B, T, Fo)
         y.backward(g.to(dev))
         return y.detach(), arg
-    (y, arg), knames = profiled(step)
+    (y, arg), knames = device_kernel_names(step)
     check_conv_ran(tag, knames, plan)
     drop = None
     if train:

@@ -4,7 +4,7 @@ test_gpu_models.py checks the scans against a plain fp64 loop with one rel-L2 ov
 gradients.  One wrong sequence of a few hundred, a few wrong time steps or one wrong 16-unit tile pass that.  Here the reference rounds
 where the kernels round, so the bounds sit one to two orders of magnitude lower, and every tensor is measured four ways:
   * rel-L2 of the tensor;
-  * the per-row maximum (test_gpu_bf16_faithful.measures): a row is one (t, b) for h, c, dgx, mem, dapre and dchat, one sequence for
+  * the per-row maximum (gpu_harness.measures): a row is one (t, b) for h, c, dgx, mem, dapre and dchat, one sequence for
     dh0 and dc0, one output feature for the weight gradients, one entry for db2;
   * the per-sequence maximum  max_b ||got[:, b] - ref[:, b]|| / rms_b ||ref[:, b]||  of the (T, B, .) tensors;
   * the least-squares scale <got - ref, ref> / <ref, ref> of the weight gradients.
@@ -13,22 +13,19 @@ Every dispatch branch of plan_lstm_scan (one plan for mmt_lstm_scan_forward and 
 (csrc/api.hip) has cases, and each
 case asserts through torch.profiler that the kernel it is labelled for ran.  The four-CU scans (scan_cluster.h) run once more under
 MMT_NO_CLUSTER_SCAN=1, where the same shapes go to scan256.h; those results are checked against the reference and against the four-CU
-ones.  The switch is read once per process, so all GPU work happens in child processes (conftest.run_in_fresh_process) that hand their
-arrays back through an .npz file.
+ones.  The switch is read once per process, so all GPU work happens in child processes (gpu_harness.run_child, which calls child_main
+below) that hand their arrays back through an .npz file.  The measures (check_scan over check, seq_max and ls_scale) are gpu_harness's.
 """
 import json
-import os
 import re
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import bf16_ref as E
-import conftest
 import recipe as R
-from test_gpu_bf16_faithful import check, measures
+from gpu_harness import check_scan, device_kernel_names, run_child, tmp_dir  # noqa: F401 (tmp_dir: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -66,36 +63,6 @@ MFN_W_SCALE = 6e-4                     # 1.5e-4 (dWm at T = 300)
 
 def mfn_bounds(c):
     return MFN_EXACT if c["B"] == 1 and c["T"] <= 3 else MFN_SHORT if c["T"] <= 6 else MFN_LONG
-
-
-def seq_max(got, ref):
-    """max_b ||got[:, b] - ref[:, b]|| / rms_b ||ref[:, b]|| of (T, B, ...) tensors: the worst single sequence across all t."""
-    g = np.asarray(got, dtype=np.float64)
-    r = np.asarray(ref, dtype=np.float64)
-    g, r = g.reshape(g.shape[0], g.shape[1], -1), r.reshape(r.shape[0], r.shape[1], -1)
-    diff = np.sqrt(((g - r) ** 2).sum(axis=(0, 2)))
-    return float(diff.max() / max(np.sqrt((r * r).sum(axis=(0, 2)).mean()), 1e-300))
-
-
-def ls_scale(got, ref):
-    """<got - ref, ref> / <ref, ref>: a wrongly scaled term moves it, noise hardly does."""
-    r = np.asarray(ref, dtype=np.float64).ravel()
-    return float(np.dot(np.asarray(got, dtype=np.float64).ravel() - r, r) / np.dot(r, r))
-
-
-def check_scan(tag, got, ref, bounds, failures, seq=False, scale=None):
-    """rel-L2 and per-row maximum through check(); with seq the per-sequence maximum, with scale (its bound) the least-squares scale."""
-    check(tag, got, ref, bounds[0], bounds[1], failures=failures)
-    if seq:
-        s = seq_max(got, ref)
-        print("%-52s seq-max %.2e" % (tag, s))
-        if s > bounds[2]:
-            failures.append("%s: per-sequence maximum %.3e > %.1e" % (tag, s, bounds[2]))
-    if scale is not None:
-        s = ls_scale(got, ref)
-        print("%-52s scale %.2e" % (tag, s))
-        if abs(s) > scale:
-            failures.append("%s: least-squares scale %.3e > %.1e" % (tag, s, scale))
 
 
 # ------------------------------------------------------------------------------------------------ dispatch (csrc/api.hip)
@@ -237,89 +204,61 @@ def lstm_loss(h, c, gh, gc):
 
 
 # ------------------------------------------------------------------------------------------------ child process
-_CHILD = r"""
-import json, sys
-import numpy as np
-import torch
-from torch.autograd import DeviceType
-from torch.profiler import profile, ProfilerActivity
-import test_gpu_bf16_scans as S
-from multimodal_transformer_amd import functional as F
-kind, out_path = sys.argv[1], sys.argv[2]
-ids = set(json.loads(sys.argv[3]))
-dev = torch.device("cuda:0")
-out = {}
-def run(fn):
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        res = fn()
-        torch.cuda.synchronize()
-    F.check_device_errors()                 # the four-CU scans' exchange time-out word must be zero
-    return res, [e.name for e in prof.events() if e.device_type == DeviceType.CUDA]
-for c in (S.LSTM_CASES if kind == "lstm" else S.MFN_CASES):
-    cid = c["id"]
-    if cid not in ids:
-        continue
-    if kind == "lstm":
-        gx, W, h0, c0, gh, gc = (None if t is None else t.to(dev) for t in S.lstm_inputs(c))
-        leaves = [None if t is None else t.requires_grad_() for t in (gx, W, h0, c0)]
-        def step():
-            h, cc = F.lstm_scan(*leaves)
-            S.lstm_loss(h, cc, gh, gc).backward()
-            return h.detach(), cc.detach()
-        (h, cc), names = run(step)
-        res = {"h": h, "c": cc, "dgx": leaves[0].grad, "dW": leaves[1].grad}
-        if c["init"]:
-            res["dh0"], res["dc0"] = leaves[2].grad, leaves[3].grad
-    else:
-        apre, chat, Wm, W2, b2, g = (t.to(dev) for t in S.mfn_inputs(c))
-        leaves = [t.requires_grad_() for t in (apre, chat, Wm, W2, b2)]
-        T, B, p, seed = c["T"], c["B"], c["p"], S.mfn_seed(c)
-        def step():
-            mem = F.mfn_mem_scan(*leaves, dropout_p=p, seed=seed)
-            (mem * g).sum().backward()
-            return mem.detach()
-        mem, names = run(step)
-        res = dict(zip(("mem", "dapre", "dchat", "dWm", "dW2", "db2"), [mem] + [t.grad for t in leaves]))
-        if p > 0:
-            keep, sc = F.dropout_mask(p, seed, 1000, T * B * 128, dev)
-            res["keep"] = keep.reshape(T, B, 128)
-            out[cid + ":scale"] = np.array(sc)
-    for k, v in res.items():
-        out[cid + ":" + k] = v.cpu().numpy()
-    out[cid + ":names"] = np.array(json.dumps(names if names else None))
-torch.cuda.synchronize()
-F.check_device_errors()
-np.savez(out_path, **out)
-"""
+def child_main(kind, out_path, payload_json):
+    """The GPU runs of the cases whose ids the payload lists, in a process of their own: kind "lstm" or "mfn"."""
+    from multimodal_transformer_amd import functional as F
+    ids = set(json.loads(payload_json))
+    dev = torch.device("cuda:0")
+    out = {}
+
+    def run(fn):
+        res, names = device_kernel_names(fn)
+        F.check_device_errors()                 # the four-CU scans' exchange time-out word must be zero
+        return res, names
+    for c in (LSTM_CASES if kind == "lstm" else MFN_CASES):
+        cid = c["id"]
+        if cid not in ids:
+            continue
+        if kind == "lstm":
+            gx, W, h0, c0, gh, gc = (None if t is None else t.to(dev) for t in lstm_inputs(c))
+            leaves = [None if t is None else t.requires_grad_() for t in (gx, W, h0, c0)]
+
+            def step():
+                h, cc = F.lstm_scan(*leaves)
+                lstm_loss(h, cc, gh, gc).backward()
+                return h.detach(), cc.detach()
+            (h, cc), names = run(step)
+            res = {"h": h, "c": cc, "dgx": leaves[0].grad, "dW": leaves[1].grad}
+            if c["init"]:
+                res["dh0"], res["dc0"] = leaves[2].grad, leaves[3].grad
+        else:
+            apre, chat, Wm, W2, b2, g = (t.to(dev) for t in mfn_inputs(c))
+            leaves = [t.requires_grad_() for t in (apre, chat, Wm, W2, b2)]
+            T, B, p, seed = c["T"], c["B"], c["p"], mfn_seed(c)
+
+            def step():
+                mem = F.mfn_mem_scan(*leaves, dropout_p=p, seed=seed)
+                (mem * g).sum().backward()
+                return mem.detach()
+            mem, names = run(step)
+            res = dict(zip(("mem", "dapre", "dchat", "dWm", "dW2", "db2"), [mem] + [t.grad for t in leaves]))
+            if p > 0:
+                keep, sc = F.dropout_mask(p, seed, 1000, T * B * 128, dev)
+                res["keep"] = keep.reshape(T, B, 128)
+                out[cid + ":scale"] = np.array(sc)
+        for k, v in res.items():
+            out[cid + ":" + k] = v.cpu().numpy()
+        out[cid + ":names"] = np.array(json.dumps(names))
+    torch.cuda.synchronize()
+    F.check_device_errors()
+    np.savez(out_path, **out)
+
 
 _SWITCHES = {"default": {}, "no_cluster": {"MMT_NO_CLUSTER_SCAN": "1"}}
-_RUNS = {}
 
 
 def _child(kind, switch, cases, tmp_dir):
-    key = (kind, switch)
-    if key not in _RUNS:
-        env = dict(os.environ)
-        for s in _SWITCHES.values():
-            for k in s:
-                env.pop(k, None)
-        env.update(_SWITCHES[switch])
-        env["PYTHONPATH"] = os.pathsep.join([conftest.ROOT, os.path.join(conftest.ROOT, "tests"), conftest.GOLDEN,
-                                             env.get("PYTHONPATH", "")])
-        out = os.path.join(str(tmp_dir), "%s_%s.npz" % key)
-        res = conftest.run_in_fresh_process([sys.executable, "-c", _CHILD, kind, out, json.dumps([c["id"] for c in cases])], env,
-                                            timeout=600)
-        if res is None:
-            pytest.skip("no launcher process (tests were collected with the GPU already initialised)")
-        assert res["rc"] == 0, res["stderr"][-3000:]
-        with np.load(out) as z:
-            _RUNS[key] = {k: z[k] for k in z.files}
-    return _RUNS[key]
-
-
-@pytest.fixture(scope="module")
-def tmp_dir(tmp_path_factory):
-    return tmp_path_factory.mktemp("bf16_scans")
+    return run_child(__name__, kind, switch, [c["id"] for c in cases], tmp_dir, _SWITCHES, timeout=600)
 
 
 def _names(run, cid):

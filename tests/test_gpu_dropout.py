@@ -13,16 +13,10 @@ import torch
 
 import oracle
 import recipe as R
-from test_gpu_parity import OUT_RTOL, RELU_GRAD_RTOL, CCC_MIN, _report, mta
 from conftest import grad_close
+from gpu_harness import OUT_RTOL, RELU_GRAD_RTOL, CCC_MIN, _report, dev, mta  # noqa: F401 (dev: a fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def _masks(dev, p, seed, n_layers, B, T, d, h, f):

@@ -8,28 +8,13 @@ import torch
 import oracle
 import recipe as R
 from conftest import rel_l2
+from gpu_harness import OUT_RTOL, RELU_GRAD_RTOL, dev, seeded_encoder  # noqa: F401 (dev: a fixture)
 
 pytestmark = pytest.mark.gpu
-OUT_RTOL = 2e-2
-RELU_GRAD_RTOL = 9e-2
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-def _encoder(d, h, n, dev, seed=17):
-    from multimodal_transformer_amd import multiTransformer as MT
-    enc = MT.Encoder(MT.EncoderLayer(d, MT.MultiHeadedAttention(h, d), MT.PositionwiseFeedForward(d, R.D_FF, 0.1), 0.1), n)
-    p32 = R.gen_params(R.shapes_of(enc.state_dict()), seed)
-    enc.load_state_dict(p32)
-    return enc.to(dev).eval(), p32
 
 
 def _check_encoder(dev, d, h, n, B, T, lengths, tag):
-    enc, p32 = _encoder(d, h, n, dev)
+    enc, p32 = seeded_encoder(d, h, n, dev, 17)
     x = R.gen_normal(tag + ":x", (B, T, d), 17)
     g = R.gen_normal(tag + ":g", (B, T, d), 17)
     mask = R.prefix_mask(lengths, T)
@@ -82,7 +67,7 @@ def test_wide_model_512(dev):
 def test_long_sequence_eval_and_dropout_limit(dev):
     """T = 2500 runs in eval mode; train-mode attention dropout is limited to T <= 4096 (24-bit pair index) and says so"""
     from multimodal_transformer_amd import multiTransformer as MT
-    enc, p32 = _encoder(128, 8, 1, dev)
+    enc, p32 = seeded_encoder(128, 8, 1, dev, 17)
     T = 2500
     x = R.gen_normal("edge:long:x", (1, T, 128), 17)
     mask = R.prefix_mask([T], T)
@@ -126,7 +111,7 @@ def test_refusals(dev):
 def test_encoder_gradients_share_one_flat_buffer(dev):
     """data parallelism reduces ONE buffer per step: every parameter gradient of the fused stack must be a view of it"""
     from multimodal_transformer_amd import parallel
-    enc, _ = _encoder(128, 8, 3, dev)
+    enc, _ = seeded_encoder(128, 8, 3, dev, 17)
     enc.train()
     x = torch.randn(2, 40, 128, device=dev, requires_grad=True)
     enc(x, torch.ones(2, 40, 1, device=dev)).sum().backward()
@@ -273,7 +258,7 @@ def test_results_do_not_depend_on_unwritten_lds(dev, d, h, B, T, p):
     """a kernel may only read LDS it wrote: fill every CU's LDS with NaN bit patterns between two identical seeded runs
     (what the first process on a freshly powered GPU can find there) and require bit-identical outputs and gradients"""
     from multimodal_transformer_amd import functional as F
-    enc, _ = _encoder(d, h, 2, dev)
+    enc, _ = seeded_encoder(d, h, 2, dev, 17)
     flat = torch.cat([q.reshape(-1) for q in enc.flat_parameters()]).detach()
     x = R.gen_normal("poison:x", (B, T, d), 23).to(dev)
     g = R.gen_normal("poison:g", (B, T, d), 23).to(dev)
@@ -317,7 +302,7 @@ def test_second_backward_of_one_forward_raises(dev, op):
     elif op == "highway":
         y = F.highway(x, leaf(d, d), leaf(d), leaf(d, d), leaf(d), dropout_p=0.3, seed=3)
     elif op == "encoder_stack":
-        enc, _ = _encoder(d, h, 2, dev)
+        enc, _ = seeded_encoder(d, h, 2, dev, 17)
         flat = torch.cat([q.reshape(-1) for q in enc.flat_parameters()]).detach().requires_grad_()
         y = F.encoder_stack(x, mask, flat, h, R.D_FF, 2, dropout_p=0.1, seed=3)
     else:

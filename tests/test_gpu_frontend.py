@@ -1,7 +1,7 @@
 """GPU parity of the window-encoder front-end (csrc/convpool.h, multimodal_transformer_amd/models.py) against the
 fixtures captured from the reference's models.py and against the CPU oracle.
 
-Tolerances as in test_gpu_parity.py (bf16 MFMA operands, fp32 accumulation): outputs <= 2e-2 rel-L2.  The max-pool
+Tolerances as in test_gpu_parity.py's docstring (gpu_harness.py's constants; bf16 MFMA operands, fp32 accumulation): outputs <= 2e-2 rel-L2.  The max-pool
 adds an index choice: where two conv positions of a window tie to within bf16 round-off the kernel may pick the other
 one, which reroutes that (window, channel)'s whole gradient — the same mechanism as a ReLU mask flip — so weight
 gradients are compared (a) tightly against the exact gradient FOR THE KERNEL'S OWN argmax, and (b) against the
@@ -17,19 +17,9 @@ import torch
 import oracle
 import recipe as R
 from conftest import load_golden, rel_l2, grad_close
+from gpu_harness import OUT_RTOL, GRAD_RTOL, RELU_GRAD_RTOL, dev, load_named  # noqa: F401 (dev: a fixture)
 
 pytestmark = pytest.mark.gpu
-
-OUT_RTOL = 2e-2
-GRAD_RTOL = 4e-2
-RELU_GRAD_RTOL = 9e-2
-CCC_MIN = 1 - 1e-3
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
 
 
 def _conv_fp64(x, w, b):
@@ -121,17 +111,11 @@ def test_conv_maxpool_rejects_what_it_cannot_do(dev):
         F.conv_maxpool(torch.zeros(3, 5, 16), torch.zeros(8, 16, 2), torch.zeros(8))               # CPU tensors
 
 
-def _load_named(model, seed=R.SEED):
-    p32 = R.gen_params(R.shapes_of(model.state_dict()), seed)
-    model.load_state_dict(p32)
-    return p32
-
-
 def test_highway_golden(dev):
     from multimodal_transformer_amd import models as M
     fx = load_golden("fe_highway")
     hw = M.Highway(256)
-    p32 = _load_named(hw)
+    p32 = load_named(hw)
     assert abs(R.weights_checksum(p32) - float(fx["checksum"])) <= 1e-6 * float(fx["checksum"])
     hw = hw.to(dev)
     x = R.gen_normal("fe_highway:x", (12, 256), R.SEED).to(dev).requires_grad_()
@@ -153,7 +137,7 @@ def test_highway_train_mode_mask_replay(dev, shape):
     from multimodal_transformer_amd import models as M, functional as F
     rows, n = shape
     hw = M.Highway(n)
-    p32 = _load_named(hw)
+    p32 = load_named(hw)
     hw = hw.to(dev)
     x_c = R.gen_normal("fe_highway_drop:x%d" % n, (rows, n), R.SEED)
     g_c = R.gen_normal("fe_highway_drop:g%d" % n, (rows, n), R.SEED)
@@ -196,7 +180,7 @@ def test_multi_cnn_transformer_golden(dev, name, cls, mods, extra):
     from multimodal_transformer_amd import models as M, eval_ccc
     fx = load_golden(name)
     model = getattr(M, cls)(mods, R.FE_DIMS, *extra, device=dev)
-    p32 = _load_named(model)
+    p32 = load_named(model)
     assert abs(R.weights_checksum(p32) - float(fx["checksum"])) <= 1e-6 * float(fx["checksum"]), "state_dict differs from the reference's"
     model = model.to(dev).eval()
     lengths = list(fx["lengths"])

@@ -19,12 +19,9 @@ import torch
 import oracle
 import recipe as R
 from conftest import rel_l2
+from gpu_harness import OUT_RTOL, RELU_GRAD_RTOL, CCC_MIN, dev, load_named, seeded_encoder  # noqa: F401 (dev: a fixture)
 
 pytestmark = pytest.mark.gpu
-
-OUT_RTOL = 2e-2
-RELU_GRAD_RTOL = 9e-2
-CCC_MIN = 1 - 1e-3
 
 FULL = {
     "C2": dict(B=32, T=300, d=40, h=4, N=6),          # configs[1]: d_k = 10 (a padded head), T in the one-kernel-backward range
@@ -32,21 +29,6 @@ FULL = {
     "C4x8": dict(B=256, T=500, d=128, h=8, N=6),      # configs[3] WHOLE batch on one GPU (bench.py's config_full_batch line)
     "C5e": dict(B=16, T=1000, d=256, h=8, N=6),       # 16 of the 64 sequences/GPU of configs[4]: same T, d, h, N
 }
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-def _encoder(cfg, dev, seed):
-    from multimodal_transformer_amd import multiTransformer as MT
-    d, h, n = cfg["d"], cfg["h"], cfg["N"]
-    proto = MT.Encoder(MT.EncoderLayer(d, MT.MultiHeadedAttention(h, d), MT.PositionwiseFeedForward(d, R.D_FF, 0.1), 0.1), n)
-    p32 = R.gen_params(R.shapes_of(proto.state_dict()), seed)
-    proto.load_state_dict(p32)
-    return proto.to(dev).eval(), p32
 
 
 def _lengths(B, T):
@@ -70,7 +52,7 @@ def _run(enc, x, mask, g):
 def test_full_size_properties_and_oracle_rows(dev, name):
     cfg = FULL[name]
     B, T, d, h = cfg["B"], cfg["T"], cfg["d"], cfg["h"]
-    enc, p32 = _encoder(cfg, dev, 5)
+    enc, p32 = seeded_encoder(d, h, cfg["N"], dev, 5)
     lengths = _lengths(B, T)
     mask_c = R.prefix_mask(lengths, T)
     x_c = R.gen_normal(name + ":full:x", (B, T, d), 5)
@@ -186,12 +168,6 @@ def test_full_size_blank_rows_are_uniform_attention(dev):
     assert torch.equal(F.sdpa(q2, k, v, mask, h), out)
 
 
-def _load_named(model, seed):
-    p32 = R.gen_params(R.shapes_of(model.state_dict()), seed)
-    model.load_state_dict(p32)
-    return p32
-
-
 def _check_sequences(name, model_out, oracle_fn, lengths, picks):
     """model_out: (B,T,1) valence of the full batch on the GPU; oracle_fn(b) -> (1,T,1) CPU reference of sequence b."""
     from multimodal_transformer_amd import eval_ccc
@@ -219,7 +195,7 @@ def test_full_size_sft_model_configs3(dev):
     from multimodal_transformer_amd import multiTransformer as MT
     B, T = 32, 500
     model = MT.NLPTransformer(512, embed_dim=128, h=8, device=dev)
-    p32 = _load_named(model, 9)
+    p32 = load_named(model, 9)
     model = model.to(dev).eval()
     lengths = _lengths(B, T)
     mask_c = R.prefix_mask(lengths, T)
@@ -239,7 +215,7 @@ def test_full_size_mft_model_configs2(dev):
     B, T = 32, 300
     mods = R.MODS_AVL
     model = MT.MultiTransformer(mods, R.EMBED_AVL, device=dev)
-    p32 = _load_named(model, 13)
+    p32 = load_named(model, 13)
     model = model.to(dev).eval()
     lengths = _lengths(B, T)
     mask_c = R.prefix_mask(lengths, T)
@@ -272,7 +248,7 @@ def test_full_size_mft_model_configs4(dev):
     B, T = 64, 1000
     mods = R.MODS_AVL
     model = MT.MultiTransformer(mods, R.EMBED_AVL, device=dev)
-    p32 = _load_named(model, 29)
+    p32 = load_named(model, 29)
     model = model.to(dev).eval()
     lengths = _lengths(B, T)
     mask_c = R.prefix_mask(lengths, T)
@@ -303,7 +279,7 @@ def test_sub_batch_streams_match_single_stream(dev):
     parameter gradients to summation order; in train mode the step runs and every gradient is finite."""
     cfg = FULL["C4"]
     B, T, d = cfg["B"], cfg["T"], cfg["d"]
-    enc, _ = _encoder(cfg, dev, 5)
+    enc, _ = seeded_encoder(d, cfg["h"], cfg["N"], dev, 5)
     lengths = _lengths(B, T)
     mask = R.prefix_mask(lengths, T).to(dev)
     x = R.gen_normal("split:x", (B, T, d), 5).to(dev)

@@ -2,7 +2,7 @@
 
 * functional.local_attention (csrc/local_attn.h) against an fp64 torch restatement of the reference's softmax(dim=1) + pad_packed
   zeroing + convolve (transformer/B1-LSTM/models.py:10-25,186-207), forward and both gradients, and bit-identical on a second run;
-* the models against the fixtures of tests/golden/make_golden_lstm.py (eval mode, the tolerances of test_gpu_frontend.py);
+* the models against the fixtures of tests/golden/make_golden_lstm.py (eval mode, the tolerances of gpu_harness.py);
 * a train-mode step: finite, not the eval result, repeatable from the same generator state, hand-written kernels only, and the same
   bits when replayed from a hipGraph.
 """
@@ -13,20 +13,11 @@ import torch
 import lstm_cases as C
 import recipe as R
 from conftest import load_golden, rel_l2
+from gpu_harness import OUT_RTOL, RELU_GRAD_RTOL, CCC_MIN, dev, device_kernel_names, library_kernels  # noqa: F401 (dev: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-OUT_RTOL = 2e-2
-GRAD_RTOL = 4e-2
-RELU_GRAD_RTOL = 9e-2
-CCC_MIN = 1 - 1e-3
 LA_RTOL = 1e-5
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
 
 
 def _local_attention_fp64(z, h, valid):
@@ -236,25 +227,6 @@ def test_train_step_finite_differs_from_eval_and_repeats(dev):
     assert (y.cpu()[R.prefix_mask(lengths, y.shape[1]) == 0] == 0).all()
 
 
-def _device_kernel_names(step):
-    """names of the device kernels one call of `step` launches (torch.profiler); None if the profiler reports no device activity"""
-    from torch.profiler import profile, ProfilerActivity
-    from torch.autograd import DeviceType
-    step()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        step()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events() if e.device_type == DeviceType.CUDA]
-    return names or None
-
-
-def _library_kernels(names):
-    """kernels that are not ours: ATen element-wise / reduction / copy / cat kernels, rocBLAS / hipBLASLt / MIOpen GEMMs"""
-    bad = ("at::", "at_cuda", "elementwise", "Cijk_", "rocblas", "hipblas", "miopen", "MIOpen", "CatArray", "reduce_kernel", "vectorized_")
-    return sorted(set(n for n in names if any(b in n for b in bad)))
-
-
 @pytest.mark.parametrize("which", ["b1", "b3"])
 def test_train_step_runs_no_library_kernel(dev, which):
     from multimodal_transformer_amd import models as M
@@ -270,13 +242,13 @@ def test_train_step_runs_no_library_kernel(dev, which):
         x = {m: R.gen_normal("b3nolib:" + m, (B, T, wl[m], dims[m]), 3).to(dev) for m in mods}
     model.train()
     step, params = _step_fn(model, x, lengths, mask, tgt)
-    names = _device_kernel_names(step)
+    names = device_kernel_names(step, warm=True)[1]
     if names is None:
         pytest.skip("torch.profiler reports no device kernels here")
     assert len([n for n in names if "kernel" in n]) > 10, names[:10]
     if which == "b1":
         assert any("local_attn" in n for n in names)
-    assert _library_kernels(names) == [], "library kernels in a %s train step: %s" % (which, _library_kernels(names))
+    assert library_kernels(names) == [], "library kernels in a %s train step: %s" % (which, library_kernels(names))
     for p in params:
         assert p.grad is None or torch.isfinite(p.grad).all()
 

@@ -1,6 +1,6 @@
 """GPU parity tests for the T-sequential scans and the sequence models (HIP path vs oracle / golden).
 
-Tolerances as in test_gpu_parity.py (bf16 MFMA operands, fp32 state): outputs within OUT_RTOL relative-L2,
+Tolerances as in test_gpu_parity.py's docstring (gpu_harness's constants; bf16 MFMA operands, fp32 state): outputs within OUT_RTOL relative-L2,
 gradients within GRAD_RTOL (RELU_GRAD_RTOL where a ReLU lies on the path), valence CCC >= 1 - 1e-3, and the
 mask product exact (outputs are exactly 0 where mask == 0).
 """
@@ -11,15 +11,10 @@ import torch
 import oracle
 import recipe as R
 from conftest import load_golden, rel_l2, grad_close
-from test_gpu_parity import OUT_RTOL, GRAD_RTOL, RELU_GRAD_RTOL, CCC_MIN, _report, mta
+from gpu_harness import (OUT_RTOL, GRAD_RTOL, RELU_GRAD_RTOL, CCC_MIN, _report, dev, device_kernel_names, library_kernels,  # noqa: F401
+                         load_named, mta)                                                                  # (dev: a fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def _oracle_lstm(gx, W, h0, c0):
@@ -147,7 +142,7 @@ def test_mfn_gate_train_mode_mask_replay(dev, T, B, monkeypatch):
     MT, F, L = mta().multiTransformer, mta().functional, mta()._lib
     mods = R.MODS_AVL
     mfn = MT.MFN(mods, {m: 256 for m in mods}, 1, device=dev)
-    p32 = _load_into(mfn, seed=31)
+    p32 = load_named(mfn, seed=31)
     mfn = mfn.to(dev).train()
     seeds = {2: 777001 + T, 4: 777002 + T}
     real = L.next_dropout_seed
@@ -177,18 +172,12 @@ def test_mfn_gate_train_mode_mask_replay(dev, T, B, monkeypatch):
         assert grad_close(got, want, RELU_GRAD_RTOL, 3e-3 * scale), "%s: rel-L2 %.3e" % (n, rel_l2(got, want))
 
 
-def _load_into(module, seed=R.SEED):
-    p32 = R.gen_params(R.shapes_of(module.state_dict()), seed)
-    module.load_state_dict(p32)
-    return p32
-
-
 def test_mfn_gate_golden(dev):
     fx = load_golden("mfn_avl")
     MT = mta().multiTransformer
     mods = R.MODS_AVL
     mfn = MT.MFN(mods, {m: 256 for m in mods}, 1, device=dev)
-    p32 = _load_into(mfn)
+    p32 = load_named(mfn)
     assert abs(R.weights_checksum(p32) - float(fx["checksum"])) <= 1e-6 * float(fx["checksum"])
     mfn = mfn.to(dev).eval()
     ins = {m: R.gen_normal("mfn:" + m, (20, 3, 256), R.SEED).to(dev).requires_grad_() for m in mods}
@@ -247,7 +236,7 @@ def test_nlp_transformer_golden(dev, name, kw):
     fx = load_golden(name)
     MT = mta().multiTransformer
     model = MT.NLPTransformer(512, device=dev, **kw)
-    _load_into(model)
+    load_named(model)
     model = model.to(dev).eval()
     lengths = list(fx["lengths"])
     x = torch.tanh(R.gen_normal(name + ":x", (4, 50, 512), R.SEED)).to(dev)
@@ -258,7 +247,7 @@ def test_uni_full_transformer_golden(dev):
     fx = load_golden("model_b2_text")
     MT = mta().multiTransformer
     model = MT.UniFullTransformer(300, device=dev)
-    _load_into(model)
+    load_named(model)
     model = model.to(dev).eval()
     lengths = list(fx["lengths"])
     x = R.gen_normal("model_b2:x", (4, 50, 300), R.SEED).to(dev)
@@ -270,7 +259,7 @@ def test_multi_transformer_golden(dev):
     MT = mta().multiTransformer
     mods = R.MODS_AVL
     model = MT.MultiTransformer(mods, R.EMBED_AVL, device=dev)
-    _load_into(model)
+    load_named(model)
     model = model.to(dev).eval()
     lengths = list(fx["lengths"])
     ins = {m: R.gen_normal("model_mft:" + m, (4, 50, R.EMBED_AVL[m]), R.SEED).to(dev) for m in mods}
@@ -284,7 +273,7 @@ def test_multi_transformer_sweep_shapes_golden(dev, name, mods, embed):
     fx = load_golden(name)
     MT = mta().multiTransformer
     model = MT.MultiTransformer(mods, embed, device=dev)
-    _load_into(model)
+    load_named(model)
     model = model.to(dev).eval()
     lengths = list(fx["lengths"])
     ins = {m: R.gen_normal(name + ":" + m, (4, 50, embed[m]), R.SEED).to(dev) for m in mods}
@@ -385,7 +374,7 @@ def test_evaluate_loop_matches_per_sequence_oracle(dev):
     from multimodal_transformer_amd import batching
     MT = mta().multiTransformer
     model = MT.NLPTransformer(512, embed_dim=40, h=4, N=2, device=dev)
-    p32 = _load_into(model, 19)
+    p32 = load_named(model, 19)
     model = model.to(dev).eval()
     n, T = 7, 30
     lengths = [30, 12, 25, 30, 2, 17, 9]
@@ -524,25 +513,6 @@ def test_linear_with_an_input_width_that_is_no_multiple_of_four(dev, K):
     assert _report("odd K=%d db" % K, bs.grad.cpu(), bd.grad) < GRAD_RTOL
 
 
-def _device_kernel_names(step):
-    """names of the device kernels one call of `step` launches (torch.profiler); None if the profiler reports no device activity"""
-    from torch.profiler import profile, ProfilerActivity
-    from torch.autograd import DeviceType
-    step()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        step()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events() if e.device_type == DeviceType.CUDA]
-    return names or None
-
-
-def _library_kernels(names):
-    """kernels that are not ours: ATen element-wise / reduction / copy / cat kernels, rocBLAS / hipBLASLt / MIOpen GEMMs"""
-    bad = ("at::", "at_cuda", "elementwise", "Cijk_", "rocblas", "hipblas", "miopen", "MIOpen", "CatArray", "reduce_kernel", "vectorized_")
-    return sorted(set(n for n in names if any(b in n for b in bad)))
-
-
 @pytest.mark.parametrize("which", ["mft", "sft", "raw_sft", "raw_mft"])
 def test_train_step_runs_no_library_kernel(dev, which):
     """One train-mode forward + loss + backward of the whole MFT / SFT sequence model launches hand-written HIP kernels only — no ATen
@@ -583,11 +553,11 @@ def test_train_step_runs_no_library_kernel(dev, which):
             p.grad = None
         F.mse_sum_loss_backward(model(x, lengths, mask) if raw else model(x, mask, lengths), tgt, sum(lengths))
 
-    names = _device_kernel_names(step)
+    names = device_kernel_names(step, warm=True)[1]
     if names is None:
         pytest.skip("torch.profiler reports no device kernels on this box")
     ours = [n for n in names if "kernel" in n]
     assert len(ours) > 20, names[:10]
-    assert _library_kernels(names) == [], "library kernels in a %s train step: %s" % (which, _library_kernels(names))
+    assert library_kernels(names) == [], "library kernels in a %s train step: %s" % (which, library_kernels(names))
     for p in params:
         assert p.grad is None or torch.isfinite(p.grad).all()

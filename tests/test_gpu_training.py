@@ -9,14 +9,9 @@ import torch
 import oracle
 import recipe as R
 from conftest import rel_l2
+from gpu_harness import dev  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
 
 
 def _batches(n, B, T, lengths):
