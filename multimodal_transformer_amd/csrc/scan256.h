@@ -1,16 +1,19 @@
 // LSTM scans for hidden sizes 129..256 (the reference's default embed_dim = 256 decoder,
 // transformer/SFT/multiTransformer.py:423,444) at small batches (one sequence per workgroup, B <= 256).
+// plan_lstm_scan (api.hip) comes here (LSTM_SCAN256) for HPAD = 256 and BT == 1 when the four-CU family (scan_cluster.h) does not take
+// the scan: B > 32, its workgroups not resident together, or MMT_NO_CLUSTER_SCAN set.
 //
 // W_rec is 4H x H = 512 KB of bf16 at H = 256: exactly the size of a CU's whole register file, so it cannot be resident
-// the way it is for H <= 128 (scan.h).  The generic kernel re-streamed all of it from L2 every step (7-14 us/step).
+// the way it is for H <= 128 (scan.h, scan_units.h).  The generic kernel re-streamed all of it from L2 every step (7-14 us/step).
 // Here a wave owns 32 hidden units (two MFMA row tiles); HALF of its weight fragments (the first RES k-blocks of every
 // gate/tile) stay in registers for the whole scan, the other half is streamed from L2 in 4-fragment groups through a
 // 2-deep register ring that runs ahead across the step boundary (the weights do not depend on h, so the first groups of
 // step t+1 are in flight while step t does its gate math and barrier).  L2 traffic per step halves and its latency hides
 // behind the dependent part of the step.  Inputs come through the cooperative LDS ring and the gate math is "dense"
-// (one lane = one hidden unit) exactly as in scan.h's COOP form.
+// (one lane = one hidden unit): a wave's MFMA results are re-dealt through LDS (xch) to the lanes that own a unit.  The four-CU
+// scans (scan_cluster.h) fetch their inputs through the same kind of ring.
 #pragma once
-#include "scan.h"
+#include "scan_common.h"
 
 #define S256_KP 256
 #define S256_LDH (S256_KP + 8)
@@ -37,9 +40,7 @@ __global__ __launch_bounds__(512) void lstm_scan_fwd256_kernel(const float* __re
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
-        for (int ut = 0; ut < 2; ++ut)
-#pragma unroll
-            for (int ks = 0; ks < RES; ++ks) a[q][ut][ks] = *reinterpret_cast<const bf16x8*>(wbase + q * gs + ut * 16 * S256_KP + ks * 32);
+        for (int ut = 0; ut < 2; ++ut) load_wfrags(a[q][ut], wbase + q * gs + ut * 16 * S256_KP);
     bf16x8 sw[2][4];                                                       // streamed ring: group g = (ks = RES + g/2, ut = g&1)
     auto load_group = [&](bf16x8 (&dst)[4], int g) {
         const int ks = RES + (g >> 1), ut = g & 1;
@@ -49,8 +50,7 @@ __global__ __launch_bounds__(512) void lstm_scan_fwd256_kernel(const float* __re
     load_group(sw[0], 0);
     load_group(sw[1], 1);
 
-    for (int i = tid; i < 2 * 16 * S256_LDH; i += blockDim.x) hbuf[i] = (bf16)0.f;
-    __syncthreads();
+    lds_clear(hbuf, 2 * 16 * S256_LDH);
     // dense role: lanes 0..31 of a wave own the wave's 32 units of THE sequence
     const int du = lane & 31, ud = ubase + du;
     const bool lived = lane < 32 && ud < H;
@@ -158,9 +158,7 @@ __global__ __launch_bounds__(512) void lstm_scan_bwd256_kernel(const float* __re
     const bf16* wbase = Wb + (size_t)(ubase + l15) * KP4 + 8 * lq;          // tile ut: + ut*16*KP4 (ragged last tile: see forward)
     bf16x8 a[2][RESB];
 #pragma unroll
-    for (int ut = 0; ut < 2; ++ut)
-#pragma unroll
-        for (int kb = 0; kb < RESB; ++kb) a[ut][kb] = *reinterpret_cast<const bf16x8*>(wbase + ut * 16 * KP4 + kb * 32);
+    for (int ut = 0; ut < 2; ++ut) load_wfrags(a[ut], wbase + ut * 16 * KP4);
     bf16x8 sw[2][4];                                                       // group g = (k-blocks RESB + 4*(g>>1) .. +3, tile g&1)
     auto load_group = [&](bf16x8 (&dst)[4], int g) {
         const int kb0 = RESB + 4 * (g >> 1), ut = g & 1;
@@ -169,8 +167,7 @@ __global__ __launch_bounds__(512) void lstm_scan_bwd256_kernel(const float* __re
     };
     load_group(sw[0], 0);
     load_group(sw[1], 1);
-    for (int i = tid; i < 2 * 16 * ldg; i += blockDim.x) gbuf[i] = (bf16)0.f;
-    __syncthreads();
+    lds_clear(gbuf, 2 * 16 * ldg);
 
     const int du = lane & 31, ud = ubase + du;
     const bool lived = lane < 32 && ud < H;
@@ -214,14 +211,8 @@ __global__ __launch_bounds__(512) void lstm_scan_bwd256_kernel(const float* __re
         const float dhe = sl[6 * H], dce = sl[7 * H];
         if (ld_on) *reinterpret_cast<f32x4*>(gslot + ((it + 1) & 1) * 8 * S256_KP + cof) = cslot;
         cfetch(cslot, t - 1 - PF);
-        const float dh = dhd + dhe;
-        const float th = tanh_f(ct);
-        const float dct = dcd + dce + dh * og * (1.f - th * th);
-        const float dgo = lived ? dh * th * og * (1.f - og) : 0.f;       // selects: a dead lane's dh may be anything
-        const float dgi = lived ? dct * gg * ig * (1.f - ig) : 0.f;
-        const float dgf = lived ? dct * cp * fg * (1.f - fg) : 0.f;
-        const float dgg = lived ? dct * ig * (1.f - gg * gg) : 0.f;
-        dcd = lived ? dct * fg : 0.f;
+        float dgi, dgf, dgg, dgo;
+        lstm_cell_bwd(lived, ig, fg, gg, og, ct, cp, dhd, dhe, dce, dcd, dgi, dgf, dgg, dgo);
         if (lane < 32) {
             bf16* gw = gbuf + cur * 16 * ldg + ud;                         // row 0 = the sequence
             gw[0] = (bf16)dgi; gw[S256_KP] = (bf16)dgf; gw[2 * S256_KP] = (bf16)dgg; gw[3 * S256_KP] = (bf16)dgo;

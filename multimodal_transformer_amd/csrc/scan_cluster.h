@@ -1,4 +1,6 @@
 // LSTM scans for hidden sizes 129..256 and batches of up to 32 sequences: FOUR workgroups (CUs) per sequence.
+// plan_lstm_scan (api.hip) tries this family first (LSTM_CLUSTER): HPAD = 256, B <= 32, the workgroups resident together (cl4_fits)
+// and MMT_NO_CLUSTER_SCAN not set.
 //
 // W_rec at H = 256 is 512 KB of bf16 — a CU's whole register file — so one CU cannot keep it resident (scan256.h keeps
 // half and streams half: 5.5 / 7.5 us per step).  Here the hidden units of a sequence are split over 4 workgroups of
@@ -15,7 +17,7 @@
 // XCD.  Nothing can guarantee residency against other streams or processes holding CUs: every wait is bounded and a
 // time-out raises a device error word (cl_wait_granule) instead of silently consuming a stale granule.
 #pragma once
-#include "scan.h"
+#include "scan_common.h"
 
 #define CL_NP 4                         // workgroups per sequence
 #define CL_UW 64                        // hidden units per workgroup
@@ -77,9 +79,7 @@ __global__ __launch_bounds__(256) void lstm_scan_fwd_cl4_kernel(const float* __r
     const size_t gs = (size_t)HP16 * CL_KP;
     bf16x8 a[4][KS];
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) a[q][ks] = *reinterpret_cast<const bf16x8*>(wbase + q * gs + ks * 32);
+    for (int q = 0; q < 4; ++q) load_wfrags(a[q], wbase + q * gs);
 
     for (int i = tid; i < 2 * LDH; i += 256) hbuf[i] = (bf16)0.f;
     __syncthreads();
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void lstm_scan_fwd_cl4_kernel(const float* __r
         f32x4 acc[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // h W^T (scan.h, cooperative form): A = the h row — only row 0, the sequence, is live —, B = this wave's rows of W_rec, so
+        // h W^T (operands swapped as in scan_units.h): A = the h row — only row 0, the sequence, is live —, B = this wave's rows of W_rec, so
         // register 0 of lanes 0..15 holds the pre-activation of the lane's own unit: no re-deal through LDS
         const bf16* hb = hbuf + cur * LDH + 8 * lq;
 #pragma unroll
@@ -185,8 +185,7 @@ __global__ __launch_bounds__(256) void lstm_scan_bwd_cl4_kernel(const float* __r
     const int wr_ = (ubase + l15) < HP16 ? ubase + l15 : HP16 - 1;
     const bf16* wbase = Wb + (size_t)wr_ * KP4 + 8 * lq;
     bf16x8 a[KS4];
-#pragma unroll
-    for (int kb = 0; kb < KS4; ++kb) a[kb] = *reinterpret_cast<const bf16x8*>(wbase + kb * 32);
+    load_wfrags(a, wbase);
     for (int i = tid; i < 2 * LDG; i += 256) gbuf[i] = (bf16)0.f;
     __syncthreads();
 
@@ -235,15 +234,8 @@ __global__ __launch_bounds__(256) void lstm_scan_bwd_cl4_kernel(const float* __r
         const float dhe = sl[6 * CL_UW], dce = sl[7 * CL_UW];
         if (ld_on) *reinterpret_cast<f32x4*>(gslot + ((it + 1) & 1) * 8 * CL_UW + ld_dst) = cslot;
         cfetch(cslot, t - 1 - PF);
-        const float dh = dhd + dhe;
-        const float th = tanh_f(ct);
-        const float dct = dcd + dce + dh * og * (1.f - th * th);
-        // selects, not products with 0: a dead lane's dh comes from rows that are not weights and may hold anything
-        const float dgo = lived ? dh * th * og * (1.f - og) : 0.f;
-        const float dgi = lived ? dct * gg * ig * (1.f - ig) : 0.f;
-        const float dgf = lived ? dct * cp * fg * (1.f - fg) : 0.f;
-        const float dgg = lived ? dct * ig * (1.f - gg * gg) : 0.f;
-        dcd = lived ? dct * fg : 0.f;
+        float dgi, dgf, dgg, dgo;
+        lstm_cell_bwd(lived, ig, fg, gg, og, ct, cp, dhd, dhe, dce, dcd, dgi, dgf, dgg, dgo);
         // own gate gradients into the LDS vector and out to the other three workgroups (4 granules per lane pair)
         const float ni = __shfl_down(dgi, 1), nf = __shfl_down(dgf, 1), ng = __shfl_down(dgg, 1), no = __shfl_down(dgo, 1);
         cl_u64* mine = xseq + ((it & 1) * CL_NP + part) * 128;

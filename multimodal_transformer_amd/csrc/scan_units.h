@@ -1,4 +1,5 @@
 // LSTM scans for ONE or TWO sequences per workgroup (batches of up to 512 sequences: every sequence — or pair — has a CU of its own).
+// plan_lstm_scan (api.hip) comes here (LSTM_UNITS) for BT <= 2 when neither H > 128 family takes the scan.
 //
 // These workgroups run two waves per SIMD, and a wave in that regime issues roughly one instruction per 10 cycles whatever the
 // instruction is (tools/valu_micro.hip): a time step costs what its instruction stream costs.  Two things follow.
@@ -15,11 +16,11 @@
 // 16-32 VGPRs per step, which is why round 2 fetched the inputs cooperatively through an LDS ring: a global load, an LDS write, four to
 // eight LDS reads and a page of scalar address arithmetic per step.)  16 lanes x 4 bytes are one 64-byte segment per gate and wave.
 //
-// Stores go out as `global_store_dword voff, vdata, s[base]` (scan.h st_uniform): one instruction each.
+// Stores go out as `global_store_dword voff, vdata, s[base]` (scan_common.h st_uniform): one instruction each.
 // Gate order i, f, g, o (torch).  Reference: nn.LSTMCell loop transformer/MFT/multiTransformer.py:200-208, nn.LSTM step loop
 // transformer/SFT/multiTransformer.py:471-476.
 #pragma once
-#include "scan.h"
+#include "scan_common.h"
 
 // grid = ceil(B / NR); block = 64 * (HP16/16) <= NT.  HPAD = 32*KS.  WREG: W_rec fragments in registers for the whole scan (HPAD <= 128),
 // else re-streamed from L2 every step.
@@ -43,12 +44,9 @@ __global__ __launch_bounds__(NT) void lstm_scan_fwd_u_kernel(const float* __rest
     bf16x8 a[WREG ? 4 : 1][WREG ? KS : 1];
     if (WREG) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) a[q][ks] = *reinterpret_cast<const bf16x8*>(wrow + q * wq + ks * 32);
+        for (int q = 0; q < 4; ++q) load_wfrags(a[q], wrow + q * wq);
     }
-    for (int i = threadIdx.x; i < 2 * 16 * ldh; i += blockDim.x) hbuf[i] = (bf16)0.f;
-    __syncthreads();
+    lds_clear(hbuf, 2 * 16 * ldh);
     float cd[NR];
 #pragma unroll
     for (int r = 0; r < NR; ++r) {

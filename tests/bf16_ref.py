@@ -33,12 +33,12 @@ Sites, read from the kernel sources (csrc/):
   * the one-kernel backward in train mode (attn_bwd_pair.h) rounds P m / c and dS / c, c = 1/(1-p), and scales the sums by c: a
     different rounding of the same operands, but dQ = sum_j dS_j K_j cancels (sum_j dS_j = 0), so it moves dQ by ~3.5e-3 rel-L2.
 
-  * LSTM scan forward (scan_units.h:58,125, scan256.h:61,122, scan_cluster.h:89,140, scan.h:80,137): the MFMA operands bf16(h_{t-1})
+  * LSTM scan forward (scan_units.h:56,123, scan256.h:61,122, scan_cluster.h:89,140, scan.h:70,127): the MFMA operands bf16(h_{t-1})
     (h0 included) and bf16(W_rec); gx, the gate pre-activations and activations, c and the stored h are fp32.  Backward
-    (scan_units.h:249, scan256.h:227, scan_cluster.h:252, scan.h:227): the recurrent product dh_{t-1} = bf16(dG_t) W_rec; dgx = dG in
+    (scan_units.h:247, scan256.h:218, scan_cluster.h:244, scan.h:214): the recurrent product dh_{t-1} = bf16(dG_t) W_rec; dgx = dG in
     fp32; dW_rec = bf16(dG)^T bf16(h_prev) (functional._wgrad).  One line places all of it (``lstm_scan``):
         pre_t = gx_t + round_bwd(round_fwd(h_{t-1}) @ round_fwd(W_rec)^T);
-  * MFN memory scan forward (scan.h:302-387 and the _sw twins): u = drop(ReLU(apre + bf16(mem) bf16(Wm)^T)), z_g = bf16(u_g) bf16(W2_g)^T
+  * MFN memory scan forward (mfn_scan.h, mfn_mem_scan_fwd_kernel :36-121, and the _sw twins): u = drop(ReLU(apre + bf16(mem) bf16(Wm)^T)), z_g = bf16(u_g) bf16(W2_g)^T
     + b2_g, mem = sigmoid(z_1) mem + sigmoid(z_2) chat; mem and everything written stays fp32.  Backward: du = bf16(dz) W2, dmem
     from bf16(dapre) Wm; dapre, dchat and dz are fp32; dWm, dW2 and db2 go through _wgrad, which rounds its operand, so
     db2 = colsum(bf16(dz)) (``mfn_mem_scan``: the bias sits inside round_bwd).
@@ -57,7 +57,7 @@ Sites, read from the kernel sources (csrc/):
     dgate = g (proj - x) in fp32 (:122); dproj and dgate become bf16 operands inside the two affine backwards (grad_prep_kernel),
     dx sums the three fp32 paths (copy2d).  ``linear_pair`` is two affine maps of one input, dx their fp32 sum.
 
-Not emulated: the fp32 hardware exp2 / log2 / reciprocal (the scans' sigmoid_f / tanh_f, scan.h:15-16; tanh_f(x) = 2 sigmoid(2x) - 1 loses
+Not emulated: the fp32 hardware exp2 / log2 / reciprocal (the scans' sigmoid_f / tanh_f, scan_common.h:12-13; tanh_f(x) = 2 sigmoid(2x) - 1 loses
 relative accuracy near 0, about 6e-8 absolute, so every measure of the scans is per row, never per element; the affine map's tanh and
 sigmoid epilogues are the same two formulas), and the kernels' fp32
 accumulation order.  The latter cannot be: fp32 noise (~1e-7) tips a
