@@ -244,7 +244,7 @@ int mmt_mfn_mem_scan_backward(const float* dmem_all, const float* chat, const fl
  *                                                             same class in MFT/models.py:57-79, B2-Trans/models.py:57-79)
  * x fp32 (N, W, D) contiguous: N = B*T windows (the reference loops over the batch; windows are independent), D % 4 == 0,
  * W >= 2.  weight fp32 (F, D, 2) in nn.Conv1d's layout, bias (F).  out fp32 (N, F); argmax int32 (N, F): the conv position
- * of the maximum (first one on ties), saved for the backward.  Only kernel size 2 (the reference's constant, :82). */
+ * of the maximum (first one on ties), saved for the backward.  Kernel size 2 (the reference's constant, :82); other sizes: mmt_convpool_k_*. */
 size_t mmt_convpool_workspace_bytes(int N, int W, int D, int F);
 int mmt_convpool_forward(const float* x, const float* weight, const float* bias, float* out, int32_t* argmax,
                          void* workspace, size_t workspace_bytes, int N, int W, int D, int F, mmt_stream_t stream);
@@ -252,6 +252,21 @@ int mmt_convpool_forward(const float* x, const float* weight, const float* bias,
  * differentiates them either). */
 int mmt_convpool_backward(const float* x, const float* dout, const int32_t* argmax, float* dweight, float* dbias,
                           void* workspace, size_t workspace_bytes, int N, int W, int D, int F, mmt_stream_t stream);
+
+/* ---- Window encoder with K taps: Conv1d(D -> F, kernel K, bias) followed by the global max-pool over the W-K+1 conv
+ *      positions, for 1 <= K <= 5.  The reference passes its k argument straight to nn.Conv1d
+ *                                                             transformer/SFT/models.py:57-79 (CNN), :82-93 (k reaches every CNN)
+ * Arguments as mmt_convpool_*, with weight / dweight fp32 (F, D, K) in nn.Conv1d's layout, W >= K, argmax in [0, W-K] (first
+ * maximum on ties).  K outside 1..5: MMT_EUNSUPPORTED ("kernel size"); W < K, non-positive sizes, null pointers: MMT_EINVAL;
+ * D % 4 != 0: MMT_EUNSUPPORTED.  The workspace query returns 0 for a refused shape, with mmt_last_error() set.  Same numerics
+ * as the 2-tap entries (bf16 operands, fp32 accumulation, bias after the pool, no atomics); K = 2 is accepted but runs other
+ * kernels than mmt_convpool_* (the Python layer keeps k = 2 on those). */
+size_t mmt_convpool_k_workspace_bytes(int N, int W, int D, int F, int K);
+int mmt_convpool_k_forward(const float* x, const float* weight, const float* bias, float* out, int32_t* argmax,
+                           void* workspace, size_t workspace_bytes, int N, int W, int D, int F, int K, mmt_stream_t stream);
+/* dout (N, F) -> dweight (F, D, K), dbias (F).  There is no dx. */
+int mmt_convpool_k_backward(const float* x, const float* dout, const int32_t* argmax, float* dweight, float* dbias,
+                            void* workspace, size_t workspace_bytes, int N, int W, int D, int F, int K, mmt_stream_t stream);
 
 /* ---- Training loss and its gradient in one pass.
  * Replaces criterion(output, target) / sum(lengths) and its autograd backward   transformer/SFT/train.py:133-139 (criterion :538)

@@ -63,6 +63,9 @@ SIGNATURES = {
     "mmt_convpool_workspace_bytes": (_SZ, [_I] * 4),
     "mmt_convpool_forward": (_I, [_P] * 6 + [_SZ] + [_I] * 4 + [_P]),
     "mmt_convpool_backward": (_I, [_P] * 6 + [_SZ] + [_I] * 4 + [_P]),
+    "mmt_convpool_k_workspace_bytes": (_SZ, [_I] * 5),
+    "mmt_convpool_k_forward": (_I, [_P] * 6 + [_SZ] + [_I] * 5 + [_P]),
+    "mmt_convpool_k_backward": (_I, [_P] * 6 + [_SZ] + [_I] * 5 + [_P]),
     "mmt_mse_sum_scratch_doubles": (_SZ, [_SZ]),
     "mmt_mse_sum_forward": (_I, [_P, _P, _F, _P, _P, _P, _SZ, _P]),
     "mmt_adam_step": (_I, [_P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _P]),

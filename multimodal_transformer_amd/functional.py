@@ -582,6 +582,59 @@ def conv_maxpool(x, weight, bias):
     return _ConvPoolFn.apply(x, weight, bias)
 
 
+CONV_K_MAX = 5      # csrc/convk.h CK_MAXK
+
+
+class _ConvPoolKFn(torch.autograd.Function):
+    """_ConvPoolFn with K = weight.shape[2] taps, 1 <= K <= 5, on the K-tap kernels (csrc/convk.h, mmt_convpool_k_*).  Same contract:
+    x (N,W,D) is input data, the index output is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _lib.require_hip(x, weight, bias)
+        if x.requires_grad:
+            raise NotImplementedError("conv_maxpool_k: the windows are input data; a gradient w.r.t. them is not implemented "
+                                      "(the reference never asks for one)")
+        x_, w_, b_ = _f32c(x), _f32c(weight), _f32c(bias)
+        N, W, D = x_.shape
+        if w_.dim() != 3 or w_.shape[1] != D:
+            raise NotImplementedError("conv_maxpool_k: weight must be (F, D, K) = nn.Conv1d(D, F, kernel_size=K).weight, got %s"
+                                      % (tuple(w_.shape),))
+        F_, K = w_.shape[0], w_.shape[2]
+        nbytes = _lib.load().mmt_convpool_k_workspace_bytes(N, W, D, F_, K)
+        if nbytes == 0:             # refused: the launch with nothing to run raises the library's own message
+            _lib.launch("mmt_convpool_k_forward", None, None, None, None, None, None, 0, N, W, D, F_, K)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x_.device)
+        out = torch.empty(N, F_, dtype=torch.float32, device=x_.device)
+        arg = torch.empty(N, F_, dtype=torch.int32, device=x_.device)
+        _lib.launch("mmt_convpool_k_forward", x_, w_, b_, out, arg, ws, nbytes, N, W, D, F_, K)
+        ctx.save_for_backward(x_, arg)
+        ctx.dims = (N, W, D, F_, K, nbytes)
+        ctx.mark_non_differentiable(arg)
+        ctx.set_materialize_grads(False)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dout, _darg):
+        x_, arg = ctx.saved_tensors
+        N, W, D, F_, K, nbytes = ctx.dims
+        if dout is None:
+            return None, None, None
+        g = _f32c(dout)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
+        dw, db = torch.empty(F_, D, K, dtype=torch.float32, device=g.device), torch.empty(F_, dtype=torch.float32, device=g.device)
+        _lib.launch("mmt_convpool_k_backward", x_, g, arg, dw, db, ws, nbytes, N, W, D, F_, K)
+        return None, dw, db
+
+
+def conv_maxpool_k(x, weight, bias):
+    """x (N,W,D) windows, weight (F,D,K) with 1 <= K <= 5, bias (F) -> (out (N,F), argmax positions (N,F) int32 in [0, W-K]).
+    K = 2 is ``conv_maxpool`` itself (the product has one 2-tap path); the other sizes run the K-tap kernels."""
+    if weight.dim() == 3 and weight.shape[2] == 2:
+        return _ConvPoolFn.apply(x, weight, bias)
+    return _ConvPoolKFn.apply(x, weight, bias)
+
+
 def _mem_scan_fwd(apre, chat, Wm, W2, b2, T, B, dropout_p, seed):
     """The MFN memory recurrence on contiguous fp32 tensors with rows t*B + b -> (mem_all, u_all, g_all), shaped like apre's rows."""
     MD, HG = W2.shape[1], W2.shape[2]

@@ -62,9 +62,12 @@ class CNN(nn.Module):
         self.conv1d = nn.Conv1d(word_embed_size, window_embed_size, k, bias=True)
 
     def forward_windows(self, x):
-        if self.k != 2:
-            raise NotImplementedError("CNN: only the reference's kernel size k=2 is implemented on the HIP path")
-        out, _ = F_hip.conv_maxpool(x, self.conv1d.weight, self.conv1d.bias)
+        if self.k == 2:
+            out, _ = F_hip.conv_maxpool(x, self.conv1d.weight, self.conv1d.bias)
+            return out
+        if not 1 <= self.k <= F_hip.CONV_K_MAX:
+            raise NotImplementedError("CNN: kernel sizes 1..%d are implemented on the HIP path, got k=%d" % (F_hip.CONV_K_MAX, self.k))
+        out, _ = F_hip.conv_maxpool_k(x, self.conv1d.weight, self.conv1d.bias)
         return out
 
     def forward(self, x_reshape):
