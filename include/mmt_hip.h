@@ -200,6 +200,29 @@ int mmt_lstm_scan_backward(const float* dh_all, const float* dc_all, const float
                            const float* c_all, const float* acts, float* dgx, float* dh0, float* dc0,
                            void* workspace, size_t workspace_bytes, int T, int B, int H, mmt_stream_t stream);
 
+/* ---- Stacked LSTM scan: the autoregressive decoder with n_layers = L > 1.
+ * Replaces the per-step call of a multi-layer nn.LSTM on [o_{t-1} ; enc_t]   transformer/SFT/multiTransformer.py:444-446,463-483
+ *                                                                           transformer/MFT/multiTransformer.py:335-337,357-376
+ * With d = H and gate order i,f,g,o:  o_{-1} = 0 (zeros, not h0[L-1]);  h^l_{-1} = h0[l], c^l_{-1} = c0[l];
+ *   g^0_t = gx0_t + [o_{t-1} ; h^0_{t-1}] P_0^T          gx0 (T,B,4H) = enc_t W_ih_l0[:, d:]^T + b_ih_l0 + b_hh_l0, computed by the caller
+ *   g^l_t = bias_{l-1} + [h^{l-1}_t ; h^l_{t-1}] P_l^T   l = 1 .. L-1;    o_t = h^{L-1}_t
+ * P (L,4H,2H) fp32 packed weights: P_0 = [W_ih_l0[:, :d] | W_hh_l0], P_l = [W_ih_l | W_hh_l]; bias (L-1,4H) = b_ih_l + b_hh_l of
+ * layers >= 1; h0, c0 (L,B,H) or NULL (zeros).  Outputs h_all, c_all (L,T,B,H) and the gate activations acts (L,T,B,4H) kept for the
+ * backward.  With the first H columns of P_0 zero this is a plain stacked LSTM.
+ * Limits: 2 <= L <= 4, H % 4 == 0, H <= 128, B <= 512; anything else returns MMT_EINVAL (the workspace query returns 0) with the limit
+ * named in mmt_last_error().  One workgroup scans its sequences alone: no device error word.  bf16 MFMA operands, fp32 accumulation
+ * and cell state, as mmt_lstm_scan_*. */
+size_t mmt_lstm_stack_workspace_bytes(int H, int L);
+int mmt_lstm_stack_scan_forward(const float* gx0, const float* P, const float* bias, const float* h0, const float* c0,
+                                float* h_all, float* c_all, float* acts, void* workspace, size_t workspace_bytes,
+                                int T, int B, int H, int L, mmt_stream_t stream);
+/* dh_top (T,B,H): the gradient on the TOP layer's outputs h_all[L-1] (or NULL); c0, c_all, acts as the forward had them.
+ * dG (L,T,B,4H): the gate pre-activation gradients — dG[0] is the gradient of gx0, dG[l] the operand of dP_l = dG[l]^T [x_a ; x_b] and
+ * of the bias gradients (column sums), which the caller forms in batched GEMMs.  dh0, dc0 (L,B,H) or NULL. */
+int mmt_lstm_stack_scan_backward(const float* dh_top, const float* P, const float* c0, const float* c_all, const float* acts,
+                                 float* dG, float* dh0, float* dc0, void* workspace, size_t workspace_bytes,
+                                 int T, int B, int H, int L, mmt_stream_t stream);
+
 /* ---- Local attention of the LSTM baselines: the softmax of the attention MLP's logits and the convolution of the LSTM outputs
  * with them.  Replaces `attn = self.attn(embed)`'s nn.Softmax(dim=1), pad_packed_sequence's zeroing and convolve / pad_shift
  *                                                             transformer/B1-LSTM/models.py:10-25,186-207

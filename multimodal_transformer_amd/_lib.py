@@ -53,6 +53,9 @@ SIGNATURES = {
     "mmt_lstm_scan_workspace_bytes": (_SZ, [_I]),
     "mmt_lstm_scan_forward": (_I, [_P] * 8 + [_SZ] + [_I] * 3 + [_P]),
     "mmt_lstm_scan_backward": (_I, [_P] * 10 + [_SZ] + [_I] * 3 + [_P]),
+    "mmt_lstm_stack_workspace_bytes": (_SZ, [_I, _I]),
+    "mmt_lstm_stack_scan_forward": (_I, [_P] * 9 + [_SZ] + [_I] * 4 + [_P]),
+    "mmt_lstm_stack_scan_backward": (_I, [_P] * 9 + [_SZ] + [_I] * 4 + [_P]),
     "mmt_local_attn_forward": (_I, [_P] * 5 + [_I] * 4 + [_P]),
     "mmt_local_attn_workspace_bytes": (_SZ, [_I] * 4),
     "mmt_local_attn_backward": (_I, [_P] * 7 + [_SZ] + [_I] * 4 + [_P]),

@@ -535,6 +535,98 @@ def lstm_scan(gx, W_rec, h0=None, c0=None):
     return _LstmScanFn.apply(gx, W_rec, h0, c0)
 
 
+def _stack_limits(T, B, H, L):
+    """The limits of the stacked scan (csrc/scan_stack_plan.h), refused before any launch with the limit named."""
+    if not 2 <= L <= 4:
+        raise NotImplementedError("lstm_stack_scan: %d layers; the stacked scan takes 2 <= n_layers <= 4 (one layer: lstm_scan)" % L)
+    if H % 4 or not 0 < H <= 128:
+        raise NotImplementedError("lstm_stack_scan: hidden size %d; the stacked scan takes multiples of 4 up to 128 "
+                                  "(its contraction is 2H <= 256 wide)" % H)
+    if B > 512:
+        raise NotImplementedError("lstm_stack_scan: batch %d; the stacked scan takes at most 512 sequences" % B)
+    if T < 1 or B < 1:
+        raise ValueError("lstm_stack_scan: empty input (T=%d, B=%d)" % (T, B))
+
+
+def _stack_ws(H, L, device):
+    return _lib.POOL.get(_lib.load().mmt_lstm_stack_workspace_bytes(H, L), device, tag=("lstm_stack", H, L))
+
+
+class _LstmStackScanFn(torch.autograd.Function):
+    """h_top, h_all, c_all = stacked scan(gx0, P, bias, h0, c0): L coupled LSTM layers whose top output feeds back into layer 0 — the
+    decoder of transformer/SFT/multiTransformer.py:463-483 with n_layers = L > 1 (csrc/scan_stack.h, include/mmt_hip.h
+    mmt_lstm_stack_scan_*).  gx0 (T,B,4H) holds enc_t W_ih_l0[:, d:]^T + b_0; P (L,4H,2H) the packed weights, bias (L-1,4H) the biases
+    of layers >= 1, h0 / c0 (L,B,H) or None.  Only h_top = h_all[L-1] (T,B,H) carries a gradient; h_all / c_all (L,T,B,H) are returned
+    for inspection.  The weight and bias gradients are batched after the scan: dP_l = dG_l^T [x_a ; x_b] and the column sums of dG_l."""
+
+    @staticmethod
+    def forward(ctx, gx0, P, bias, h0, c0):
+        ctx.set_materialize_grads(False)
+        _lib.require_hip(gx0, P, bias, h0, c0)
+        gx_, P_, b_, h0_, c0_ = _f32c(gx0), _f32c(P), _f32c(bias), _f32c(h0), _f32c(c0)
+        T, B, H4 = gx_.shape
+        H, L = H4 // 4, P_.shape[0]
+        _stack_limits(T, B, H, L)
+        if P_.shape != (L, 4 * H, 2 * H) or b_.shape != (L - 1, 4 * H):
+            raise ValueError("lstm_stack_scan: P must be (L,4H,2H) and bias (L-1,4H) for gx0 %s, got %s and %s"
+                             % (tuple(gx_.shape), tuple(P_.shape), tuple(b_.shape)))
+        for name, t in (("h0", h0_), ("c0", c0_)):
+            if t is not None and t.shape != (L, B, H):
+                raise ValueError("lstm_stack_scan: %s must be (L,B,H) = (%d,%d,%d), got %s" % (name, L, B, H, tuple(t.shape)))
+        dev = gx_.device
+        ws = _stack_ws(H, L, dev)
+        h_all = torch.empty(L, T, B, H, dtype=torch.float32, device=dev)
+        c_all = torch.empty_like(h_all)
+        acts = torch.empty(L, T, B, 4 * H, dtype=torch.float32, device=dev)
+        _lib.launch("mmt_lstm_stack_scan_forward", gx_, P_, b_, h0_, c0_, h_all, c_all, acts, ws, ws.numel(), T, B, H, L)
+        _lib.POOL.put(ws)                           # the backward prepares its own fragments: nothing is kept in the workspace
+        ctx.save_for_backward(P_, h0_, c0_, h_all, c_all, acts)
+        ctx.dims = (T, B, H, L)
+        h_top = h_all[L - 1]
+        ctx.mark_non_differentiable(h_all, c_all)
+        return h_top, h_all, c_all
+
+    @staticmethod
+    def backward(ctx, dh_top, _dh_all, _dc_all):
+        P_, h0_, c0_, h_all, c_all, acts = ctx.saved_tensors
+        T, B, H, L = ctx.dims
+        dev = h_all.device
+        need = ctx.needs_input_grad
+        dG = torch.empty(L, T, B, 4 * H, dtype=torch.float32, device=dev)
+        dh0, dc0 = (torch.empty(L, B, H, dtype=torch.float32, device=dev) for _ in range(2))
+        ws = _stack_ws(H, L, dev)
+        _lib.launch("mmt_lstm_stack_scan_backward", _f32c(dh_top), P_, c0_, c_all, acts, dG, dh0, dc0, ws, ws.numel(), T, B, H, L)
+        _lib.POOL.put(ws)
+        dP = dbias = None
+        if need[1] or need[2]:
+            # dP_l = sum_{t,b} dG_l[t,b,:]^T [x_a ; x_b][t,b,:]: the operand rows are h_all shifted by one step (h0 / zeros in step 0)
+            n, S = T * B, T * B * H
+            X = torch.empty(L, n, 2 * H, dtype=torch.float32, device=dev)
+            segs = []
+            for l in range(L):
+                xo = l * n * 2 * H
+                if l == 0:                          # x_a = o_{t-1}: zeros, then the top layer's outputs
+                    segs += [_seg(X, 2 * H, B, H, dst_off=xo),
+                             _seg(X, 2 * H, n - B, H, src=h_all, src_ld=H, src_off=(L - 1) * S, dst_off=xo + B * 2 * H)]
+                else:                               # x_a = h^{l-1}_t
+                    segs.append(_seg(X, 2 * H, n, H, src=h_all, src_ld=H, src_off=(l - 1) * S, dst_off=xo))
+                segs += [_seg(X, 2 * H, B, H, src=h0_, src_ld=H, src_off=l * B * H, dst_off=xo + H),          # x_b = h^l_{t-1}
+                         _seg(X, 2 * H, n - B, H, src=h_all, src_ld=H, src_off=l * S, dst_off=xo + B * 2 * H + H)]
+            copy2d(segs)
+            dP = torch.empty_like(P_)
+            dbias = torch.empty(L - 1, 4 * H, dtype=torch.float32, device=dev)
+            for l in range(L):
+                _wgrad(dG[l].view(n, 4 * H), X[l], P_[l], dP[l], dbias[l - 1] if l else None)
+        return (dG[0] if need[0] else None, dP if need[1] else None, dbias if need[2] else None,
+                dh0 if (h0_ is not None and need[3]) else None, dc0 if (c0_ is not None and need[4]) else None)
+
+
+def lstm_stack_scan(gx0, P, bias, h0=None, c0=None, return_states=False):
+    """The top layer's outputs (T,B,H) of the stacked scan; return_states: also h_all, c_all (L,T,B,H), which carry no gradient."""
+    h_top, h_all, c_all = _LstmStackScanFn.apply(gx0, P, bias, h0, c0)
+    return (h_top, h_all, c_all) if return_states else h_top
+
+
 class _ConvPoolFn(torch.autograd.Function):
     """out = max over positions of Conv1d(D -> F, kernel 2)(window) + bias — the reference's CNN.forward
     (transformer/SFT/models.py:57-79).  x (N,W,D) is input data: no gradient flows to it."""
@@ -854,6 +946,88 @@ class _DecoderPackFn(torch.autograd.Function):
 
 def decoder_pack(W_ih, W_hh, b_ih, b_hh):
     return _DecoderPackFn.apply(W_ih, W_hh, b_ih, b_hh)
+
+
+class _DecoderStackPackFn(torch.autograd.Function):
+    """Operands of the stacked decoder scan from a multi-layer nn.LSTM's parameters (lstm_stack_scan; transformer/SFT/multiTransformer.py
+    :444-446,463-476 with n_layers = L > 1): Wx = W_ih_l0[:, d:] (multiplies enc_t, batched over T), bias0 = b_ih_l0 + b_hh_l0,
+    P (L,4d,2d) with P_0 = [W_ih_l0[:, :d] | W_hh_l0] and P_l = [W_ih_l | W_hh_l], bias (L-1,4d) = b_ih_l + b_hh_l.  Arguments: the four
+    parameters of every layer, layer by layer.  ONE node: the gradients go back to weight_ih_l*, weight_hh_l*, bias_* by one copy launch."""
+
+    @staticmethod
+    def forward(ctx, *params):
+        _lib.require_hip(*params)
+        ps = [_f32c(t) for t in params]
+        L = len(ps) // 4
+        G, d = ps[1].shape
+        if len(ps) != 4 * L or L < 2 or ps[0].shape != (G, 2 * d) or any(ps[4 * l].shape != (G, d) for l in range(1, L)):
+            raise ValueError("decoder_stack_pack: nn.LSTM(2d, d, L >= 2) parameters expected")
+        like = ps[0]
+        Wx, bias0, P, bias = _new(G, d, like=like), _new(G, like=like), _new(L, G, 2 * d, like=like), _new(L - 1, G, like=like)
+        segs = [_seg(Wx, d, G, d, src=ps[0], src_ld=2 * d, src_off=d), _seg(bias0, G, 1, G, src=ps[2], src_ld=G, src2=ps[3], src2_ld=G),
+                _seg(P, 2 * d, G, d, src=ps[0], src_ld=2 * d), _seg(P, 2 * d, G, d, src=ps[1], src_ld=d, dst_off=d)]
+        for l in range(1, L):
+            Wi, Wh, bi, bh = ps[4 * l:4 * l + 4]
+            po = l * G * 2 * d
+            segs += [_seg(P, 2 * d, G, d, src=Wi, src_ld=d, dst_off=po), _seg(P, 2 * d, G, d, src=Wh, src_ld=d, dst_off=po + d),
+                     _seg(bias, G, 1, G, src=bi, src_ld=G, src2=bh, src2_ld=G, dst_off=(l - 1) * G)]
+        copy2d(segs)
+        ctx.dims = (L, G, d)
+        return Wx, bias0, P, bias
+
+    @staticmethod
+    def backward(ctx, dWx, dbias0, dP, dbias):
+        L, G, d = ctx.dims
+        like = next(t for t in (dWx, dbias0, dP, dbias) if t is not None)
+        dWx, dbias0, dP, dbias = _f32c(dWx), _f32c(dbias0), _f32c(dP), _f32c(dbias)         # an absent gradient: zeros (src None)
+        dWi0, dWh0, db0 = _new(G, 2 * d, like=like), _new(G, d, like=like), _new(G, like=like)
+        segs = [_seg(dWi0, 2 * d, G, d, src=dP, src_ld=2 * d), _seg(dWi0, 2 * d, G, d, src=dWx, src_ld=d, dst_off=d),
+                _seg(dWh0, d, G, d, src=dP, src_ld=2 * d, src_off=d), _seg(db0, G, 1, G, src=dbias0, src_ld=G)]
+        outs = [dWi0, dWh0, db0, db0]
+        for l in range(1, L):
+            dWi, dWh, db = _new(G, d, like=like), _new(G, d, like=like), _new(G, like=like)
+            po = l * G * 2 * d
+            segs += [_seg(dWi, d, G, d, src=dP, src_ld=2 * d, src_off=po), _seg(dWh, d, G, d, src=dP, src_ld=2 * d, src_off=po + d),
+                     _seg(db, G, 1, G, src=dbias, src_ld=G, src_off=(l - 1) * G)]
+            outs += [dWi, dWh, db, db]
+        copy2d(segs)
+        return tuple(outs)
+
+
+def decoder_stack_pack(lstm):
+    """(Wx, bias0, P, bias) of a multi-layer decoder ``nn.LSTM(2d, d, L)`` for ``lstm_stack_scan``."""
+    params = []
+    for l in range(lstm.num_layers):
+        params += [getattr(lstm, "%s_l%d" % (n, l)) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+    return _DecoderStackPackFn.apply(*params)
+
+
+class _BroadcastLayersFn(torch.autograd.Function):
+    """(L,1,n) parameter -> (L,B,n) contiguous (``dec_h0.repeat(1, B, 1)``, transformer/SFT/multiTransformer.py:465-466) as ONE copy;
+    backward: the column sums per layer."""
+
+    @staticmethod
+    def forward(ctx, rows, B):
+        _lib.require_hip(rows)
+        r_ = _f32c(rows)
+        L, n = r_.shape[0], r_.shape[-1]
+        y = _new(L, B, n, like=r_)
+        copy2d([_seg(y, n, B, n, src=r_, src_ld=0, src_off=l * n, dst_off=l * B * n) for l in range(L)])
+        ctx.dims = (L, B, n, tuple(rows.shape))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L, B, n, shape = ctx.dims
+        g = _f32c(dy)
+        drows = _new(L, n, like=g)
+        for l in range(L):
+            _lib.launch("mmt_colsum", g[l], drows[l], B, n, n)
+        return drows.view(shape), None
+
+
+def broadcast_layers(rows, B):
+    return _BroadcastLayersFn.apply(rows, int(B))
 
 
 class _Add2Fn(torch.autograd.Function):

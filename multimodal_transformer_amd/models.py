@@ -201,6 +201,7 @@ class _LocalAttnLSTM(nn.Module):
         z       = Linear(E->L)(ReLU(Linear(E->E)(embed)))                         (B,T,L)    the attention MLP  } one node on the
         gx      = embed W_ih^T + (b_ih + b_hh)                                    (T,B,4H)   time-major for the scan } time-major embed
         h       = LSTM scan of gx with zero h0 / c0                               (T,B,H)
+                  n_layers > 1: layer l scans h^{l-1} W_ih_l^T + (b_ih_l + b_hh_l); the top layer is h
         context = convolve(h * mask, softmax over TIME of z)                      (B,T,H)    functional.local_attention
         out     = Linear(E->1)(ReLU(Linear(H->E)(context)) [Dropout]) * mask      (B,T,1)
 
@@ -233,8 +234,6 @@ class _LocalAttnLSTM(nn.Module):
         if len(lengths) != B or int(max(lengths)) != T:
             raise ValueError("%s: the input's time axis (%d) must equal max(lengths) and len(lengths) the batch (%d); got lengths %s"
                              % (type(self).__name__, T, B, list(lengths)))
-        if self.n_layers != 1:
-            raise NotImplementedError("%s: only the reference's single-layer LSTM (n_layers=1) is implemented" % type(self).__name__)
         if mask is None:
             raise ValueError("%s: the (B,T,1) mask is required (the reference multiplies the output by it)" % type(self).__name__)
         p_in = float(self.embed[0].p) if self.training else 0.0
@@ -247,6 +246,10 @@ class _LocalAttnLSTM(nn.Module):
                                     lstm.weight_ih_l0, F_hip.add2(lstm.bias_ih_l0, lstm.bias_hh_l0), act1=1)
         z = F_hip.batch_major(F_hip.linear(hid, self.attn[2].weight, self.attn[2].bias))
         h_all, _ = F_hip.lstm_scan(gx, lstm.weight_hh_l0)
+        for l in range(1, self.n_layers):               # nn.LSTM's upper layers read the layer below: independent scans, rows stay time-major
+            gx = F_hip.linear(h_all, getattr(lstm, "weight_ih_l%d" % l),
+                              F_hip.add2(getattr(lstm, "bias_ih_l%d" % l), getattr(lstm, "bias_hh_l%d" % l)))
+            h_all, _ = F_hip.lstm_scan(gx, getattr(lstm, "weight_hh_l%d" % l))
         context = F_hip.local_attention(z, h_all, mask)
         dec0, last = self.decoder[0], self.decoder[-1]
         p_dec = float(self.decoder[2].p) if (self.training and self._dec_dropout is not None) else 0.0

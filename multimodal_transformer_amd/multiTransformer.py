@@ -395,16 +395,16 @@ class MultiTransformerB3(nn.Module):
 
 
 class _DecoderMixin:
-    """Autoregressive 1-layer LSTM decoder + MLP shared by UniTransformer and NLPTransformer
-    (transformer/SFT/multiTransformer.py:463-483).  Step t feeds [o_{t-1}; enc_t] with o = h, so
+    """Autoregressive LSTM decoder + MLP shared by UniTransformer and NLPTransformer
+    (transformer/SFT/multiTransformer.py:463-483).  One layer: step t feeds [o_{t-1}; enc_t] with o = h, so
         gates_t = enc_t W_ih[:, d:]^T + b  +  h_{t-1} (W_ih[:, :d] + W_hh)^T          for t >= 1
         gates_0 = enc_0 W_ih[:, d:]^T + b  +  h0 W_hh^T                               (o_{-1} = 0, h_{-1} = dec_h0)
-    i.e. one batched input projection plus one LSTM scan with W_rec = W_ih[:, :d] + W_hh."""
+    i.e. one batched input projection plus one LSTM scan with W_rec = W_ih[:, :d] + W_hh.  More layers: _decode_stacked."""
 
     def _decode(self, enc, mask):
         B, T, d = enc.shape
         if self.decoder.num_layers != 1:
-            raise NotImplementedError("only the reference's single-layer decoder is supported")
+            return self._decode_stacked(enc, mask)
         Wx, W_rec, Whh, bias = F_hip.decoder_pack(self.decoder.weight_ih_l0, self.decoder.weight_hh_l0,
                                                   self.decoder.bias_ih_l0, self.decoder.bias_hh_l0)
         gx = F_hip.linear(F_hip.time_major(enc), Wx, bias)                                  # (T,B,4d)
@@ -412,6 +412,25 @@ class _DecoderMixin:
         h_all, _ = F_hip.lstm_scan(gx, W_rec, None, F_hip.broadcast_rows(self.dec_c0, B))
         hid = F_hip.linear(h_all, self.out[0].weight, self.out[0].bias, act=1)              # rows stay time-major ...
         return F_hip.batch_major(F_hip.linear(hid, self.out[2].weight, self.out[2].bias), mask)   # ... until the mask pass
+
+
+    def _decode_stacked(self, enc, mask):
+        """n_layers = L > 1: o is the TOP layer's output and every layer has its own state, so the layers are coupled inside each step
+        (functional.lstm_stack_scan, csrc/scan_stack.h):
+            gates^0_t = enc_t W_ih_l0[:, d:]^T + b_0  +  [o_{t-1} ; h^0_{t-1}] [W_ih_l0[:, :d] | W_hh_l0]^T         o_{-1} = 0
+            gates^l_t = b_l  +  [h^{l-1}_t ; h^l_{t-1}] [W_ih_l | W_hh_l]^T                                          h^l_{-1} = dec_h0[l]
+        The enc term is one batched projection as above.  2 <= L <= 4, embed_dim % 4 == 0 and <= 128, batch <= 512."""
+        B, T, d = enc.shape
+        L = self.decoder.num_layers
+        if not 2 <= L <= 4 or d % 4 or d > 128 or B > 512:
+            raise NotImplementedError("%s: a decoder with n_layers > 1 runs on the stacked scan, which takes 2 <= n_layers <= 4, embed_dim a "
+                                      "multiple of 4 up to 128 and batches up to 512 (got n_layers=%d, embed_dim=%d, batch=%d)"
+                                      % (type(self).__name__, L, d, B))
+        Wx, bias0, P, bias = F_hip.decoder_stack_pack(self.decoder)
+        gx = F_hip.linear(F_hip.time_major(enc), Wx, bias0)                                 # (T,B,4d)
+        h_top = F_hip.lstm_stack_scan(gx, P, bias, F_hip.broadcast_layers(self.dec_h0, B), F_hip.broadcast_layers(self.dec_c0, B))
+        hid = F_hip.linear(h_top, self.out[0].weight, self.out[0].bias, act=1)
+        return F_hip.batch_major(F_hip.linear(hid, self.out[2].weight, self.out[2].bias), mask)
 
 
 class UniTransformer(nn.Module, _DecoderMixin):
