@@ -223,6 +223,30 @@ int mmt_lstm_stack_scan_backward(const float* dh_top, const float* P, const floa
                                  float* dG, float* dh0, float* dc0, void* workspace, size_t workspace_bytes,
                                  int T, int B, int H, int L, mmt_stream_t stream);
 
+/* ---- LSTM scan with the read-out MLP inside its recurrence: the decoder loop of the encoder-decoder LSTM, nn.LSTM(1 + H, H) called one
+ * step at a time on [p_{t-1} ; ctx_t] with p_t = out(h_t)                          transformer/MFT/models.py:290-305
+ *   gates_t = gxc_t + p_{t-1} w_p + h_{t-1} W_hh^T,  (h_t, c_t) = cell(gates_t, c_{t-1}),  p_{-1} = p_init, h_{-1} = h0, c_{-1} = c0
+ *   u_t = ReLU(W1 h_t + b1),  p_t = w2 . u_t + b2
+ * gxc (T,B,4H) = ctx W_ih[:, 1:]^T + b_ih + b_hh (one batched GEMM before the scan); w_p (4H) = W_ih[:, 0]; W_hh (4H,H); W1 (E,H),
+ * b1 (E) = out.0; w2 (E), b2 (1) = out.2; h0, c0 (B,H) or NULL (zeros).  Outputs p_all (T+1,B): row 0 holds p_init and row t + 1
+ * holds p_t (rows 0 .. T-1 are the p_{t-1} operand of dw_p); h_all, c_all (T,B,H), acts (T,B,4H), u_all (T,B,E) kept for the backward.
+ * Limits: H % 4 == 0, 4 <= H <= 128, E % 4 == 0, 4 <= E <= 128, B <= 512: MMT_EUNSUPPORTED with the limit named in mmt_last_error()
+ * (the workspace query returns 0); T or B < 1, null pointers: MMT_EINVAL.  One workgroup scans its sequences alone: no device error
+ * word.  bf16 MFMA operands (h, W_hh, W1; backward: dG, du), everything else and every sum fp32. */
+size_t mmt_lstm_fb_scan_workspace_bytes(int H, int E);
+int mmt_lstm_fb_scan_forward(const float* gxc, const float* w_p, const float* W_hh, const float* W1, const float* b1,
+                             const float* w2, const float* b2, const float* h0, const float* c0, float p_init,
+                             float* h_all, float* c_all, float* acts, float* u_all, float* p_all,
+                             void* workspace, size_t workspace_bytes, int T, int B, int H, int E, mmt_stream_t stream);
+/* The backward of the loop above (transformer/MFT/models.py:290-305), t = T-1 .. 0.  dp_ext (T,B): the gradient on p_all.
+ * dG (T,B,4H): the gate pre-activation gradients — the gradient of gxc, and the operand of dW_hh = dG^T h_prev and dw_p = sum p_prev dG;
+ * du (T,B,E): the gradient of the MLP's pre-activations (dW1 = du^T h, db1 = its column sums); dp (T,B): the full gradient of p_t
+ * (dw2 = sum dp u, db2 = sum dp).  The caller forms those in batched GEMMs.  dh0, dc0 (B,H) or NULL. */
+int mmt_lstm_fb_scan_backward(const float* dp_ext, const float* w_p, const float* W_hh, const float* W1, const float* w2,
+                              const float* c0, const float* c_all, const float* acts, const float* u_all,
+                              float* dG, float* du, float* dp, float* dh0, float* dc0,
+                              void* workspace, size_t workspace_bytes, int T, int B, int H, int E, mmt_stream_t stream);
+
 /* ---- Local attention of the LSTM baselines: the softmax of the attention MLP's logits and the convolution of the LSTM outputs
  * with them.  Replaces `attn = self.attn(embed)`'s nn.Softmax(dim=1), pad_packed_sequence's zeroing and convolve / pad_shift
  *                                                             transformer/B1-LSTM/models.py:10-25,186-207

@@ -56,6 +56,9 @@ SIGNATURES = {
     "mmt_lstm_stack_workspace_bytes": (_SZ, [_I, _I]),
     "mmt_lstm_stack_scan_forward": (_I, [_P] * 9 + [_SZ] + [_I] * 4 + [_P]),
     "mmt_lstm_stack_scan_backward": (_I, [_P] * 9 + [_SZ] + [_I] * 4 + [_P]),
+    "mmt_lstm_fb_scan_workspace_bytes": (_SZ, [_I, _I]),
+    "mmt_lstm_fb_scan_forward": (_I, [_P] * 9 + [_F] + [_P] * 6 + [_SZ] + [_I] * 4 + [_P]),
+    "mmt_lstm_fb_scan_backward": (_I, [_P] * 15 + [_SZ] + [_I] * 4 + [_P]),
     "mmt_local_attn_forward": (_I, [_P] * 5 + [_I] * 4 + [_P]),
     "mmt_local_attn_workspace_bytes": (_SZ, [_I] * 4),
     "mmt_local_attn_backward": (_I, [_P] * 7 + [_SZ] + [_I] * 4 + [_P]),

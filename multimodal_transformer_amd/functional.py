@@ -627,6 +627,120 @@ def lstm_stack_scan(gx0, P, bias, h0=None, c0=None, return_states=False):
     return (h_top, h_all, c_all) if return_states else h_top
 
 
+def _fb_limits(T, B, H, E):
+    """The limits of the feedback scan (csrc/scan_fb_plan.h), refused before any launch with the limit named."""
+    if H % 4 or not 4 <= H <= 128:
+        raise NotImplementedError("lstm_fb_scan: hidden size %d; the scan with the read-out in its recurrence takes h_dim in multiples of 4 "
+                                  "from 4 to 128 (W_hh and the read-out stay in registers)" % H)
+    if E % 4 or not 4 <= E <= 128:
+        raise NotImplementedError("lstm_fb_scan: read-out width %d; the scan takes embed_dim in multiples of 4 from 4 to 128" % E)
+    if B > 512:
+        raise NotImplementedError("lstm_fb_scan: batch %d; the scan takes at most 512 sequences" % B)
+    if T < 1 or B < 1:
+        raise ValueError("lstm_fb_scan: empty input (T=%d, B=%d)" % (T, B))
+
+
+def _fb_ws(H, E, device):
+    return _lib.POOL.get(_lib.load().mmt_lstm_fb_scan_workspace_bytes(H, E), device, tag=("lstm_fb", H, E))
+
+
+class _LstmFbScanFn(torch.autograd.Function):
+    """p_all, h_all, c_all, u_all = feedback scan(gxc, w_p, W_hh, W1, b1, w2, b2, h0, c0; p_init): an LSTM whose input at step t holds
+    p_{t-1} = out(h_{t-1}), the read-out MLP of the previous state — the decoder loop of MultiEDLSTM, transformer/MFT/models.py:290-305
+    (csrc/scan_fb.h, include/mmt_hip.h mmt_lstm_fb_scan_*).  gxc (T,B,4H) holds ctx_t W_ih[:, 1:]^T + b_ih + b_hh, w_p (4H) = W_ih[:, 0],
+    W1 (E,H) / b1 (E) and w2 (E or (1,E)) / b2 (1) the read-out, h0 / c0 (B,H) or None, p_init a python float (no gradient).
+    Only p_all (T,B) carries a gradient.  The parameter gradients are batched after the scan from its dG, du and dp:
+    [dW_hh | dw_p] = dG^T [h_prev | p_prev], dW1 = du^T h, db1 = colsum du, dw2 = dp^T u, db2 = sum dp."""
+
+    @staticmethod
+    def forward(ctx, gxc, w_p, W_hh, W1, b1, w2, b2, h0, c0, p_init):
+        ctx.set_materialize_grads(False)
+        _lib.require_hip(gxc, w_p, W_hh, W1, b1, w2, b2, h0, c0)
+        gx_, wp_, Wh_, W1_, b1_, w2_, b2_, h0_, c0_ = (_f32c(t) for t in (gxc, w_p, W_hh, W1, b1, w2, b2, h0, c0))
+        if gx_.dim() != 3 or gx_.shape[2] % 4:
+            raise ValueError("lstm_fb_scan: gxc must be (T,B,4H), got %s" % (tuple(gx_.shape),))
+        T, B, H4 = gx_.shape
+        H, E = H4 // 4, W1_.shape[0]
+        _fb_limits(T, B, H, E)
+        if wp_.numel() != 4 * H or Wh_.shape != (4 * H, H) or W1_.shape != (E, H) or b1_.numel() != E or w2_.numel() != E or b2_.numel() != 1:
+            raise ValueError("lstm_fb_scan: for gxc %s and W1 %s: w_p (4H), W_hh (4H,H), b1 (E), w2 (E), b2 (1) expected"
+                             % (tuple(gx_.shape), tuple(W1_.shape)))
+        for name, t in (("h0", h0_), ("c0", c0_)):
+            if t is not None and t.shape != (B, H):
+                raise ValueError("lstm_fb_scan: %s must be (B,H) = (%d,%d), got %s" % (name, B, H, tuple(t.shape)))
+        dev = gx_.device
+        ws = _fb_ws(H, E, dev)
+        h_all = torch.empty(T, B, H, dtype=torch.float32, device=dev)
+        c_all = torch.empty_like(h_all)
+        acts = torch.empty(T, B, 4 * H, dtype=torch.float32, device=dev)
+        u_all = torch.empty(T, B, E, dtype=torch.float32, device=dev)
+        pfull = torch.empty(T + 1, B, dtype=torch.float32, device=dev)          # row 0: p_init, row t + 1: p_t
+        _lib.launch("mmt_lstm_fb_scan_forward", gx_, wp_, Wh_, W1_, b1_, w2_, b2_, h0_, c0_, float(p_init), h_all, c_all, acts, u_all, pfull,
+                    ws, ws.numel(), T, B, H, E)
+        _lib.POOL.put(ws)                           # the backward prepares its own fragments: nothing is kept in the workspace
+        ctx.save_for_backward(wp_, Wh_, W1_, w2_, h0_, c0_, h_all, c_all, acts, u_all, pfull)
+        ctx.dims = (T, B, H, E)
+        ctx.shapes = (tuple(w_p.shape), tuple(w2.shape), tuple(b2.shape))
+        p_all = pfull[1:]
+        ctx.mark_non_differentiable(h_all, c_all, u_all)
+        return p_all, h_all, c_all, u_all
+
+    @staticmethod
+    def backward(ctx, dp_all, _dh_all, _dc_all, _du_all):
+        wp_, Wh_, W1_, w2_, h0_, c0_, h_all, c_all, acts, u_all, pfull = ctx.saved_tensors
+        T, B, H, E = ctx.dims
+        dev = h_all.device
+        need = ctx.needs_input_grad
+        n = T * B
+        g = _f32c(dp_all)
+        if g is None:
+            g = _new(T, B, like=h_all)
+            copy2d([_seg(g, B, T, B)])
+        dG = torch.empty(T, B, 4 * H, dtype=torch.float32, device=dev)
+        du = torch.empty(T, B, E, dtype=torch.float32, device=dev)
+        dp = torch.empty(T, B, dtype=torch.float32, device=dev)
+        dh0, dc0 = (torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(2))
+        ws = _fb_ws(H, E, dev)
+        _lib.launch("mmt_lstm_fb_scan_backward", g, wp_, Wh_, W1_, w2_, c0_, c_all, acts, u_all, dG, du, dp, dh0, dc0, ws, ws.numel(), T, B, H, E)
+        _lib.POOL.put(ws)
+        dwp = dWhh = dW1 = db1 = dw2 = db2 = None
+        K = H + 4                                   # p_{t-1} and three zero columns: the row kernels take widths in multiples of 4
+        segs, X, dp4 = [], None, None
+        if need[1] or need[2]:
+            # [dW_hh | dw_p] = sum_{t,b} dG[t,b,:]^T [h_{t-1} | p_{t-1}][b,:]: the operand rows are h_all / p shifted by one step
+            X = torch.empty(n, K, dtype=torch.float32, device=dev)
+            segs += [_seg(X, K, B, H, src=h0_, src_ld=H), _seg(X, K, n - B, H, src=h_all, src_ld=H, dst_off=B * K),
+                     _seg(X, K, n, 1, src=pfull, src_ld=1, dst_off=H), _seg(X, K, n, 3, dst_off=H + 1)]
+        if need[5] or need[6]:
+            # dw2 = sum dp_t u_t, db2 = sum dp_t: dp as the first of four columns of a gradient operand
+            dp4 = torch.empty(n, 4, dtype=torch.float32, device=dev)
+            segs += [_seg(dp4, 4, n, 1, src=dp, src_ld=1), _seg(dp4, 4, n, 3, dst_off=1)]
+        copy2d(segs)
+        if X is not None:
+            dWX = torch.empty(4 * H, K, dtype=torch.float32, device=dev)
+            _wgrad(dG.view(n, 4 * H), X, dWX, dWX)
+            dWhh, dwp = torch.empty_like(Wh_), torch.empty(4 * H, dtype=torch.float32, device=dev)
+            copy2d([_seg(dWhh, H, 4 * H, H, src=dWX, src_ld=K), _seg(dwp, 1, 4 * H, 1, src=dWX, src_ld=K, src_off=H)])
+        if need[3] or need[4]:
+            dW1, db1 = torch.empty_like(W1_), torch.empty(E, dtype=torch.float32, device=dev)
+            _wgrad(du.view(n, E), h_all.view(n, H), W1_, dW1, db1)
+        if dp4 is not None:
+            dW2x, db2x = torch.empty(4, E, dtype=torch.float32, device=dev), torch.empty(4, dtype=torch.float32, device=dev)
+            _wgrad(dp4, u_all.view(n, E), dW2x, dW2x, db2x)
+            dw2, db2 = dW2x[0], db2x[:1]
+        wp_shape, w2_shape, b2_shape = ctx.shapes
+        return (dG if need[0] else None, dwp.view(wp_shape) if need[1] else None, dWhh if need[2] else None, dW1 if need[3] else None,
+                db1 if need[4] else None, dw2.view(w2_shape) if need[5] else None, db2.view(b2_shape) if need[6] else None,
+                dh0 if (h0_ is not None and need[7]) else None, dc0 if (c0_ is not None and need[8]) else None, None)
+
+
+def lstm_fb_scan(gxc, w_p, W_hh, W1, b1, w2, b2, h0=None, c0=None, p_init=0.0, return_states=False):
+    """p_all (T,B) of the scan with the read-out MLP in its recurrence (see _LstmFbScanFn); return_states: also h_all, c_all (T,B,H) and
+    u_all (T,B,E), which carry no gradient."""
+    p_all, h_all, c_all, u_all = _LstmFbScanFn.apply(gxc, w_p, W_hh, W1, b1, w2, b2, h0, c0, float(p_init))
+    return (p_all, h_all, c_all, u_all) if return_states else p_all
+
+
 class _ConvPoolFn(torch.autograd.Function):
     """out = max over positions of Conv1d(D -> F, kernel 2)(window) + bias — the reference's CNN.forward
     (transformer/SFT/models.py:57-79).  x (N,W,D) is input data: no gradient flows to it."""
@@ -1000,6 +1114,41 @@ def decoder_stack_pack(lstm):
     for l in range(lstm.num_layers):
         params += [getattr(lstm, "%s_l%d" % (n, l)) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
     return _DecoderStackPackFn.apply(*params)
+
+
+class _DecoderFbPackFn(torch.autograd.Function):
+    """Operands of the feedback scan from the parameters of MultiEDLSTM's decoder nn.LSTM(1 + H, H) (transformer/MFT/models.py:256,299-301;
+    step t feeds [p_{t-1} ; ctx_t]): w_p = W_ih[:, 0] (multiplies the fed-back prediction), W_c = W_ih[:, 1:] (multiplies ctx_t, batched
+    over T) and bias = b_ih + b_hh.  ONE node: the gradients go back to weight_ih_l0 and both biases by one copy launch."""
+
+    @staticmethod
+    def forward(ctx, W_ih, b_ih, b_hh):
+        _lib.require_hip(W_ih, b_ih, b_hh)
+        Wi, bi, bh = _f32c(W_ih), _f32c(b_ih), _f32c(b_hh)
+        G, K = Wi.shape
+        if G % 4 or K != G // 4 + 1 or bi.shape != (G,) or bh.shape != (G,):
+            raise ValueError("decoder_fb_pack: nn.LSTM(1 + H, H) parameters expected, got weight_ih %s" % (tuple(Wi.shape),))
+        H = K - 1
+        wp, Wc, bias = _new(G, like=Wi), _new(G, H, like=Wi), _new(G, like=Wi)
+        copy2d([_seg(wp, 1, G, 1, src=Wi, src_ld=K), _seg(Wc, H, G, H, src=Wi, src_ld=K, src_off=1),
+                _seg(bias, G, 1, G, src=bi, src_ld=G, src2=bh, src2_ld=G)])
+        ctx.dims = (G, H)
+        return wp, Wc, bias
+
+    @staticmethod
+    def backward(ctx, dwp, dWc, dbias):
+        G, H = ctx.dims
+        like = next(t for t in (dwp, dWc, dbias) if t is not None)
+        dwp, dWc, dbias = _f32c(dwp), _f32c(dWc), _f32c(dbias)                  # an absent gradient: zeros (src None)
+        dWi, db = _new(G, H + 1, like=like), _new(G, like=like)
+        copy2d([_seg(dWi, H + 1, G, 1, src=dwp, src_ld=1), _seg(dWi, H + 1, G, H, src=dWc, src_ld=H, dst_off=1),
+                _seg(db, G, 1, G, src=dbias, src_ld=G)])
+        return dWi, db, db
+
+
+def decoder_fb_pack(lstm):
+    """(w_p, W_c, bias) of a one-layer decoder ``nn.LSTM(1 + H, H)`` for ``lstm_fb_scan``."""
+    return _DecoderFbPackFn.apply(lstm.weight_ih_l0, lstm.bias_ih_l0, lstm.bias_hh_l0)
 
 
 class _BroadcastLayersFn(torch.autograd.Function):

@@ -9,7 +9,8 @@
     transformer/B1-LSTM/models.py:79-133  ReLU Highway, concat -> MultiLSTM with local attention           (``MultiCNNLSTM``)
 
 and the two copies of the LSTM baseline's sequence model: ``MultiLSTM`` (transformer/SFT/models.py:144-225, byte-identical in MFT,
-B2-Trans, B3-MFN and Performance-Eval) and ``MultiLSTMB1`` (transformer/B1-LSTM/models.py:135-216).
+B2-Trans, B3-MFN and Performance-Eval) and ``MultiLSTMB1`` (transformer/B1-LSTM/models.py:135-216), and the encoder-decoder LSTM
+``MultiEDLSTM`` (transformer/MFT/models.py:222-308).
 
 The reference walks the batch in a Python loop (SFT/models.py:123) and runs Conv1d + MaxPool1d per sequence; windows are
 independent, so here all B*T windows of a modality go through ONE fused conv-GEMM + max-pool HIP kernel
@@ -229,7 +230,9 @@ class _LocalAttnLSTM(nn.Module):
         self.device = _hip_device(device)
         self.to(self.device)
 
-    def forward(self, inputs, mask, lengths, target=None, output_feats=False):
+    def _front(self, inputs, mask, lengths, lstm, h0=None, c0=None):
+        """embed -> attention logits and LSTM scan -> local attention: (B,T,H) context.  ``lstm``: the nn.LSTM that reads the embedding;
+        h0 / c0: its initial state rows (n_layers,1,H) broadcast over the batch, or None for zeros (then nothing is launched for them)."""
         B, T = inputs.shape[0], inputs.shape[1]
         if len(lengths) != B or int(max(lengths)) != T:
             raise ValueError("%s: the input's time axis (%d) must equal max(lengths) and len(lengths) the batch (%d); got lengths %s"
@@ -239,18 +242,25 @@ class _LocalAttnLSTM(nn.Module):
         p_in = float(self.embed[0].p) if self.training else 0.0
         seed = _lib.next_dropout_seed(inputs.device, 7, holder=self) if p_in > 0.0 else 0
         embed = F_hip.linear(inputs, self.embed[1].weight, self.embed[1].bias, act=1, in_dropout=p_in, seed=seed)
-        lstm = self.lstm
         # both consumers of the embedding read it time-major (one gradient node for it: no library add in the backward); the attention
         # MLP's (T,B,L) logits go back to batch-major, a copy of B*T*L floats
         hid, gx = F_hip.linear_pair(F_hip.time_major(embed), self.attn[0].weight, self.attn[0].bias,
                                     lstm.weight_ih_l0, F_hip.add2(lstm.bias_ih_l0, lstm.bias_hh_l0), act1=1)
         z = F_hip.batch_major(F_hip.linear(hid, self.attn[2].weight, self.attn[2].bias))
-        h_all, _ = F_hip.lstm_scan(gx, lstm.weight_hh_l0)
+
+        hb, cb = (None if rows is None else F_hip.broadcast_layers(rows, B) for rows in (h0, c0))      # (n_layers,B,H)
+
+        def init(t, l):                                 # one layer: a view (indexing a layer would put a library kernel into the backward)
+            return None if t is None else (t.view(B, -1) if self.n_layers == 1 else t[l])
+        h_all, _ = F_hip.lstm_scan(gx, lstm.weight_hh_l0, init(hb, 0), init(cb, 0))
         for l in range(1, self.n_layers):               # nn.LSTM's upper layers read the layer below: independent scans, rows stay time-major
             gx = F_hip.linear(h_all, getattr(lstm, "weight_ih_l%d" % l),
                               F_hip.add2(getattr(lstm, "bias_ih_l%d" % l), getattr(lstm, "bias_hh_l%d" % l)))
-            h_all, _ = F_hip.lstm_scan(gx, getattr(lstm, "weight_hh_l%d" % l))
-        context = F_hip.local_attention(z, h_all, mask)
+            h_all, _ = F_hip.lstm_scan(gx, getattr(lstm, "weight_hh_l%d" % l), init(hb, l), init(cb, l))
+        return F_hip.local_attention(z, h_all, mask)
+
+    def forward(self, inputs, mask, lengths, target=None, output_feats=False):
+        context = self._front(inputs, mask, lengths, self.lstm)
         dec0, last = self.decoder[0], self.decoder[-1]
         p_dec = float(self.decoder[2].p) if (self.training and self._dec_dropout is not None) else 0.0
         seed_dec = _lib.next_dropout_seed(inputs.device, 8, holder=self) if p_dec > 0.0 else 0
@@ -274,6 +284,52 @@ class MultiLSTMB1(_LocalAttnLSTM):
 
     def __init__(self, window_embed_size, embed_dim=512, h_dim=256, n_layers=1, attn_len=5, device=torch.device("cuda:0")):
         super().__init__(window_embed_size, embed_dim, h_dim, n_layers, attn_len, device)
+
+
+class MultiEDLSTM(_LocalAttnLSTM):
+    """The encoder-decoder LSTM: transformer/MFT/models.py:222-308 (the SFT, B2-Trans, B3-MFN and Performance-Eval copies are the same).
+
+        context = the front of the LSTM baseline (``_front``) with ``encoder`` as its LSTM, started from enc_h0 / enc_c0       (B,T,H)
+        gxc     = context W_c^T + (b_ih + b_hh),  W_c = decoder.weight_ih_l0[:, 1:]                                          (T,B,4H)
+        p       = functional.lstm_fb_scan: decoder LSTM steps on [p_{t-1} ; context_t] from dec_h0 / dec_c0, p_{-1} = tgt_init,
+                  p_t = out(h_t) — the read-out MLP runs inside the recurrence (csrc/scan_fb.h)                               (T,B)
+        out     = p * mask                                                                                                   (B,T,1)
+
+    The decoder runs all T steps of the padded batch, as the reference does; it is causal and masked outputs carry no gradient.
+    ``target`` is accepted and ignored, as in the reference.  Limits (raised as NotImplementedError at the first forward): n_layers == 1,
+    and h_dim and embed_dim multiples of 4 in [4,128] — the reference's default h_dim = 512 is outside them."""
+
+    def __init__(self, window_embed_size, embed_dim=128, h_dim=512, n_layers=1, attn_len=3, device=torch.device("cuda:0")):
+        nn.Module.__init__(self)
+        self.embed_dim = embed_dim
+        self.h_dim = h_dim
+        self.n_layers = n_layers
+        self.attn_len = attn_len
+        self.embed = nn.Sequential(nn.Dropout(self._embed_p), nn.Linear(window_embed_size, embed_dim), nn.ReLU())
+        self.attn = nn.Sequential(nn.Linear(embed_dim, embed_dim), nn.ReLU(), nn.Linear(embed_dim, attn_len), nn.Softmax(dim=1))
+        self.encoder = nn.LSTM(embed_dim, h_dim, n_layers, batch_first=True)
+        self.enc_h0 = nn.Parameter(torch.zeros(n_layers, 1, h_dim))
+        self.enc_c0 = nn.Parameter(torch.zeros(n_layers, 1, h_dim))
+        self.decoder = nn.LSTM(1 + h_dim, h_dim, n_layers, batch_first=True)
+        self.dec_h0 = nn.Parameter(torch.zeros(n_layers, 1, h_dim))
+        self.dec_c0 = nn.Parameter(torch.zeros(n_layers, 1, h_dim))
+        self.out = nn.Sequential(nn.Linear(h_dim, embed_dim), nn.ReLU(), nn.Linear(embed_dim, 1))
+        self.device = _hip_device(device)
+        self.to(self.device)
+
+    def forward(self, inputs, mask, lengths, target=None, tgt_init=0.0):
+        if self.n_layers != 1:
+            raise NotImplementedError("MultiEDLSTM: n_layers = %d; the decoder scan with the read-out in its recurrence takes n_layers == 1"
+                                      % self.n_layers)
+        B, T = inputs.shape[0], inputs.shape[1]
+        F_hip._fb_limits(max(T, 1), max(B, 1), self.h_dim, self.embed_dim)      # before any launch, with the limit named
+        context = self._front(inputs, mask, lengths, self.encoder, self.enc_h0, self.enc_c0)
+        w_p, W_c, bias = F_hip.decoder_fb_pack(self.decoder)
+        gxc = F_hip.linear(F_hip.time_major(context), W_c, bias)
+        p = F_hip.lstm_fb_scan(gxc, w_p, self.decoder.weight_hh_l0, self.out[0].weight, self.out[0].bias, self.out[2].weight,
+                               self.out[2].bias, F_hip.broadcast_layers(self.dec_h0, B).view(B, -1),
+                               F_hip.broadcast_layers(self.dec_c0, B).view(B, -1), p_init=float(tgt_init))
+        return F_hip.batch_major(p.reshape(T, B, 1), mask.float())
 
 
 class MultiCNNLSTM(_FrontEnd):
