@@ -264,6 +264,24 @@ size_t mmt_local_attn_workspace_bytes(int B, int T, int H, int L);
 int mmt_local_attn_backward(const float* dctx, const float* attn, const float* h, const float* valid, float* dz, float* dh,
                             void* workspace, size_t workspace_bytes, int B, int T, int H, int L, mmt_stream_t stream);
 
+/* ---- Autoregressive read-out of the LSTM baseline MultiARLSTM: the teacher-forced sum and the free-running step loop
+ *                                                             transformer/MFT/models.py:381-386 (teacher-forced), :388-397 (free-running),
+ *                                                             :399 (mask); the same lines in SFT, B2-Trans, B3-MFN, Performance-Eval
+ *                                                             and B1-LSTM
+ * in_part (B,T) = decoder(context); w (B,T,K) = autoreg(context), K = ar_order; mask (B,T) {0,1}; target (B,T) or NULL.
+ *   target given:  p[b,t] = in_part[b,t] + sum_{i<K} w[b,t,i] target[b,t-i],  target[b,s<0] = 0 (not p_init); tap 0 reads the current target
+ *   target NULL:   p[b,t] = in_part[b,t] + sum_{k<K} w[b,t,k] p[b,t-K+k],     p[b,s<0] = p_init; tap K-1 reads the newest prediction
+ * Outputs p (B,T), kept for the backward, and out (B,T) = p * mask.  The free-running loop is ONE launch (a wave per sequence).
+ * 1 <= K <= 16: anything else MMT_EUNSUPPORTED with the limit named in mmt_last_error(), before any launch; B or T < 1, null pointers:
+ * MMT_EINVAL.  T < K, T = 1 and B = 1 are legal.  fp32, no atomics, no workspace. */
+int mmt_ar_combine_forward(const float* in_part, const float* w, const float* mask, const float* target, float p_init,
+                           float* p, float* out, int B, int T, int K, mmt_stream_t stream);
+/* dout (B,T) on out -> din_part (B,T) = dout * mask and dw (B,T,K) = din_part[b,t] * hist, one element-wise launch.  The reference
+ * detaches the fed-back predictions (:392), so nothing flows through the history.  hist (B,T): the target (teacher_forced != 0: tap k
+ * reads target[b,t-k], zero before step 0) or the forward's p (teacher_forced == 0: tap k reads p[b,t-K+k], p_init before step 0). */
+int mmt_ar_combine_backward(const float* dout, const float* mask, const float* hist, int teacher_forced, float p_init,
+                            float* din_part, float* dw, int B, int T, int K, mmt_stream_t stream);
+
 /* ---- MFN delta-memory recurrence.  Replaces the memory update inside MFN.forward's time loop
  *                                                             transformer/MFT/multiTransformer.py:221-224
  * apre (T,B,128): gamma{1,2}_fc1 applied to the `attended` part of `both` (+bias), rows [gamma1(64); gamma2(64)];

@@ -62,6 +62,8 @@ SIGNATURES = {
     "mmt_local_attn_forward": (_I, [_P] * 5 + [_I] * 4 + [_P]),
     "mmt_local_attn_workspace_bytes": (_SZ, [_I] * 4),
     "mmt_local_attn_backward": (_I, [_P] * 7 + [_SZ] + [_I] * 4 + [_P]),
+    "mmt_ar_combine_forward": (_I, [_P] * 4 + [_F] + [_P] * 2 + [_I] * 3 + [_P]),
+    "mmt_ar_combine_backward": (_I, [_P] * 3 + [_I, _F] + [_P] * 2 + [_I] * 3 + [_P]),
     "mmt_mfn_mem_scan_workspace_bytes": (_SZ, []),
     "mmt_mfn_mem_scan_forward": (_I, [_P] * 9 + [_SZ] + [_I] * 4 + [_F, _U64, _P]),
     "mmt_mfn_mem_scan_forward_devseed": (_I, [_P] * 9 + [_SZ] + [_I] * 4 + [_F, _P, _P]),

@@ -6,6 +6,7 @@ Each Function is the forward/backward pair of one reference class:
   sdpa           <- attention()                      :22-34
   linear         <- nn.Linear (+ReLU) call sites     :15-20,43,55,65
   local_attention <- softmax(dim=1) + convolve of the LSTM baselines   transformer/B1-LSTM/models.py:10-25,186-207
+  ar_combine     <- the autoregressive read-out of MultiARLSTM        transformer/MFT/models.py:381-399
 All tensors must live on a HIP device; there is no CPU path.  Every C call goes through ``_lib.launch``.
 """
 import ctypes
@@ -739,6 +740,74 @@ def lstm_fb_scan(gxc, w_p, W_hh, W1, b1, w2, b2, h0=None, c0=None, p_init=0.0, r
     u_all (T,B,E), which carry no gradient."""
     p_all, h_all, c_all, u_all = _LstmFbScanFn.apply(gxc, w_p, W_hh, W1, b1, w2, b2, h0, c0, float(p_init))
     return (p_all, h_all, c_all, u_all) if return_states else p_all
+
+
+AR_ORDER_MAX = 16   # csrc/ar_combine.h MMT_AR_MAXK (the tap cap of local_attn.h)
+
+
+def _ar_limits(K):
+    """The limit of the autoregressive read-out (csrc/ar_combine.h), refused before any launch with the limit named."""
+    if not 1 <= K <= AR_ORDER_MAX:
+        raise NotImplementedError("ar_combine: ar_order %d; the autoregressive read-out takes 1 <= ar_order <= %d" % (K, AR_ORDER_MAX))
+
+
+def _scan_limits(H, who="lstm_scan"):
+    """The hidden sizes mmt_lstm_scan_* takes, for callers that must refuse a size before any launch."""
+    if H % 4 or not 4 <= H <= 256:
+        raise NotImplementedError("%s: hidden size %d; lstm_scan takes h_dim in multiples of 4 from 4 to 256" % (who, H))
+
+
+class _ArCombineFn(torch.autograd.Function):
+    """out, p = the autoregressive read-out of MultiARLSTM (transformer/MFT/models.py:381-399; csrc/ar_combine.h, mmt_ar_combine_*).
+    in_part (B,T[,1]) and ar_w (B,T,K) carry gradients; mask (B,T[,1]) and target (B,T[,1]) or None are data; p_init a python float.
+      target given: p[b,t] = in_part[b,t] + sum_i ar_w[b,t,i] target[b,t-i], zeros before step 0 (tap 0 reads the current target);
+      target None:  p[b,t] = in_part[b,t] + sum_k ar_w[b,t,k] p[b,t-K+k], p_init before step 0 — the step loop as ONE launch.
+    out = p * mask.  The reference detaches the fed-back predictions, so the backward is one element-wise launch in both branches:
+    d in_part = dout * mask, d ar_w[b,t,k] = d in_part[b,t] * (the value tap k read).  p (unmasked) carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, in_part, ar_w, mask, target, p_init):
+        ctx.set_materialize_grads(False)
+        _lib.require_hip(in_part, ar_w, mask, target)
+        if target is not None and target.requires_grad:
+            raise NotImplementedError("ar_combine: the target is input data; a gradient w.r.t. it is not implemented "
+                                      "(the reference never asks for one)")
+        if ar_w.dim() != 3:
+            raise ValueError("ar_combine: ar_w must be (B,T,ar_order), got %s" % (tuple(ar_w.shape),))
+        B, T, K = ar_w.shape
+        _ar_limits(K)
+        if T < 1 or B < 1:
+            raise ValueError("ar_combine: empty input (B=%d, T=%d)" % (B, T))
+        for name, t in (("in_part", in_part), ("mask", mask), ("target", target)):
+            if t is not None and (t.numel() != B * T or tuple(t.shape[:2]) != (B, T)):
+                raise ValueError("ar_combine: %s must be (B,T[,1]) = (%d,%d[,1]), got %s" % (name, B, T, tuple(t.shape)))
+        c_, w_, m_, t_ = _f32c(in_part), _f32c(ar_w), _f32c(mask), _f32c(target)
+        p = _new(B, T, 1, like=w_)
+        out = _new(B, T, 1, like=w_)
+        _lib.launch("mmt_ar_combine_forward", c_, w_, m_, t_, float(p_init), p, out, B, T, K)
+        ctx.save_for_backward(m_, p if t_ is None else t_)
+        ctx.cfg = (B, T, K, t_ is not None, float(p_init), tuple(in_part.shape))
+        ctx.mark_non_differentiable(p)
+        return out, p
+
+    @staticmethod
+    def backward(ctx, dout, _dp):
+        if dout is None:
+            return None, None, None, None, None
+        m_, hist = ctx.saved_tensors
+        B, T, K, teacher, p_init, in_shape = ctx.cfg
+        g = _f32c(dout)
+        din, dw = _new(*in_shape, like=g), _new(B, T, K, like=g)
+        _lib.launch("mmt_ar_combine_backward", g, m_, hist, int(teacher), p_init, din, dw, B, T, K)
+        return din, dw, None, None, None
+
+
+def ar_combine(in_part, ar_w, mask, target=None, p_init=0.0, return_p=False):
+    """(B,T,1) masked predictions of the autoregressive read-out (see _ArCombineFn): teacher-forced on ``target``, free-running from
+    ``p_init`` (a python number, passed by value: capturable in a hipGraph) without one.  return_p: also the unmasked p (B,T,1), which
+    carries no gradient."""
+    out, p = _ArCombineFn.apply(in_part, ar_w, mask, target, float(p_init))
+    return (out, p) if return_p else out
 
 
 class _ConvPoolFn(torch.autograd.Function):

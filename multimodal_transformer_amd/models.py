@@ -10,7 +10,8 @@
 
 and the two copies of the LSTM baseline's sequence model: ``MultiLSTM`` (transformer/SFT/models.py:144-225, byte-identical in MFT,
 B2-Trans, B3-MFN and Performance-Eval) and ``MultiLSTMB1`` (transformer/B1-LSTM/models.py:135-216), and the encoder-decoder LSTM
-``MultiEDLSTM`` (transformer/MFT/models.py:222-308).
+``MultiEDLSTM`` (transformer/MFT/models.py:222-308) and the LSTM baseline with an autoregressive read-out ``MultiARLSTM``
+(transformer/MFT/models.py:310-400).
 
 The reference walks the batch in a Python loop (SFT/models.py:123) and runs Conv1d + MaxPool1d per sequence; windows are
 independent, so here all B*T windows of a modality go through ONE fused conv-GEMM + max-pool HIP kernel
@@ -330,6 +331,47 @@ class MultiEDLSTM(_LocalAttnLSTM):
                                self.out[2].bias, F_hip.broadcast_layers(self.dec_h0, B).view(B, -1),
                                F_hip.broadcast_layers(self.dec_c0, B).view(B, -1), p_init=float(tgt_init))
         return F_hip.batch_major(p.reshape(T, B, 1), mask.float())
+
+
+class MultiARLSTM(_LocalAttnLSTM):
+    """The LSTM baseline with an autoregressive read-out: transformer/MFT/models.py:310-400 (the SFT, B2-Trans, B3-MFN, Performance-Eval
+    and B1-LSTM copies are the same).
+
+        context = the front of the LSTM baseline (``_front``), zero initial states, n_layers as MultiLSTM takes them           (B,T,H)
+        in_part = decoder(context) = Linear(E->1)(ReLU(Linear(H->E)(context)))                                                 (B,T,1)
+        w       = autoreg(context) = Linear(H->ar_order)                                                                       (B,T,K)
+        out     = functional.ar_combine(in_part, w, mask, target, tgt_init)                                                    (B,T,1)
+
+    With a ``target`` the read-out is teacher-forced: in_part + sum_i w[:,t,i] target[:,t-i], zeros before step 0, tap 0 on the current
+    target (:381-386).  Without one it runs on its own predictions from ``tgt_init``, tap K-1 on the newest (:388-397): the reference's
+    step loop, here one kernel launch (csrc/ar_combine.h); as there, the fed-back predictions carry no gradient.  decoder[0] and autoreg
+    read the context through one autograd node (``linear_pair``), so its two gradients are summed by a hand-written kernel.
+    Limits (raised as NotImplementedError at the first forward, before any launch): 1 <= ar_order <= 16, and h_dim a multiple of 4 in
+    [4,256], what ``lstm_scan`` takes — the reference's default h_dim = 512 is outside them."""
+
+    def __init__(self, window_embed_size, embed_dim=128, h_dim=512, n_layers=1, attn_len=7, ar_order=1, device=torch.device("cuda:0")):
+        nn.Module.__init__(self)
+        self.embed_dim = embed_dim
+        self.h_dim = h_dim
+        self.n_layers = n_layers
+        self.attn_len = attn_len
+        self.ar_order = ar_order
+        self.embed = nn.Sequential(nn.Dropout(self._embed_p), nn.Linear(window_embed_size, embed_dim), nn.ReLU())
+        self.attn = nn.Sequential(nn.Linear(embed_dim, embed_dim), nn.ReLU(), nn.Linear(embed_dim, attn_len), nn.Softmax(dim=1))
+        self.lstm = nn.LSTM(embed_dim, h_dim, n_layers, batch_first=True)
+        self.decoder = nn.Sequential(nn.Linear(h_dim, embed_dim), nn.ReLU(), nn.Linear(embed_dim, 1))
+        self.autoreg = nn.Linear(h_dim, ar_order)
+        self.device = _hip_device(device)
+        self.to(self.device)
+
+    def forward(self, inputs, mask, lengths, target=None, tgt_init=0.0):
+        F_hip._ar_limits(self.ar_order)                 # both before any launch, with the limit named
+        F_hip._scan_limits(self.h_dim, "MultiARLSTM")
+        context = self._front(inputs, mask, lengths, self.lstm)
+        dec0, last = self.decoder[0], self.decoder[2]
+        hid, w = F_hip.linear_pair(context, dec0.weight, dec0.bias, self.autoreg.weight, self.autoreg.bias, act1=1)
+        in_part = F_hip.linear(hid, last.weight, last.bias)
+        return F_hip.ar_combine(in_part, w, mask, target, p_init=float(tgt_init))
 
 
 class MultiCNNLSTM(_FrontEnd):
