@@ -118,6 +118,16 @@ int mmt_sdpa_backward(const float* dctx, const float* mask, float* dq, float* dk
                       void* workspace, size_t workspace_bytes, int B, int T, int d, int h,
                       float dropout_p, uint64_t seed, mmt_stream_t stream);
 
+/* ---- The attention probabilities, materialised on request.
+ * Replaces p_attn, the second return value of attention(), which MultiHeadedAttention keeps as self.attn
+ *                                                              transformer/MFT/multiTransformer.py:22-34,59
+ * q,k: (B,T,d) fp32 as for mmt_sdpa_forward; mask (B,T,1) blanks QUERY rows (such a row is exactly 1/T); may be NULL.
+ * probs: (B,h,T,T) fp32, [b][head][query][key]: the post-dropout probabilities mmt_sdpa_forward uses for the same q, k, mask,
+ * dropout_p and seed (same operand rounding; in train mode the same keep decisions, dropped = 0, kept = P/(1-p)).
+ * d_k <= 64 and T <= 4096.  No workspace; one launch. */
+int mmt_attn_probs_forward(const float* q, const float* k, const float* mask, float* probs,
+                           int B, int T, int d, int h, float dropout_p, uint64_t seed, mmt_stream_t stream);
+
 /* ---- Fused affine map  y = act(x W^T + b) [* rowscale] on bf16 MFMA.
  * Replaces nn.Linear (+ F.relu) call sites of the path: PositionwiseFeedForward (:15-20), the four
  * attention projections (:43,55,65), embeds and read-out MLPs (:270,296,340-342,400-402).

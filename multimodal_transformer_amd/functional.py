@@ -4,6 +4,7 @@ Each Function is the forward/backward pair of one reference class:
   encoder_stack  <- Encoder.forward                  transformer/MFT/multiTransformer.py:73-76
   layer_norm     <- LayerNorm.forward                :88-91
   sdpa           <- attention()                      :22-34
+  attn_probs     <- p_attn / MultiHeadedAttention.attn :22-34,59
   linear         <- nn.Linear (+ReLU) call sites     :15-20,43,55,65
   local_attention <- softmax(dim=1) + convolve of the LSTM baselines   transformer/B1-LSTM/models.py:10-25,186-207
   ar_combine     <- the autoregressive read-out of MultiARLSTM        transformer/MFT/models.py:381-399
@@ -270,6 +271,27 @@ def sdpa(q, k, v, mask, h, dropout_p=0.0, seed=0):
     """q,k,v: (B,T,d) with head i in columns [i*d/h,(i+1)*d/h); mask (B,T,1) blanks query rows; -> (B,T,d).
     dropout_p / seed: train-mode dropout on the probabilities (transformer/MFT/multiTransformer.py:32-33)."""
     return _SdpaFn.apply(q, k, v, mask, int(h), float(dropout_p), int(seed))
+
+
+def attn_probs(q, k, mask, h, dropout_p=0.0, seed=0):
+    """The probabilities ``sdpa(q, k, v, mask, h, dropout_p, seed)`` uses, materialised: (B,h,T,T) fp32, [b][head][query][key]
+    (transformer/MFT/multiTransformer.py:22-34, the reference's ``self.attn`` of :59).  Same operand rounding as the attention core; in
+    train mode the same keep decisions for the same seed, dropped = 0 and kept = P/(1-p).  A blanked query row is exactly 1/T.
+    No autograd graph: the reference never differentiates the map."""
+    _lib.require_hip(q, k, mask)
+    _lib.load()
+    q_, k_, m_ = _f32c(q), _f32c(k), _f32c(mask)
+    B, T, d = q_.shape
+    if k_.shape != q_.shape:
+        raise NotImplementedError("attn_probs: query and key must share the shape (B,T,d)")
+    if m_ is not None and m_.numel() != B * T:
+        raise NotImplementedError("attn_probs: only the reference's query-row mask of shape (B,T,1) is supported")
+    h = int(h)
+    if h <= 0 or d % h or d // h > 64 or T > 4096:         # refused by the library before anything as large as the map is allocated
+        _lib.launch("mmt_attn_probs_forward", None, None, None, None, B, T, d, h, 0.0, 0)
+    out = torch.empty((B, h, T, T), dtype=torch.float32, device=q_.device)
+    _lib.launch("mmt_attn_probs_forward", q_, k_, m_, out, B, T, d, h, float(dropout_p), int(seed))
+    return out
 
 
 def _linear_ws(x_, N):

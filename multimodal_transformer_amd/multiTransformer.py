@@ -7,8 +7,10 @@ All arithmetic runs in hand-written HIP kernels through ``libmmt_hip.so``; calli
 on CPU tensors raises (there is no CPU path).
 
 Deviations, all documented in DESIGN.md:
-  * ``MultiHeadedAttention.attn`` stays ``None``: the (B,h,T,T) probability tensor is never
-    materialised (the reference writes it at :59 and never reads it).
+  * ``MultiHeadedAttention.attn`` stays ``None`` unless asked for: the attention core never materialises the
+    (B,h,T,T) probability tensor (the reference writes it at :59 and never reads it).  ``keep_attention(model)``
+    / ``MultiHeadedAttention.keep_attn = True`` / ``attention_with_map(...)`` have a kernel of its own
+    write it beside the core, with the core's rounding and dropout decisions.
   * train-mode dropout draws from a counter-based generator inside the kernels, not from torch's
     global generator: training-mode parity with the reference is statistical, eval-mode is numerical.
 """
@@ -58,12 +60,7 @@ class PositionwiseFeedForward(nn.Module):
         return F_hip.linear(self.dropout(hidden), self.w_2.weight, self.w_2.bias)
 
 
-def attention(query, key, value, mask=None, dropout=None):
-    """Scaled dot-product attention on (B,h,T,d_k) tensors (:22-34).
-
-    ``mask`` is the reference's (B,1,T,1) (or (B,T,1)) float mask: rows where it is 0 are blanked.
-    Returns (context (B,h,T,d_k), None): the probabilities are not materialised.
-    """
+def _attention(query, key, value, mask, dropout, need_attn):
     p = float(dropout.p) if dropout is not None and getattr(dropout, "training", False) else 0.0     # nn.Dropout: identity in eval
     B, h, T, dk = query.shape
 
@@ -75,13 +72,37 @@ def attention(query, key, value, mask=None, dropout=None):
         if mask.numel() != B * T:
             raise NotImplementedError("attention(): only the query-row mask (B,1,T,1)/(B,T,1) of the reference is supported")
         m = mask.reshape(B, T, 1)
-    ctx = F_hip.sdpa(merge(query), merge(key), merge(value), m, h, dropout_p=p,
-                     seed=_lib.next_dropout_seed(query.device, 3) if p > 0.0 else 0)
-    return ctx.reshape(B, T, h, dk).transpose(1, 2), None
+    seed = _lib.next_dropout_seed(query.device, 3) if p > 0.0 else 0
+    q, k = merge(query), merge(key)
+    ctx = F_hip.sdpa(q, k, merge(value), m, h, dropout_p=p, seed=seed)
+    p_attn = F_hip.attn_probs(q, k, m, h, dropout_p=p, seed=seed) if need_attn else None       # one seed serves both kernels
+    return ctx.reshape(B, T, h, dk).transpose(1, 2), p_attn
+
+
+def attention(query, key, value, mask=None, dropout=None):
+    """Scaled dot-product attention on (B,h,T,d_k) tensors (:22-34).
+
+    ``mask`` is the reference's (B,1,T,1) (or (B,T,1)) float mask: rows where it is 0 are blanked.
+    Returns (context (B,h,T,d_k), None): the probabilities are not materialised (``attention_with_map`` returns them).
+    """
+    return _attention(query, key, value, mask, dropout, False)
+
+
+def attention_with_map(query, key, value, mask=None, dropout=None):
+    """``attention`` with the reference's second return value: (context (B,h,T,d_k), p_attn (B,h,T,T)).  The map is the one the context
+    was formed with (post-dropout in train mode, the same seed serves both kernels), detached.  ``attention`` itself keeps the
+    reference's five parameters (:22), so the request is a function of its own and not a sixth keyword."""
+    return _attention(query, key, value, mask, dropout, True)
 
 
 class MultiHeadedAttention(nn.Module):
-    """(:36-65).  ``linears`` = [query, key, value, output] projections."""
+    """(:36-65).  ``linears`` = [query, key, value, output] projections.
+
+    ``keep_attn`` (a class attribute, off; ``keep_attention`` sets it per instance): ``forward`` leaves the detached (B,h,T,T)
+    probabilities of its call in ``self.attn`` as the reference does (:59), written by one extra kernel.  A diagnostic: an Encoder
+    holding such a layer runs layer by layer instead of as the fused stack."""
+
+    keep_attn = False
 
     def __init__(self, h, d_model, dropout=0.1):
         super().__init__()
@@ -101,8 +122,27 @@ class MultiHeadedAttention(nn.Module):
             if mask.numel() != B * query.size(1):
                 raise NotImplementedError("only the reference's query-row mask of shape (B,T,1) is supported")
             m = mask.reshape(B, -1, 1)
-        ctx = F_hip.sdpa(q, k, v, m, self.h, dropout_p=p, seed=_lib.next_dropout_seed(q.device, 3) if p > 0.0 else 0)
+        seed = _lib.next_dropout_seed(q.device, 3) if p > 0.0 else 0
+        ctx = F_hip.sdpa(q, k, v, m, self.h, dropout_p=p, seed=seed)
+        self.attn = F_hip.attn_probs(q, k, m, self.h, dropout_p=p, seed=seed) if self.keep_attn else None
         return F_hip.linear(ctx, self.linears[3].weight, self.linears[3].bias)
+
+
+def keep_attention(module, on=True):
+    """Set ``keep_attn`` on every MultiHeadedAttention below ``module`` (the SFT / MFT / B2 models, the per-modality encoders of
+    MultiTransformer) -> {qualified name: module}.  After the next forward each holds its (B,h,T,T) map in ``.attn``.
+
+    While the flag is set an Encoder runs layer by layer, not as the fused stack: same arithmetic in eval mode within the kernels'
+    rounding, but in train mode the layer-by-layer path draws other dropout seeds than the fused stack does.  The flag is a
+    diagnostic, not a training mode; ``keep_attention(module, False)`` restores the fused path."""
+    found = {}
+    for name, m in module.named_modules():
+        if isinstance(m, MultiHeadedAttention):
+            m.keep_attn = bool(on)
+            if not on:
+                m.attn = None
+            found[name] = m
+    return found
 
 
 class SublayerConnection(nn.Module):
@@ -193,6 +233,8 @@ class Encoder(nn.Module):
         l0 = self.layers[0]
         if not all(type(l) is EncoderLayer and l._is_standard() for l in self.layers):
             return False
+        if any(l.self_attn.keep_attn for l in self.layers):       # the fused stack never forms the map: run layer by layer
+            return False
         h, f = l0.self_attn.h, l0.feed_forward.w_1.weight.shape[0]
         p = l0.sublayer[0].dropout.p
         for l in self.layers:
@@ -215,6 +257,9 @@ class Encoder(nn.Module):
                 x = layer(x, mask)
             return self.norm(x)
         l0 = self.layers[0]
+        for l in self.layers:                    # the fused stack forms no map: one kept by an earlier layer-by-layer call is stale
+            if l.self_attn.attn is not None:
+                l.self_attn.attn = None
         p = l0.sublayer[0].dropout.p if self.training else 0.0
         k = self._sub_batch_streams(x)
         seed = [_lib.next_dropout_seed(x.device, 1, holder=self, index=i) for i in range(k)] if p > 0.0 else 0
