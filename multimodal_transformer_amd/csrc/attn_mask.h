@@ -28,29 +28,40 @@
 
 #define MMT_MASK_BLOCK_WORDS 32
 
-// keep bits of one 32x32 block: W[key] bit q = 1 iff (query q, key) of the block is kept
+// keep bits of one 32x32 block: W[key] bit q = 1 iff (query q, key) of the block is kept.  CHAINS: independent hash chains in flight
+// (keys drawn together); every W[key] is its own function of (dc, blk, key), so the bits do not depend on it.
+template <int CHAINS = 32>
 __device__ __forceinline__ void attn_keep_block(const DropCfg& dc, uint32_t blk, uint32_t (&W)[32]) {
+    static_assert(CHAINS > 0 && 32 % CHAINS == 0, "the keys of a block are drawn in equal groups");
     const uint32_t thr = dc.thr16;
     const int b0 = thr ? __builtin_ctz(thr) : 16;                 // wave-uniform
-#pragma unroll
-    for (int key = 0; key < 32; ++key) W[key] = 0;                // the drop words D; threshold bits below b0 leave them 0
     // threshold bit outermost (a uniform, rolled loop), the 32 keys unrolled inside: 32 independent hash chains in flight (124 VGPRs,
     // 4 waves per SIMD).  16 or 8 chains at 6 or 8 waves per SIMD (all 6144 waves of configs[3] resident at once) measured the same
     // 58-60 us: the kernel is bound by the total integer instruction issue, not by latency, occupancy or its tail.
-    uint32_t x = drop_lin(dc.s0, blk * 512u) + (uint32_t)b0 * MMT_DROP_C1;   // word index blk*512 + key*16 + b  (< 2^24 for Tp <= 4096)
+    // (CHAINS < 32: the rolled loop runs once per group of CHAINS keys, on the group's own words D — the form that fits beside a row
+    // chain's 80 VGPRs, rowgemm.h.  Updating a part of W in a loop instead makes hipcc 7.2 carry W as one 32-register tuple and copy
+    // it every trip.)
+    const uint32_t x0 = drop_lin(dc.s0, blk * 512u) + (uint32_t)b0 * MMT_DROP_C1;   // word index blk*512 + key*16 + b  (< 2^24 for Tp <= 4096)
+#pragma unroll
+    for (int k0 = 0; k0 < 32; k0 += CHAINS) {
+        uint32_t D[CHAINS];                                       // the drop words; threshold bits below b0 leave them 0
+#pragma unroll
+        for (int i = 0; i < CHAINS; ++i) D[i] = 0;
+        uint32_t x = x0;
 #pragma unroll 1
-    for (int b = b0; b < 16; ++b) {
-        if ((thr >> b) & 1u) {
+        for (int b = b0; b < 16; ++b) {
+            if ((thr >> b) & 1u) {
 #pragma unroll
-            for (int key = 0; key < 32; ++key) W[key] |= drop_fin(x + (uint32_t)(16 * key) * MMT_DROP_C1, dc.s1);
-        } else {
+                for (int i = 0; i < CHAINS; ++i) D[i] |= drop_fin(x + (uint32_t)(16 * (k0 + i)) * MMT_DROP_C1, dc.s1);
+            } else {
 #pragma unroll
-            for (int key = 0; key < 32; ++key) W[key] &= drop_fin(x + (uint32_t)(16 * key) * MMT_DROP_C1, dc.s1);
+                for (int i = 0; i < CHAINS; ++i) D[i] &= drop_fin(x + (uint32_t)(16 * (k0 + i)) * MMT_DROP_C1, dc.s1);
+            }
+            x += MMT_DROP_C1;
         }
-        x += MMT_DROP_C1;
-    }
 #pragma unroll
-    for (int key = 0; key < 32; ++key) W[key] = ~W[key];
+        for (int i = 0; i < CHAINS; ++i) W[k0 + i] = ~D[i];
+    }
 }
 
 // in-register transpose of a 32x32 bit matrix: on return A[i] bit j = old A[j] bit i
@@ -86,6 +97,19 @@ struct MaskGenParams {
     uint32_t s0[16], s1[16];               // stream keys of the layers' attention dropout (make_drop(p, seed, 4l+0))
     const uint64_t* seedword;              // non-null: device-resident seed (common.h drop_resolve); s0[l] then holds the stream id 4l+0
 };
+// what the generator needs of ONE layer: its two arrays and its stream keys (seedword non-null: s0 is the stream id, as above)
+struct MaskGenLayer {
+    uint16_t* lq; uint16_t* lk;
+    int nbh, nt;
+    uint32_t thr16, s0, s1;
+    const uint64_t* seedword;
+};
+__device__ __forceinline__ MaskGenLayer mask_gen_layer(const MaskGenParams& P, int layer) {
+    MaskGenLayer G;
+    G.lq = P.lq + (size_t)layer * P.layer_words; G.lk = P.lk + (size_t)layer * P.layer_words;
+    G.nbh = P.nbh; G.nt = P.nt; G.thr16 = P.thr16; G.s0 = P.s0[layer]; G.s1 = P.s1[layer]; G.seedword = P.seedword;
+    return G;
+}
 
 // rows[x] = 32 bits over the lane index (x = the register-side index): the 64 lane words of one block, 8 x 16 bytes, into this lane's
 // row of the wave's LDS patch
@@ -108,10 +132,16 @@ __device__ __forceinline__ void park_lane_block(uint16_t* row, const uint32_t (&
 // at configs[3]).  The wave parks its 64 blocks in LDS and writes them out with the lanes laid along memory (no change in the
 // kernel's own time — it is bound by integer issue — but whole lines reach the fabric): LQ blocks of a wave are contiguous (1 KB per store instruction), LK blocks are
 // written as whole 128-byte lines by 8 lanes each.
-__device__ __forceinline__ void attn_mask_gen_block(const MaskGenParams& P, int layer, int bx) {
-    __shared__ __attribute__((aligned(16))) uint16_t patch[4][64 * MMT_MASK_LDS_ROW];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t g0 = (size_t)bx * 256 + wave * 64;                         // first block of the wave
+// `patch`: the workgroup's LDS patches, MMT_MASK_PATCH_WORDS per generator wave (the caller's own static or dynamic LDS); `first`:
+// the workgroup's first block; waves >= gen_waves of the workgroup take no part.  CHAINS: attn_keep_block.
+#define MMT_MASK_PATCH_WORDS (64 * MMT_MASK_LDS_ROW)
+#define MMT_MASK_GEN_WAVES 4           // generator waves per workgroup of the two stand-alone kernels
+template <int CHAINS = 32>
+__device__ __forceinline__ void attn_mask_gen_block(const MaskGenLayer& P, uint16_t* patch, size_t first, int gen_waves) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (scalar: so is all that follows from it)
+    if (wave >= gen_waves) return;
+    patch += wave * MMT_MASK_PATCH_WORDS;
+    const size_t g0 = first + wave * 64;                                    // first block of the wave
     const size_t per_bh = (size_t)P.nt * P.nt, total = (size_t)P.nbh * per_bh;
     if (g0 >= total) return;                                                // whole wave (no workgroup barrier below)
     const size_t g = g0 + lane;
@@ -119,26 +149,28 @@ __device__ __forceinline__ void attn_mask_gen_block(const MaskGenParams& P, int 
     const size_t gc = live ? g : total - 1;
     const int bh = (int)(gc / per_bh);
     const int rem = (int)(gc - (size_t)bh * per_bh), qt = rem / P.nt, kt = rem - qt * P.nt;
-    DropCfg base; base.thr16 = P.thr16; base.scale = 1.f; base.s0 = P.s0[layer]; base.s1 = P.s1[layer];
+    DropCfg base; base.thr16 = P.thr16; base.scale = 1.f; base.s0 = P.s0; base.s1 = P.s1;
     const DropCfg dc = drop_substream(drop_resolve(base, P.seedword), (uint32_t)bh);
     uint32_t W[32];
-    attn_keep_block(dc, (uint32_t)(qt * P.nt + kt), W);                    // W[key] bit query
-    uint16_t* const mine = patch[wave] + lane * MMT_MASK_LDS_ROW;
+    attn_keep_block<CHAINS>(dc, (uint32_t)(qt * P.nt + kt), W);            // W[key] bit query
+    uint16_t* const mine = patch + lane * MMT_MASK_LDS_ROW;
     // flush role: in store instruction i this lane moves piece (lane & 7) of the wave's block 8 i + (lane >> 3)
     const int fp = lane & 7;
-    const uint16_t* const from = patch[wave] + (lane >> 3) * MMT_MASK_LDS_ROW + 8 * fp;
+    const uint16_t* from;
+    // (formed after the park, from a lane index the compiler cannot see through: formed above, the address is live across the draw and
+    // the park, where the 80-VGPR form has no register for it)
+    auto flush_from = [&] { int l = lane; asm volatile("" : "+v"(l)); return patch + (l >> 3) * MMT_MASK_LDS_ROW + 8 * (l & 7); };
     // ---- LK: key on the lane: lane-side index = key, its row = W[key] (bits over the queries = the register side)
     park_lane_block(mine, W);
+    from = flush_from();
     {
-        // (bh, q tile, k tile) of block lane >> 3, then + 8 blocks per instruction
+        // (bh, q tile, k tile) of block lane >> 3 — its owner lane has them — then + 8 blocks per instruction
         size_t gb = g0 + (lane >> 3);
-        int bb = (int)((gb < total ? gb : total - 1) / per_bh);
-        int rb = (int)((gb < total ? gb : total - 1) - (size_t)bb * per_bh), qb = rb / P.nt, kb = rb - qb * P.nt;
-        uint16_t* const lk = P.lk + (size_t)layer * P.layer_words;
+        int bb = __shfl(bh, lane >> 3), qb = __shfl(qt, lane >> 3), kb = __shfl(kt, lane >> 3);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const u32x4_t v = *reinterpret_cast<const u32x4_t*>(from + 8 * i * MMT_MASK_LDS_ROW);
-            if (gb < total) *reinterpret_cast<u32x4_t*>(lk + ((size_t)bb * per_bh + (size_t)kb * P.nt + qb) * 64 + 8 * fp) = v;
+            if (gb < total) *reinterpret_cast<u32x4_t*>(P.lk + ((size_t)bb * per_bh + (size_t)kb * P.nt + qb) * 64 + 8 * fp) = v;
             gb += 8; kb += 8;
             while (kb >= P.nt) { kb -= P.nt; if (++qb == P.nt) { qb = 0; ++bb; } }
         }
@@ -146,8 +178,9 @@ __device__ __forceinline__ void attn_mask_gen_block(const MaskGenParams& P, int 
     transpose32(W);                                                        // W[query] bit key
     // ---- LQ: block index == g: the wave's 64 blocks are contiguous in memory
     park_lane_block(mine, W);              // (same wave wrote and read the patch: program order is enough, no barrier)
+    from = flush_from();
     {
-        uint16_t* const lq = P.lq + (size_t)layer * P.layer_words + g0 * 64;
+        uint16_t* const lq = P.lq + g0 * 64;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const u32x4_t v = *reinterpret_cast<const u32x4_t*>(from + 8 * i * MMT_MASK_LDS_ROW);
@@ -156,7 +189,11 @@ __device__ __forceinline__ void attn_mask_gen_block(const MaskGenParams& P, int 
     }
 }
 
-__global__ __launch_bounds__(256, 4) void attn_mask_gen_kernel(const MaskGenParams P) { attn_mask_gen_block(P, blockIdx.y, blockIdx.x); }
+// grid = (blocks of 256, layers)
+__global__ __launch_bounds__(256, 4) void attn_mask_gen_kernel(const MaskGenParams P) {
+    __shared__ __attribute__((aligned(16))) uint16_t patch[MMT_MASK_GEN_WAVES * MMT_MASK_PATCH_WORDS];
+    attn_mask_gen_block(mask_gen_layer(P, blockIdx.y), patch, (size_t)blockIdx.x * (64 * MMT_MASK_GEN_WAVES), MMT_MASK_GEN_WAVES);
+}
 
 __host__ inline size_t attn_mask_layer_words(int nbh, int nt) { return (size_t)nbh * nt * nt * 64; }      // uint16 words per layer and orientation
 

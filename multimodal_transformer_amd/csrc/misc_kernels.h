@@ -121,11 +121,15 @@ __global__ void encoder_prep_kernel(const float* __restrict__ params, bf16* __re
 // `gen_blocks` workgroups of a layer draw its attention-dropout decisions, the last `gridDim.x - gen_blocks` prepare its weights — they
 // are dispatched last and run in the slots the generator's incomplete last round leaves free.  (Placed first, 900 small preparation
 // workgroups per layer at the generator's occupancy — its registers and 36 KB of LDS — made the launch 8 us LONGER than the two apart.)
+// P.nlayers may be fewer than the grid's layers: the other layers' decisions then ride in the forward row chains (rowgemm.h) and
+// this launch only prepares their weights.
 __global__ __launch_bounds__(256, 4) void encoder_prep_maskgen_kernel(const float* __restrict__ params, bf16* __restrict__ wprep,
                                                                       float* __restrict__ bprep, LayerLayout L, int gen_blocks,
                                                                       const MaskGenParams P) {
+    __shared__ __attribute__((aligned(16))) uint16_t patch[MMT_MASK_GEN_WAVES * MMT_MASK_PATCH_WORDS];
     if ((int)blockIdx.x >= gen_blocks) { encoder_prep_block(params, wprep, bprep, L, blockIdx.y, blockIdx.x - gen_blocks, gridDim.x - gen_blocks); return; }
-    attn_mask_gen_block(P, blockIdx.y, blockIdx.x);
+    if ((int)blockIdx.y >= P.nlayers) return;          // the later layers' decisions ride in the forward row chains (rowgemm.h): prepare only
+    attn_mask_gen_block(mask_gen_layer(P, blockIdx.y), patch, (size_t)blockIdx.x * (64 * MMT_MASK_GEN_WAVES), MMT_MASK_GEN_WAVES);
 }
 
 // generic: fp32 [N][K] (ld = K) -> bf16 [NP][KP] zero padded, optionally transposed source

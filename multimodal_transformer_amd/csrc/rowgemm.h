@@ -18,6 +18,7 @@
 // backward boundary chain at the end of this file.
 #pragma once
 #include "common.h"
+#include "attn_mask.h"
 
 // (`//@phase` comment lines mark the phase boundaries of a stage: tools/build_phase.sh builds a diagnostic library from a PATCHED COPY of this
 // file in which they are cycle stamps — tools/make_phase.py; this file holds no diagnostic code)
@@ -746,7 +747,10 @@ __global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 51
 // final LayerNorm of the stack applied to the last stage's output tile while it is still in LDS (y == nullptr: none)
 struct LnOut { const float* a; const float* b; float eps; float* y; float* stats; int d; };
 struct RowChain3 { RowGemmParams a, b, c; int lda_max, ldf, ldx, lda2; LnOut ln; };   // LDS geometry decided by the host
-struct RowChain4 { RowGemmParams a, b, c, d; int lda_max, ldf, ldx, lda2; };
+// MaskRide: the next layer's attention-dropout decisions, drawn by extra workgroups of encoder_post_attn_fwd4_kernel<*, 128>
+// (workgroups >= chain_wgs; gen_wgs == 0: none)
+struct MaskRide { MaskGenLayer g; int chain_wgs, gen_wgs, gen_waves; };
+struct RowChain4 { RowGemmParams a, b, c, d; int lda_max, ldf, ldx, lda2; MaskRide ride; };
 
 template <typename CH>
 __host__ __device__ inline size_t rowchain_lds_bytes(const CH& ch, bool with_g) {
@@ -910,9 +914,27 @@ __device__ __forceinline__ RowGemmParams qkv256(RowGemmParams p) { p = shape_pin
 __device__ __forceinline__ RowGemmParams dO256(RowGemmParams p) { p = shape_pin<256, 256>(p); p.h = 8; p.DKP = 32; return p; }
 __device__ __forceinline__ RowGemmParams lnbwd256(RowGemmParams p) { p.no_gs = 1; return p; }
 
+// The SHAPE 128 instance carries a second ROLE.  Its chain is latency-bound (the vector ALUs of a SIMD are busy 47 % of the time with
+// its four waves) and its 76 VGPRs and 51 200 B of LDS leave room for a third workgroup per CU, while the attention-dropout generator
+// (attn_mask.h) is bound by integer vector issue and depends on nothing.  So the workgroups past the chain's tiles draw the NEXT
+// layer's decisions: they are last in the grid, hence the youngest waves of a SIMD, which its oldest-first arbitration gives the issue
+// slots the chain leaves idle.  A generator wave parks its blocks in the launch's dynamic LDS (MMT_RIDE_WAVES patches fit the chain's
+// bytes), runs at priority 0 and meets no workgroup barrier; the rest of its workgroup's waves end at once.  Nothing waits on
+// anything across workgroups: a generator workgroup dispatched late only lengthens its own launch.  The host (api.hip
+// mask_ride_waves) decides whether anything rides; 6 waves per SIMD = three workgroups per CU.
+#define MMT_RIDE_WAVES 4
+#define MMT_RIDE_CHAINS 16             // hash chains in flight per generator lane: the draw inside the chain's register budget
+#define MMT_RIDE_OCC 6
 template <bool DEVSEED, int SHAPE = 0>
-__global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 512) ? 4 : 2) void encoder_post_attn_fwd4_kernel(const RowChain4 ch) {
+__global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 512) ? ((SHAPE == 128 && MMT_RTHREADS == 512) ? MMT_RIDE_OCC : 4) : 2)
+void encoder_post_attn_fwd4_kernel(const RowChain4 ch) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (SHAPE == 128 && (int)blockIdx.x >= ch.ride.chain_wgs) {          // generator role
+        __builtin_amdgcn_s_setprio(0);
+        attn_mask_gen_block<MMT_RIDE_CHAINS>(ch.ride.g, reinterpret_cast<uint16_t*>(smem),
+                                             (size_t)((int)blockIdx.x - ch.ride.chain_wgs) * (64 * ch.ride.gen_waves), ch.ride.gen_waves);
+        return;
+    }
     warm_weights(ch.b.W, ch.b.NP, ch.b.KP); warm_weights(ch.c.W, ch.c.NP, ch.c.KP);
     warm_weights(ch.d.W, ch.d.NP, ch.d.KP);
     if (SHAPE == 128) {
