@@ -194,12 +194,17 @@ __device__ __forceinline__ DropCfg drop_resolve(DropCfg c, const uint64_t* __res
     return c;
 }
 // state[0]: the seed the NEXT train-mode forward uses.  seed block <- state and the stream keys, state <- splitmix64(state).
-__global__ void seed_advance_kernel(uint64_t* __restrict__ state, uint64_t* __restrict__ seedblock, uint32_t first_stream, int nstreams) {
+// The work of ONE workgroup of at least `nstreams` threads, all of which call it: a kernel of its own below, or one extra workgroup of
+// a launch in which nothing reads the block (misc_kernels.h encoder_prep_seed_kernel).
+__device__ __forceinline__ void seed_advance_block(uint64_t* __restrict__ state, uint64_t* __restrict__ seedblock, uint32_t first_stream, int nstreams) {
     const uint64_t s = state[0];
     const int i = threadIdx.x;
     if (i < nstreams) seedblock[1 + i] = splitmix64(splitmix64(s) + 0x100000001B3ull * (uint64_t)(first_stream + i));
     __syncthreads();                            // every thread has read the state
     if (i == 0) { seedblock[0] = s; state[0] = splitmix64(s); }
+}
+__global__ void seed_advance_kernel(uint64_t* __restrict__ state, uint64_t* __restrict__ seedblock, uint32_t first_stream, int nstreams) {
+    seed_advance_block(state, seedblock, first_stream, nstreams);
 }
 // `bits`: resolution of the drop probability, P(drop) = round(p * 2^bits) / 2^bits.  16 for the streams that compare a 16-bit hash half
 // with the threshold; 12 for the attention-probability stream, whose bit-parallel generator (attn_mask.h) spends one hash word per

@@ -55,15 +55,16 @@ __device__ __forceinline__ int unpad_head(int c, const LayerLayout& L) {
 }
 
 // Prepared (bf16, padded, transposed) weights and padded biases of one layer: block bx of nbx; every element is computed from its coordinates
+// (32-bit element indices — a layer's block is far below 2^32 elements at every width the row kernels accept —: the run-time divisions
+// are the kernel's instruction stream, and a 64-bit one costs several times a 32-bit one)
 __device__ __forceinline__ void encoder_prep_block(const float* __restrict__ params, bf16* __restrict__ wprep, float* __restrict__ bprep,
                                                    const LayerLayout& L, int layer, int bx, int nbx) {
     const float* P = params + (size_t)layer * L.stride();
     bf16* W = wprep + (size_t)layer * L.pstride();
     float* Bp = bprep + (size_t)layer * L.qstride();
-    const size_t total = L.pstride();
+    const unsigned total = (unsigned)L.pstride(), nq = (unsigned)L.qstride();
     const int d = L.d, f = L.f;
-    for (size_t idx = (size_t)bx * blockDim.x + threadIdx.x; idx < total + L.qstride();
-         idx += (size_t)nbx * blockDim.x) {
+    for (unsigned idx = (unsigned)bx * blockDim.x + threadIdx.x; idx < total + nq; idx += (unsigned)nbx * blockDim.x) {
         if (idx >= total) {                 // padded fp32 biases
             const int i = (int)(idx - total);
             float v = 0.f;
@@ -77,52 +78,66 @@ __device__ __forceinline__ void encoder_prep_block(const float* __restrict__ par
             continue;
         }
         float v = 0.f;
-        if (idx < L.pWqkvT()) {             // Wqkv [NQ][DP]: row = (wi*h+head)*DKP+e, col = input feature
+        if (idx < (unsigned)L.pWqkvT()) {             // Wqkv [NQ][DP]: row = (wi*h+head)*DKP+e, col = input feature
             const int n = (int)(idx / L.DP), k = (int)(idx % L.DP), wi = n / L.HD;
             if (wi < 3 && k < d) { const int s = unpad_head(n - wi * L.HD, L); if (s >= 0) v = P[L.oW(wi) + (size_t)s * d + k]; }
-        } else if (idx < L.pWo()) {         // Wqkv^T [DP][NQ]
-            const size_t i = idx - L.pWqkvT();
+        } else if (idx < (unsigned)L.pWo()) {         // Wqkv^T [DP][NQ]
+            const unsigned i = idx - (unsigned)L.pWqkvT();
             const int k = (int)(i / L.NQ), n = (int)(i % L.NQ), wi = n / L.HD;
             if (wi < 3 && k < d) { const int s = unpad_head(n - wi * L.HD, L); if (s >= 0) v = P[L.oW(wi) + (size_t)s * d + k]; }
-        } else if (idx < L.pWoT()) {        // Wo [DP][HDP]: col = head-padded context feature
-            const size_t i = idx - L.pWo();
+        } else if (idx < (unsigned)L.pWoT()) {        // Wo [DP][HDP]: col = head-padded context feature
+            const unsigned i = idx - (unsigned)L.pWo();
             const int n = (int)(i / L.HDP), c = (int)(i % L.HDP);
             if (n < d) { const int s = unpad_head(c, L); if (s >= 0) v = P[L.oW(3) + (size_t)n * d + s]; }
-        } else if (idx < L.pW1()) {         // Wo^T [HDP][DP]
-            const size_t i = idx - L.pWoT();
+        } else if (idx < (unsigned)L.pW1()) {         // Wo^T [HDP][DP]
+            const unsigned i = idx - (unsigned)L.pWoT();
             const int c = (int)(i / L.DP), n = (int)(i % L.DP);
             if (n < d) { const int s = unpad_head(c, L); if (s >= 0) v = P[L.oW(3) + (size_t)n * d + s]; }
-        } else if (idx < L.pW1T()) {        // W1 [FP][DP]
-            const size_t i = idx - L.pW1();
+        } else if (idx < (unsigned)L.pW1T()) {        // W1 [FP][DP]
+            const unsigned i = idx - (unsigned)L.pW1();
             const int n = (int)(i / L.DP), k = (int)(i % L.DP);
             if (n < f && k < d) v = P[L.oW1() + (size_t)n * d + k];
-        } else if (idx < L.pW2()) {         // W1^T [DP][FP]
-            const size_t i = idx - L.pW1T();
+        } else if (idx < (unsigned)L.pW2()) {         // W1^T [DP][FP]
+            const unsigned i = idx - (unsigned)L.pW1T();
             const int k = (int)(i / L.FP), n = (int)(i % L.FP);
             if (n < f && k < d) v = P[L.oW1() + (size_t)n * d + k];
-        } else if (idx < L.pW2T()) {        // W2 [DP][FP]
-            const size_t i = idx - L.pW2();
+        } else if (idx < (unsigned)L.pW2T()) {        // W2 [DP][FP]
+            const unsigned i = idx - (unsigned)L.pW2();
             const int n = (int)(i / L.FP), k = (int)(i % L.FP);
             if (n < d && k < f) v = P[L.oW2() + (size_t)n * f + k];
         } else {                            // W2^T [FP][DP]
-            const size_t i = idx - L.pW2T();
+            const unsigned i = idx - (unsigned)L.pW2T();
             const int k = (int)(i / L.DP), n = (int)(i % L.DP);
             if (n < d && k < f) v = P[L.oW2() + (size_t)n * f + k];
         }
         W[idx] = (bf16)v;
     }
 }
-// grid = (blocks, n_layers)
+// grid = (blocks, n_layers): eval mode, and train mode where every layer's attention-dropout decisions ride in the row kernels
+// (rowgemm.h), so that this launch has nothing to draw and runs at the preparation's own registers, without LDS, one element per thread.
 __global__ void encoder_prep_kernel(const float* __restrict__ params, bf16* __restrict__ wprep,
                                     float* __restrict__ bprep, LayerLayout L) {
     encoder_prep_block(params, wprep, bprep, L, blockIdx.y, blockIdx.x, gridDim.x);
 }
-// Train mode: weight preparation and the dropout-bit generator are independent, so they share ONE launch (grid.y = layer): the first
+// The same with a device-resident seed (common.h): grid = (blocks + 1, n_layers), and the last workgroup of layer 0 advances the seed —
+// nothing in this launch reads the seed block, and the block is complete when the next launch starts.
+__global__ void encoder_prep_seed_kernel(const float* __restrict__ params, bf16* __restrict__ wprep, float* __restrict__ bprep, LayerLayout L,
+                                         uint64_t* __restrict__ seed_state, uint64_t* __restrict__ seedblock, int nstreams) {
+    const int nbx = (int)gridDim.x - 1;
+    if ((int)blockIdx.x == nbx) {               // (workgroup-uniform: the barrier inside is met by the whole workgroup)
+        if (blockIdx.y == 0) seed_advance_block(seed_state, seedblock, 0, nstreams);
+        return;
+    }
+    encoder_prep_block(params, wprep, bprep, L, blockIdx.y, blockIdx.x, nbx);
+}
+// Train mode where the first launch draws decisions (every shape but the d_model = 128 fixed one, and MMT_NO_MASK_RIDE /
+// MMT_NO_CHAIN4): weight preparation and the dropout-bit generator are independent, so they share ONE launch (grid.y = layer): the first
 // `gen_blocks` workgroups of a layer draw its attention-dropout decisions, the last `gridDim.x - gen_blocks` prepare its weights — they
 // are dispatched last and run in the slots the generator's incomplete last round leaves free.  (Placed first, 900 small preparation
 // workgroups per layer at the generator's occupancy — its registers and 36 KB of LDS — made the launch 8 us LONGER than the two apart.)
 // P.nlayers may be fewer than the grid's layers: the other layers' decisions then ride in the forward row chains (rowgemm.h) and
-// this launch only prepares their weights.
+// this launch only prepares their weights (where the chains can carry riders, layer 0's `ln1+qkv` can too and this kernel is not
+// launched at all: api.hip encoder_forward_impl).
 __global__ __launch_bounds__(256, 4) void encoder_prep_maskgen_kernel(const float* __restrict__ params, bf16* __restrict__ wprep,
                                                                       float* __restrict__ bprep, LayerLayout L, int gen_blocks,
                                                                       const MaskGenParams P) {

@@ -747,8 +747,8 @@ __global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 51
 // final LayerNorm of the stack applied to the last stage's output tile while it is still in LDS (y == nullptr: none)
 struct LnOut { const float* a; const float* b; float eps; float* y; float* stats; int d; };
 struct RowChain3 { RowGemmParams a, b, c; int lda_max, ldf, ldx, lda2; LnOut ln; };   // LDS geometry decided by the host
-// MaskRide: the next layer's attention-dropout decisions, drawn by extra workgroups of encoder_post_attn_fwd4_kernel<*, 128>
-// (workgroups >= chain_wgs; gen_wgs == 0: none)
+// MaskRide: one layer's attention-dropout decisions, drawn by extra workgroups of a d_model = 128 forward launch (workgroups >=
+// chain_wgs; gen_wgs == 0: none): the next layer's in encoder_post_attn_fwd4_kernel<*, 128>, layer 0's in encoder_ln1_qkv128_kernel
 struct MaskRide { MaskGenLayer g; int chain_wgs, gen_wgs, gen_waves; };
 struct RowChain4 { RowGemmParams a, b, c, d; int lda_max, ldf, ldx, lda2; MaskRide ride; };
 
@@ -960,9 +960,26 @@ void encoder_post_attn_fwd4_kernel(const RowChain4 ch) {
     rowgemm_stage<EPI_FRAG, true, ASRC_X, 0, false>(role_qkv(ch.d), sm);
 }
 
-// layer 0's two single-stage launches as fixed-shape instances (SHAPE 128)
-__global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 512) ? 4 : 2) void encoder_ln1_qkv128_kernel(const RowGemmParams p) {
+// layer 0's two single-stage launches as fixed-shape instances (SHAPE 128).
+// `ln1+qkv` carries the same generator role as the chain above, for layer 0's OWN decisions (the attention kernel behind it is their
+// first reader): workgroups >= ride.chain_wgs (= its tiles; gen_wgs == 0: none) draw them into the launch's dynamic LDS, which the host
+// sizes as max(the tile's 25 600 B, MMT_HEAD_RIDE_WAVES patches) — three such workgroups fit a CU's 160 KB either way —, so the forward
+// pass needs no generator launch in front of it.  Launch bounds as the chain's, for the third workgroup per CU; the tile workgroups
+// run the instructions they ran at (512, 4).
+#ifndef MMT_HEAD_RIDE_WAVES
+#define MMT_HEAD_RIDE_WAVES 4          // generator waves per riding workgroup of ln1+qkv (DESIGN 6 has 2 measured beside it)
+#endif
+struct RowGemmRide { RowGemmParams p; MaskRide ride; };
+__global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 512) ? (MMT_RTHREADS == 512 ? MMT_RIDE_OCC : 4) : 2)
+void encoder_ln1_qkv128_kernel(const RowGemmRide a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    if ((int)blockIdx.x >= a.ride.chain_wgs) {                             // generator role
+        __builtin_amdgcn_s_setprio(0);
+        attn_mask_gen_block<MMT_RIDE_CHAINS>(a.ride.g, reinterpret_cast<uint16_t*>(smem),
+                                             (size_t)((int)blockIdx.x - a.ride.chain_wgs) * (64 * a.ride.gen_waves), a.ride.gen_waves);
+        return;
+    }
+    const RowGemmParams& p = a.p;
     const RowSmem sm = carve_fixed<MMT_FIX128_LDA_FWD, MMT_FIX128_LDF, false, 0, 0>(smem);
     RowGemmParams q = qkv128(role_qkv(p));
     q.lda = 128;
