@@ -42,6 +42,25 @@ Sites, read from the kernel sources (csrc/):
     + b2_g, mem = sigmoid(z_1) mem + sigmoid(z_2) chat; mem and everything written stays fp32.  Backward: du = bf16(dz) W2, dmem
     from bf16(dapre) Wm; dapre, dchat and dz are fp32; dWm, dW2 and db2 go through _wgrad, which rounds its operand, so
     db2 = colsum(bf16(dz)) (``mfn_mem_scan``: the bias sits inside round_bwd).
+  * stacked LSTM scan forward (scan_stack.h lstm_stack_fwd_kernel): the MFMA operands (:138-140) are the bf16 state tiles [x_a ; x_b]
+    and bf16(P_l) (lstm_stack_prep_kernel :38); every layer's h tile is bf16, h0 included (:82, :153); the zeros tile (:58, :115)
+    stands for o_{-1}; gx0, the biases of layers >= 1 (:75, :146-149), the gates, c and the stored h_all / c_all / acts (:160-163) are
+    fp32.  Backward (lstm_stack_bwd_kernel): [dx_a ; dx_b] = bf16(dG^l_t) bf16(P_l) (:251 the gradient tile, :45 the fragments,
+    :278-279 the two halves), dgx0 = dG^0 in fp32 (:258-259), dh0 = the carried x_b half in fp32 (:298).  Batched after the scan
+    (functional.py _LstmStackScanFn.backward :641-642, through _wgrad): dP_l = bf16(dG_l)^T bf16([x_a ; x_b]) with the operand rows
+    taken from the fp32 h_all / h0 (their bf16 is the LDS tile's), dbias_{l-1} = colsum(bf16(dG_l)).  One line per layer-step
+    (``lstm_stack_scan``): pre^0_t = gx0_t + round_bwd(round_fwd([o_{t-1} ; h^0_{t-1}]) @ round_fwd(P_0)^T),
+    pre^l_t = round_bwd(round_fwd([h^{l-1}_t ; h^l_{t-1}]) @ round_fwd(P_l)^T + bias_{l-1});
+  * feedback LSTM scan forward (scan_fb.h lstm_fb_scan_fwd_kernel): gates_t = gxc_t + p_{t-1} w_p + bf16(h_{t-1}) bf16(W_hh)^T with the
+    p w_p term in fp32 (:182-183; the h tile :100, :187; the fragments lstm_fb_prep_kernel :32, :41); the read-out product reads the
+    SAME h tile as the next step's gate product (:172-176, the last step :213-218); u_t = ReLU(. + b1) stored unrounded (:141-143),
+    p_t = b2 + the wave partial sums of w2 . u in fp32 (:142, :147-155).  Backward (lstm_fb_scan_bwd_kernel): dp_t = g_t + dG_{t+1} . w_p
+    from the fp32 dG (:310-312, :343), du_t = dp_t w2 [u_t > 0] stored fp32 and fed to the MFMA as bf16 (:321-323),
+    dh_t = bf16(dG_{t+1}) bf16(W_hh) + bf16(du_t) bf16(W1) (:300, :332, the tile :340), dgxc = dG in fp32 (:351).  Batched after the
+    scan (functional.py _LstmFbScanFn.backward, through _wgrad): [dW_hh | dw_p] = bf16(dG)^T bf16([h_prev | p_prev]) (:744),
+    dW1 = bf16(du)^T bf16(h), db1 = colsum(bf16(du)) (:749), dw2 = bf16(dp)^T bf16(u), db2 = sum(bf16(dp)) (:752).  ``lstm_fb_scan``:
+    the two terms whose two gradients are rounded differently are explicit Functions (``_FbGates``: p w_p + the recurrent product;
+    ``_FbReadout``: w2 . u + b2), the read-out layer is round_bwd(round_fwd(h) @ round_fwd(W1)^T + b1).
 
   * window encoder forward (convpool.h): weights bf16 (convpool_prep_kernel, :43), the raw rows bf16 while staging (:103-107); the sums
     S[n, p, f] = bf16(x)[n, p] . bf16(w)[f, :, 0] + bf16(x)[n, p+1] . bf16(w)[f, :, 1] in fp32; the pool takes the FIRST maximum (:169
@@ -389,6 +408,137 @@ def mfn_mem_scan(apre, chat, Wm, W2, b2, drop=None, rounding=True, mutate=None):
         mem = torch.sigmoid(z[0]) * mem + torch.sigmoid(z[1]) * chat[t]
         out.append(mem)
     return torch.stack(out)
+
+
+def _cell(pre, c, H):
+    i, f = torch.sigmoid(pre[:, :H]), torch.sigmoid(pre[:, H:2 * H])
+    g, o = torch.tanh(pre[:, 2 * H:3 * H]), torch.sigmoid(pre[:, 3 * H:])
+    c = f * c + i * g
+    return o * torch.tanh(c), c, torch.cat([i, f, g, o], dim=1)
+
+
+def lstm_stack_scan(gx0, P, bias, h0=None, c0=None, rounding=True, mutate=None):
+    """Same arguments as functional.lstm_stack_scan: gx0 (T, B, 4H), P (L, 4H, 2H) = [x_a columns | x_b columns], bias (L-1, 4H), h0 / c0
+    (L, B, H) or None (zeros); o_{-1} = 0 -> (h_top (T, B, H), h_all, c_all (L, T, B, H)).  With rounding=False it is
+    lstm_stack_ref.forward / backward.
+    mutate (tests only): {"xa": f(t, l, x_a) and "xb": f(t, l, x_b) -> what layer-step (t, l) multiplies, "c": f(t, l, c) -> what it
+    carries, "bias": f(l, bias_{l-1}) -> the bias of layer l >= 1, "pre": f(t, l, product, bias_{l-1}) -> the gate pre-activations of a
+    layer >= 1 (in place of round_bwd(product + bias))}."""
+    rf, rb = _sites(rounding)
+    m = mutate or {}
+    T, B, H4 = gx0.shape
+    H, L = H4 // 4, P.shape[0]
+    h = [h0[l] if h0 is not None else gx0.new_zeros(B, H) for l in range(L)]
+    c = [c0[l] if c0 is not None else gx0.new_zeros(B, H) for l in range(L)]
+    Pr = [rf(P[l]).t() for l in range(L)]
+    bs = [None] + [m["bias"](l, bias[l - 1]) if "bias" in m else bias[l - 1] for l in range(1, L)]
+    o = gx0.new_zeros(B, H)                                     # the zeros tile
+    hs, cs = [[] for _ in range(L)], [[] for _ in range(L)]
+    for t in range(T):
+        for l in range(L):
+            xa, xb = (o if l == 0 else h[l - 1]), h[l]
+            if "xa" in m:
+                xa = m["xa"](t, l, xa)
+            if "xb" in m:
+                xb = m["xb"](t, l, xb)
+            cin = m["c"](t, l, c[l]) if "c" in m else c[l]
+            prod = rf(torch.cat([xa, xb], dim=1)) @ Pr[l]
+            if l == 0:
+                pre = gx0[t] + rb(prod)
+            else:
+                pre = m["pre"](t, l, prod, bs[l]) if "pre" in m else rb(prod + bs[l])
+            h[l], c[l], _ = _cell(pre, cin, H)
+            hs[l].append(h[l])
+            cs[l].append(c[l])
+        o = h[L - 1]
+    h_all = torch.stack([torch.stack(x) for x in hs])
+    return h_all[L - 1], h_all, torch.stack([torch.stack(x) for x in cs])
+
+
+class _FbGates(torch.autograd.Function):
+    """p w_p + hr Wr^T on the rounded hr = bf16(h_{t-1}), Wr = bf16(W_hh).  Backward: ONE rounding of dG serves dh = bf16(dG) Wr,
+    dW_hh = bf16(dG)^T hr and dw_p = bf16(dG)^T bf16(p) (functional._wgrad on [h_prev | p_prev]); dp = dG . w_p from the fp32 dG."""
+    @staticmethod
+    def forward(ctx, p, w_p, hr, Wr):
+        ctx.save_for_backward(p, w_p, hr, Wr)
+        return p.unsqueeze(1) * w_p.unsqueeze(0) + hr @ Wr.t()
+
+    @staticmethod
+    def backward(ctx, g):
+        p, w_p, hr, Wr = ctx.saved_tensors
+        gb = bf16(g)
+        return g @ w_p, gb.t() @ bf16(p), gb @ Wr, gb.t() @ hr
+
+
+class _FbReadout(torch.autograd.Function):
+    """p = u . w2 + b2.  Backward: du = dp w2 from the fp32 dp; dw2 = bf16(dp)^T bf16(u), db2 = sum(bf16(dp)) (functional._wgrad)."""
+    @staticmethod
+    def forward(ctx, u, w2, b2):
+        ctx.save_for_backward(u, w2)
+        return u @ w2 + b2
+
+    @staticmethod
+    def backward(ctx, g):
+        u, w2 = ctx.saved_tensors
+        gb = bf16(g)
+        return g.unsqueeze(1) * w2.unsqueeze(0), gb @ bf16(u), gb.sum().reshape(1)
+
+
+def fb_readout(u, w2, b2, rounding=True):
+    """p (B,) = u . w2 + b2 of lstm_fb_scan, with the kernels' backward roundings"""
+    return _FbReadout.apply(u, w2, b2) if rounding else u @ w2 + b2
+
+
+def lstm_fb_scan(gxc, w_p, W_hh, W1, b1, w2, b2, h0=None, c0=None, p_init=0.0, rounding=True, mutate=None, saved=None):
+    """Same arguments as functional.lstm_fb_scan: gxc (T, B, 4H), w_p (4H), W_hh (4H, H), W1 (E, H), b1 (E), w2 (E), b2 (1), h0 / c0
+    (B, H) or None (zeros), p_init a float -> (p_all (T, B), h_all, c_all (T, B, H), u_all (T, B, E)).  With rounding=False it is
+    lstm_fb_ref.forward / backward.  The gate product of step t + 1 and the read-out of step t read ONE bf16 h tile.
+    mutate (tests only): {"h": f(t, h_{t-1}) -> what step t's gate product multiplies, "p": f(t, p_{t-1}) -> what it feeds back,
+    "c": f(t, c_{t-1}) -> what it carries, "u": f(t, u_t) -> what the read-out sums, "mask": f(t, [z_t > 0]) -> the read-out ReLU's
+    mask in the BACKWARD (a 0 / 1 tensor), "readout": f(t, u, w2, b2) -> p_t}.
+    saved (tests only): a dict that receives "acts" (T, B, 4H: the gate activations the forward kernel saves) and "grads", a function
+    to call after backward() -> {"dG" (T, B, 4H), "du" (T, B, E), "dp" (T, B)}: the unrounded tensors the backward kernel stores."""
+    rf, rb = _sites(rounding)
+    m = mutate or {}
+    T, B, H4 = gxc.shape
+    H = H4 // 4
+    w_p, w2, b2 = w_p.reshape(-1), w2.reshape(-1), b2.reshape(-1)
+    h = h0 if h0 is not None else gxc.new_zeros(B, H)
+    c = c0 if c0 is not None else gxc.new_zeros(B, H)
+    p = gxc.new_full((B,), float(p_init))
+    Wr, W1r = rf(W_hh), rf(W1).t()
+    hr = rf(h)
+    ps, hs, cs, us, acts, keep = [], [], [], [], [], {"dG": [], "du": [], "dp": []}
+    for t in range(T):
+        hin = rf(m["h"](t, h)) if "h" in m else hr
+        pin = m["p"](t, p) if "p" in m else p
+        cin = m["c"](t, c) if "c" in m else c
+        if rounding:
+            pre = gxc[t] + _FbGates.apply(pin, w_p, hin, Wr)
+        else:
+            pre = gxc[t] + pin.unsqueeze(1) * w_p.unsqueeze(0) + hin @ Wr.t()
+        h, c, a = _cell(pre, cin, H)
+        hr = rf(h)
+        z = rb(hr @ W1r + b1)
+        u = torch.relu(z)
+        if "mask" in m:
+            zb = z * m["mask"](t, (z > 0).to(z.dtype).detach())
+            u = zb + (u - zb).detach()
+        useen = m["u"](t, u) if "u" in m else u
+        p = m["readout"](t, useen, w2, b2) if "readout" in m else fb_readout(useen, w2, b2, rounding)
+        if saved is not None:
+            for k, v in (("dG", pre), ("du", z), ("dp", p)):
+                v.retain_grad()
+                keep[k].append(v)
+        ps.append(p)
+        hs.append(h)
+        cs.append(c)
+        us.append(u)
+        acts.append(a)
+    if saved is not None:
+        saved["acts"] = torch.stack(acts).detach()
+        saved["grads"] = lambda: {k: torch.stack([x.grad for x in v]) for k, v in keep.items()}
+    return torch.stack(ps), torch.stack(hs), torch.stack(cs), torch.stack(us)
 
 
 # ------------------------------------------------------------------------------------------------ window encoder

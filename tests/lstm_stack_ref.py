@@ -9,7 +9,12 @@ The decoder recurrence of transformer/SFT/multiTransformer.py:463-483 with nn.LS
 
 in numpy, forward and the hand-derived backward, so that nothing of torch's LSTM is in it.  With the x_a columns of P_0 zero and zero
 initial states it is a plain stacked LSTM (nn.LSTM(E, H, L) on a whole sequence): pack_plain.  bf16=True rounds the operands of every
-recurrent product (the state rows, the gate gradients and P) to bf16 as the kernels do; the sums stay fp64.
+recurrent product (the state rows, the gate gradients and P) to bf16 as the kernels do; the sums stay fp64.  That mode is NOT faithful
+for the gradients batched after the scan: backward() forms dP and dbias from the unrounded dG and the unrounded state rows, while the
+device rounds both operands (dP_l = bf16(dG_l)^T bf16([x_a ; x_b]), dbias_{l-1} = colsum(bf16(dG_l))).  Against bf16_ref.lstm_stack_scan
+at (T, B, H, L) = (13, 3, 40, 3) its dP differs by 2e-3 rel-L2 (1e-2 per row) and its dbias by 1e-3, while its forward, dgx0, dh0 and
+dc0 agree to 1e-16 (tests/test_bf16_ref.py test_lstm_stack_ref_bf16_mode_leaves_the_batched_gradients_unrounded).  The bf16-faithful
+tier (tests/test_gpu_bf16_stack_fb.py) uses bf16_ref.lstm_stack_scan, never this mode.
 o_init="h0_top" is the WRONG reading o_{-1} = dec_h0[L-1], kept so that a test can show the fixtures tell the two apart.
 """
 import numpy as np

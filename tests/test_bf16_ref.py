@@ -800,3 +800,263 @@ def test_highway_bounds_see_a_mutant():
     rel, row = measures(m[4].numpy(), ref[4].numpy())
     print("mutant sigmoid' from bf16(pre): dWg rel-L2 %.2e row-max %.2e" % (rel, row))
     assert rel > FE.HW_GRAD[0] or row > FE.HW_GRAD[1]
+
+
+# ------------------------------------------------------------------------------------------ stacked and feedback LSTM scans
+def _nrel(a, b):
+    a, b = (np.asarray(x.detach() if torch.is_tensor(x) else x, dtype=np.float64) for x in (a, b))
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
+
+
+def _stack_plain(inp, w):
+    """lstm_stack_ref.forward / backward on a test_gpu_bf16_stack_fb input dict -> the arrays of stack_ref()"""
+    import lstm_stack_ref as SR
+    n = {k: None if v is None else v.numpy() for k, v in inp.items()}
+    h_all, c_all, acts = SR.forward(n["gx0"], n["P"], n["bias"], n["h0"], n["c0"])
+    g = SR.backward(w.numpy(), n["P"], n["h0"], n["c0"], h_all, c_all, acts)
+    out = dict(h_top=h_all[-1], h_all=h_all, c_all=c_all, dgx0=g["dgx0"], dP=g["dP"], dbias=g["dbias"])
+    if inp["h0"] is not None:
+        out["dh0"], out["dc0"] = g["dh0"], g["dc0"]
+    return out, g
+
+
+@pytest.mark.parametrize("init", [False, True])
+@pytest.mark.parametrize("L", [2, 4])
+def test_lstm_stack_scan_without_rounding_is_the_plain_reference(L, init):
+    import test_gpu_bf16_stack_fb as S
+    c = S._sc(5, 3, 40, L, init=init)
+    inputs = S.stack_inputs(c)
+    a = S.stack_ref(c, inputs, rounding=False)
+    b, _ = _stack_plain(*inputs)
+    assert set(a) == set(b)
+    for k in b:
+        assert _nrel(a[k], b[k]) <= 1e-12, k
+
+
+@pytest.mark.parametrize("init", [False, True])
+def test_lstm_fb_scan_without_rounding_is_the_plain_reference(init):
+    import lstm_fb_ref as FR
+    import test_gpu_bf16_stack_fb as S
+    c = S._fc(5, 3, 40, 24, init=init)
+    inp, w = S.fb_inputs(c)
+    saved = {}
+    a = S.fb_ref(c, (inp, w), saved=saved, rounding=False)
+    n = {k: None if v is None else v.numpy() for k, v in inp.items()}
+    outs = FR.forward(**n, p_init=S.P_INIT)
+    g = FR.backward(w.numpy(), n["w_p"], n["W_hh"], n["W1"], n["w2"], n["h0"], n["c0"], S.P_INIT, *outs)
+    b = dict(zip(("p_all", "h_all", "c_all", "acts", "u_all"), outs))
+    for k in ("p_all", "h_all", "c_all", "u_all"):
+        assert _nrel(a[k], b[k]) <= 1e-12, k
+    for k in S.FB_KEYS:
+        if n[k] is not None:
+            assert _nrel(a["d" + k], g["d" + k].reshape(a["d" + k].shape)) <= 1e-12, k
+    assert "dh0" in a or not init
+    gr = saved["grads"]()                               # what the C entry point's buffers are compared with
+    assert _nrel(saved["acts"], b["acts"]) <= 1e-12
+    for k, r in (("dG", g["dgxc"]), ("du", g["du"]), ("dp", g["dp"])):
+        assert _nrel(gr[k], r) <= 1e-12, k
+
+
+def test_lstm_stack_ref_bf16_mode_leaves_the_batched_gradients_unrounded():
+    """lstm_stack_ref's own bf16=True mode rounds inside the recurrence only: forward, dgx0, dh0, dc0 agree with bf16_ref, dP and dbias
+    (batched from the unrounded dG and states) do not."""
+    import lstm_stack_ref as SR
+    import test_gpu_bf16_stack_fb as S
+    c = S._sc(13, 3, 40, 3)
+    inp, w = S.stack_inputs(c)
+    a = S.stack_ref(c, (inp, w))
+    n = {k: v.numpy() for k, v in inp.items()}
+    h_all, c_all, acts = SR.forward(n["gx0"], n["P"], n["bias"], n["h0"], n["c0"], bf16=True)
+    g = SR.backward(w.numpy(), n["P"], n["h0"], n["c0"], h_all, c_all, acts, bf16=True)
+    assert _nrel(h_all, a["h_all"]) <= 1e-12 and _nrel(c_all, a["c_all"]) <= 1e-12
+    for k in ("dgx0", "dh0", "dc0"):
+        assert _nrel(g[k], a[k]) <= 1e-12, k
+    print("lstm_stack_ref bf16=True against bf16_ref: dP %.2e, dbias %.2e" % (_nrel(g["dP"], a["dP"]), _nrel(g["dbias"], a["dbias"])))
+    assert _nrel(g["dP"], a["dP"]) > 1e-4 and _nrel(g["dbias"], a["dbias"]) > 1e-4
+
+
+def _largest(cases, S):
+    """per tier: the largest case (elements of the state tensor), the longest if it is another one, and the saturated runs"""
+    out = []
+    for t in ("short", "wide", "long"):
+        cs = [c for c in cases if S.tier(c) == t]
+        if not cs:
+            continue
+        if t == "long":                                 # the long tier: every case
+            out += cs
+            continue
+        size = lambda c: c["T"] * c["B"] * c["H"] * c.get("L", 1) * c.get("E", 1)      # noqa: E731
+        big, lng = max(cs, key=size), max(cs, key=lambda c: (c["T"], size(c)))
+        out += [big] if big is lng else [big, lng]
+    return out + [c for c in cases if c.get("gs", 1.0) != 1.0]                         # and the saturated runs
+
+
+def _fb_with_buffers(S, c, **kw):
+    saved = {}
+    a = S.fb_ref(c, saved=saved, **kw)
+    return a, {k: v.numpy() for k, v in saved["grads"]().items()}
+
+
+def test_stack_fb_jitter_floor():
+    """The floor of every bound in test_gpu_bf16_stack_fb.py: how far fp32-level noise (half an fp32 ulp before every bf16 rounding)
+    moves the reference from itself, at the largest and at the longest case of every tier, on every measure that file applies.  Every
+    bound there must sit at or above this floor; a per-row bound of None must be explained by it."""
+    import test_gpu_bf16_stack_fb as S
+    t0 = time.time()
+    bad = []
+
+    def floor(kind, c, a, b):
+        for name, group, measure, v in S.figures(kind, b, a):
+            bd = S.bound_of(kind, c, group, measure)
+            print("jitter floor %-6s %-5s %-28s %-8s %-5s %.2e (bound %s)" % (kind, S.tier(c), c["id"], name, measure, v,
+                                                                             "None" if bd is None else "%.1e" % bd))
+            if bd is not None and v > bd:
+                bad.append((c["id"], name, measure, v, bd))
+    for c in _largest(S.STACK_CASES, S):
+        a = S.stack_ref(c)
+        with E.jitter(6e-8, 1):
+            b = S.stack_ref(c)
+        floor("stack", c, a, b)
+    for c in _largest(S.FB_CASES, S):
+        a = S.fb_ref(c)
+        with E.jitter(6e-8, 1):
+            b = S.fb_ref(c)
+        floor("fb", c, a, b)
+    for c in _largest(S.FB_BWD_CASES, S):               # the C entry point's buffers, at the cases that read them
+        _, ga = _fb_with_buffers(S, c)
+        with E.jitter(6e-8, 1):
+            _, gb = _fb_with_buffers(S, c)
+        floor("fb_bwd", c, ga, gb)
+    print("%.1f s" % (time.time() - t0))
+    assert not bad, bad
+
+
+# Mutations of the two references, each a subtle kernel bug (the sizes to see: single-step faults, a 5 % bias error): each must exceed
+# the bound test_gpu_bf16_stack_fb.py applies to its tier on the named tensor and measure.
+_MT, _MB = 7, 1                                        # the step and the sequence of the single-step mutants
+
+
+def _sm_stale_o(lv):
+    hist = {}
+
+    def xa(t, l, x):                                    # sequence _MB's layer 0 reads o_{t-2} at step _MT
+        if l == 0:
+            hist[t] = x
+            if t == _MT:
+                x = x.clone()
+                x[_MB] = hist[t - 1][_MB]
+        return x
+    return {"xa": xa}
+
+
+def _sm_drop_feedback_grad(lv):
+    def xa(t, l, x):                                    # the gradient through o_{_MT-1} into the top layer is dropped for sequence _MB
+        if l == 0 and t == _MT:
+            x = torch.cat([x[:_MB], x[_MB:_MB + 1].detach(), x[_MB + 1:]])
+        return x
+    return {"xa": xa}
+
+
+def _sm_ragged_bias(lv):
+    L, H = lv["P"].shape[0], lv["P"].shape[2] // 2
+    last = (H - 1) // 16 * 16                           # the last, ragged 16-unit tile of the top layer: its bias x 1.05
+
+    def bias(l, b):
+        if l != L - 1:
+            return b
+        s = torch.ones_like(b)
+        for q in range(4):
+            s[q * H + last:(q + 1) * H] = 1.05
+        return b * s
+    return {"bias": bias}
+
+
+def _sm_wrong_half(lv):
+    hist = {}
+
+    def xb(t, l, x):
+        hist[t, l] = x                                  # h^l_{t-1}
+        return x
+
+    def xa(t, l, x):                                    # layer 1 reads h^0_{t-1} instead of h^0_t at step _MT: the other half of the buffer
+        return hist[t, 0] if (l == 1 and t == _MT) else x
+    return {"xa": xa, "xb": xb}
+
+
+def _sm_o_init(lv):
+    L = lv["P"].shape[0]
+    return {"xa": lambda t, l, x: lv["h0"][L - 1] if (t == 0 and l == 0) else x}     # o_{-1} = h0[L-1] instead of zeros
+
+
+def _sm_dbias_unrounded(lv):
+    return {"pre": lambda t, l, prod, b: E.round_bwd(prod) + b}                        # dbias summed from the unrounded dG
+
+
+def _fm_stale_p(lv):
+    hist = {}
+
+    def p(t, x):                                        # sequence _MB is fed p_{t-2} at step _MT
+        hist[t] = x
+        if t == _MT:
+            x = torch.cat([x[:_MB], hist[t - 1][_MB:_MB + 1], x[_MB + 1:]])
+        return x
+    return {"p": p}
+
+
+def _fm_stale_mask(lv):
+    hist = {}
+
+    def mask(t, mk):                                    # the backward of step _MT takes the ReLU mask of u_{t-1}
+        hist[t] = mk
+        return hist[t - 1] if t == _MT else mk
+    return {"mask": mask}
+
+
+def _fm_no_wp_term(lv):
+    return {"p": lambda t, x: x.detach() if t == _MT + 1 else x}                       # dp_{_MT} without dG_{_MT+1} . w_p
+
+
+def _fm_db2_unrounded(lv):
+    def readout(t, u, w2, b2):
+        return E.fb_readout(u, w2, b2.detach()) + (b2 - b2.detach())
+    return {"readout": readout}
+
+
+def _fm_last_tile(inputs):
+    """w2 . u without the rows of the last read-out tile: an input edit (rows >= 16 floor((E-1)/16) of w2 scaled by 0)"""
+    inp, w = inputs
+    E_ = inp["w2"].numel()
+    w2 = inp["w2"].clone()
+    w2[(E_ - 1) // 16 * 16:] = 0.0
+    return dict(inp, w2=w2), w
+
+
+# (name, kind, case, hooks from the leaves or None, input edit or None, tensor, measure)
+def _stack_fb_mutants():
+    import test_gpu_bf16_stack_fb as S
+    s, f = S._sc(13, 3, 40, 3), S._fc(13, 3, 40, 24)
+    return [("stale_o", "stack", s, _sm_stale_o, None, "h_all", "row"),
+            ("drop_feedback_grad", "stack", s, _sm_drop_feedback_grad, None, "dP0.xb", "scale"),
+            ("ragged_tile_bias", "stack", s, _sm_ragged_bias, None, "h_top", "rel"),
+            ("wrong_buffer_half", "stack", s, _sm_wrong_half, None, "h_all", "row"),
+            ("o_init_h0_top", "stack", s, _sm_o_init, None, "h_top", "row"),
+            ("dbias_unrounded", "stack", s, _sm_dbias_unrounded, None, "dbias", "row"),
+            ("stale_p", "fb", f, _fm_stale_p, None, "h_all", "row"),
+            ("stale_relu_mask", "fb", f, _fm_stale_mask, None, "dgxc", "row"),
+            ("last_readout_tile", "fb", f, None, _fm_last_tile, "p_all", "rel"),
+            ("dp_without_wp_term", "fb", f, _fm_no_wp_term, None, "dgxc", "row"),
+            ("db2_unrounded", "fb", f, _fm_db2_unrounded, None, "db2", "row")]
+
+
+@pytest.mark.parametrize("i", range(11))
+def test_stack_fb_bounds_see_a_mutant(i):
+    import test_gpu_bf16_stack_fb as S
+    name, kind, c, hooks, edit, tensor, measure = _stack_fb_mutants()[i]
+    run = S.stack_ref if kind == "stack" else S.fb_ref
+    inputs = (S.stack_inputs if kind == "stack" else S.fb_inputs)(c)
+    ref = run(c, inputs)
+    got = run(c, edit(inputs) if edit else inputs, mutate=hooks)
+    figs = S.figures(kind, got, ref)
+    v, bd = next((v, S.bound_of(kind, c, g, m)) for n, g, m, v in figs if n == tensor and m == measure)
+    print("mutant %s (%s, tier %s): %s %s %.3e (bound %.1e)" % (name, c["id"], S.tier(c), tensor, measure, v, bd))
+    assert v > bd
