@@ -15,7 +15,8 @@
 //            FRAG  (attention operand fragment layout (R) for Q/K/V or dO, plus delta = rowsum(dO.O)),
 //            LNBWD (LayerNorm backward fused behind the input-gradient GEMM + residual gradient).
 // Stages chain inside one kernel (the tile stays in LDS between them): the forward chains, the backward chain and the
-// backward boundary chain at the end of this file.
+// backward boundary chain at the end of this file.  Their LDS geometry has one source, chain_kind_geom below: api.hip sizes and
+// refuses launches with it, the fixed-shape instances (ChainShape) carve from it at compile time.
 #pragma once
 #include "common.h"
 #include "attn_mask.h"
@@ -730,9 +731,12 @@ __device__ __forceinline__ void warm_weights(const bf16* W, int NP, int KP) {
     asm volatile("" :: "v"(acc));
 }
 
+// launch bounds of the row kernels: `n` workgroups' worth of waves per SIMD at the 8-wave or 16-window geometries, 2 at 32 windows x 4 waves
+#define MMT_ROW_OCC(n) ((MMT_ROWS == 16 || MMT_RTHREADS == 512) ? (n) : 2)
+
 // ---- single stage ------------------------------------------------------------------------------
 template <int EPI, bool LNPRO, bool WIDE = false, bool DEVSEED = false>
-__global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 512) ? 4 : 2) void rowgemm_kernel(const RowGemmParams p) {
+__global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC(4)) void rowgemm_kernel(const RowGemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     RowSmem sm;
     sm.As = reinterpret_cast<bf16*>(smem);
@@ -746,15 +750,42 @@ __global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 51
 // ---- chained stages ------------------------------------------------------------------------------
 // final LayerNorm of the stack applied to the last stage's output tile while it is still in LDS (y == nullptr: none)
 struct LnOut { const float* a; const float* b; float eps; float* y; float* stats; int d; };
-struct RowChain3 { RowGemmParams a, b, c; int lda_max, ldf, ldx, lda2; LnOut ln; };   // LDS geometry decided by the host
+struct RowChain3 { RowGemmParams a, b, c; int lda_max, ldf, ldx, lda2; LnOut ln; };   // LDS geometry: chain_kind_geom, filled in by the host's launch
 // MaskRide: one layer's attention-dropout decisions, drawn by extra workgroups of a d_model = 128 forward launch (workgroups >=
 // chain_wgs; gen_wgs == 0: none): the next layer's in encoder_post_attn_fwd4_kernel<*, 128>, layer 0's in encoder_ln1_qkv128_kernel
 struct MaskRide { MaskGenLayer g; int chain_wgs, gen_wgs, gen_waves; };
 struct RowChain4 { RowGemmParams a, b, c, d; int lda_max, ldf, ldx, lda2; MaskRide ride; };
 
-template <typename CH>
-__host__ __device__ inline size_t rowchain_lds_bytes(const CH& ch, bool with_g) {
-    return (size_t)MMT_ROWS * ch.lda_max * 2 + (size_t)MMT_ROWS * ch.ldf * 4 * (with_g ? 2 : 1) + (size_t)MMT_ROWS * ch.ldx * 4 + (size_t)MMT_ROWS * ch.lda2 * 2;
+// LDS geometry of the chained kernels: THE place that knows it — the host sizes and refuses launches with it, the generic kernels carve
+// what it put into their RowChain, the fixed-shape instances carve from it at compile time.  As: bf16 [MMT_ROWS][lda_max]; Fs (and Gs
+// behind it when with_g): fp32 [MMT_ROWS][ldf]; Xs: fp32 [MMT_ROWS][ldx]; A2: bf16 [MMT_ROWS][lda2].
+//   kmax:   the widest A tile staged in As (a K-chunked first stage counts one chunk);
+//   lnb_np: width of the full fp32 rows the chain needs in Fs — the output width of its LayerNorm-backward stages, whose epilogue also
+//           needs a second fp32 tile (Gs) unless the column sums recompute x-hat (no_gs); 0: 128-column chunks only.
+struct ChainGeom { int lda_max, ldf, ldx, lda2; bool with_g; size_t lds; };
+__host__ __device__ constexpr ChainGeom chain_geom(int kmax, int lnb_np, bool no_gs, int ldx, int lda2) {
+    const int lda_max = kmax + 8, ldf = (lnb_np > 128 ? lnb_np : 128) + 4;
+    const bool with_g = lnb_np > 0 && !no_gs;
+    return ChainGeom{lda_max, ldf, ldx, lda2, with_g,
+                     (size_t)MMT_ROWS * lda_max * 2 + (size_t)MMT_ROWS * ldf * 4 * (with_g ? 2 : 1) + (size_t)MMT_ROWS * ldx * 4 + (size_t)MMT_ROWS * lda2 * 2};
+}
+// K-chunking of the dQKV tile (K = NQ) in the LayerNorm-1 backward: d_model = 256 has K = 768, in LDS one chunk of 512 at a time
+__host__ __device__ constexpr int qkv_kchunk(int NQ) { return NQ > 512 ? 512 : 0; }
+__host__ __device__ constexpr int imax(int a, int b) { return a > b ? a : b; }
+// ... of each kind of kernel, from the padded widths of the layer (common.h LayerLayout: DP d_model, FP d_ff, HDP h d_k, NQ 3 h d_k).
+// The two single stages are the d_model = 128 instances' (the generic rowgemm_kernel sizes itself: rowgemm_lds_bytes, the same bytes at
+// DP >= 128 and fewer below).
+enum ChainKind { CHAIN_FWD = 0, CHAIN_BWD, CHAIN_BOUNDARY, STAGE_LN1_QKV, STAGE_BWD_QKV };
+__host__ __device__ constexpr ChainGeom chain_kind_geom(int kind, int DP, int FP, int HDP, int NQ) {
+    const int qc = qkv_kchunk(NQ), qk = qc ? qc : NQ;            // columns of the dQKV tile staged at a time
+    const bool no_gs = DP > 128;                                 // a second fp32 tile would leave one workgroup per CU; K-chunking implies it too
+    switch (kind) {
+    case CHAIN_FWD:      return chain_geom(imax(HDP, imax(DP, FP)), 0, false, DP + 4, FP + 8);     // x1 / x2 kept in Xs, hid in A2; no LayerNorm backward
+    case CHAIN_BWD:      return chain_geom(imax(DP, FP), DP, no_gs, 0, FP + 8);                    // dh in A2
+    case CHAIN_BOUNDARY: return chain_geom(imax(qk, imax(DP, FP)), DP, no_gs || qc, 0, FP + 8);    // the dQKV tile first, then CHAIN_BWD's stages
+    case STAGE_LN1_QKV:  return chain_geom(DP, DP, true, 0, 0);                                    // (the LayerNorm prologue reads full fp32 rows from Fs)
+    default:             return chain_geom(qk, DP, no_gs || qc, 0, 0);                             // STAGE_BWD_QKV
+    }
 }
 template <typename CH>
 __device__ __forceinline__ RowSmem rowchain_carve(char* smem, const CH& ch, bool with_g) {
@@ -836,45 +867,12 @@ __device__ __forceinline__ RowGemmParams role_bwd_relu(RowGemmParams p) {       
     return p;
 }
 
-// Forward, after the attention core of a layer:   x1 = x + drop(ctx Wo^T + bo)        (out-proj + residual; x1 kept in LDS)
-//                                                 hid = drop(relu(LN2(x1) W1^T + b1))  (hid kept in LDS as the next A tile)
-//                                                 x2 = x1 + drop(hid W2^T + b2)        (residual read from LDS)
-template <int K_, int N_> __device__ __forceinline__ RowGemmParams shape_pin(RowGemmParams p);
-template <int LDA_MAX, int LDF, bool WITH_G, int LDX, int LDA2> __device__ __forceinline__ RowSmem carve_fixed(char* smem);
-template <bool DEVSEED, int SHAPE = 0>
-__global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 512) ? 4 : 2) void encoder_post_attn_fwd_kernel(const RowChain3 ch) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    warm_weights(ch.b.W, ch.b.NP, ch.b.KP); warm_weights(ch.c.W, ch.c.NP, ch.c.KP);
-    if (SHAPE == 128) {                                         // (fixed-shape instances: see below)
-        const RowSmem sm = carve_fixed<136, 132, false, 132, 136>(smem);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_X, DEVSEED>(shape_pin<128, 128>(role_plain(ch.a)), sm);
-        rowgemm_stage<EPI_PLAIN, true, ASRC_X, KEEP_A2, DEVSEED>(shape_pin<128, 128>(role_ffn1(ch.b)), sm);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_A2, RES_X | KEEP_X, DEVSEED>(shape_pin<128, 128>(role_plain(ch.c)), sm);
-        if (ch.ln.y) ln_tile_out(sm.Xs, sm.ldx, ch.ln, ch.c.M);
-        return;
-    }
-    if (SHAPE == 256) {
-        const RowSmem sm = carve_fixed<264, 132, false, 260, 136>(smem);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_X, DEVSEED>(shape_pin<256, 256>(role_plain(ch.a)), sm);
-        rowgemm_stage<EPI_PLAIN, true, ASRC_X, KEEP_A2, DEVSEED>(shape_pin<256, 128>(role_ffn1(ch.b)), sm);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_A2, RES_X | KEEP_X, DEVSEED>(shape_pin<128, 256>(role_plain(ch.c)), sm);
-        if (ch.ln.y) ln_tile_out(sm.Xs, sm.ldx, ch.ln, ch.c.M);
-        return;
-    }
-    const RowSmem sm = rowchain_carve(smem, ch, false);
-    rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_X, DEVSEED>(role_plain(ch.a), sm);
-    rowgemm_stage<EPI_PLAIN, true, ASRC_X, KEEP_A2, DEVSEED>(role_ffn1(ch.b), sm);
-    rowgemm_stage<EPI_PLAIN, false, ASRC_A2, RES_X | KEEP_X, DEVSEED>(role_plain(ch.c), sm);
-    if (ch.ln.y) ln_tile_out(sm.Xs, sm.ldx, ch.ln, ch.c.M);          // last layer: the stack's final LayerNorm, from the tile in LDS
-}
-
-// The same chain followed by the NEXT layer's LayerNorm-1 + Q/K/V projection (its input x2 is already in LDS): every
-// layer but the last.  One launch and one round trip of the residual stream less per layer.
-// ---- fixed-shape instances.  The chains above take every width, stride and the LDS geometry at run time; 70 % of their static
+// ---- fixed-shape instances.  The chains take every width, stride and the LDS geometry at run time; 70 % of their static
 // instruction stream was integer / scalar bookkeeping (address arithmetic, bounds compares, branches) around 12 % floating point.
 // For the widths of the BASELINE configs the host selects an instance in which the stages' shapes, leading dimensions and the LDS
-// carve are pinned like the roles (shape_pin, carve_fixed): the arithmetic folds into immediates (configs[3]: 2 879 -> 1 989
-// static instructions in the 4-stage forward chain, -11 % time).  SHAPE: 0 = generic; 128 = d_model = d_ff = h d_k = 128, 8 heads of 16.
+// carve are pinned like the roles: the arithmetic folds into immediates (configs[3]: 2 879 -> 1 989 static instructions in the
+// 4-stage forward chain, -11 % time).  A shape is described ONCE, by its widths (ShapeWidths); the per-stage pins and the carve of
+// every kernel follow from them (ChainShape), and the host launches with the same chain_kind_geom of the same widths.
 template <int K_, int N_> __device__ __forceinline__ RowGemmParams shape_pin(RowGemmParams p) {
     p.K = K_; p.KP = K_; p.N = N_; p.NP = N_;
     p.lda = K_; p.lda_out = K_;                                 // A row-major [M][K] (and its bf16 copy)
@@ -895,24 +893,47 @@ __device__ __forceinline__ RowSmem carve_fixed(char* smem) {
     sm.lda2 = LDA2;
     return sm;
 }
-// the geometry chain_geom (api.hip) gives launch_rowchain for SHAPE 128; it refuses the fixed instance when its own numbers differ
-#define MMT_FIX128_LDF 132
-#define MMT_FIX128_LDA2 136
-#define MMT_FIX128_LDA_FWD 136
-#define MMT_FIX128_LDA_BND 392
-__device__ __forceinline__ RowGemmParams qkv128(RowGemmParams p) { p = shape_pin<128, 384>(p); p.lda_out = 128; p.h = 8; p.DKP = 16; return p; }
-__device__ __forceinline__ RowGemmParams dO128(RowGemmParams p) { p = shape_pin<128, 128>(p); p.h = 8; p.DKP = 16; return p; }
-// SHAPE 256 = the MFT's per-modality stacks (configs[2], configs[4]): d_model = h d_k = 256 (8 heads of 32), d_ff = 128; the backward
-// chains are the WIDE instances (K-chunked dQKV tile, x-hat recomputed)
-#define MMT_FIX256_LDA 264
-#define MMT_FIX256_LDA_BND 520
-#define MMT_FIX256_LDF_FWD 132
-#define MMT_FIX256_LDF_BWD 260
-#define MMT_FIX256_LDX 260
-#define MMT_FIX256_LDA2 136
-__device__ __forceinline__ RowGemmParams qkv256(RowGemmParams p) { p = shape_pin<256, 768>(p); p.lda_out = 256; p.h = 8; p.DKP = 32; return p; }
-__device__ __forceinline__ RowGemmParams dO256(RowGemmParams p) { p = shape_pin<256, 256>(p); p.h = 8; p.DKP = 32; return p; }
-__device__ __forceinline__ RowGemmParams lnbwd256(RowGemmParams p) { p.no_gs = 1; return p; }
+// SHAPE: 0 = generic (widths at run time); 128 = d_model = d_ff = h d_k = 128, 8 heads of 16 (configs[3]); 256 = the MFT's per-modality
+// stacks (configs[2], configs[4]): d_model = h d_k = 256 (8 heads of 32), d_ff = 128
+template <int SHAPE> struct ShapeWidths { static constexpr int D = 0, F = 0, HD = 0, NQ = 0, H = 0, DKP = 0; };
+template <> struct ShapeWidths<128> { static constexpr int D = 128, F = 128, HD = 128, NQ = 384, H = 8, DKP = 16; };
+template <> struct ShapeWidths<256> { static constexpr int D = 256, F = 128, HD = 256, NQ = 768, H = 8, DKP = 32; };
+template <int SHAPE> struct ChainShape : ShapeWidths<SHAPE> {
+    using W = ShapeWidths<SHAPE>;
+    using P = RowGemmParams;
+    // the shape's backward kernels are the WIDE instances (x-hat recomputed; its dQKV tile K-chunked: QCHUNK)
+    static constexpr bool WIDE = W::D > 128;
+    static constexpr int QCHUNK = qkv_kchunk(W::NQ);
+    static constexpr ChainGeom geom(int kind) { return chain_kind_geom(kind, W::D, W::F, W::HD, W::NQ); }
+    // LDS carve of the shape's kernel of kind KIND, from the constants of its own geometry.  (SHAPE 0: rowchain_carve, from the kernel's
+    // argument; the kernels choose between the two themselves — a carve function that is handed the kernel argument by reference changes
+    // how hipcc loads that argument in the stages, and the fixed instances came out 1 to 15 instructions different)
+    template <int KIND> static __device__ __forceinline__ RowSmem carve(char* smem) {
+        constexpr ChainGeom g = geom(KIND);
+        return carve_fixed<g.lda_max, g.ldf, g.with_g, g.ldx, g.lda2>(smem);
+    }
+    // One pin per stage role: the stage's parameters (its role already pinned: role_*) with, for a fixed shape, its <K, N>, strides
+    // and head split pinned too; generic: unchanged
+    template <int K_, int N_> static __device__ __forceinline__ P pin(P p) { if constexpr (SHAPE == 0) return p; else return shape_pin<K_, N_>(p); }
+    static __device__ __forceinline__ P heads(P p) { if constexpr (SHAPE != 0) { p.h = W::H; p.DKP = W::DKP; } return p; }
+    static __device__ __forceinline__ P lnbwd(P p) { if constexpr (WIDE) p.no_gs = 1; return p; }
+    static __device__ __forceinline__ P outproj(P p)   { return pin<W::HD, W::D>(p); }
+    static __device__ __forceinline__ P ffn1(P p)      { return pin<W::D, W::F>(p); }
+    static __device__ __forceinline__ P ffn2(P p)      { return pin<W::F, W::D>(p); }
+    static __device__ __forceinline__ P qkv(P p)       { p = pin<W::D, W::NQ>(p); if constexpr (SHAPE != 0) p.lda_out = W::D; return heads(p); }
+    static __device__ __forceinline__ P bwd_relu(P p)  { return pin<W::D, W::F>(p); }
+    static __device__ __forceinline__ P lnbwd_ffn(P p) { return lnbwd(pin<W::F, W::D>(p)); }
+    static __device__ __forceinline__ P lnbwd_qkv(P p) { p = lnbwd(pin<W::NQ, W::D>(p)); if constexpr (QCHUNK != 0) p.kchunk = QCHUNK; return p; }
+    static __device__ __forceinline__ P dO(P p)        { return heads(pin<W::D, W::HD>(p)); }
+};
+// the numbers, for the reader: As / Fs / A2 row strides (Xs: D + 4 in the forward chains, none in the backward)
+static_assert(ChainShape<128>::geom(CHAIN_FWD).lda_max == 136 && ChainShape<128>::geom(CHAIN_BOUNDARY).lda_max == 392 &&
+              ChainShape<128>::geom(CHAIN_FWD).ldf == 132 && ChainShape<128>::geom(CHAIN_BWD).ldf == 132 && ChainShape<128>::geom(CHAIN_FWD).lda2 == 136 &&
+              ChainShape<128>::geom(CHAIN_BWD).with_g && !ChainShape<128>::WIDE && ChainShape<128>::QCHUNK == 0, "SHAPE 128: 136 / 392 / 132 / 136");
+static_assert(ChainShape<256>::geom(CHAIN_FWD).lda_max == 264 && ChainShape<256>::geom(CHAIN_BOUNDARY).lda_max == 520 &&
+              ChainShape<256>::geom(CHAIN_FWD).ldf == 132 && ChainShape<256>::geom(CHAIN_BWD).ldf == 260 && ChainShape<256>::geom(CHAIN_FWD).ldx == 260 &&
+              ChainShape<256>::geom(CHAIN_FWD).lda2 == 136 && !ChainShape<256>::geom(CHAIN_BWD).with_g && ChainShape<256>::WIDE &&
+              ChainShape<256>::QCHUNK == 512, "SHAPE 256: 264 / 520 / 132 / 260 / 260 / 136");
 
 // The SHAPE 128 instance carries a second ROLE.  Its chain is latency-bound (the vector ALUs of a SIMD are busy 47 % of the time with
 // its four waves) and its 76 VGPRs and 51 200 B of LDS leave room for a third workgroup per CU, while the attention-dropout generator
@@ -925,39 +946,44 @@ __device__ __forceinline__ RowGemmParams lnbwd256(RowGemmParams p) { p.no_gs = 1
 #define MMT_RIDE_WAVES 4
 #define MMT_RIDE_CHAINS 16             // hash chains in flight per generator lane: the draw inside the chain's register budget
 #define MMT_RIDE_OCC 6
+
+// the generator role, of the workgroups past the tiles (blockIdx.x >= ride.chain_wgs): each draws its share of the decisions
+__device__ __forceinline__ void mask_ride_generate(const MaskRide& ride, char* smem) {
+    __builtin_amdgcn_s_setprio(0);
+    attn_mask_gen_block<MMT_RIDE_CHAINS>(ride.g, reinterpret_cast<uint16_t*>(smem),
+                                         (size_t)(blockIdx.x - (unsigned)ride.chain_wgs) * (64 * ride.gen_waves), ride.gen_waves);
+}
+
+// Forward, after the attention core of a layer:   x1 = x + drop(ctx Wo^T + bo)        (out-proj + residual; x1 kept in LDS)
+//                                                 hid = drop(relu(LN2(x1) W1^T + b1))  (hid kept in LDS as the next A tile)
+//                                                 x2 = x1 + drop(hid W2^T + b2)        (residual read from LDS)
 template <bool DEVSEED, int SHAPE = 0>
-__global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 512) ? ((SHAPE == 128 && MMT_RTHREADS == 512) ? MMT_RIDE_OCC : 4) : 2)
-void encoder_post_attn_fwd4_kernel(const RowChain4 ch) {
+__global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC(4)) void encoder_post_attn_fwd_kernel(const RowChain3 ch) {
+    using S = ChainShape<SHAPE>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (SHAPE == 128 && (int)blockIdx.x >= ch.ride.chain_wgs) {          // generator role
-        __builtin_amdgcn_s_setprio(0);
-        attn_mask_gen_block<MMT_RIDE_CHAINS>(ch.ride.g, reinterpret_cast<uint16_t*>(smem),
-                                             (size_t)((int)blockIdx.x - ch.ride.chain_wgs) * (64 * ch.ride.gen_waves), ch.ride.gen_waves);
-        return;
-    }
+    warm_weights(ch.b.W, ch.b.NP, ch.b.KP); warm_weights(ch.c.W, ch.c.NP, ch.c.KP);
+    const RowSmem sm = SHAPE ? S::template carve<CHAIN_FWD>(smem) : rowchain_carve(smem, ch, false);
+    rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_X, DEVSEED>(S::outproj(role_plain(ch.a)), sm);
+    rowgemm_stage<EPI_PLAIN, true, ASRC_X, KEEP_A2, DEVSEED>(S::ffn1(role_ffn1(ch.b)), sm);
+    rowgemm_stage<EPI_PLAIN, false, ASRC_A2, RES_X | KEEP_X, DEVSEED>(S::ffn2(role_plain(ch.c)), sm);
+    if (ch.ln.y) ln_tile_out(sm.Xs, sm.ldx, ch.ln, ch.c.M);          // last layer: the stack's final LayerNorm, from the tile in LDS
+}
+
+// The same chain followed by the NEXT layer's LayerNorm-1 + Q/K/V projection (its input x2 is already in LDS): every
+// layer but the last.  One launch and one round trip of the residual stream less per layer.
+template <bool DEVSEED, int SHAPE = 0>
+__global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC((SHAPE == 128 && MMT_RTHREADS == 512) ? MMT_RIDE_OCC : 4))
+void encoder_post_attn_fwd4_kernel(const RowChain4 ch) {
+    using S = ChainShape<SHAPE>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (SHAPE == 128 && (int)blockIdx.x >= ch.ride.chain_wgs) { mask_ride_generate(ch.ride, smem); return; }
     warm_weights(ch.b.W, ch.b.NP, ch.b.KP); warm_weights(ch.c.W, ch.c.NP, ch.c.KP);
     warm_weights(ch.d.W, ch.d.NP, ch.d.KP);
-    if (SHAPE == 128) {
-        const RowSmem sm = carve_fixed<MMT_FIX128_LDA_FWD, MMT_FIX128_LDF, false, 132, MMT_FIX128_LDA2>(smem);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_X, DEVSEED>(shape_pin<128, 128>(role_plain(ch.a)), sm);
-        rowgemm_stage<EPI_PLAIN, true, ASRC_X, KEEP_A2, DEVSEED>(shape_pin<128, 128>(role_ffn1(ch.b)), sm);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_A2, RES_X | KEEP_X, DEVSEED>(shape_pin<128, 128>(role_plain(ch.c)), sm);
-        rowgemm_stage<EPI_FRAG, true, ASRC_X, 0, false>(qkv128(role_qkv(ch.d)), sm);
-        return;
-    }
-    if (SHAPE == 256) {
-        const RowSmem sm = carve_fixed<MMT_FIX256_LDA, MMT_FIX256_LDF_FWD, false, MMT_FIX256_LDX, MMT_FIX256_LDA2>(smem);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_X, DEVSEED>(shape_pin<256, 256>(role_plain(ch.a)), sm);
-        rowgemm_stage<EPI_PLAIN, true, ASRC_X, KEEP_A2, DEVSEED>(shape_pin<256, 128>(role_ffn1(ch.b)), sm);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_A2, RES_X | KEEP_X, DEVSEED>(shape_pin<128, 256>(role_plain(ch.c)), sm);
-        rowgemm_stage<EPI_FRAG, true, ASRC_X, 0, false>(qkv256(role_qkv(ch.d)), sm);
-        return;
-    }
-    const RowSmem sm = rowchain_carve(smem, ch, false);
-    rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_X, DEVSEED>(role_plain(ch.a), sm);
-    rowgemm_stage<EPI_PLAIN, true, ASRC_X, KEEP_A2, DEVSEED>(role_ffn1(ch.b), sm);
-    rowgemm_stage<EPI_PLAIN, false, ASRC_A2, RES_X | KEEP_X, DEVSEED>(role_plain(ch.c), sm);
-    rowgemm_stage<EPI_FRAG, true, ASRC_X, 0, false>(role_qkv(ch.d), sm);
+    const RowSmem sm = SHAPE ? S::template carve<CHAIN_FWD>(smem) : rowchain_carve(smem, ch, false);
+    rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_X, DEVSEED>(S::outproj(role_plain(ch.a)), sm);
+    rowgemm_stage<EPI_PLAIN, true, ASRC_X, KEEP_A2, DEVSEED>(S::ffn1(role_ffn1(ch.b)), sm);
+    rowgemm_stage<EPI_PLAIN, false, ASRC_A2, RES_X | KEEP_X, DEVSEED>(S::ffn2(role_plain(ch.c)), sm);
+    rowgemm_stage<EPI_FRAG, true, ASRC_X, 0, false>(S::qkv(role_qkv(ch.d)), sm);
 }
 
 // layer 0's two single-stage launches as fixed-shape instances (SHAPE 128).
@@ -970,56 +996,37 @@ void encoder_post_attn_fwd4_kernel(const RowChain4 ch) {
 #define MMT_HEAD_RIDE_WAVES 4          // generator waves per riding workgroup of ln1+qkv (DESIGN 6 has 2 measured beside it)
 #endif
 struct RowGemmRide { RowGemmParams p; MaskRide ride; };
-__global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 512) ? (MMT_RTHREADS == 512 ? MMT_RIDE_OCC : 4) : 2)
+__global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC(MMT_RTHREADS == 512 ? MMT_RIDE_OCC : 4))
 void encoder_ln1_qkv128_kernel(const RowGemmRide a) {
+    using S = ChainShape<128>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if ((int)blockIdx.x >= a.ride.chain_wgs) {                             // generator role
-        __builtin_amdgcn_s_setprio(0);
-        attn_mask_gen_block<MMT_RIDE_CHAINS>(a.ride.g, reinterpret_cast<uint16_t*>(smem),
-                                             (size_t)((int)blockIdx.x - a.ride.chain_wgs) * (64 * a.ride.gen_waves), a.ride.gen_waves);
-        return;
-    }
-    const RowGemmParams& p = a.p;
-    const RowSmem sm = carve_fixed<MMT_FIX128_LDA_FWD, MMT_FIX128_LDF, false, 0, 0>(smem);
-    RowGemmParams q = qkv128(role_qkv(p));
-    q.lda = 128;
-    rowgemm_stage<EPI_FRAG, true, ASRC_GLOBAL, 0, false>(q, sm);
+    if ((int)blockIdx.x >= a.ride.chain_wgs) { mask_ride_generate(a.ride, smem); return; }
+    rowgemm_stage<EPI_FRAG, true, ASRC_GLOBAL, 0, false>(S::qkv(role_qkv(a.p)), S::carve<STAGE_LN1_QKV>(smem));
 }
 template <bool DEVSEED>
-__global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 512) ? 4 : 2) void encoder_bwd_qkv_ln1_128_kernel(const RowGemmParams p) {
+__global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC(4)) void encoder_bwd_qkv_ln1_128_kernel(const RowGemmParams p) {
+    using S = ChainShape<128>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const RowSmem sm = carve_fixed<MMT_FIX128_LDA_BND, MMT_FIX128_LDF, true, 0, 0>(smem);
-    RowGemmParams q = shape_pin<384, 128>(role_lnbwd(p));
-    q.next_drop.thr16 = 0; q.kchunk = 0; q.no_gs = 0;
-    rowgemm_stage<EPI_LNBWD, false, ASRC_GLOBAL, 0, DEVSEED, false>(q, sm);
+    RowGemmParams q = S::lnbwd_qkv(role_lnbwd(p));
+    q.next_drop.thr16 = 0; q.kchunk = 0; q.no_gs = 0;           // (what the chains leave to the host: nothing follows this stage)
+    rowgemm_stage<EPI_LNBWD, false, ASRC_GLOBAL, 0, DEVSEED, false>(q, S::carve<STAGE_BWD_QKV>(smem));
 }
 
 // Backward, from the layer-output gradient dx2 down to the attention core's operands:
 //     dh  = (drop'(dx2) W2) * relu'(hid) * drop'          (dh kept in LDS as the next A tile; dx2^T, dh^T emitted for dW)
 //     dx1 = dx2 + LN2bwd(dh W1)                            (drop'(dx1) kept in LDS as the next A tile)
 //     dO  = drop'(dx1) Wo  -> fragment layouts + delta     (dx1^T emitted for dW)
+// WIDE: the d_model > 128 variant of the LayerNorm-backward stages; a fixed shape exists as one of the two only (ChainShape::WIDE).
 template <bool WIDE, bool DEVSEED, int SHAPE = 0>
-__global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 512) ? 4 : 2) void encoder_pre_attn_bwd_kernel(const RowChain3 ch) {
+__global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC(4)) void encoder_pre_attn_bwd_kernel(const RowChain3 ch) {
+    using S = ChainShape<SHAPE>;
+    static_assert(SHAPE == 0 || WIDE == S::WIDE, "a fixed shape's backward exists as its own WIDE / not-WIDE instance only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     warm_weights(ch.b.W, ch.b.NP, ch.b.KP); warm_weights(ch.c.W, ch.c.NP, ch.c.KP);
-    if (SHAPE == 128 && !WIDE) {
-        const RowSmem sm = carve_fixed<MMT_FIX128_LDA_FWD, MMT_FIX128_LDF, true, 0, MMT_FIX128_LDA2>(smem);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_A2, DEVSEED>(shape_pin<128, 128>(role_bwd_relu(ch.a)), sm);
-        rowgemm_stage<EPI_LNBWD, false, ASRC_A2, KEEP_AS, DEVSEED, WIDE>(shape_pin<128, 128>(role_lnbwd(ch.b)), sm);
-        rowgemm_stage<EPI_FRAG, false, ASRC_AS, 0, false>(dO128(role_dO(ch.c)), sm);
-        return;
-    }
-    if (SHAPE == 256 && WIDE) {
-        const RowSmem sm = carve_fixed<MMT_FIX256_LDA, MMT_FIX256_LDF_BWD, false, 0, MMT_FIX256_LDA2>(smem);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_A2, DEVSEED>(shape_pin<256, 128>(role_bwd_relu(ch.a)), sm);
-        rowgemm_stage<EPI_LNBWD, false, ASRC_A2, KEEP_AS, DEVSEED, WIDE>(lnbwd256(shape_pin<128, 256>(role_lnbwd(ch.b))), sm);
-        rowgemm_stage<EPI_FRAG, false, ASRC_AS, 0, false>(dO256(role_dO(ch.c)), sm);
-        return;
-    }
-    const RowSmem sm = rowchain_carve(smem, ch, !WIDE);
-    rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_A2, DEVSEED>(role_bwd_relu(ch.a), sm);
-    rowgemm_stage<EPI_LNBWD, false, ASRC_A2, KEEP_AS, DEVSEED, WIDE>(role_lnbwd(ch.b), sm);      // dx1 -> global (fp32) and, as the next A tile, LDS (bf16)
-    rowgemm_stage<EPI_FRAG, false, ASRC_AS, 0, false>(role_dO(ch.c), sm);
+    const RowSmem sm = SHAPE ? S::template carve<CHAIN_BWD>(smem) : rowchain_carve(smem, ch, !WIDE);
+    rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_A2, DEVSEED>(S::bwd_relu(role_bwd_relu(ch.a)), sm);
+    rowgemm_stage<EPI_LNBWD, false, ASRC_A2, KEEP_AS, DEVSEED, WIDE>(S::lnbwd_ffn(role_lnbwd(ch.b)), sm);      // dx1 -> global (fp32) and, as the next A tile, LDS (bf16)
+    rowgemm_stage<EPI_FRAG, false, ASRC_AS, 0, false>(S::dO(role_dO(ch.c)), sm);
 }
 
 
@@ -1030,30 +1037,14 @@ __global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 51
 // launch and one staging pass less per layer than `bwd_qkv+ln1` followed by the chain.  (WIDE: 83 KB of LDS at d_model = 256, one
 // workgroup per CU — at that width two workgroups sharing a CU take twice as long each anyway)
 template <bool WIDE, bool DEVSEED, int SHAPE = 0>
-__global__ __launch_bounds__(MMT_RTHREADS, (MMT_ROWS == 16 || MMT_RTHREADS == 512) ? 4 : 2) void encoder_bwd_boundary_kernel(const RowChain4 ch) {
+__global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC(4)) void encoder_bwd_boundary_kernel(const RowChain4 ch) {
+    using S = ChainShape<SHAPE>;
+    static_assert(SHAPE == 0 || WIDE == S::WIDE, "a fixed shape's backward exists as its own WIDE / not-WIDE instance only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     warm_weights(ch.b.W, ch.b.NP, ch.b.KP); warm_weights(ch.c.W, ch.c.NP, ch.c.KP); warm_weights(ch.d.W, ch.d.NP, ch.d.KP);
-    if (SHAPE == 128 && !WIDE) {
-        const RowSmem sm = carve_fixed<MMT_FIX128_LDA_BND, MMT_FIX128_LDF, true, 0, MMT_FIX128_LDA2>(smem);
-        rowgemm_stage<EPI_LNBWD, false, ASRC_GLOBAL, KEEP_AS, DEVSEED, WIDE>(shape_pin<384, 128>(role_lnbwd(ch.a)), sm);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_AS, KEEP_A2, DEVSEED>(shape_pin<128, 128>(role_bwd_relu(ch.b)), sm);
-        rowgemm_stage<EPI_LNBWD, false, ASRC_A2, KEEP_AS, DEVSEED, WIDE>(shape_pin<128, 128>(role_lnbwd(ch.c)), sm);
-        rowgemm_stage<EPI_FRAG, false, ASRC_AS, 0, false>(dO128(role_dO(ch.d)), sm);
-        return;
-    }
-    if (SHAPE == 256 && WIDE) {
-        const RowSmem sm = carve_fixed<MMT_FIX256_LDA_BND, MMT_FIX256_LDF_BWD, false, 0, MMT_FIX256_LDA2>(smem);
-        RowGemmParams a = lnbwd256(shape_pin<768, 256>(role_lnbwd(ch.a)));
-        a.kchunk = 512;
-        rowgemm_stage<EPI_LNBWD, false, ASRC_GLOBAL, KEEP_AS, DEVSEED, WIDE>(a, sm);
-        rowgemm_stage<EPI_PLAIN, false, ASRC_AS, KEEP_A2, DEVSEED>(shape_pin<256, 128>(role_bwd_relu(ch.b)), sm);
-        rowgemm_stage<EPI_LNBWD, false, ASRC_A2, KEEP_AS, DEVSEED, WIDE>(lnbwd256(shape_pin<128, 256>(role_lnbwd(ch.c))), sm);
-        rowgemm_stage<EPI_FRAG, false, ASRC_AS, 0, false>(dO256(role_dO(ch.d)), sm);
-        return;
-    }
-    const RowSmem sm = rowchain_carve(smem, ch, !WIDE);
-    rowgemm_stage<EPI_LNBWD, false, ASRC_GLOBAL, KEEP_AS, DEVSEED, WIDE>(role_lnbwd(ch.a), sm);        // layer l:   dx -> global (fp32) + next A tile (bf16, dropped)
-    rowgemm_stage<EPI_PLAIN, false, ASRC_AS, KEEP_A2, DEVSEED>(role_bwd_relu(ch.b), sm);                     // layer l-1: dh
-    rowgemm_stage<EPI_LNBWD, false, ASRC_A2, KEEP_AS, DEVSEED, WIDE>(role_lnbwd(ch.c), sm);                              //            dx1
-    rowgemm_stage<EPI_FRAG, false, ASRC_AS, 0, false>(role_dO(ch.d), sm);                                  //            dO fragments + delta
+    const RowSmem sm = SHAPE ? S::template carve<CHAIN_BOUNDARY>(smem) : rowchain_carve(smem, ch, !WIDE);
+    rowgemm_stage<EPI_LNBWD, false, ASRC_GLOBAL, KEEP_AS, DEVSEED, WIDE>(S::lnbwd_qkv(role_lnbwd(ch.a)), sm);      // layer l:   dx -> global (fp32) + next A tile (bf16, dropped)
+    rowgemm_stage<EPI_PLAIN, false, ASRC_AS, KEEP_A2, DEVSEED>(S::bwd_relu(role_bwd_relu(ch.b)), sm);                  // layer l-1: dh
+    rowgemm_stage<EPI_LNBWD, false, ASRC_A2, KEEP_AS, DEVSEED, WIDE>(S::lnbwd_ffn(role_lnbwd(ch.c)), sm);          //            dx1
+    rowgemm_stage<EPI_FRAG, false, ASRC_AS, 0, false>(S::dO(role_dO(ch.d)), sm);                                //            dO fragments + delta
 }
