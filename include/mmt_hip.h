@@ -128,6 +128,49 @@ int mmt_sdpa_backward(const float* dctx, const float* mask, float* dq, float* dk
 int mmt_attn_probs_forward(const float* q, const float* k, const float* mask, float* probs,
                            int B, int T, int d, int h, float dropout_p, uint64_t seed, mmt_stream_t stream);
 
+/* ---- Key lengths: a padding mask that masks KEYS (opt-in; no counterpart in the reference, whose attention() blanks query rows
+ * only and lets every window attend the padded windows behind its sequence: transformer/MFT/multiTransformer.py:29-31).
+ * key_lengths: int32 (B,) in device memory.  Sequence b attends keys 0 .. key_lengths[b]-1: later keys score -inf, their probabilities
+ * are exactly 0, their dK and dV exactly 0.  The query-row mask keeps its meaning (a blanked row is uniform over the visible keys and
+ * passes no gradient to q).  The kernels clamp every length they read into [1, T].  Each `_keys` entry is the plain entry of the same
+ * name plus the trailing `key_lengths` (NULL: MMT_EINVAL), with the plain entry's workspace; with every length equal to T it computes
+ * what the plain entry computes.  The backward always runs as two kernels (dK/dV, dQ).
+ * mmt_key_lengths: len[b] = 1 + index of the last non-zero entry of row b of mask (B,T) fp32, 1 for an all-zero row — holes inside
+ * the prefix stay attended.  One launch, capture-safe. */
+int mmt_key_lengths(const float* mask, int32_t* key_lengths, int B, int T, mmt_stream_t stream);
+/* mmt_sdpa_forward / mmt_sdpa_backward with key lengths                       (attention(), :22-34) */
+int mmt_sdpa_forward_keys(const float* q, const float* k, const float* v, const float* mask, float* ctx,
+                          void* workspace, size_t workspace_bytes, int B, int T, int d, int h,
+                          float dropout_p, uint64_t seed, mmt_stream_t stream, const int32_t* key_lengths);
+int mmt_sdpa_backward_keys(const float* dctx, const float* mask, float* dq, float* dk, float* dv,
+                           void* workspace, size_t workspace_bytes, int B, int T, int d, int h,
+                           float dropout_p, uint64_t seed, mmt_stream_t stream, const int32_t* key_lengths);
+/* mmt_attn_probs_forward with key lengths: columns >= key_lengths[b] are exact zeros, a blanked query row is 1/key_lengths[b]
+ * on the visible columns                                                      (p_attn, :22-34,59) */
+int mmt_attn_probs_forward_keys(const float* q, const float* k, const float* mask, float* probs,
+                                int B, int T, int d, int h, float dropout_p, uint64_t seed, mmt_stream_t stream,
+                                const int32_t* key_lengths);
+/* mmt_encoder_forward / mmt_encoder_backward and their device-seeded twins with key lengths: every layer's attention uses them
+ *                                                                             (Encoder.forward, :72-83) */
+int mmt_encoder_forward_keys(const float* x, const float* mask, const float* params, float* y,
+                             void* workspace, size_t workspace_bytes,
+                             int B, int T, int d, int h, int f, int n_layers, float eps,
+                             float dropout_p, uint64_t seed, mmt_stream_t stream, const int32_t* key_lengths);
+int mmt_encoder_backward_keys(const float* dy, const float* x, const float* mask, const float* params,
+                              float* dx, float* dparams,
+                              void* workspace, size_t workspace_bytes,
+                              int B, int T, int d, int h, int f, int n_layers, float eps,
+                              float dropout_p, uint64_t seed, mmt_stream_t stream, const int32_t* key_lengths);
+int mmt_encoder_forward_keys_devseed(const float* x, const float* mask, const float* params, float* y,
+                                     void* workspace, size_t workspace_bytes,
+                                     int B, int T, int d, int h, int f, int n_layers, float eps,
+                                     float dropout_p, uint64_t* seed_state, mmt_stream_t stream, const int32_t* key_lengths);
+int mmt_encoder_backward_keys_devseed(const float* dy, const float* x, const float* mask, const float* params,
+                                      float* dx, float* dparams,
+                                      void* workspace, size_t workspace_bytes,
+                                      int B, int T, int d, int h, int f, int n_layers, float eps,
+                                      float dropout_p, mmt_stream_t stream, const int32_t* key_lengths);
+
 /* ---- Fused affine map  y = act(x W^T + b) [* rowscale] on bf16 MFMA.
  * Replaces nn.Linear (+ F.relu) call sites of the path: PositionwiseFeedForward (:15-20), the four
  * attention projections (:43,55,65), embeds and read-out MLPs (:270,296,340-342,400-402).

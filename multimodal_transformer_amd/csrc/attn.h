@@ -8,6 +8,12 @@
 // zeroed by attn_bwd_dq_kernel (which takes the row mask).  Otherwise only index masking lives here:
 // keys/queries >= T in the last tile.
 //
+// Key lengths (opt-in, the *_keys_kernel entries): sequence b sees keys 0 .. len[b]-1 only.  That IS the tail masking
+// with T replaced by len[b]: the key-sweeping kernels run ceil(len/32) tiles and their peeled tail compares against len; the dK/dV
+// kernel, whose waves own key tiles, masks the tile on the boundary and stores zeros for the tiles behind it.  Every kernel body
+// below is written once, as a __device__ function with a compile-time KEYS flag; the plain kernels instantiate KEYS = false, in which
+// every use of the length folds away.  A length is read once per workgroup, clamped into [1, T], and is wave-uniform.
+//
 // Scores are kept in the log2 domain: the producer stores Q' = (x Wq^T + bq) * log2(e)/sqrt(d_k), so
 // P = 2^(S' - L) with L = rowmax + log2(rowsum) saved per query for the backward pass.
 #pragma once
@@ -103,6 +109,11 @@ __device__ __forceinline__ void progress_prio(int step, int nsteps) {
     else if (step == q3) __builtin_amdgcn_s_setprio(0);
 }
 
+// keys sequence b attends to: its key length clamped into [1, T] (no value of that tensor moves an access out of bounds), as a scalar
+__device__ __forceinline__ int attn_key_len(const int* __restrict__ key_lengths, int b, int T) {
+    return __builtin_amdgcn_readfirstlane(min(max(key_lengths[b], 1), T));
+}
+
 struct AttnBlock { int bx, bh; bool valid; };
 __device__ __forceinline__ AttnBlock attn_block(int nx, int nbh) {
     const int L = blockIdx.x, grp = L / (8 * nx), rem = L - grp * 8 * nx;
@@ -116,11 +127,12 @@ __host__ inline int attn_grid(int nx, int nbh) { return nx * 8 * ((nbh + 7) / 8)
 
 // (`//@ name` comment lines mark the phase boundaries at which tools/make_diag.py inserts cycle stamps into the GENERATED stamped twin of this
 // kernel — diagnostic builds only; this file holds no diagnostic code)
-template <int DKP, bool DROP>
-__global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_kernel(
+template <int DKP, bool DROP, bool KEYS>
+__device__ __forceinline__ void attn_fwd_body(
         const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
         bf16* __restrict__ ctx, float* __restrict__ lse,
-        int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
+        int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
+        const int* __restrict__ key_lengths) {
     constexpr int KS = DKP / 16;
     constexpr int DKB = DKP < 32 ? DKP : 32;           // feature rows of this launch's output block
     constexpr bool ONES = (DKP == 16) && !DROP;        // row sums through the MFMA
@@ -140,6 +152,9 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_kernel(
     const int qtc = live ? qt : nt - 1;
     const int bh = ab.bh, b = bh / h, head = bh - b * h;
     const int Tp = nt * 32;
+    // keys that exist for this sequence and the tiles that hold them: (T, nt), or the sequence's key length and its tiles
+    const int Tk = KEYS ? attn_key_len(key_lengths, b, T) : T;
+    const int nk = KEYS ? (Tk + 31) >> 5 : nt;
     const bf16* Qb = Qr + (size_t)bh * fragR_elems(Tp, DKP);
     const bf16* Kb = Kr + (size_t)bh * fragR_elems(Tp, DKP);
     const bf16* Vb = Vr + (size_t)bh * fragR_elems(Tp, DKP) + (size_t)fb * 4 * 256;      // feature group 4 fb of tile 0
@@ -187,7 +202,7 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_kernel(
     auto body = [&](auto tail_tag, int kt) {
         constexpr bool TAIL = decltype(tail_tag)::value;
         //@ loop_top
-        progress_prio(kt, nt);
+        progress_prio(kt, nk);
         const uint32_t tw = mw;                          // this tile's keep bits
         if (DROP && !TAIL) mw = mrow[(size_t)(kt + 1) * 64];
         if (!TAIL) stg.load(kt + 1);                    // next tile in flight behind this tile's arithmetic
@@ -209,9 +224,9 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_kernel(
             for (int ss = 1; ss < KS; ++ss)
                 s = mfma32(*reinterpret_cast<const bf16x8*>(sk + ((2 * ss + hh) * 32 + r) * 8), qf[ss], s);
         }
-        if (TAIL) {                                     // keys >= T do not exist
+        if (TAIL) {                                     // keys >= T (>= the key length) do not exist
 #pragma unroll
-            for (int i = 0; i < 16; ++i) s[i] = (kt * 32 + acc32_row(i, hh) < T) ? s[i] : -INFINITY;
+            for (int i = 0; i < 16; ++i) s[i] = (kt * 32 + acc32_row(i, hh) < Tk) ? s[i] : -INFINITY;
         }
         // (no inline asm here: hipcc's hazard recognizer does not count an asm statement as a reader of MFMA results)
         float tmax = fmaxf(fmaxf(s[0], s[1]), s[2]);
@@ -255,8 +270,8 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_kernel(
         __syncthreads();        // stage[(kt+1)&1] was last read at tile kt-1, i.e. before the previous barrier
         //@ barrier
     };
-    for (int kt = 0; kt < nt - 1; ++kt) body(std::false_type{}, kt);
-    body(std::true_type{}, nt - 1);
+    for (int kt = 0; kt < nk - 1; ++kt) body(std::false_type{}, kt);
+    body(std::true_type{}, nk - 1);
     //@ swept
     if (!live) return;
     float ltot;
@@ -279,6 +294,22 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_kernel(
     }
     //@ exit
 }
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
+        bf16* __restrict__ ctx, float* __restrict__ lse,
+        int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
+    attn_fwd_body<DKP, DROP, false>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, nullptr);
+}
+// ... with key lengths: sequence b attends keys < key_lengths[b]
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_keys_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
+        bf16* __restrict__ ctx, float* __restrict__ lse,
+        int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
+        const int* __restrict__ key_lengths) {
+    attn_fwd_body<DKP, DROP, true>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, key_lengths);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Backward, part A: dK, dV.  Wave w owns key tile kt = 4*blockIdx.x + w (the key on the lane column) and
@@ -286,12 +317,13 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_kernel(
 //     S'  = Q' K^T - L      (-L, stored negated, is the accumulator init: P = 2^S' needs no subtraction)
 //     dPc = dO V^T - delta  (same trick with -delta = -rowsum(dO . O))
 //     dS  = P * dPc ;  dV^T += dO^T P ;  dK^T += Q'^T dS     (P, dS accumulators ARE the B operands)
-template <int DKP, bool DROP>
-__global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_kernel(
+template <int DKP, bool DROP, bool KEYS>
+__device__ __forceinline__ void attn_bwd_dkv_body(
         const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr, const bf16* __restrict__ dOr,
         const float* __restrict__ lse, const float* __restrict__ delta,
         bf16* __restrict__ dkv, int lddkv,      // row-major [M][lddkv]; dK at column HD, dV at 2*HD
-        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb) {
+        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb,
+        const int* __restrict__ key_lengths) {
     constexpr int KS = DKP / 16;
     constexpr int DKB = DKP < 32 ? DKP : 32;
     // pieces: R-layout tile (in LDS with its 8-feature groups 576 bytes apart: the products that contract over the queries read
@@ -309,6 +341,21 @@ __global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_k
     const int ktc = live ? kt : nt - 1;
     const int bh = ab.bh, b = bh / h, head = bh - b * h;
     const int Tp = nt * 32, HD = h * DKP;
+    const int Tk = KEYS ? attn_key_len(key_lengths, b, T) : T;          // keys that exist for this sequence
+    // dK = dV = 0 for this lane's key (a key that no query attends), 32-feature block fb
+    auto store_zeros = [&]() {
+        const int t = kt * 32 + r;
+        if (!live || t >= T) return;
+        const size_t m = (size_t)b * T + t;
+        const bf16x4 z = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+#pragma unroll
+        for (int g = 0; g < DKB / 8; ++g) {
+            const int e0 = head * DKP + 32 * fb + 8 * g + 4 * hh;
+            *reinterpret_cast<bf16x4*>(dkv + m * lddkv + HD + e0) = z;
+            *reinterpret_cast<bf16x4*>(dkv + m * lddkv + 2 * HD + e0) = z;
+        }
+    };
+    if (KEYS && ab.bx * 128 >= Tk) { store_zeros(); return; }          // all four key tiles behind the length: whole workgroup, before any barrier
     const size_t offR = (size_t)bh * fragR_elems(Tp, DKP);
     const bf16 *Krb = Kr + offR, *Vrb = Vr + offR;
     const uint16_t* mrow = maskK + ((size_t)bh * nt + ktc) * nt * 64 + lane;      // LK layout: this lane's word of one block per query tile
@@ -343,13 +390,24 @@ __global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_k
     // 16-lane group's 16 features, and receives feature row r; slot j <-> query 16 s2 + 8 (j >> 2) + 4 hh + (j & 3)
     const int g1 = (lane >> 4) & 1, tq = (lane >> 2) & 3, tpp = lane & 3;
     const int toff = (((ONEACC ? 0 : 4 * fb + 2 * g1) + (tpp >> 1)) * MMT_TR_OCT + 4 * hh + tq) * 8 + 4 * (tpp & 1);
-    const bool key_tail = (ktc == nt - 1) && (T & 31);
-    const bool key_ok = (ktc * 32 + r) < T;
+    const bool key_tail = KEYS ? (ktc * 32 + 32 > Tk) : (ktc == nt - 1) && (T & 31);
+    const bool key_ok = (ktc * 32 + r) < Tk;
     stg.store(stage[0]);
     __syncthreads();
+    if (KEYS && ktc * 32 >= Tk) {
+        // a wave whose key tile lies wholly behind the length (wave-uniform; some other wave of the workgroup has visible keys): it has
+        // nothing to sweep, but the workgroup stages cooperatively — it keeps moving its pieces and meets the one barrier per tile
+        for (int qt = 0; qt < nt; ++qt) {
+            if (qt + 1 < nt) { stg.load(qt + 1); stg.store(stage[(qt + 1) & 1]); }
+            __syncthreads();
+        }
+        store_zeros();
+        return;
+    }
 
     // Tile body without conditional code (see attn_fwd_kernel): the key-tail mask is a per-lane multiplier that is
     // simply 1 everywhere except in the wave that owns the last key tile, and the query tail is the peeled last tile.
+    // (KEYS: a select instead — a key behind the length is a real window, whose 2^(S' - L) may be inf)
     const float kmul = (key_tail && !key_ok) ? 0.f : 1.f;
     auto body = [&](auto tail_tag, int qt) {
         constexpr bool QTAIL = decltype(tail_tag)::value;
@@ -387,7 +445,7 @@ __global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_k
         }
         if (key_tail) {                                 // wave-uniform, loop-invariant: only the last key tile's wave pays
 #pragma unroll
-            for (int j = 0; j < 16; ++j) s[j] *= kmul;
+            for (int j = 0; j < 16; ++j) s[j] = KEYS ? (key_ok ? s[j] : 0.f) : s[j] * kmul;
         }
         if (DROP) {
             // dropped probabilities Pd = P*m/(1-p):  dV^T += dO^T Pd ;  dS = P * ((dO V^T)*m/(1-p) - delta); delta unchanged.
@@ -437,19 +495,38 @@ __global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_k
         }
     }
 }
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr, const bf16* __restrict__ dOr,
+        const float* __restrict__ lse, const float* __restrict__ delta,
+        bf16* __restrict__ dkv, int lddkv,
+        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb) {
+    attn_bwd_dkv_body<DKP, DROP, false>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, nullptr);
+}
+// ... with key lengths: dK = dV = 0 for keys >= key_lengths[b]
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_keys_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr, const bf16* __restrict__ dOr,
+        const float* __restrict__ lse, const float* __restrict__ delta,
+        bf16* __restrict__ dkv, int lddkv,
+        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb,
+        const int* __restrict__ key_lengths) {
+    attn_bwd_dkv_body<DKP, DROP, true>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, key_lengths);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Backward, part B: dQ.  Same orientation as the forward (query on the lane): wave w owns query tile
 // qt = 4*blockIdx.x + w and sweeps all key tiles; L and delta are lane constants; the dS^T accumulator
 // (keys in registers) is the B operand of dQ^T += K^T dS^T.  The epilogue applies 1/sqrt(d_k) and the
 // query-row mask (blanked rows pass no gradient to Q) and writes columns [0,HD) of dQKV in both layouts.
-template <int DKP, bool DROP>
-__global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_kernel(
+template <int DKP, bool DROP, bool KEYS>
+__device__ __forceinline__ void attn_bwd_dq_body(
         const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
         const bf16* __restrict__ dOr, const float* __restrict__ lse, const float* __restrict__ delta,
         const float* __restrict__ rowmask, float scale,
         bf16* __restrict__ dqkv, int lddqkv,
-        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
+        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
+        const int* __restrict__ key_lengths) {
     constexpr int KS = DKP / 16;
     constexpr int DKB = DKP < 32 ? DKP : 32;
     constexpr int PR = DKP * 4, PRL = (DKP / 8) * MMT_TR_OCT;      // K tile padded in LDS: K^T fragments by transposing reads
@@ -463,6 +540,8 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_kernel(
     const int qtc = live ? qt : nt - 1;
     const int bh = ab.bh, b = bh / h, head = bh - b * h;
     const int Tp = nt * 32;
+    const int Tk = KEYS ? attn_key_len(key_lengths, b, T) : T;          // keys that exist for this sequence, and their tiles
+    const int nk = KEYS ? (Tk + 31) >> 5 : nt;
     const size_t offR = (size_t)bh * fragR_elems(Tp, DKP);
     const bf16 *Qrb = Qr + offR, *dOrb = dOr + offR;
     const uint16_t* mrow = maskQ + ((size_t)bh * nt + qtc) * nt * 64 + lane;      // LQ layout
@@ -498,8 +577,8 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_kernel(
     // Tile body without conditional code between MFMAs and their consumers (see attn_fwd_kernel); key tail peeled.
     auto body = [&](auto tail_tag, int kt) {
         constexpr bool TAIL = decltype(tail_tag)::value;
-        const bool more = kt + 1 < nt;
-        progress_prio(kt, nt);
+        const bool more = kt + 1 < nk;
+        progress_prio(kt, nk);
         const uint32_t tw = mw;
         if (DROP && more) mw = mrow[(size_t)(kt + 1) * 64];
         if (more) stg.load(kt + 1);
@@ -521,7 +600,7 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_kernel(
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             float pv = fast_exp2(s[j]);
-            if (TAIL) pv = (kt * 32 + acc32_row(j, hh) < T) ? pv : 0.f;       // keys >= T do not exist
+            if (TAIL) pv = (kt * 32 + acc32_row(j, hh) < Tk) ? pv : 0.f;      // keys >= T (>= the key length) do not exist
             s[j] = pv;
         }
         if (DROP) {
@@ -540,8 +619,8 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_kernel(
         if (more) stg.store(stage[(kt + 1) & 1]);
         __syncthreads();
     };
-    for (int kt = 0; kt < nt - 1; ++kt) body(std::false_type{}, kt);
-    if (T & 31) body(std::true_type{}, nt - 1); else body(std::false_type{}, nt - 1);
+    for (int kt = 0; kt < nk - 1; ++kt) body(std::false_type{}, kt);
+    if (Tk & 31) body(std::true_type{}, nk - 1); else body(std::false_type{}, nk - 1);
     if (!live) return;
     const int t = qt * 32 + r;
     if (t < T) {
@@ -555,5 +634,45 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_kernel(
             const int e0 = head * DKP + 32 * fb + 8 * g + 4 * hh;
             *reinterpret_cast<bf16x4*>(dqkv + m * lddqkv + e0) = v;
         }
+    }
+}
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
+        const bf16* __restrict__ dOr, const float* __restrict__ lse, const float* __restrict__ delta,
+        const float* __restrict__ rowmask, float scale,
+        bf16* __restrict__ dqkv, int lddqkv,
+        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
+    attn_bwd_dq_body<DKP, DROP, false>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, nullptr);
+}
+// ... with key lengths: the sweep ends at key_lengths[b]
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_keys_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
+        const bf16* __restrict__ dOr, const float* __restrict__ lse, const float* __restrict__ delta,
+        const float* __restrict__ rowmask, float scale,
+        bf16* __restrict__ dqkv, int lddqkv,
+        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
+        const int* __restrict__ key_lengths) {
+    attn_bwd_dq_body<DKP, DROP, true>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, key_lengths);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Key lengths from a mask (B, T): len[b] = 1 + index of the last non-zero entry of row b, 1 for an all-zero row.  One workgroup per
+// sequence; a prefix mask (what padding produces) gives its length, holes inside the prefix stay attended.
+__global__ __launch_bounds__(MMT_THREADS) void key_lengths_kernel(const float* __restrict__ mask, int* __restrict__ out, int T) {
+    __shared__ int part[MMT_THREADS / 64];
+    const float* row = mask + (size_t)blockIdx.x * T;
+    int last = 0;                                       // 1 + index, 0: none seen
+    for (int t = threadIdx.x; t < T; t += MMT_THREADS) if (row[t] != 0.0f) last = t + 1;      // ascending t: the thread's last hit stays
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) last = max(last, __shfl_xor(last, o));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = last;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int m = part[0];
+#pragma unroll
+        for (int w = 1; w < MMT_THREADS / 64; ++w) m = max(m, part[w]);
+        out[blockIdx.x] = max(m, 1);
     }
 }

@@ -22,6 +22,9 @@
 // 64 key tiles the wave's lanes draw the 64 blocks (q tile, kt0 + lane) and park them in a wave-private LDS patch (33-word rows:
 // conflict-free); tile kt then takes word `key r` of block kt - kt0 and lane_word() picks the 16 queries of the lane's half in
 // accumulator order — the LK orientation of attn_mask.h.  Every block is drawn exactly once.
+//
+// Key lengths (attn_probs_keys_kernel; attn.h): both sweeps end after the ceil(len/32) key tiles of the sequence, keys >= len score
+// MASKED like keys >= T, and — the output buffer is uninitialised — the columns behind the length are written as exact zeros.
 #pragma once
 #include "common.h"
 #include "attn_mask.h"
@@ -52,10 +55,10 @@ __device__ __forceinline__ bf16x8 probs_frag(const float* __restrict__ row, int 
     return out;
 }
 
-template <int DKP, bool DROP>
-__global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_kernel(
+template <int DKP, bool DROP, bool KEYS>
+__device__ __forceinline__ void attn_probs_body(
         const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
-        int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop) {
+        int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop, const int* __restrict__ key_lengths) {
     constexpr int KS = DKP / 16;
     __shared__ uint32_t patch[DROP ? 4 * 64 * MMT_PROBS_PATCH_ROW : 1];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -65,6 +68,8 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_kernel(
     const int qt = ab.bx * 4 + wave;
     if (qt >= nt) return;                               // waves share nothing: no barrier below
     const int bh = ab.bh, b = bh / h, head = bh - b * h;
+    const int Tk = KEYS ? attn_key_len(key_lengths, b, T) : T;          // keys that exist for this sequence, and their tiles
+    const int nk = KEYS ? (Tk + 31) >> 5 : nt;
 
     // A operand: Q' of query r of the tile (a query >= T reads row T-1 and is never stored), features 16 s + 8 hh .. + 7
     bf16x8 qf[KS];
@@ -90,7 +95,7 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_kernel(
         for (int i = 0; i < 16; ++i) s[i] = 0.f;
 #pragma unroll
         for (int ss = 0; ss < KS; ++ss) s = mfma32(qf[ss], kf[ss], s);
-        const bool kok = kt * 32 + r < T;
+        const bool kok = kt * 32 + r < Tk;
 #pragma unroll
         for (int i = 0; i < 16; ++i) s[i] = kok ? s[i] : MMT_PROBS_MASKED;
         return s;
@@ -102,8 +107,8 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_kernel(
     for (int i = 0; i < 16; ++i) { m[i] = MMT_PROBS_MASKED; l[i] = 0.f; }
     bf16x8 kf[KS], kn[KS];
     kfrag(0, kf);
-    for (int kt = 0; kt < nt; ++kt) {
-        kfrag(min(kt + 1, nt - 1), kn);                 // next tile in flight behind this tile's arithmetic (the last one re-reads itself)
+    for (int kt = 0; kt < nk; ++kt) {
+        kfrag(min(kt + 1, nk - 1), kn);                 // next tile in flight behind this tile's arithmetic (the last one re-reads itself)
         const f32x16 s = scores(kf, kt);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -135,14 +140,14 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_kernel(
     float* const prow = P + ((size_t)bh * T + (size_t)qt * 32) * T;       // row `query in tile` at + query * T
     const bool qfull = qt * 32 + 32 <= T;
     kfrag(0, kf);
-    for (int kt = 0; kt < nt; ++kt) {
+    for (int kt = 0; kt < nk; ++kt) {
         if (DROP && (kt & 63) == 0) {                   // wave-uniform: the keep bits of blocks (qt, kt + lane), one block per lane
             uint32_t W[32];
             attn_keep_block(dc, (uint32_t)(qt * nt + min(kt + lane, nt - 1)), W);      // W[key] bit query
 #pragma unroll
             for (int key = 0; key < 32; ++key) mine[lane * MMT_PROBS_PATCH_ROW + key] = W[key];
         }
-        kfrag(min(kt + 1, nt - 1), kn);
+        kfrag(min(kt + 1, nk - 1), kn);
         f32x16 s = scores(kf, kt);
 #pragma unroll
         for (int i = 0; i < 16; ++i) s[i] = fast_exp2(s[i] - m[i]) * l[i];
@@ -163,4 +168,26 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_kernel(
 #pragma unroll
         for (int s2 = 0; s2 < KS; ++s2) kf[s2] = kn[s2];
     }
+    if (KEYS) {     // the key tiles behind the length: zeros (the boundary tile's columns >= len were stored above, as 2^(MASKED - max) == 0)
+        for (int kt = nk; kt < nt; ++kt) {
+            float* const pk = prow + kt * 32 + r;
+            const bool kok = kt * 32 + r < T;
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (kok && qt * 32 + acc32_row(i, hh) < T) pk[(size_t)acc32_row(i, hh) * T] = 0.f;
+        }
+    }
+}
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_kernel(
+        const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
+        int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop) {
+    attn_probs_body<DKP, DROP, false>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, nullptr);
+}
+// ... with key lengths: columns >= key_lengths[b] are exact zeros
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_keys_kernel(
+        const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
+        int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop, const int* __restrict__ key_lengths) {
+    attn_probs_body<DKP, DROP, true>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, key_lengths);
 }

@@ -41,15 +41,47 @@ def _seed_pair(seed):
     return (0, seed.state) if isinstance(seed, _lib.DeviceSeed) else (int(seed), None)
 
 
-def _launch_seeded(name, seed, *args, state_arg=True):
+def _launch_seeded(name, seed, *args, state_arg=True, key_lengths=None):
     """``name`` with the seed by value behind ``args``, or its twin ``name``_devseed with the DeviceSeed's state word there, which the
-    launch reads and advances.  ``state_arg=False``: the twin takes no seed (the encoder backward finds it in its forward's workspace)."""
+    launch reads and advances.  ``state_arg=False``: the twin takes no seed (the encoder backward finds it in its forward's workspace).
+    ``key_lengths``: the ``_keys`` form of either (_lib.launch)."""
     if not isinstance(seed, _lib.DeviceSeed):
-        _lib.launch(name, *args, seed)
+        _lib.launch(name, *args, seed, key_lengths=key_lengths)
     elif state_arg:
-        _lib.launch(name + "_devseed", *args, seed.state)
+        _lib.launch(name + "_devseed", *args, seed.state, key_lengths=key_lengths)
     else:
-        _lib.launch(name + "_devseed", *args)
+        _lib.launch(name + "_devseed", *args, key_lengths=key_lengths)
+
+
+# Key lengths: a padding mask that masks KEYS (opt-in; the reference blanks query rows only, transformer/MFT/multiTransformer.py:29-31).
+def key_lengths(mask):
+    """(B,T,1) or (B,T) mask -> int32 (B,) on the mask's device: ``1 +`` the index of the last non-zero entry of each row, 1 for an
+    all-zero row.  For the prefix masks that padding produces this is the sequence length.  Holes INSIDE the prefix stay attended as
+    keys (their query rows are still blanked by the mask itself).  One kernel launch, no host synchronisation: safe under hipGraph capture."""
+    _lib.require_hip(mask)
+    _lib.load()
+    m_ = _f32c(mask)
+    if m_.dim() < 2 or m_.numel() == 0 or m_.numel() != m_.shape[0] * max(m_.shape[1:]):
+        raise ValueError("key_lengths: mask must have the shape (B,T,1), (B,1,T,1) or (B,T), got %s" % (tuple(mask.shape),))
+    m_ = m_.view(m_.shape[0], -1)
+    B, T = m_.shape
+    out = torch.empty(B, dtype=torch.int32, device=m_.device)
+    _lib.launch("mmt_key_lengths", m_, out, B, T)
+    return out
+
+
+def _check_key_lengths(op, key_lengths, B, device):
+    """A ``key_lengths`` argument is None or a contiguous int32 (B,) tensor on ``device``: anything else raises before any launch."""
+    if key_lengths is None:
+        return None
+    if not isinstance(key_lengths, torch.Tensor) or key_lengths.dtype != torch.int32:
+        raise ValueError("%s: key_lengths must be an int32 tensor (functional.key_lengths(mask)), got %s"
+                         % (op, getattr(key_lengths, "dtype", type(key_lengths).__name__)))
+    if tuple(key_lengths.shape) != (B,):
+        raise ValueError("%s: key_lengths must have the shape (B,) = (%d,), got %s" % (op, B, tuple(key_lengths.shape)))
+    if key_lengths.device != device:
+        raise ValueError("%s: key_lengths is on %s, the operands on %s" % (op, key_lengths.device, device))
+    return key_lengths.detach().contiguous()
 
 
 # Pool workspaces held from forward to backward (_lib.WorkspacePool): the Functions that keep one use these two.
@@ -100,12 +132,13 @@ def _chunk_seed(seed, i, nsplit=1):
     return seed if i == 0 else _lib.mix64(seed, i)
 
 
-def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit):
+def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths=None):
     """The fused stack's forward, one launch per sub-batch on a stream of its own; keeps on ``ctx`` what _encoder_bwd needs."""
     lib = _lib.load()
     _lib.require_hip(x, mask, flat_params)
     x_, m_, p_ = _f32c(x), _f32c(mask), _f32c(flat_params)
     B, T, d = x_.shape
+    kl_ = _check_key_lengths("encoder_stack", key_lengths, B, x_.device)
     if m_.numel() != B * T:
         raise ValueError("mask must have B*T = %d elements (shape (B,T,1)), got %s" % (B * T, tuple(mask.shape)))
     m_ = m_.view(B, T)
@@ -127,13 +160,15 @@ def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, s
                 _lib.launch("mmt_encoder_forward", None, None, None, None, None, 0, *dims, eps, 0.0, 0)
             ws = _lib.POOL.get(nbytes, x_.device, tag=("encoder",) + dims + (train,))
             sd = _chunk_seed(seed, i, len(chunks))
-            _launch_seeded("mmt_encoder_forward", sd, x_[b0:b1], m_[b0:b1], p_, y[b0:b1], ws, nbytes, *dims, eps, dropout_p)
+            _launch_seeded("mmt_encoder_forward", sd, x_[b0:b1], m_[b0:b1], p_, y[b0:b1], ws, nbytes, *dims, eps, dropout_p,
+                           key_lengths=None if kl_ is None else kl_[b0:b1])
             parts.append((b0, b1, ws, sd))
     _SPLIT_STREAMS.end(main, streams)
     if _hold(ctx, *[ws for _, _, ws, _ in parts]):
         ctx.save_for_backward(x_, m_, p_)
         ctx.parts = [(b0, b1, sd) for b0, b1, _, sd in parts]
         ctx.cfg = (T, d, h, d_ff, n_layers, eps, dropout_p)
+        ctx.key_lengths = kl_
     return y
 
 
@@ -142,6 +177,7 @@ def _encoder_bwd(ctx, dy):
     wss = _take_ws(ctx, "encoder_stack")
     x_, m_, p_ = ctx.saved_tensors
     T, d, h, d_ff, n_layers, eps, dropout_p = ctx.cfg
+    kl_ = ctx.key_lengths
     dy_ = _f32c(dy)
     dx = torch.empty_like(x_)
     dps = [torch.empty_like(p_) for _ in wss]       # fresh buffers per call: returned gradient views never alias later calls
@@ -149,7 +185,8 @@ def _encoder_bwd(ctx, dy):
     for (b0, b1, sd), ws, dp, st in zip(ctx.parts, wss, dps, streams):
         with torch.cuda.stream(st):
             _launch_seeded("mmt_encoder_backward", sd, dy_[b0:b1], x_[b0:b1], m_[b0:b1], p_, dx[b0:b1], dp, ws, ws.numel(),
-                           b1 - b0, T, d, h, d_ff, n_layers, eps, dropout_p, state_arg=False)
+                           b1 - b0, T, d, h, d_ff, n_layers, eps, dropout_p, state_arg=False,
+                           key_lengths=None if kl_ is None else kl_[b0:b1])
             _lib.POOL.put(ws)
     _SPLIT_STREAMS.end(main, streams)
     if len(dps) > 1:                                # the sub-batches' parameter gradients, summed into the first buffer
@@ -161,20 +198,22 @@ def _encoder_bwd(ctx, dy):
 
 class _EncoderStackFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit):
-        return _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit)
+    def forward(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths=None):
+        return _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths)
 
     @staticmethod
     def backward(ctx, dy):
         dx, dflat = _encoder_bwd(ctx, dy)
-        return dx, None, dflat, None, None, None, None, None, None, None
+        return dx, None, dflat, None, None, None, None, None, None, None, None
 
 
-def encoder_stack(x, mask, flat_params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, nsplit=1):
+def encoder_stack(x, mask, flat_params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, nsplit=1, key_lengths=None):
     """``seed``: a python int (by value) or a ``_lib.DeviceSeed`` (device-resident: fresh masks at every hipGraph replay), or one
-    of either per sub-batch stream; ``nsplit``: run the batch as that many sub-batches on HIP streams of their own (see _SPLIT_STREAMS)."""
+    of either per sub-batch stream; ``nsplit``: run the batch as that many sub-batches on HIP streams of their own (see _SPLIT_STREAMS).
+    ``key_lengths``: int32 (B,) (``key_lengths(mask)``): sequence b attends keys < key_lengths[b] in every layer; None: the
+    reference's semantics, every key is attended.  Sub-batches take their slice of the lengths."""
     return _EncoderStackFn.apply(x, mask, flat_params, int(h), int(d_ff), int(n_layers), float(eps), float(dropout_p), _seed_arg(seed),
-                                 int(nsplit))
+                                 int(nsplit), key_lengths)
 
 
 class _EncoderStackParamsFn(torch.autograd.Function):
@@ -184,24 +223,24 @@ class _EncoderStackParamsFn(torch.autograd.Function):
     buffer in place with one collective and no staging copies (``parallel.allreduce_gradients``)."""
 
     @staticmethod
-    def forward(ctx, x, mask, h, d_ff, n_layers, eps, dropout_p, seed, flat, nsplit, *params):
+    def forward(ctx, x, mask, h, d_ff, n_layers, eps, dropout_p, seed, flat, nsplit, key_lengths, *params):
         # `flat`: the parameters' own storage when they are views of one buffer (multiTransformer.Encoder keeps them that way), else
         # None and the buffer is assembled here (one concatenation kernel per step)
         if flat is None:
             flat = torch.cat([q.detach().reshape(-1) for q in params]).float()
         ctx.shapes = [tuple(q.shape) for q in params]
-        return _encoder_fwd(ctx, x, mask, flat, h, d_ff, n_layers, eps, dropout_p, seed, nsplit)
+        return _encoder_fwd(ctx, x, mask, flat, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths)
 
     @staticmethod
     def backward(ctx, dy):
         dx, dflat = _encoder_bwd(ctx, dy)
         grads = [g.view(shp) for g, shp in zip(dflat.split([math.prod(shp) for shp in ctx.shapes]), ctx.shapes)]
-        return (dx, None, None, None, None, None, None, None, None, None) + tuple(grads)
+        return (dx, None, None, None, None, None, None, None, None, None, None) + tuple(grads)
 
 
-def encoder_stack_params(x, mask, params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, flat=None, nsplit=1):
+def encoder_stack_params(x, mask, params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, flat=None, nsplit=1, key_lengths=None):
     return _EncoderStackParamsFn.apply(x, mask, int(h), int(d_ff), int(n_layers), float(eps), float(dropout_p), _seed_arg(seed), flat,
-                                       int(nsplit), *params)
+                                       int(nsplit), key_lengths, *params)
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -236,11 +275,12 @@ def layer_norm(x, a_2, b_2, eps=1e-6):
 
 class _SdpaFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, mask, h, dropout_p, seed):
+    def forward(ctx, q, k, v, mask, h, dropout_p, seed, key_lengths=None):
         lib = _lib.load()
         _lib.require_hip(q, k, v, mask)
         q_, k_, v_, m_ = _f32c(q), _f32c(k), _f32c(v), _f32c(mask)
         B, T, d = q_.shape
+        kl_ = _check_key_lengths("sdpa", key_lengths, B, q_.device)
         if k_.shape != q_.shape or v_.shape != q_.shape:
             raise NotImplementedError("sdpa: query, key and value must share the shape (B,T,d)")
         if m_ is not None and m_.numel() != B * T:
@@ -251,9 +291,9 @@ class _SdpaFn(torch.autograd.Function):
             _lib.launch("mmt_sdpa_forward", None, None, None, None, None, None, 0, B, T, d, h, 0.0, 0)
         ws = _lib.POOL.get(nbytes, q_.device, tag=("sdpa", B, T, d, h, train))
         out = torch.empty_like(q_)
-        _lib.launch("mmt_sdpa_forward", q_, k_, v_, m_, out, ws, nbytes, B, T, d, h, dropout_p, seed)
+        _lib.launch("mmt_sdpa_forward", q_, k_, v_, m_, out, ws, nbytes, B, T, d, h, dropout_p, seed, key_lengths=kl_)
         if _hold(ctx, ws):
-            ctx.cfg, ctx.mask = (B, T, d, h, dropout_p, seed), m_
+            ctx.cfg, ctx.mask, ctx.key_lengths = (B, T, d, h, dropout_p, seed), m_, kl_
         return out
 
     @staticmethod
@@ -262,21 +302,24 @@ class _SdpaFn(torch.autograd.Function):
         B, T, d, h, dropout_p, seed = ctx.cfg
         g = _f32c(dctx)
         dq, dk, dv = (torch.empty_like(g) for _ in range(3))
-        _lib.launch("mmt_sdpa_backward", g, ctx.mask, dq, dk, dv, ws, ws.numel(), B, T, d, h, dropout_p, seed)
+        _lib.launch("mmt_sdpa_backward", g, ctx.mask, dq, dk, dv, ws, ws.numel(), B, T, d, h, dropout_p, seed, key_lengths=ctx.key_lengths)
         _lib.POOL.put(ws)
-        return dq, dk, dv, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None
 
 
-def sdpa(q, k, v, mask, h, dropout_p=0.0, seed=0):
+def sdpa(q, k, v, mask, h, dropout_p=0.0, seed=0, key_lengths=None):
     """q,k,v: (B,T,d) with head i in columns [i*d/h,(i+1)*d/h); mask (B,T,1) blanks query rows; -> (B,T,d).
-    dropout_p / seed: train-mode dropout on the probabilities (transformer/MFT/multiTransformer.py:32-33)."""
-    return _SdpaFn.apply(q, k, v, mask, int(h), float(dropout_p), int(seed))
+    dropout_p / seed: train-mode dropout on the probabilities (transformer/MFT/multiTransformer.py:32-33).
+    key_lengths: int32 (B,) (``key_lengths(mask)``): sequence b attends keys < key_lengths[b] only — later keys get probability 0 and
+    dk = dv = 0, a blanked query row is uniform over the visible keys; values outside [1, T] are clamped.  None: every key is attended."""
+    return _SdpaFn.apply(q, k, v, mask, int(h), float(dropout_p), int(seed), key_lengths)
 
 
-def attn_probs(q, k, mask, h, dropout_p=0.0, seed=0):
+def attn_probs(q, k, mask, h, dropout_p=0.0, seed=0, key_lengths=None):
     """The probabilities ``sdpa(q, k, v, mask, h, dropout_p, seed)`` uses, materialised: (B,h,T,T) fp32, [b][head][query][key]
     (transformer/MFT/multiTransformer.py:22-34, the reference's ``self.attn`` of :59).  Same operand rounding as the attention core; in
     train mode the same keep decisions for the same seed, dropped = 0 and kept = P/(1-p).  A blanked query row is exactly 1/T.
+    key_lengths: as for ``sdpa``; columns >= key_lengths[b] are exact zeros and a blanked query row is 1/key_lengths[b] on the others.
     No autograd graph: the reference never differentiates the map."""
     _lib.require_hip(q, k, mask)
     _lib.load()
@@ -286,11 +329,12 @@ def attn_probs(q, k, mask, h, dropout_p=0.0, seed=0):
         raise NotImplementedError("attn_probs: query and key must share the shape (B,T,d)")
     if m_ is not None and m_.numel() != B * T:
         raise NotImplementedError("attn_probs: only the reference's query-row mask of shape (B,T,1) is supported")
+    kl_ = _check_key_lengths("attn_probs", key_lengths, B, q_.device)
     h = int(h)
     if h <= 0 or d % h or d // h > 64 or T > 4096:         # refused by the library before anything as large as the map is allocated
         _lib.launch("mmt_attn_probs_forward", None, None, None, None, B, T, d, h, 0.0, 0)
     out = torch.empty((B, h, T, T), dtype=torch.float32, device=q_.device)
-    _lib.launch("mmt_attn_probs_forward", q_, k_, m_, out, B, T, d, h, float(dropout_p), int(seed))
+    _lib.launch("mmt_attn_probs_forward", q_, k_, m_, out, B, T, d, h, float(dropout_p), int(seed), key_lengths=kl_)
     return out
 
 

@@ -11,6 +11,9 @@ Deviations, all documented in DESIGN.md:
     (B,h,T,T) probability tensor (the reference writes it at :59 and never reads it).  ``keep_attention(model)``
     / ``MultiHeadedAttention.keep_attn = True`` / ``attention_with_map(...)`` have a kernel of its own
     write it beside the core, with the core's rounding and dropout decisions.
+  * ``mask_padded_keys(model)`` / ``MultiHeadedAttention.mask_keys = True`` (off by default, no counterpart in the reference):
+    the padding mask then masks KEYS too, so a sequence attends only its own windows and its output no longer depends on the
+    batch it is padded into.  Results then differ from the reference's by design.
   * train-mode dropout draws from a counter-based generator inside the kernels, not from torch's
     global generator: training-mode parity with the reference is statistical, eval-mode is numerical.
 """
@@ -100,9 +103,16 @@ class MultiHeadedAttention(nn.Module):
 
     ``keep_attn`` (a class attribute, off; ``keep_attention`` sets it per instance): ``forward`` leaves the detached (B,h,T,T)
     probabilities of its call in ``self.attn`` as the reference does (:59), written by one extra kernel.  A diagnostic: an Encoder
-    holding such a layer runs layer by layer instead of as the fused stack."""
+    holding such a layer runs layer by layer instead of as the fused stack.
+
+    ``mask_keys`` (a class attribute, off; ``mask_padded_keys`` sets it per instance): with a mask given, sequence b attends only the
+    keys in front of its key length, ``1 +`` the index of the last non-zero mask entry of its row (``functional.key_lengths``): the
+    padded windows behind a sequence get probability exactly 0 and no gradient as keys or values.  The reference (:29-31) blanks
+    query rows only, so every window also attends its batch's padding; this flag removes that dependence on the batch.  Holes
+    inside the prefix stay attended.  ``keep_attn`` then shows the zeros."""
 
     keep_attn = False
+    mask_keys = False
 
     def __init__(self, h, d_model, dropout=0.1):
         super().__init__()
@@ -123,8 +133,9 @@ class MultiHeadedAttention(nn.Module):
                 raise NotImplementedError("only the reference's query-row mask of shape (B,T,1) is supported")
             m = mask.reshape(B, -1, 1)
         seed = _lib.next_dropout_seed(q.device, 3) if p > 0.0 else 0
-        ctx = F_hip.sdpa(q, k, v, m, self.h, dropout_p=p, seed=seed)
-        self.attn = F_hip.attn_probs(q, k, m, self.h, dropout_p=p, seed=seed) if self.keep_attn else None
+        kl = F_hip.key_lengths(m) if self.mask_keys and m is not None else None      # derived once, serves both kernels
+        ctx = F_hip.sdpa(q, k, v, m, self.h, dropout_p=p, seed=seed, key_lengths=kl)
+        self.attn = F_hip.attn_probs(q, k, m, self.h, dropout_p=p, seed=seed, key_lengths=kl) if self.keep_attn else None
         return F_hip.linear(ctx, self.linears[3].weight, self.linears[3].bias)
 
 
@@ -141,6 +152,23 @@ def keep_attention(module, on=True):
             m.keep_attn = bool(on)
             if not on:
                 m.attn = None
+            found[name] = m
+    return found
+
+
+def mask_padded_keys(module, on=True):
+    """Set ``mask_keys`` on every MultiHeadedAttention below ``module`` (the SFT / MFT / B2 models, every modality's stack of
+    MultiTransformer, the MultiCNNTransformer wrappers) -> {qualified name: module}.  From the next forward on a sequence attends only
+    its own windows: keys behind its length (``functional.key_lengths`` of the mask) are masked in every layer, forward and backward.
+
+    An Encoder keeps running as the fused stack (it derives the lengths once per call); only layers that disagree about the flag make
+    it run layer by layer.  Outputs then differ from the reference's, which lets padded windows be attended — by design: they no
+    longer depend on the batch a sequence sits in.  ``mask_padded_keys(module, False)`` restores the reference's semantics and the
+    plain kernels."""
+    found = {}
+    for name, m in module.named_modules():
+        if isinstance(m, MultiHeadedAttention):
+            m.mask_keys = bool(on)
             found[name] = m
     return found
 
@@ -235,6 +263,8 @@ class Encoder(nn.Module):
             return False
         if any(l.self_attn.keep_attn for l in self.layers):       # the fused stack never forms the map: run layer by layer
             return False
+        if any(l.self_attn.mask_keys != l0.self_attn.mask_keys for l in self.layers):      # one set of key lengths serves the whole stack
+            return False
         h, f = l0.self_attn.h, l0.feed_forward.w_1.weight.shape[0]
         p = l0.sublayer[0].dropout.p
         for l in self.layers:
@@ -264,9 +294,10 @@ class Encoder(nn.Module):
         k = self._sub_batch_streams(x)
         seed = [_lib.next_dropout_seed(x.device, 1, holder=self, index=i) for i in range(k)] if p > 0.0 else 0
         ps = self.flat_parameters()
+        kl = F_hip.key_lengths(mask) if l0.self_attn.mask_keys else None       # mask_padded_keys: derived once per call, for every layer
         return F_hip.encoder_stack_params(x, mask, ps, l0.self_attn.h, l0.feed_forward.w_1.weight.shape[0],
                                           len(self.layers), eps=self.norm.eps, dropout_p=p, seed=seed,
-                                          flat=self._flat_storage(ps) if x.is_cuda else None, nsplit=k)
+                                          flat=self._flat_storage(ps) if x.is_cuda else None, nsplit=k, key_lengths=kl)
 
     sub_batch_streams = 1        # set to 2: the batch runs as two halves on two HIP streams (functional._SPLIT_STREAMS); opt-in
     sub_batch_min_windows = 8192
