@@ -171,6 +171,46 @@ int mmt_encoder_backward_keys_devseed(const float* dy, const float* x, const flo
                                       int B, int T, int d, int h, int f, int n_layers, float eps,
                                       float dropout_p, mmt_stream_t stream, const int32_t* key_lengths);
 
+/* ---- Causal self-attention (opt-in; no counterpart in the reference, whose attention() lets window t attend every window of the
+ * batch row, later ones included: scores.masked_fill(mask == 0, -1e9) blanks query rows only, transformer/MFT/multiTransformer.py:29-31).
+ * Query t of a sequence sees keys 0 .. t of that sequence: later keys score -inf, their probability is exactly 0 and they get no dK or
+ * dV from that query.  The query-row mask keeps its meaning (a blanked row t is uniform over its t + 1 visible keys and passes no
+ * gradient to q); row 0 attends one key, so in eval mode its context is bf16(v[b, 0]).  Dropout bits are drawn as for the plain entry,
+ * per position for the whole T x T block; bits above the diagonal are never read.  Each `_causal` entry has the plain entry's exact
+ * signature and workspace.  The backward always runs as two kernels (dK/dV, dQ).  There is no form with key lengths: a valid window
+ * t < len of a prefix-masked batch sees keys <= t < len only, so causal attention already keeps it from the padding behind its sequence. */
+/* mmt_sdpa_forward / mmt_sdpa_backward, causal                                (attention(), :22-34; departs from :27-31) */
+int mmt_sdpa_forward_causal(const float* q, const float* k, const float* v, const float* mask, float* ctx,
+                            void* workspace, size_t workspace_bytes, int B, int T, int d, int h,
+                            float dropout_p, uint64_t seed, mmt_stream_t stream);
+int mmt_sdpa_backward_causal(const float* dctx, const float* mask, float* dq, float* dk, float* dv,
+                             void* workspace, size_t workspace_bytes, int B, int T, int d, int h,
+                             float dropout_p, uint64_t seed, mmt_stream_t stream);
+/* mmt_attn_probs_forward, causal: entries above the diagonal are exact zeros, a blanked query row t is 1/(t+1) on columns 0 .. t
+ *                                                                             (p_attn, :22-34,59; departs from :27-31) */
+int mmt_attn_probs_forward_causal(const float* q, const float* k, const float* mask, float* probs,
+                                  int B, int T, int d, int h, float dropout_p, uint64_t seed, mmt_stream_t stream);
+/* mmt_encoder_forward / mmt_encoder_backward and their device-seeded twins, causal: every layer's self-attention is causal
+ *                                                                             (Encoder.forward, :72-83; departs from :27-31) */
+int mmt_encoder_forward_causal(const float* x, const float* mask, const float* params, float* y,
+                               void* workspace, size_t workspace_bytes,
+                               int B, int T, int d, int h, int f, int n_layers, float eps,
+                               float dropout_p, uint64_t seed, mmt_stream_t stream);
+int mmt_encoder_backward_causal(const float* dy, const float* x, const float* mask, const float* params,
+                                float* dx, float* dparams,
+                                void* workspace, size_t workspace_bytes,
+                                int B, int T, int d, int h, int f, int n_layers, float eps,
+                                float dropout_p, uint64_t seed, mmt_stream_t stream);
+int mmt_encoder_forward_causal_devseed(const float* x, const float* mask, const float* params, float* y,
+                                       void* workspace, size_t workspace_bytes,
+                                       int B, int T, int d, int h, int f, int n_layers, float eps,
+                                       float dropout_p, uint64_t* seed_state, mmt_stream_t stream);
+int mmt_encoder_backward_causal_devseed(const float* dy, const float* x, const float* mask, const float* params,
+                                        float* dx, float* dparams,
+                                        void* workspace, size_t workspace_bytes,
+                                        int B, int T, int d, int h, int f, int n_layers, float eps,
+                                        float dropout_p, mmt_stream_t stream);
+
 /* ---- Fused affine map  y = act(x W^T + b) [* rowscale] on bf16 MFMA.
  * Replaces nn.Linear (+ F.relu) call sites of the path: PositionwiseFeedForward (:15-20), the four
  * attention projections (:43,55,65), embeds and read-out MLPs (:270,296,340-342,400-402).

@@ -48,6 +48,14 @@ SIGNATURES = {
     "mmt_encoder_backward_keys": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _U64, _P, _P]),
     "mmt_encoder_forward_keys_devseed": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _P, _P, _P]),
     "mmt_encoder_backward_keys_devseed": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _P, _P]),
+    # causal: the plain entry's exact arguments
+    "mmt_sdpa_forward_causal": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_F, _U64, _P]),
+    "mmt_sdpa_backward_causal": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_F, _U64, _P]),
+    "mmt_attn_probs_forward_causal": (_I, [_P, _P, _P, _P] + [_I] * 4 + [_F, _U64, _P]),
+    "mmt_encoder_forward_causal": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _U64, _P]),
+    "mmt_encoder_backward_causal": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _U64, _P]),
+    "mmt_encoder_forward_causal_devseed": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _P, _P]),
+    "mmt_encoder_backward_causal_devseed": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _P]),
     "mmt_linear_workspace_bytes": (_SZ, [_I] * 3),
     "mmt_linear_forward": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),
     "mmt_linear_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),
@@ -142,11 +150,14 @@ def require_hip(*tensors):
                                "(move the module and its inputs to a HIP device)" % t.device)
 
 
-def launch(name, *args, key_lengths=None):
+def launch(name, *args, key_lengths=None, causal=False):
     """Call the C entry point ``name`` on the current stream (read now: StreamFork's ``torch.cuda.stream`` blocks rely on it).  A tensor
     goes as its data_ptr(), None as a null pointer, every other argument unchanged; a non-zero return code raises.
-    ``key_lengths`` (an int32 (B,) device tensor): call the entry's ``_keys`` form, which takes that tensor behind the stream."""
+    ``key_lengths`` (an int32 (B,) device tensor): call the entry's ``_keys`` form, which takes that tensor behind the stream.
+    ``causal``: call the entry's ``_causal`` form, which takes the entry's own arguments (never with ``key_lengths``: functional.py refuses)."""
     argv = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args] + [torch.cuda.current_stream().cuda_stream]
+    if causal:
+        name = name[:-len("_devseed")] + "_causal_devseed" if name.endswith("_devseed") else name + "_causal"
     if key_lengths is not None:
         name = name[:-len("_devseed")] + "_keys_devseed" if name.endswith("_devseed") else name + "_keys"
         argv.append(key_lengths.data_ptr())

@@ -14,6 +14,12 @@
 // below is written once, as a __device__ function with a compile-time KEYS flag; the plain kernels instantiate KEYS = false, in which
 // every use of the length folds away.  A length is read once per workgroup, clamped into [1, T], and is wave-uniform.
 //
+// Causal (opt-in, the *_causal_kernel entries): query t sees keys 0 .. t of its sequence.  The flag of the bodies is a
+// three-valued compile-time MODE (plain, keys, causal), so keys and causal cannot be combined.  A wave that owns query tile qt sweeps
+// key tiles 0 .. qt: the tiles in front of the diagonal run the full body, the diagonal tile a separately instantiated DIAG body
+// (key > query, or key >= T, masked by a select), and behind it the wave only keeps staging for the workgroup, whose sweep ends at
+// the diagonal of its last query tile.  The dK/dV kernel, whose waves own key tiles, mirrors that: idle in front of the diagonal.
+//
 // Scores are kept in the log2 domain: the producer stores Q' = (x Wq^T + bq) * log2(e)/sqrt(d_k), so
 // P = 2^(S' - L) with L = rowmax + log2(rowsum) saved per query for the backward pass.
 #pragma once
@@ -114,6 +120,12 @@ __device__ __forceinline__ int attn_key_len(const int* __restrict__ key_lengths,
     return __builtin_amdgcn_readfirstlane(min(max(key_lengths[b], 1), T));
 }
 
+enum AttnMode { ATTN_PLAIN = 0, ATTN_KEYS = 1, ATTN_CAUSAL = 2 };
+// tags of the tile bodies: the hot tile, the tile that holds the tail of the swept axis, the tile on the causal diagonal
+using TileFull = std::integral_constant<int, 0>;
+using TileTail = std::integral_constant<int, 1>;
+using TileDiag = std::integral_constant<int, 2>;
+
 struct AttnBlock { int bx, bh; bool valid; };
 __device__ __forceinline__ AttnBlock attn_block(int nx, int nbh) {
     const int L = blockIdx.x, grp = L / (8 * nx), rem = L - grp * 8 * nx;
@@ -124,15 +136,27 @@ __device__ __forceinline__ AttnBlock attn_block(int nx, int nbh) {
     return a;
 }
 __host__ inline int attn_grid(int nx, int nbh) { return nx * 8 * ((nbh + 7) / 8); }
+// Causal: the tile quads of a head sweep 4, 8, .. key tiles (forward, dQ; dK/dV the other way round), and the whole grid of a training
+// shape is resident at once, so a launch lasts as long as the CU that holds the most work.  With attn_block's decoding the workgroups
+// an XCD receives carry bx = 0, 1, .. nx-1, 0, 1, ..: dealt round-robin to its 32 CUs, every workgroup of a CU has the SAME bx when nx
+// divides 32, and the CUs of the last quads set the time (measured: DESIGN.md 4.4).  Rotating bx by one per 32 workgroups of the XCD
+// gives each CU every quad in turn; ids congruent mod 8 still carry the same head, and (bx, bh) is still hit exactly once.
+__device__ __forceinline__ AttnBlock attn_block_causal(int nx, int nbh) {
+    AttnBlock a = attn_block(nx, nbh);
+    const int grp = blockIdx.x / (8 * nx);
+    a.bx = (a.bx + ((grp * nx) >> 5)) % nx;
+    return a;
+}
 
 // (`//@ name` comment lines mark the phase boundaries at which tools/make_diag.py inserts cycle stamps into the GENERATED stamped twin of this
 // kernel — diagnostic builds only; this file holds no diagnostic code)
-template <int DKP, bool DROP, bool KEYS>
+template <int DKP, bool DROP, int MODE>
 __device__ __forceinline__ void attn_fwd_body(
         const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
         bf16* __restrict__ ctx, float* __restrict__ lse,
         int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
         const int* __restrict__ key_lengths) {
+    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL;
     constexpr int KS = DKP / 16;
     constexpr int DKB = DKP < 32 ? DKP : 32;           // feature rows of this launch's output block
     constexpr bool ONES = (DKP == 16) && !DROP;        // row sums through the MFMA
@@ -145,16 +169,17 @@ __device__ __forceinline__ void attn_fwd_body(
     __shared__ __attribute__((aligned(16))) bf16 zeros[256];          // what the lanes of the padding feature rows (>= d_k) read
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const AttnBlock ab = attn_block((nt + 3) >> 2, nbh);
+    const AttnBlock ab = CAUSAL ? attn_block_causal((nt + 3) >> 2, nbh) : attn_block((nt + 3) >> 2, nbh);
     if (!ab.valid) return;                              // whole workgroup, before any barrier
     const int qt = ab.bx * 4 + wave;
     const bool live = qt < nt;                          // idle waves still stage and synchronise
     const int qtc = live ? qt : nt - 1;
     const int bh = ab.bh, b = bh / h, head = bh - b * h;
     const int Tp = nt * 32;
-    // keys that exist for this sequence and the tiles that hold them: (T, nt), or the sequence's key length and its tiles
+    // keys that exist for this sequence and the tiles that hold them: (T, nt), or the sequence's key length and its tiles;
+    // causal: the workgroup's sweep ends at the diagonal of its last query tile
     const int Tk = KEYS ? attn_key_len(key_lengths, b, T) : T;
-    const int nk = KEYS ? (Tk + 31) >> 5 : nt;
+    const int nk = KEYS ? (Tk + 31) >> 5 : CAUSAL ? min(nt, ab.bx * 4 + 4) : nt;
     const bf16* Qb = Qr + (size_t)bh * fragR_elems(Tp, DKP);
     const bf16* Kb = Kr + (size_t)bh * fragR_elems(Tp, DKP);
     const bf16* Vb = Vr + (size_t)bh * fragR_elems(Tp, DKP) + (size_t)fb * 4 * 256;      // feature group 4 fb of tile 0
@@ -199,13 +224,16 @@ __device__ __forceinline__ void attn_fwd_body(
     // states, which is wrong on the taken path — seen as 27 % wrong dQ in attn_bwd_dq_kernel<32>), TAIL = true for the
     // last key tile, whose index masking is then straight-line code.
     //@ prologue
-    auto body = [&](auto tail_tag, int kt) {
-        constexpr bool TAIL = decltype(tail_tag)::value;
+    auto body = [&](auto tile_tag, int kt) {
+        constexpr bool TAIL = (int)decltype(tile_tag)::value == 1, DIAG = (int)decltype(tile_tag)::value == 2;
+        // the workgroup stages one tile ahead: compile-time off in the last tile of a plain or keyed sweep; causal: the wave's
+        // diagonal tile is not the workgroup's last one unless the wave owns the last query tile
+        const bool more = CAUSAL ? kt + 1 < nk : !TAIL;
         //@ loop_top
         progress_prio(kt, nk);
         const uint32_t tw = mw;                          // this tile's keep bits
-        if (DROP && !TAIL) mw = mrow[(size_t)(kt + 1) * 64];
-        if (!TAIL) stg.load(kt + 1);                    // next tile in flight behind this tile's arithmetic
+        if (DROP && !TAIL && !DIAG) mw = mrow[(size_t)(kt + 1) * 64];
+        if (more) stg.load(kt + 1);                     // next tile in flight behind this tile's arithmetic
         const bf16* sk = stage[kt & 1];
         const bf16* sv = vpad ? zeros : sk + PK * 8 + voff;
         // S' - m straight out of the MFMA: the accumulator init is a register set that holds -m for the whole sweep and is rewritten
@@ -227,6 +255,10 @@ __device__ __forceinline__ void attn_fwd_body(
         if (TAIL) {                                     // keys >= T (>= the key length) do not exist
 #pragma unroll
             for (int i = 0; i < 16; ++i) s[i] = (kt * 32 + acc32_row(i, hh) < Tk) ? s[i] : -INFINITY;
+        }
+        if (DIAG) {                                     // kt == qt: keys behind the query, and keys >= T, do not exist.  Key 32 kt is
+#pragma unroll                                          // visible to every query of the tile, so every row keeps a finite maximum
+            for (int i = 0; i < 16; ++i) s[i] = (acc32_row(i, hh) <= r && kt * 32 + acc32_row(i, hh) < T) ? s[i] : -INFINITY;
         }
         // (no inline asm here: hipcc's hazard recognizer does not count an asm statement as a reader of MFMA results)
         float tmax = fmaxf(fmaxf(s[0], s[1]), s[2]);
@@ -265,13 +297,25 @@ __device__ __forceinline__ void attn_fwd_body(
             o = mfma32(va, pack8(s, s2), o);
         }
         //@ pv
-        if (!TAIL) stg.store(stage[(kt + 1) & 1]);
+        if (more) stg.store(stage[(kt + 1) & 1]);
         //@ stage_wait
         __syncthreads();        // stage[(kt+1)&1] was last read at tile kt-1, i.e. before the previous barrier
         //@ barrier
     };
-    for (int kt = 0; kt < nk - 1; ++kt) body(std::false_type{}, kt);
-    body(std::true_type{}, nk - 1);
+    if constexpr (CAUSAL) {
+        // three wave-uniform states, each a whole body: in front of the diagonal, on it, behind it (and a wave without a query tile):
+        // nothing to compute, but the workgroup stages cooperatively — keep moving pieces and meet the one barrier per tile
+        for (int kt = 0; kt < (live ? qt : 0); ++kt) body(TileFull{}, kt);
+        if (live) body(TileDiag{}, qt);
+        __builtin_amdgcn_s_setprio(0);
+        for (int kt = live ? qt + 1 : 0; kt < nk; ++kt) {
+            if (kt + 1 < nk) { stg.load(kt + 1); stg.store(stage[(kt + 1) & 1]); }
+            __syncthreads();
+        }
+    } else {
+        for (int kt = 0; kt < nk - 1; ++kt) body(TileFull{}, kt);
+        body(TileTail{}, nk - 1);
+    }
     //@ swept
     if (!live) return;
     float ltot;
@@ -299,7 +343,7 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_kernel(
         const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
         bf16* __restrict__ ctx, float* __restrict__ lse,
         int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
-    attn_fwd_body<DKP, DROP, false>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, nullptr);
+    attn_fwd_body<DKP, DROP, ATTN_PLAIN>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, nullptr);
 }
 // ... with key lengths: sequence b attends keys < key_lengths[b]
 template <int DKP, bool DROP>
@@ -308,7 +352,15 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_keys_kernel(
         bf16* __restrict__ ctx, float* __restrict__ lse,
         int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
         const int* __restrict__ key_lengths) {
-    attn_fwd_body<DKP, DROP, true>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, key_lengths);
+    attn_fwd_body<DKP, DROP, ATTN_KEYS>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, key_lengths);
+}
+// ... causal: query t attends keys <= t
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_causal_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
+        bf16* __restrict__ ctx, float* __restrict__ lse,
+        int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
+    attn_fwd_body<DKP, DROP, ATTN_CAUSAL>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -317,13 +369,14 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_keys_kernel(
 //     S'  = Q' K^T - L      (-L, stored negated, is the accumulator init: P = 2^S' needs no subtraction)
 //     dPc = dO V^T - delta  (same trick with -delta = -rowsum(dO . O))
 //     dS  = P * dPc ;  dV^T += dO^T P ;  dK^T += Q'^T dS     (P, dS accumulators ARE the B operands)
-template <int DKP, bool DROP, bool KEYS>
+template <int DKP, bool DROP, int MODE>
 __device__ __forceinline__ void attn_bwd_dkv_body(
         const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr, const bf16* __restrict__ dOr,
         const float* __restrict__ lse, const float* __restrict__ delta,
         bf16* __restrict__ dkv, int lddkv,      // row-major [M][lddkv]; dK at column HD, dV at 2*HD
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb,
         const int* __restrict__ key_lengths) {
+    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL;
     constexpr int KS = DKP / 16;
     constexpr int DKB = DKP < 32 ? DKP : 32;
     // pieces: R-layout tile (in LDS with its 8-feature groups 576 bytes apart: the products that contract over the queries read
@@ -334,7 +387,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
     __shared__ __attribute__((aligned(16))) bf16 zeros[256];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const AttnBlock ab = attn_block((nt + 3) >> 2, nbh);
+    const AttnBlock ab = CAUSAL ? attn_block_causal((nt + 3) >> 2, nbh) : attn_block((nt + 3) >> 2, nbh);
     if (!ab.valid) return;                              // whole workgroup, before any barrier
     const int kt = ab.bx * 4 + wave;
     const bool live = kt < nt;
@@ -359,7 +412,8 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
     const size_t offR = (size_t)bh * fragR_elems(Tp, DKP);
     const bf16 *Krb = Kr + offR, *Vrb = Vr + offR;
     const uint16_t* mrow = maskK + ((size_t)bh * nt + ktc) * nt * 64 + lane;      // LK layout: this lane's word of one block per query tile
-    uint32_t mw = DROP ? mrow[0] : 0u;
+    const int q0 = CAUSAL ? ab.bx * 4 : 0;              // first query tile of the workgroup's sweep (causal: no earlier query sees its keys)
+    uint32_t mw = DROP ? mrow[(size_t)(CAUSAL ? ktc : 0) * 64] : 0u;      // causal: the wave's first working tile is its diagonal one
     const uint32_t scale_bits = __builtin_bit_cast(uint32_t, drop_scale);
 
     TileStager<4, (TOTAL + MMT_THREADS - 1) / MMT_THREADS> stg;
@@ -370,7 +424,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
         const int lds0[4] = {0, PRL, 2 * PRL, 2 * PRL + PC}, pad[4] = {MMT_TR_OCT - 32, MMT_TR_OCT - 32, 0, 0};
         stg.init(base, pieces, strides, lds0, pad, threadIdx.x);
     }
-    stg.load(0);
+    stg.load(q0);
     zeros[threadIdx.x] = (bf16)0.f;
     bf16x8 kfr[KS], vfr[KS];
 #pragma unroll
@@ -390,9 +444,10 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
     // 16-lane group's 16 features, and receives feature row r; slot j <-> query 16 s2 + 8 (j >> 2) + 4 hh + (j & 3)
     const int g1 = (lane >> 4) & 1, tq = (lane >> 2) & 3, tpp = lane & 3;
     const int toff = (((ONEACC ? 0 : 4 * fb + 2 * g1) + (tpp >> 1)) * MMT_TR_OCT + 4 * hh + tq) * 8 + 4 * (tpp & 1);
-    const bool key_tail = KEYS ? (ktc * 32 + 32 > Tk) : (ktc == nt - 1) && (T & 31);
+    // (causal: a key >= T is seen by queries >= T only, which the DIAG body masks)
+    const bool key_tail = CAUSAL ? false : KEYS ? (ktc * 32 + 32 > Tk) : (ktc == nt - 1) && (T & 31);
     const bool key_ok = (ktc * 32 + r) < Tk;
-    stg.store(stage[0]);
+    stg.store(stage[0]);                                // (q0 is a multiple of 4: tile qt sits in stage[qt & 1] in every mode)
     __syncthreads();
     if (KEYS && ktc * 32 >= Tk) {
         // a wave whose key tile lies wholly behind the length (wave-uniform; some other wave of the workgroup has visible keys): it has
@@ -409,10 +464,10 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
     // simply 1 everywhere except in the wave that owns the last key tile, and the query tail is the peeled last tile.
     // (KEYS: a select instead — a key behind the length is a real window, whose 2^(S' - L) may be inf)
     const float kmul = (key_tail && !key_ok) ? 0.f : 1.f;
-    auto body = [&](auto tail_tag, int qt) {
-        constexpr bool QTAIL = decltype(tail_tag)::value;
+    auto body = [&](auto tile_tag, int qt) {
+        constexpr bool QTAIL = (int)decltype(tile_tag)::value == 1, DIAG = (int)decltype(tile_tag)::value == 2;
         const bool more = qt + 1 < nt;                  // scalar, loop-invariant except at the very last tile
-        progress_prio(qt, nt);
+        progress_prio(qt - q0, nt - q0);
         const uint32_t tw = mw;
         if (DROP && more) mw = mrow[(size_t)(qt + 1) * 64];
         if (more) stg.load(qt + 1);
@@ -441,6 +496,8 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
         for (int j = 0; j < 16; ++j) {
             float pv = fast_exp2(s[j]);
             if (QTAIL) pv = (qt * 32 + acc32_row(j, hh) < T) ? pv : 0.f;      // queries >= T do not exist
+            // qt == kt: neither do queries in front of the key (a select: L of such a query is from ITS keys, 2^(S' - L) may be inf)
+            if (DIAG) pv = (acc32_row(j, hh) >= r && qt * 32 + acc32_row(j, hh) < T) ? pv : 0.f;
             s[j] = pv;
         }
         if (key_tail) {                                 // wave-uniform, loop-invariant: only the last key tile's wave pays
@@ -473,8 +530,22 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
         if (more) stg.store(stage[(qt + 1) & 1]);
         __syncthreads();
     };
-    for (int qt = 0; qt < nt - 1; ++qt) body(std::false_type{}, qt);
-    if (T & 31) body(std::true_type{}, nt - 1); else body(std::false_type{}, nt - 1);
+    if constexpr (CAUSAL) {
+        // wave-uniform states, each a whole body: idle in front of the diagonal (staging and the barrier only; a wave without a key tile
+        // stays there), the DIAG body on it, the full body behind it, the peeled query tail last.  No key tile is without queries.
+        for (int qt = q0; qt < (live ? kt : nt); ++qt) {
+            if (qt + 1 < nt) { stg.load(qt + 1); stg.store(stage[(qt + 1) & 1]); }
+            __syncthreads();
+        }
+        if (live) {
+            body(TileDiag{}, kt);                       // (on the last tile it is the query tail's body too)
+            for (int qt = kt + 1; qt < nt - 1; ++qt) body(TileFull{}, qt);
+            if (kt < nt - 1) { if (T & 31) body(TileTail{}, nt - 1); else body(TileFull{}, nt - 1); }
+        }
+    } else {
+        for (int qt = 0; qt < nt - 1; ++qt) body(TileFull{}, qt);
+        if (T & 31) body(TileTail{}, nt - 1); else body(TileFull{}, nt - 1);
+    }
     if (!live) return;
     // dK = ln2 * acc (scores are in the log2 domain), dV = acc; rows e = acc32_row, column key = r
     const float LN2 = 0.6931471805599453f;
@@ -501,7 +572,7 @@ __global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_k
         const float* __restrict__ lse, const float* __restrict__ delta,
         bf16* __restrict__ dkv, int lddkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb) {
-    attn_bwd_dkv_body<DKP, DROP, false>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, nullptr);
+    attn_bwd_dkv_body<DKP, DROP, ATTN_PLAIN>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, nullptr);
 }
 // ... with key lengths: dK = dV = 0 for keys >= key_lengths[b]
 template <int DKP, bool DROP>
@@ -511,7 +582,16 @@ __global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_k
         bf16* __restrict__ dkv, int lddkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb,
         const int* __restrict__ key_lengths) {
-    attn_bwd_dkv_body<DKP, DROP, true>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, key_lengths);
+    attn_bwd_dkv_body<DKP, DROP, ATTN_KEYS>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, key_lengths);
+}
+// ... causal: key t gets dK, dV from queries >= t
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_causal_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr, const bf16* __restrict__ dOr,
+        const float* __restrict__ lse, const float* __restrict__ delta,
+        bf16* __restrict__ dkv, int lddkv,
+        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb) {
+    attn_bwd_dkv_body<DKP, DROP, ATTN_CAUSAL>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -519,7 +599,7 @@ __global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_k
 // qt = 4*blockIdx.x + w and sweeps all key tiles; L and delta are lane constants; the dS^T accumulator
 // (keys in registers) is the B operand of dQ^T += K^T dS^T.  The epilogue applies 1/sqrt(d_k) and the
 // query-row mask (blanked rows pass no gradient to Q) and writes columns [0,HD) of dQKV in both layouts.
-template <int DKP, bool DROP, bool KEYS>
+template <int DKP, bool DROP, int MODE>
 __device__ __forceinline__ void attn_bwd_dq_body(
         const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
         const bf16* __restrict__ dOr, const float* __restrict__ lse, const float* __restrict__ delta,
@@ -527,13 +607,14 @@ __device__ __forceinline__ void attn_bwd_dq_body(
         bf16* __restrict__ dqkv, int lddqkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
         const int* __restrict__ key_lengths) {
+    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL;
     constexpr int KS = DKP / 16;
     constexpr int DKB = DKP < 32 ? DKP : 32;
     constexpr int PR = DKP * 4, PRL = (DKP / 8) * MMT_TR_OCT;      // K tile padded in LDS: K^T fragments by transposing reads
     __shared__ __attribute__((aligned(16))) bf16 stage[2][(PRL + PR) * 8];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const AttnBlock ab = attn_block((nt + 3) >> 2, nbh);
+    const AttnBlock ab = CAUSAL ? attn_block_causal((nt + 3) >> 2, nbh) : attn_block((nt + 3) >> 2, nbh);
     if (!ab.valid) return;                              // whole workgroup, before any barrier
     const int qt = ab.bx * 4 + wave;
     const bool live = qt < nt;
@@ -541,7 +622,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(
     const int bh = ab.bh, b = bh / h, head = bh - b * h;
     const int Tp = nt * 32;
     const int Tk = KEYS ? attn_key_len(key_lengths, b, T) : T;          // keys that exist for this sequence, and their tiles
-    const int nk = KEYS ? (Tk + 31) >> 5 : nt;
+    const int nk = KEYS ? (Tk + 31) >> 5 : CAUSAL ? min(nt, ab.bx * 4 + 4) : nt;      // causal: up to the diagonal of the last query tile
     const size_t offR = (size_t)bh * fragR_elems(Tp, DKP);
     const bf16 *Qrb = Qr + offR, *dOrb = dOr + offR;
     const uint16_t* mrow = maskQ + ((size_t)bh * nt + qtc) * nt * 64 + lane;      // LQ layout
@@ -575,12 +656,12 @@ __device__ __forceinline__ void attn_bwd_dq_body(
     __syncthreads();
 
     // Tile body without conditional code between MFMAs and their consumers (see attn_fwd_kernel); key tail peeled.
-    auto body = [&](auto tail_tag, int kt) {
-        constexpr bool TAIL = decltype(tail_tag)::value;
+    auto body = [&](auto tile_tag, int kt) {
+        constexpr bool TAIL = (int)decltype(tile_tag)::value == 1, DIAG = (int)decltype(tile_tag)::value == 2;
         const bool more = kt + 1 < nk;
         progress_prio(kt, nk);
         const uint32_t tw = mw;
-        if (DROP && more) mw = mrow[(size_t)(kt + 1) * 64];
+        if (DROP && more && !DIAG) mw = mrow[(size_t)(kt + 1) * 64];
         if (more) stg.load(kt + 1);
         const bf16* sk = stage[kt & 1];
         const bf16* sv = sk + PRL * 8;
@@ -601,6 +682,8 @@ __device__ __forceinline__ void attn_bwd_dq_body(
         for (int j = 0; j < 16; ++j) {
             float pv = fast_exp2(s[j]);
             if (TAIL) pv = (kt * 32 + acc32_row(j, hh) < Tk) ? pv : 0.f;      // keys >= T (>= the key length) do not exist
+            // kt == qt: neither do keys behind the query (a select: L is from the visible keys, 2^(S' - L) of a later key may be inf)
+            if (DIAG) pv = (acc32_row(j, hh) <= r && kt * 32 + acc32_row(j, hh) < T) ? pv : 0.f;
             s[j] = pv;
         }
         if (DROP) {
@@ -619,8 +702,18 @@ __device__ __forceinline__ void attn_bwd_dq_body(
         if (more) stg.store(stage[(kt + 1) & 1]);
         __syncthreads();
     };
-    for (int kt = 0; kt < nk - 1; ++kt) body(std::false_type{}, kt);
-    if (Tk & 31) body(std::true_type{}, nk - 1); else body(std::false_type{}, nk - 1);
+    if constexpr (CAUSAL) {                             // the three wave-uniform states of attn_fwd_body
+        for (int kt = 0; kt < (live ? qt : 0); ++kt) body(TileFull{}, kt);
+        if (live) body(TileDiag{}, qt);
+        __builtin_amdgcn_s_setprio(0);
+        for (int kt = live ? qt + 1 : 0; kt < nk; ++kt) {
+            if (kt + 1 < nk) { stg.load(kt + 1); stg.store(stage[(kt + 1) & 1]); }
+            __syncthreads();
+        }
+    } else {
+        for (int kt = 0; kt < nk - 1; ++kt) body(TileFull{}, kt);
+        if (Tk & 31) body(TileTail{}, nk - 1); else body(TileFull{}, nk - 1);
+    }
     if (!live) return;
     const int t = qt * 32 + r;
     if (t < T) {
@@ -643,7 +736,7 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_kernel(
         const float* __restrict__ rowmask, float scale,
         bf16* __restrict__ dqkv, int lddqkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
-    attn_bwd_dq_body<DKP, DROP, false>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, nullptr);
+    attn_bwd_dq_body<DKP, DROP, ATTN_PLAIN>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, nullptr);
 }
 // ... with key lengths: the sweep ends at key_lengths[b]
 template <int DKP, bool DROP>
@@ -654,7 +747,17 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_keys_kernel(
         bf16* __restrict__ dqkv, int lddqkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
         const int* __restrict__ key_lengths) {
-    attn_bwd_dq_body<DKP, DROP, true>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, key_lengths);
+    attn_bwd_dq_body<DKP, DROP, ATTN_KEYS>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, key_lengths);
+}
+// ... causal: the sweep of a query tile ends at its diagonal
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_causal_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
+        const bf16* __restrict__ dOr, const float* __restrict__ lse, const float* __restrict__ delta,
+        const float* __restrict__ rowmask, float scale,
+        bf16* __restrict__ dqkv, int lddqkv,
+        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
+    attn_bwd_dq_body<DKP, DROP, ATTN_CAUSAL>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -25,6 +25,11 @@
 //
 // Key lengths (attn_probs_keys_kernel; attn.h): both sweeps end after the ceil(len/32) key tiles of the sequence, keys >= len score
 // MASKED like keys >= T, and — the output buffer is uninitialised — the columns behind the length are written as exact zeros.
+//
+// Causal (attn_probs_causal_kernel; attn.h): both sweeps of query tile qt end at key tile qt, where key > query scores MASKED too, and
+// the tiles above the diagonal are written as exact zeros.  The diagonal is a select on a wave-uniform flag inside the one tile
+// body, still straight-line code: a second instantiation of the body, as attn.h has, doubles the keep-bit generator and brings the
+// d_k = 64 train instance to 256 VGPRs with scratch.
 #pragma once
 #include "common.h"
 #include "attn_mask.h"
@@ -55,10 +60,11 @@ __device__ __forceinline__ bf16x8 probs_frag(const float* __restrict__ row, int 
     return out;
 }
 
-template <int DKP, bool DROP, bool KEYS>
+template <int DKP, bool DROP, int MODE>
 __device__ __forceinline__ void attn_probs_body(
         const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
         int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop, const int* __restrict__ key_lengths) {
+    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL;
     constexpr int KS = DKP / 16;
     __shared__ uint32_t patch[DROP ? 4 * 64 * MMT_PROBS_PATCH_ROW : 1];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -69,7 +75,7 @@ __device__ __forceinline__ void attn_probs_body(
     if (qt >= nt) return;                               // waves share nothing: no barrier below
     const int bh = ab.bh, b = bh / h, head = bh - b * h;
     const int Tk = KEYS ? attn_key_len(key_lengths, b, T) : T;          // keys that exist for this sequence, and their tiles
-    const int nk = KEYS ? (Tk + 31) >> 5 : nt;
+    const int nk = KEYS ? (Tk + 31) >> 5 : CAUSAL ? qt + 1 : nt;       // causal: up to the diagonal tile
 
     // A operand: Q' of query r of the tile (a query >= T reads row T-1 and is never stored), features 16 s + 8 hh .. + 7
     bf16x8 qf[KS];
@@ -96,8 +102,14 @@ __device__ __forceinline__ void attn_probs_body(
 #pragma unroll
         for (int ss = 0; ss < KS; ++ss) s = mfma32(qf[ss], kf[ss], s);
         const bool kok = kt * 32 + r < Tk;
+        if constexpr (CAUSAL) {                         // on the diagonal tile key r is visible to the queries >= r only
+            const bool diag = kt == qt;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) s[i] = kok ? s[i] : MMT_PROBS_MASKED;
+            for (int i = 0; i < 16; ++i) s[i] = (kok && (!diag || r <= acc32_row(i, hh))) ? s[i] : MMT_PROBS_MASKED;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s[i] = kok ? s[i] : MMT_PROBS_MASKED;
+        }
         return s;
     };
 
@@ -168,7 +180,7 @@ __device__ __forceinline__ void attn_probs_body(
 #pragma unroll
         for (int s2 = 0; s2 < KS; ++s2) kf[s2] = kn[s2];
     }
-    if (KEYS) {     // the key tiles behind the length: zeros (the boundary tile's columns >= len were stored above, as 2^(MASKED - max) == 0)
+    if (KEYS || CAUSAL) {     // the key tiles behind the length / above the diagonal: zeros (the boundary tile's masked entries were stored above, as 2^(MASKED - max) == 0)
         for (int kt = nk; kt < nt; ++kt) {
             float* const pk = prow + kt * 32 + r;
             const bool kok = kt * 32 + r < T;
@@ -182,12 +194,19 @@ template <int DKP, bool DROP>
 __global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_kernel(
         const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
         int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop) {
-    attn_probs_body<DKP, DROP, false>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, nullptr);
+    attn_probs_body<DKP, DROP, ATTN_PLAIN>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, nullptr);
 }
 // ... with key lengths: columns >= key_lengths[b] are exact zeros
 template <int DKP, bool DROP>
 __global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_keys_kernel(
         const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
         int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop, const int* __restrict__ key_lengths) {
-    attn_probs_body<DKP, DROP, true>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, key_lengths);
+    attn_probs_body<DKP, DROP, ATTN_KEYS>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, key_lengths);
+}
+// ... causal: entries above the diagonal are exact zeros
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_causal_kernel(
+        const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
+        int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop) {
+    attn_probs_body<DKP, DROP, ATTN_CAUSAL>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, nullptr);
 }

@@ -41,16 +41,16 @@ def _seed_pair(seed):
     return (0, seed.state) if isinstance(seed, _lib.DeviceSeed) else (int(seed), None)
 
 
-def _launch_seeded(name, seed, *args, state_arg=True, key_lengths=None):
+def _launch_seeded(name, seed, *args, state_arg=True, key_lengths=None, causal=False):
     """``name`` with the seed by value behind ``args``, or its twin ``name``_devseed with the DeviceSeed's state word there, which the
     launch reads and advances.  ``state_arg=False``: the twin takes no seed (the encoder backward finds it in its forward's workspace).
-    ``key_lengths``: the ``_keys`` form of either (_lib.launch)."""
+    ``key_lengths`` / ``causal``: the ``_keys`` / ``_causal`` form of either (_lib.launch)."""
     if not isinstance(seed, _lib.DeviceSeed):
-        _lib.launch(name, *args, seed, key_lengths=key_lengths)
+        _lib.launch(name, *args, seed, key_lengths=key_lengths, causal=causal)
     elif state_arg:
-        _lib.launch(name + "_devseed", *args, seed.state, key_lengths=key_lengths)
+        _lib.launch(name + "_devseed", *args, seed.state, key_lengths=key_lengths, causal=causal)
     else:
-        _lib.launch(name + "_devseed", *args, key_lengths=key_lengths)
+        _lib.launch(name + "_devseed", *args, key_lengths=key_lengths, causal=causal)
 
 
 # Key lengths: a padding mask that masks KEYS (opt-in; the reference blanks query rows only, transformer/MFT/multiTransformer.py:29-31).
@@ -82,6 +82,16 @@ def _check_key_lengths(op, key_lengths, B, device):
     if key_lengths.device != device:
         raise ValueError("%s: key_lengths is on %s, the operands on %s" % (op, key_lengths.device, device))
     return key_lengths.detach().contiguous()
+
+
+# Causal self-attention (opt-in; the reference lets window t attend every window of its batch row, transformer/MFT/multiTransformer.py:27-31).
+def _check_causal(op, key_lengths, causal):
+    """``causal`` as a bool.  It is never combined with ``key_lengths``: raises before any launch."""
+    if causal and key_lengths is not None:
+        raise ValueError("%s: key_lengths and causal=True cannot be combined: a valid window t < len of a prefix-masked batch sees keys "
+                         "<= t < len only, so causal attention already keeps it from the padding behind its sequence "
+                         "(pass causal=True alone)" % op)
+    return bool(causal)
 
 
 # Pool workspaces held from forward to backward (_lib.WorkspacePool): the Functions that keep one use these two.
@@ -132,8 +142,9 @@ def _chunk_seed(seed, i, nsplit=1):
     return seed if i == 0 else _lib.mix64(seed, i)
 
 
-def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths=None):
+def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths=None, causal=False):
     """The fused stack's forward, one launch per sub-batch on a stream of its own; keeps on ``ctx`` what _encoder_bwd needs."""
+    causal = _check_causal("encoder_stack", key_lengths, causal)
     lib = _lib.load()
     _lib.require_hip(x, mask, flat_params)
     x_, m_, p_ = _f32c(x), _f32c(mask), _f32c(flat_params)
@@ -161,14 +172,14 @@ def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, s
             ws = _lib.POOL.get(nbytes, x_.device, tag=("encoder",) + dims + (train,))
             sd = _chunk_seed(seed, i, len(chunks))
             _launch_seeded("mmt_encoder_forward", sd, x_[b0:b1], m_[b0:b1], p_, y[b0:b1], ws, nbytes, *dims, eps, dropout_p,
-                           key_lengths=None if kl_ is None else kl_[b0:b1])
+                           key_lengths=None if kl_ is None else kl_[b0:b1], causal=causal)
             parts.append((b0, b1, ws, sd))
     _SPLIT_STREAMS.end(main, streams)
     if _hold(ctx, *[ws for _, _, ws, _ in parts]):
         ctx.save_for_backward(x_, m_, p_)
         ctx.parts = [(b0, b1, sd) for b0, b1, _, sd in parts]
         ctx.cfg = (T, d, h, d_ff, n_layers, eps, dropout_p)
-        ctx.key_lengths = kl_
+        ctx.key_lengths, ctx.causal = kl_, causal
     return y
 
 
@@ -186,7 +197,7 @@ def _encoder_bwd(ctx, dy):
         with torch.cuda.stream(st):
             _launch_seeded("mmt_encoder_backward", sd, dy_[b0:b1], x_[b0:b1], m_[b0:b1], p_, dx[b0:b1], dp, ws, ws.numel(),
                            b1 - b0, T, d, h, d_ff, n_layers, eps, dropout_p, state_arg=False,
-                           key_lengths=None if kl_ is None else kl_[b0:b1])
+                           key_lengths=None if kl_ is None else kl_[b0:b1], causal=ctx.causal)
             _lib.POOL.put(ws)
     _SPLIT_STREAMS.end(main, streams)
     if len(dps) > 1:                                # the sub-batches' parameter gradients, summed into the first buffer
@@ -198,22 +209,23 @@ def _encoder_bwd(ctx, dy):
 
 class _EncoderStackFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths=None):
-        return _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths)
+    def forward(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths=None, causal=False):
+        return _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths, causal)
 
     @staticmethod
     def backward(ctx, dy):
         dx, dflat = _encoder_bwd(ctx, dy)
-        return dx, None, dflat, None, None, None, None, None, None, None, None
+        return dx, None, dflat, None, None, None, None, None, None, None, None, None
 
 
-def encoder_stack(x, mask, flat_params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, nsplit=1, key_lengths=None):
+def encoder_stack(x, mask, flat_params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, nsplit=1, key_lengths=None, causal=False):
     """``seed``: a python int (by value) or a ``_lib.DeviceSeed`` (device-resident: fresh masks at every hipGraph replay), or one
     of either per sub-batch stream; ``nsplit``: run the batch as that many sub-batches on HIP streams of their own (see _SPLIT_STREAMS).
     ``key_lengths``: int32 (B,) (``key_lengths(mask)``): sequence b attends keys < key_lengths[b] in every layer; None: the
-    reference's semantics, every key is attended.  Sub-batches take their slice of the lengths."""
+    reference's semantics, every key is attended.  Sub-batches take their slice of the lengths.
+    ``causal``: window t attends windows 0 .. t in every layer (see ``sdpa``); never together with ``key_lengths`` (ValueError)."""
     return _EncoderStackFn.apply(x, mask, flat_params, int(h), int(d_ff), int(n_layers), float(eps), float(dropout_p), _seed_arg(seed),
-                                 int(nsplit), key_lengths)
+                                 int(nsplit), key_lengths, causal)
 
 
 class _EncoderStackParamsFn(torch.autograd.Function):
@@ -223,24 +235,25 @@ class _EncoderStackParamsFn(torch.autograd.Function):
     buffer in place with one collective and no staging copies (``parallel.allreduce_gradients``)."""
 
     @staticmethod
-    def forward(ctx, x, mask, h, d_ff, n_layers, eps, dropout_p, seed, flat, nsplit, key_lengths, *params):
+    def forward(ctx, x, mask, h, d_ff, n_layers, eps, dropout_p, seed, flat, nsplit, key_lengths, causal, *params):
         # `flat`: the parameters' own storage when they are views of one buffer (multiTransformer.Encoder keeps them that way), else
         # None and the buffer is assembled here (one concatenation kernel per step)
         if flat is None:
             flat = torch.cat([q.detach().reshape(-1) for q in params]).float()
         ctx.shapes = [tuple(q.shape) for q in params]
-        return _encoder_fwd(ctx, x, mask, flat, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths)
+        return _encoder_fwd(ctx, x, mask, flat, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths, causal)
 
     @staticmethod
     def backward(ctx, dy):
         dx, dflat = _encoder_bwd(ctx, dy)
         grads = [g.view(shp) for g, shp in zip(dflat.split([math.prod(shp) for shp in ctx.shapes]), ctx.shapes)]
-        return (dx, None, None, None, None, None, None, None, None, None, None) + tuple(grads)
+        return (dx, None, None, None, None, None, None, None, None, None, None, None) + tuple(grads)
 
 
-def encoder_stack_params(x, mask, params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, flat=None, nsplit=1, key_lengths=None):
+def encoder_stack_params(x, mask, params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, flat=None, nsplit=1, key_lengths=None,
+                         causal=False):
     return _EncoderStackParamsFn.apply(x, mask, int(h), int(d_ff), int(n_layers), float(eps), float(dropout_p), _seed_arg(seed), flat,
-                                       int(nsplit), key_lengths, *params)
+                                       int(nsplit), key_lengths, causal, *params)
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -275,7 +288,8 @@ def layer_norm(x, a_2, b_2, eps=1e-6):
 
 class _SdpaFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, mask, h, dropout_p, seed, key_lengths=None):
+    def forward(ctx, q, k, v, mask, h, dropout_p, seed, key_lengths=None, causal=False):
+        causal = _check_causal("sdpa", key_lengths, causal)
         lib = _lib.load()
         _lib.require_hip(q, k, v, mask)
         q_, k_, v_, m_ = _f32c(q), _f32c(k), _f32c(v), _f32c(mask)
@@ -291,9 +305,9 @@ class _SdpaFn(torch.autograd.Function):
             _lib.launch("mmt_sdpa_forward", None, None, None, None, None, None, 0, B, T, d, h, 0.0, 0)
         ws = _lib.POOL.get(nbytes, q_.device, tag=("sdpa", B, T, d, h, train))
         out = torch.empty_like(q_)
-        _lib.launch("mmt_sdpa_forward", q_, k_, v_, m_, out, ws, nbytes, B, T, d, h, dropout_p, seed, key_lengths=kl_)
+        _lib.launch("mmt_sdpa_forward", q_, k_, v_, m_, out, ws, nbytes, B, T, d, h, dropout_p, seed, key_lengths=kl_, causal=causal)
         if _hold(ctx, ws):
-            ctx.cfg, ctx.mask, ctx.key_lengths = (B, T, d, h, dropout_p, seed), m_, kl_
+            ctx.cfg, ctx.mask, ctx.key_lengths, ctx.causal = (B, T, d, h, dropout_p, seed), m_, kl_, causal
         return out
 
     @staticmethod
@@ -302,25 +316,32 @@ class _SdpaFn(torch.autograd.Function):
         B, T, d, h, dropout_p, seed = ctx.cfg
         g = _f32c(dctx)
         dq, dk, dv = (torch.empty_like(g) for _ in range(3))
-        _lib.launch("mmt_sdpa_backward", g, ctx.mask, dq, dk, dv, ws, ws.numel(), B, T, d, h, dropout_p, seed, key_lengths=ctx.key_lengths)
+        _lib.launch("mmt_sdpa_backward", g, ctx.mask, dq, dk, dv, ws, ws.numel(), B, T, d, h, dropout_p, seed, key_lengths=ctx.key_lengths,
+                    causal=ctx.causal)
         _lib.POOL.put(ws)
-        return dq, dk, dv, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
 
 
-def sdpa(q, k, v, mask, h, dropout_p=0.0, seed=0, key_lengths=None):
+def sdpa(q, k, v, mask, h, dropout_p=0.0, seed=0, key_lengths=None, causal=False):
     """q,k,v: (B,T,d) with head i in columns [i*d/h,(i+1)*d/h); mask (B,T,1) blanks query rows; -> (B,T,d).
     dropout_p / seed: train-mode dropout on the probabilities (transformer/MFT/multiTransformer.py:32-33).
     key_lengths: int32 (B,) (``key_lengths(mask)``): sequence b attends keys < key_lengths[b] only — later keys get probability 0 and
-    dk = dv = 0, a blanked query row is uniform over the visible keys; values outside [1, T] are clamped.  None: every key is attended."""
-    return _SdpaFn.apply(q, k, v, mask, int(h), float(dropout_p), int(seed), key_lengths)
+    dk = dv = 0, a blanked query row is uniform over the visible keys; values outside [1, T] are clamped.  None: every key is attended.
+    causal: query window t attends keys 0 .. t of its sequence only — later keys get probability exactly 0 and no dk, dv from that query,
+    a blanked query row t is uniform over its t + 1 visible keys, row 0 attends one key.  Dropout bits are drawn as without the flag.
+    Not combined with key_lengths (ValueError before any launch): causal attention already keeps a valid window of a prefix-masked
+    batch from the padding behind its sequence, since t < len means every visible key is < len."""
+    return _SdpaFn.apply(q, k, v, mask, int(h), float(dropout_p), int(seed), key_lengths, causal)
 
 
-def attn_probs(q, k, mask, h, dropout_p=0.0, seed=0, key_lengths=None):
+def attn_probs(q, k, mask, h, dropout_p=0.0, seed=0, key_lengths=None, causal=False):
     """The probabilities ``sdpa(q, k, v, mask, h, dropout_p, seed)`` uses, materialised: (B,h,T,T) fp32, [b][head][query][key]
     (transformer/MFT/multiTransformer.py:22-34, the reference's ``self.attn`` of :59).  Same operand rounding as the attention core; in
     train mode the same keep decisions for the same seed, dropped = 0 and kept = P/(1-p).  A blanked query row is exactly 1/T.
     key_lengths: as for ``sdpa``; columns >= key_lengths[b] are exact zeros and a blanked query row is 1/key_lengths[b] on the others.
+    causal: as for ``sdpa``; entries above the diagonal are exact zeros and a blanked query row t is 1/(t+1) on columns 0 .. t.
     No autograd graph: the reference never differentiates the map."""
+    causal = _check_causal("attn_probs", key_lengths, causal)
     _lib.require_hip(q, k, mask)
     _lib.load()
     q_, k_, m_ = _f32c(q), _f32c(k), _f32c(mask)
@@ -334,7 +355,7 @@ def attn_probs(q, k, mask, h, dropout_p=0.0, seed=0, key_lengths=None):
     if h <= 0 or d % h or d // h > 64 or T > 4096:         # refused by the library before anything as large as the map is allocated
         _lib.launch("mmt_attn_probs_forward", None, None, None, None, B, T, d, h, 0.0, 0)
     out = torch.empty((B, h, T, T), dtype=torch.float32, device=q_.device)
-    _lib.launch("mmt_attn_probs_forward", q_, k_, m_, out, B, T, d, h, float(dropout_p), int(seed), key_lengths=kl_)
+    _lib.launch("mmt_attn_probs_forward", q_, k_, m_, out, B, T, d, h, float(dropout_p), int(seed), key_lengths=kl_, causal=causal)
     return out
 
 

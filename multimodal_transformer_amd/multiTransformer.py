@@ -14,6 +14,9 @@ Deviations, all documented in DESIGN.md:
   * ``mask_padded_keys(model)`` / ``MultiHeadedAttention.mask_keys = True`` (off by default, no counterpart in the reference):
     the padding mask then masks KEYS too, so a sequence attends only its own windows and its output no longer depends on the
     batch it is padded into.  Results then differ from the reference's by design.
+  * ``causal_attention(model)`` / ``MultiHeadedAttention.causal = True`` (off by default, no counterpart in the reference): window t
+    attends windows 0 .. t only, so the model can be run and trained as an online predictor.  Results then differ from the
+    reference's by design.
   * train-mode dropout draws from a counter-based generator inside the kernels, not from torch's
     global generator: training-mode parity with the reference is statistical, eval-mode is numerical.
 """
@@ -109,10 +112,16 @@ class MultiHeadedAttention(nn.Module):
     keys in front of its key length, ``1 +`` the index of the last non-zero mask entry of its row (``functional.key_lengths``): the
     padded windows behind a sequence get probability exactly 0 and no gradient as keys or values.  The reference (:29-31) blanks
     query rows only, so every window also attends its batch's padding; this flag removes that dependence on the batch.  Holes
-    inside the prefix stay attended.  ``keep_attn`` then shows the zeros."""
+    inside the prefix stay attended.  ``keep_attn`` then shows the zeros.
+
+    ``causal`` (a class attribute, off; ``causal_attention`` sets it per instance): window t attends windows 0 .. t of its sequence only;
+    later windows get probability exactly 0 and no gradient from that query (the reference, :27-31, lets every window attend the whole
+    batch row).  ``keep_attn`` then shows the zeros above the diagonal.  Not combined with ``mask_keys`` (ValueError at the call): a valid
+    window t < len sees keys <= t < len only, so causal attention already keeps it from the padding behind its sequence."""
 
     keep_attn = False
     mask_keys = False
+    causal = False
 
     def __init__(self, h, d_model, dropout=0.1):
         super().__init__()
@@ -123,7 +132,16 @@ class MultiHeadedAttention(nn.Module):
         self.attn = None
         self.dropout = nn.Dropout(p=dropout)
 
+    def attention_mode(self):
+        """(mask_keys, causal) of this layer; both set raises ValueError, before any launch."""
+        if self.mask_keys and self.causal:
+            raise ValueError("MultiHeadedAttention: mask_keys and causal are both set and cannot be combined: a valid window t < len of a "
+                             "prefix-masked batch sees keys <= t < len only, so causal attention already keeps it from the padding "
+                             "behind its sequence (mask_padded_keys(model, False))")
+        return self.mask_keys, self.causal
+
     def forward(self, query, key, value, mask=None):
+        mask_keys, causal = self.attention_mode()
         p = float(self.dropout.p) if self.training else 0.0
         B = query.size(0)
         q, k, v = (F_hip.linear(x, l.weight, l.bias) for l, x in zip(self.linears, (query, key, value)))
@@ -133,9 +151,9 @@ class MultiHeadedAttention(nn.Module):
                 raise NotImplementedError("only the reference's query-row mask of shape (B,T,1) is supported")
             m = mask.reshape(B, -1, 1)
         seed = _lib.next_dropout_seed(q.device, 3) if p > 0.0 else 0
-        kl = F_hip.key_lengths(m) if self.mask_keys and m is not None else None      # derived once, serves both kernels
-        ctx = F_hip.sdpa(q, k, v, m, self.h, dropout_p=p, seed=seed, key_lengths=kl)
-        self.attn = F_hip.attn_probs(q, k, m, self.h, dropout_p=p, seed=seed, key_lengths=kl) if self.keep_attn else None
+        kl = F_hip.key_lengths(m) if mask_keys and m is not None else None      # derived once, serves both kernels
+        ctx = F_hip.sdpa(q, k, v, m, self.h, dropout_p=p, seed=seed, key_lengths=kl, causal=causal)
+        self.attn = F_hip.attn_probs(q, k, m, self.h, dropout_p=p, seed=seed, key_lengths=kl, causal=causal) if self.keep_attn else None
         return F_hip.linear(ctx, self.linears[3].weight, self.linears[3].bias)
 
 
@@ -169,6 +187,25 @@ def mask_padded_keys(module, on=True):
     for name, m in module.named_modules():
         if isinstance(m, MultiHeadedAttention):
             m.mask_keys = bool(on)
+            found[name] = m
+    return found
+
+
+def causal_attention(module, on=True):
+    """Set ``causal`` on every MultiHeadedAttention below ``module`` (the SFT / MFT / B2 models, every modality's stack of
+    MultiTransformer, the MultiCNNTransformer wrappers) -> {qualified name: module}.  From the next forward on window t attends
+    windows 0 .. t of its sequence only, in every layer, forward and backward: every other part of these models already runs forward in
+    time (window encoder, LayerNorm, FFN and residuals are per window), so the model's output at window t no longer depends on later
+    windows.
+
+    An Encoder keeps running as the fused stack; only layers that disagree about the flag make it run layer by layer.  Outputs then
+    differ from the reference's, whose windows attend the whole recording — by design.  Not combined with ``mask_padded_keys`` (the
+    next forward raises ValueError; causal attention already keeps a valid window from its batch's padding).
+    ``causal_attention(module, False)`` restores the reference's semantics and the plain kernels."""
+    found = {}
+    for name, m in module.named_modules():
+        if isinstance(m, MultiHeadedAttention):
+            m.causal = bool(on)
             found[name] = m
     return found
 
@@ -265,6 +302,8 @@ class Encoder(nn.Module):
             return False
         if any(l.self_attn.mask_keys != l0.self_attn.mask_keys for l in self.layers):      # one set of key lengths serves the whole stack
             return False
+        if any(l.self_attn.causal != l0.self_attn.causal for l in self.layers):            # and one attention mode
+            return False
         h, f = l0.self_attn.h, l0.feed_forward.w_1.weight.shape[0]
         p = l0.sublayer[0].dropout.p
         for l in self.layers:
@@ -287,6 +326,7 @@ class Encoder(nn.Module):
                 x = layer(x, mask)
             return self.norm(x)
         l0 = self.layers[0]
+        mask_keys, causal = l0.self_attn.attention_mode()      # the layers agree (_fusable); both set: ValueError before any launch
         for l in self.layers:                    # the fused stack forms no map: one kept by an earlier layer-by-layer call is stale
             if l.self_attn.attn is not None:
                 l.self_attn.attn = None
@@ -294,10 +334,11 @@ class Encoder(nn.Module):
         k = self._sub_batch_streams(x)
         seed = [_lib.next_dropout_seed(x.device, 1, holder=self, index=i) for i in range(k)] if p > 0.0 else 0
         ps = self.flat_parameters()
-        kl = F_hip.key_lengths(mask) if l0.self_attn.mask_keys else None       # mask_padded_keys: derived once per call, for every layer
+        kl = F_hip.key_lengths(mask) if mask_keys else None                    # mask_padded_keys: derived once per call, for every layer
         return F_hip.encoder_stack_params(x, mask, ps, l0.self_attn.h, l0.feed_forward.w_1.weight.shape[0],
                                           len(self.layers), eps=self.norm.eps, dropout_p=p, seed=seed,
-                                          flat=self._flat_storage(ps) if x.is_cuda else None, nsplit=k, key_lengths=kl)
+                                          flat=self._flat_storage(ps) if x.is_cuda else None, nsplit=k, key_lengths=kl,
+                                          causal=causal)
 
     sub_batch_streams = 1        # set to 2: the batch runs as two halves on two HIP streams (functional._SPLIT_STREAMS); opt-in
     sub_batch_min_windows = 8192
