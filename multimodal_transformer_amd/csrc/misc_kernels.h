@@ -113,6 +113,66 @@ __device__ __forceinline__ void encoder_prep_block(const float* __restrict__ par
         W[idx] = (bf16)v;
     }
 }
+// The same at a fixed shape (rowgemm.h ShapeWidths) whose heads need no padding (DKP = d_k) and whose widths are multiples of 64: the
+// prepared block is then the six source matrices Wq, Wk, Wv, Wo (D x D), W1 (F x D), W2 (D x F), each cast as it lies and cast
+// transposed, nothing zero-filled.  A workgroup of 256 threads takes a [32 rows][64 columns] tile of one source matrix: every thread
+// reads 8 consecutive fp32 (full 256-byte rows), stores them as 16 bytes of the plain form and parks them in an LDS tile, from which
+// it then gathers 8 consecutive elements of one ROW of the transposed form (16-byte stores again).  Every index is a shift or a
+// compile-time product.  Blocks [0, tiles()) are the tiles, block tiles() the layer's padded biases.  Same values as encoder_prep_block.
+template <int SHAPE> struct PrepShape {
+    using W = ShapeWidths<SHAPE>;
+    static constexpr int D = W::D, F = W::F, NQ = W::NQ;
+    static_assert(SHAPE == 0 || (W::HD == D && NQ == 3 * D && D % 64 == 0 && F % 64 == 0), "fixed-shape preparation: no head padding, widths in 64s");
+    static constexpr int TQ = (D / 32) * (D / 64), T1 = (F / 32) * (D / 64), T2 = (D / 32) * (F / 64);   // tiles of a D x D matrix, of W1, of W2
+    static constexpr int tiles() { return 4 * TQ + T1 + T2; }
+    static constexpr int blocks() { return tiles() + 1; }
+};
+template <int SHAPE>
+__device__ __forceinline__ void encoder_prep_shape_block(const float* __restrict__ params, bf16* __restrict__ wprep, float* __restrict__ bprep,
+                                                         const LayerLayout& L, int layer, int bx, float* tile) {
+    using S = PrepShape<SHAPE>;
+    constexpr int D = S::D, F = S::F, NQ = S::NQ, LDT = 65;
+    const float* P = params + (size_t)layer * L.stride();
+    bf16* Wp = wprep + (size_t)layer * L.pstride();
+    const int tid = threadIdx.x;
+    if (bx >= S::tiles()) {                      // padded fp32 biases: [bq bk bv | bo | b1 | b2], nothing to pad at this shape
+        float* Bp = bprep + (size_t)layer * L.qstride();
+        for (int i = tid; i < NQ + 2 * D + F; i += blockDim.x) {
+            size_t o;
+            if (i < NQ) o = L.ob(i / D) + (size_t)(i % D);
+            else if (i < NQ + D) o = L.ob(3) + (size_t)(i - NQ);
+            else if (i < NQ + D + F) o = L.ob1() + (size_t)(i - NQ - D);
+            else o = L.ob2() + (size_t)(i - NQ - D - F);
+            Bp[i] = P[o];
+        }
+        return;
+    }
+    // tile -> (source matrix [R][C], its plain and transposed destinations)
+    const float* src; bf16 *plain, *trans; int C, ldt, t = bx;
+    if (t < 4 * S::TQ) {
+        const int wi = t / S::TQ; t -= wi * S::TQ; C = D;
+        src = P + L.oW(wi);
+        if (wi < 3) { plain = Wp + L.pWqkv() + (size_t)wi * D * D; trans = Wp + L.pWqkvT() + wi * D; ldt = NQ; }
+        else { plain = Wp + L.pWo(); trans = Wp + L.pWoT(); ldt = D; }
+    } else if (t < 4 * S::TQ + S::T1) { t -= 4 * S::TQ; C = D; src = P + L.oW1(); plain = Wp + L.pW1(); trans = Wp + L.pW1T(); ldt = F; }
+    else { t -= 4 * S::TQ + S::T1; C = F; src = P + L.oW2(); plain = Wp + L.pW2(); trans = Wp + L.pW2T(); ldt = D; }
+    const int tc = C / 64, r0 = (t / tc) * 32, c0 = (t % tc) * 64;
+    {   const int row = tid >> 3, seg = (tid & 7) * 8;
+        const float* s = src + (size_t)(r0 + row) * C + c0 + seg;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(s), b = *reinterpret_cast<const f32x4*>(s + 4);
+        bf16x8 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { o[i] = (bf16)a[i]; o[4 + i] = (bf16)b[i]; tile[row * LDT + seg + i] = a[i]; tile[row * LDT + seg + 4 + i] = b[i]; }
+        *reinterpret_cast<bf16x8*>(plain + (size_t)(r0 + row) * C + c0 + seg) = o;
+    }
+    __syncthreads();
+    {   const int col = tid >> 2, rseg = (tid & 3) * 8;
+        bf16x8 o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = (bf16)tile[(rseg + i) * LDT + col];
+        *reinterpret_cast<bf16x8*>(trans + (size_t)(c0 + col) * ldt + r0 + rseg) = o;
+    }
+}
 // grid = (blocks, n_layers): eval mode, and train mode where every layer's attention-dropout decisions ride in the row kernels
 // (rowgemm.h), so that this launch has nothing to draw and runs at the preparation's own registers, without LDS, one element per thread.
 __global__ void encoder_prep_kernel(const float* __restrict__ params, bf16* __restrict__ wprep,
@@ -129,6 +189,24 @@ __global__ void encoder_prep_seed_kernel(const float* __restrict__ params, bf16*
         return;
     }
     encoder_prep_block(params, wprep, bprep, L, blockIdx.y, blockIdx.x, nbx);
+}
+// The two at a fixed shape (encoder_prep_shape_block): grid = (PrepShape<SHAPE>::blocks() [+ 1], n_layers), 256 threads
+template <int SHAPE>
+__global__ __launch_bounds__(256) void encoder_prep_shape_kernel(const float* __restrict__ params, bf16* __restrict__ wprep,
+                                                                 float* __restrict__ bprep, LayerLayout L) {
+    __shared__ float tile[32 * 65];
+    encoder_prep_shape_block<SHAPE>(params, wprep, bprep, L, blockIdx.y, blockIdx.x, tile);
+}
+template <int SHAPE>
+__global__ __launch_bounds__(256) void encoder_prep_shape_seed_kernel(const float* __restrict__ params, bf16* __restrict__ wprep,
+                                                                      float* __restrict__ bprep, LayerLayout L, uint64_t* __restrict__ seed_state,
+                                                                      uint64_t* __restrict__ seedblock, int nstreams) {
+    __shared__ float tile[32 * 65];
+    if ((int)blockIdx.x == (int)gridDim.x - 1) {
+        if (blockIdx.y == 0) seed_advance_block(seed_state, seedblock, 0, nstreams);
+        return;
+    }
+    encoder_prep_shape_block<SHAPE>(params, wprep, bprep, L, blockIdx.y, blockIdx.x, tile);
 }
 // Train mode where the first launch draws decisions (every shape but the d_model = 128 fixed one, and MMT_NO_MASK_RIDE /
 // MMT_NO_CHAIN4): weight preparation and the dropout-bit generator are independent, so they share ONE launch (grid.y = layer): the first
@@ -251,54 +329,7 @@ __global__ __launch_bounds__(MMT_THREADS) void layernorm_bwd_kernel(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* Fs = reinterpret_cast<float*>(smem);            // [32][DP+4]  dy
     float* Gs = Fs + 32 * (DP + 4);                        // [32][DP+4]  dy * xhat
-    const int ld = DP + 4;
-    const int row = threadIdx.x >> 3, j = threadIdx.x & 7, m = blockIdx.x * 32 + row;
-    const bool ok = m < M;
-    float mean = 0.f, rstd = 1.f;
-    if (ok) { mean = stats[2 * (size_t)m]; rstd = stats[2 * (size_t)m + 1]; }
-    float s1 = 0.f, s2 = 0.f;
-    for (int c = j * 4; c < DP; c += 32) {
-        f32x4 g = {0.f, 0.f, 0.f, 0.f}, gx = g;
-        if (ok && c < d) {
-            g = *reinterpret_cast<const f32x4*>(dy + (size_t)m * d + c);
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (size_t)m * d + c);
-            const f32x4 av = *reinterpret_cast<const f32x4*>(a + c);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float xh = (xv[i] - mean) * rstd;
-                gx[i] = g[i] * xh;
-                s1 += g[i] * av[i];
-                s2 += g[i] * av[i] * xh;
-            }
-        }
-        *reinterpret_cast<f32x4*>(Fs + row * ld + c) = g;
-        *reinterpret_cast<f32x4*>(Gs + row * ld + c) = gx;
-    }
-    s1 += __shfl_xor(s1, 1); s1 += __shfl_xor(s1, 2); s1 += __shfl_xor(s1, 4);
-    s2 += __shfl_xor(s2, 1); s2 += __shfl_xor(s2, 2); s2 += __shfl_xor(s2, 4);
-    if (ok) {
-        const float sigma = 1.0f / rstd - eps;
-        const float k1 = s1 / (float)d, k2 = s2 / ((float)(d - 1) * sigma);
-        for (int c = j * 4; c < d; c += 32) {
-            const f32x4 g = *reinterpret_cast<const f32x4*>(Fs + row * ld + c);
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (size_t)m * d + c);
-            const f32x4 av = *reinterpret_cast<const f32x4*>(a + c);
-            f32x4 o;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] = rstd * (g[i] * av[i] - k1) - k2 * ((xv[i] - mean) * rstd);
-            *reinterpret_cast<f32x4*>(dx + (size_t)m * d + c) = o;
-        }
-    }
-    __syncthreads();
-    if (colpart) {
-        for (int c = threadIdx.x; c < DP; c += MMT_THREADS) {
-            float sb = 0.f, sa = 0.f;
-#pragma unroll 8
-            for (int r = 0; r < 32; ++r) { sb += Fs[r * ld + c]; sa += Gs[r * ld + c]; }
-            colpart[(size_t)blockIdx.x * 2 * DP + c] = sb;
-            colpart[(size_t)blockIdx.x * 2 * DP + DP + c] = sa;
-        }
-    }
+    layernorm_bwd_rows<true, false>(dy, x, a, stats, eps, dx, colpart, M, d, DP, Fs, Gs, DP + 4, nullptr, 0, DropCfg{});     // rowgemm.h
 }
 
 // ---- weight gradients ---------------------------------------------------------------------------

@@ -750,7 +750,8 @@ __global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC(4)) void rowgemm_kernel(c
 // ---- chained stages ------------------------------------------------------------------------------
 // final LayerNorm of the stack applied to the last stage's output tile while it is still in LDS (y == nullptr: none)
 struct LnOut { const float* a; const float* b; float eps; float* y; float* stats; int d; };
-struct RowChain3 { RowGemmParams a, b, c; int lda_max, ldf, ldx, lda2; LnOut ln; };   // LDS geometry: chain_kind_geom, filled in by the host's launch
+struct LnBwdHead { const float* dy; const float* x; const float* a; const float* stats; float* colpart; float eps; };   // (layernorm_bwd_rows)
+struct RowChain3 { RowGemmParams a, b, c; int lda_max, ldf, ldx, lda2; LnOut ln; LnBwdHead head; };   // LDS geometry: chain_kind_geom, filled in by the host's launch
 // MaskRide: one layer's attention-dropout decisions, drawn by extra workgroups of a d_model = 128 forward launch (workgroups >=
 // chain_wgs; gen_wgs == 0: none): the next layer's in encoder_post_attn_fwd4_kernel<*, 128>, layer 0's in encoder_ln1_qkv128_kernel
 struct MaskRide { MaskGenLayer g; int chain_wgs, gen_wgs, gen_waves; };
@@ -1012,21 +1013,126 @@ __global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC(4)) void encoder_bwd_qkv_
     rowgemm_stage<EPI_LNBWD, false, ASRC_GLOBAL, 0, DEVSEED, false>(q, S::carve<STAGE_BWD_QKV>(smem));
 }
 
+// The backward of a LayerNorm alone (the stack's final norm; the stand-alone module) on one tile of 32 rows, by the first 256 threads of
+// the workgroup, 8 per row: dx = LNbwd(dy) -> global, and the tile's column sums for d ln_b (sum dy) and d ln_a (sum dy * x-hat) ->
+// colpart[tile][2][DP].  Fs, Gs: fp32 [32][ld] of LDS.  Two callers share this body, so that both give the same bits: layernorm_bwd_kernel
+// (misc_kernels.h; ALL: its workgroup has no other threads) and, KEEP, the head of the last layer's encoder_pre_attn_bwd_kernel, which
+// also leaves bf16(drop'(dx)) — zero in the pad columns and in rows >= M — in As (row stride lda) as the A tile of the stage behind it.
+template <bool ALL, bool KEEP>
+__device__ __forceinline__ void layernorm_bwd_rows(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ a,
+                                                   const float* __restrict__ stats, float eps, float* __restrict__ dx,
+                                                   float* __restrict__ colpart, int M, int d, int DP, float* Fs, float* Gs, int ld,
+                                                   bf16* As, int lda, const DropCfg& keep_drop) {
+    const bool mine = ALL || threadIdx.x < 256;
+    const int row = (threadIdx.x >> 3) & 31, j = threadIdx.x & 7, m = blockIdx.x * 32 + row;
+    const bool ok = m < M;
+    if (mine) {
+        float mean = 0.f, rstd = 1.f;
+        if (ok) { mean = stats[2 * (size_t)m]; rstd = stats[2 * (size_t)m + 1]; }
+        float s1 = 0.f, s2 = 0.f;
+        for (int c = j * 4; c < DP; c += 32) {
+            f32x4 g = {0.f, 0.f, 0.f, 0.f}, gx = g;
+            if (ok && c < d) {
+                g = *reinterpret_cast<const f32x4*>(dy + (size_t)m * d + c);
+                const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (size_t)m * d + c);
+                const f32x4 av = *reinterpret_cast<const f32x4*>(a + c);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float xh = (xv[i] - mean) * rstd;
+                    gx[i] = g[i] * xh;
+                    s1 += g[i] * av[i];
+                    s2 += g[i] * av[i] * xh;
+                }
+            }
+            *reinterpret_cast<f32x4*>(Fs + row * ld + c) = g;
+            *reinterpret_cast<f32x4*>(Gs + row * ld + c) = gx;
+        }
+        s1 += __shfl_xor(s1, 1); s1 += __shfl_xor(s1, 2); s1 += __shfl_xor(s1, 4);
+        s2 += __shfl_xor(s2, 1); s2 += __shfl_xor(s2, 2); s2 += __shfl_xor(s2, 4);
+        if (ok || KEEP) {
+            const float sigma = 1.0f / rstd - eps;
+            const float k1 = s1 / (float)d, k2 = s2 / ((float)(d - 1) * sigma);
+            for (int c = j * 4; c < (KEEP ? DP : d); c += 32) {
+                f32x4 o = {0.f, 0.f, 0.f, 0.f};
+                if (ok && c < d) {
+                    const f32x4 g = *reinterpret_cast<const f32x4*>(Fs + row * ld + c);
+                    const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (size_t)m * d + c);
+                    const f32x4 av = *reinterpret_cast<const f32x4*>(a + c);
+                    // rstd * (g a - k1) - k2 x-hat with its two fused multiply-adds spelled out: left to fp-contract, hipcc fuses this
+                    // expression differently in the two callers (in the chain it kept g a - k1 unfused for half the lanes' elements
+                    // and fused k2 x-hat instead), and dx differed in its last bit.  This is the form layernorm_bwd_kernel always had.
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float t = __builtin_fmaf(g[i], av[i], -k1), u = k2 * ((xv[i] - mean) * rstd);
+                        o[i] = __builtin_fmaf(rstd, t, -u);
+                    }
+                    *reinterpret_cast<f32x4*>(dx + (size_t)m * d + c) = o;
+                }
+                if (KEEP) {
+                    if (keep_drop.thr16 && ok && c < d) {
+#pragma unroll
+                        for (int i = 0; i < 4; i += 2) {
+                            const uint32_t w = drop_pair(keep_drop, (uint64_t)m * DP + c + i);
+                            o[i] = drop_lo(keep_drop, w, o[i]); o[i + 1] = drop_hi(keep_drop, w, o[i + 1]);
+                        }
+                    }
+                    bf16x4 o16;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) o16[i] = (bf16)o[i];
+                    *reinterpret_cast<bf16x4*>(As + row * lda + c) = o16;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (colpart && mine) {
+        for (int c = threadIdx.x; c < DP; c += 256) {
+            float sb = 0.f, sa = 0.f;
+#pragma unroll 8
+            for (int r = 0; r < 32; ++r) { sb += Fs[r * ld + c]; sa += Gs[r * ld + c]; }
+            colpart[(size_t)blockIdx.x * 2 * DP + c] = sb;
+            colpart[(size_t)blockIdx.x * 2 * DP + DP + c] = sa;
+        }
+    }
+}
+
 // Backward, from the layer-output gradient dx2 down to the attention core's operands:
 //     dh  = (drop'(dx2) W2) * relu'(hid) * drop'          (dh kept in LDS as the next A tile; dx2^T, dh^T emitted for dW)
 //     dx1 = dx2 + LN2bwd(dh W1)                            (drop'(dx1) kept in LDS as the next A tile)
 //     dO  = drop'(dx1) Wo  -> fragment layouts + delta     (dx1^T emitted for dW)
 // WIDE: the d_model > 128 variant of the LayerNorm-backward stages; a fixed shape exists as one of the two only (ChainShape::WIDE).
-template <bool WIDE, bool DEVSEED, int SHAPE = 0>
-__global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC(4)) void encoder_pre_attn_bwd_kernel(const RowChain3 ch) {
+// HEAD (the last layer's launch, not WIDE): the stack's final LayerNorm runs backward first, on the same 32 windows (ch.head;
+// layernorm_bwd_rows, the arithmetic of layernorm_bwd_kernel): dx2 goes to global memory in fp32 (ch.a.A: the LayerNorm-2 backward stage
+// reads it back as its residual gradient, as in the boundary kernel below) and, dropped and rounded to bf16, straight into the A tile.
+template <bool WIDE, bool DEVSEED, int SHAPE, bool HEAD>
+__device__ __forceinline__ void encoder_pre_attn_bwd_body(const RowChain3& ch, char* smem) {
     using S = ChainShape<SHAPE>;
     static_assert(SHAPE == 0 || WIDE == S::WIDE, "a fixed shape's backward exists as its own WIDE / not-WIDE instance only");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+    static_assert(!HEAD || (SHAPE == 128 && !WIDE && MMT_ROWS == 32 && MMT_RTHREADS >= 256), "the head: the d_model = 128 fixed shape (second fp32 tile, 32-row tiles); the generic kernels' launch list is pinned");
     warm_weights(ch.b.W, ch.b.NP, ch.b.KP); warm_weights(ch.c.W, ch.c.NP, ch.c.KP);
     const RowSmem sm = SHAPE ? S::template carve<CHAIN_BWD>(smem) : rowchain_carve(smem, ch, !WIDE);
+    if constexpr (HEAD) {
+        const RowGemmParams pa = S::bwd_relu(role_bwd_relu(ch.a));
+        const DropCfg keep = DEVSEED ? drop_resolve(pa.a_drop, pa.seedword) : pa.a_drop;
+        layernorm_bwd_rows<MMT_RTHREADS == 256, true>(ch.head.dy, ch.head.x, ch.head.a, ch.head.stats, ch.head.eps,
+                                                      const_cast<float*>(static_cast<const float*>(pa.A)), ch.head.colpart,
+                                                      pa.M, pa.K, pa.KP, sm.Fs, sm.Gs, sm.ldf, sm.As, pa.KP + 8, keep);
+        rowgemm_stage<EPI_PLAIN, false, ASRC_AS, KEEP_A2, DEVSEED>(pa, sm);
+    } else
     rowgemm_stage<EPI_PLAIN, false, ASRC_GLOBAL, KEEP_A2, DEVSEED>(S::bwd_relu(role_bwd_relu(ch.a)), sm);
     rowgemm_stage<EPI_LNBWD, false, ASRC_A2, KEEP_AS, DEVSEED, WIDE>(S::lnbwd_ffn(role_lnbwd(ch.b)), sm);      // dx1 -> global (fp32) and, as the next A tile, LDS (bf16)
     rowgemm_stage<EPI_FRAG, false, ASRC_AS, 0, false>(S::dO(role_dO(ch.c)), sm);
+}
+template <bool WIDE, bool DEVSEED, int SHAPE = 0>
+__global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC(4)) void encoder_pre_attn_bwd_kernel(const RowChain3 ch) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    encoder_pre_attn_bwd_body<WIDE, DEVSEED, SHAPE, false>(ch, smem);
+}
+// ... with the head (not WIDE), a kernel of its own
+template <bool DEVSEED, int SHAPE>
+__global__ __launch_bounds__(MMT_RTHREADS, MMT_ROW_OCC(4)) void encoder_pre_attn_bwd_head_kernel(const RowChain3 ch) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    encoder_pre_attn_bwd_body<false, DEVSEED, SHAPE, true>(ch, smem);
 }
 
 
