@@ -150,16 +150,22 @@ def require_hip(*tensors):
                                "(move the module and its inputs to a HIP device)" % t.device)
 
 
-def launch(name, *args, key_lengths=None, causal=False):
+def entry_name(name, keys=False, causal=False, devseed=False):
+    """The form of the C entry point ``name`` to call: ``name`` + {"", "_keys", "_causal"} + {"", "_devseed"} (include/mmt_hip.h)."""
+    if keys and causal:
+        raise ValueError("%s has no form with both key_lengths and causal=True" % name)
+    return name + ("_keys" if keys else "_causal" if causal else "") + ("_devseed" if devseed else "")
+
+
+def launch(name, *args, key_lengths=None, causal=False, devseed=False):
     """Call the C entry point ``name`` on the current stream (read now: StreamFork's ``torch.cuda.stream`` blocks rely on it).  A tensor
     goes as its data_ptr(), None as a null pointer, every other argument unchanged; a non-zero return code raises.
     ``key_lengths`` (an int32 (B,) device tensor): call the entry's ``_keys`` form, which takes that tensor behind the stream.
-    ``causal``: call the entry's ``_causal`` form, which takes the entry's own arguments (never with ``key_lengths``: functional.py refuses)."""
+    ``causal``: call the entry's ``_causal`` form, which takes the entry's own arguments (with ``key_lengths``: raises).
+    ``devseed``: call the device-seeded twin of that form (DeviceSeed), whose seed argument, if it takes one, is among ``args``."""
+    name = entry_name(name, key_lengths is not None, causal, devseed)
     argv = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args] + [torch.cuda.current_stream().cuda_stream]
-    if causal:
-        name = name[:-len("_devseed")] + "_causal_devseed" if name.endswith("_devseed") else name + "_causal"
     if key_lengths is not None:
-        name = name[:-len("_devseed")] + "_keys_devseed" if name.endswith("_devseed") else name + "_keys"
         argv.append(key_lengths.data_ptr())
     check(getattr(load(), name)(*argv))
 

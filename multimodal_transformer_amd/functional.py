@@ -45,12 +45,9 @@ def _launch_seeded(name, seed, *args, state_arg=True, key_lengths=None, causal=F
     """``name`` with the seed by value behind ``args``, or its twin ``name``_devseed with the DeviceSeed's state word there, which the
     launch reads and advances.  ``state_arg=False``: the twin takes no seed (the encoder backward finds it in its forward's workspace).
     ``key_lengths`` / ``causal``: the ``_keys`` / ``_causal`` form of either (_lib.launch)."""
-    if not isinstance(seed, _lib.DeviceSeed):
-        _lib.launch(name, *args, seed, key_lengths=key_lengths, causal=causal)
-    elif state_arg:
-        _lib.launch(name + "_devseed", *args, seed.state, key_lengths=key_lengths, causal=causal)
-    else:
-        _lib.launch(name + "_devseed", *args, key_lengths=key_lengths, causal=causal)
+    devseed = isinstance(seed, _lib.DeviceSeed)
+    tail = (seed,) if not devseed else (seed.state,) if state_arg else ()
+    _lib.launch(name, *args, *tail, key_lengths=key_lengths, causal=causal, devseed=devseed)
 
 
 # Key lengths: a padding mask that masks KEYS (opt-in; the reference blanks query rows only, transformer/MFT/multiTransformer.py:29-31).
@@ -898,30 +895,34 @@ def ar_combine(in_part, ar_w, mask, target=None, p_init=0.0, return_p=False):
 
 
 class _ConvPoolFn(torch.autograd.Function):
-    """out = max over positions of Conv1d(D -> F, kernel 2)(window) + bias — the reference's CNN.forward
-    (transformer/SFT/models.py:57-79).  x (N,W,D) is input data: no gradient flows to it."""
+    """out = max over positions of Conv1d(D -> F, kernel K)(window) + bias — the reference's CNN.forward
+    (transformer/SFT/models.py:57-79).  x (N,W,D) is input data: no gradient flows to it.  K = weight.shape[2]: 2 (the reference's
+    constant) runs the 2-tap kernels (mmt_convpool_*), every other 1 <= K <= 5 the K-tap kernels (csrc/convk.h, mmt_convpool_k_*).
+    ``op``: the public function called, for the messages; "conv_maxpool" takes K = 2 only."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, op):
         _lib.require_hip(x, weight, bias)
         if x.requires_grad:
-            raise NotImplementedError("conv_maxpool: the windows are input data; a gradient w.r.t. them is not implemented "
-                                      "(the reference never asks for one)")
+            raise NotImplementedError("%s: the windows are input data; a gradient w.r.t. them is not implemented "
+                                      "(the reference never asks for one)" % op)
         x_, w_, b_ = _f32c(x), _f32c(weight), _f32c(bias)
         N, W, D = x_.shape
-        F_ = w_.shape[0]
-        if w_.shape != (F_, D, 2):
-            raise NotImplementedError("conv_maxpool: weight must be (F, D, 2) = nn.Conv1d(D, F, kernel_size=2).weight, got %s"
-                                      % (tuple(w_.shape),))
-        nbytes = _lib.load().mmt_convpool_workspace_bytes(N, W, D, F_)
-        if nbytes == 0:
-            _lib.launch("mmt_convpool_forward", None, None, None, None, None, None, 0, N, W, D, F_)
+        k = "2" if op == "conv_maxpool" else "K"
+        if w_.dim() != 3 or w_.shape[1] != D or (k == "2" and w_.shape[2] != 2):
+            raise NotImplementedError("%s: weight must be (F, D, %s) = nn.Conv1d(D, F, kernel_size=%s).weight, got %s"
+                                      % (op, k, k, tuple(w_.shape)))
+        F_, K = w_.shape[0], w_.shape[2]
+        entry, dims = ("mmt_convpool", (N, W, D, F_)) if K == 2 else ("mmt_convpool_k", (N, W, D, F_, K))
+        nbytes = getattr(_lib.load(), entry + "_workspace_bytes")(*dims)
+        if nbytes == 0:             # refused: the launch with nothing to run raises the library's own message
+            _lib.launch(entry + "_forward", None, None, None, None, None, None, 0, *dims)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x_.device)
         out = torch.empty(N, F_, dtype=torch.float32, device=x_.device)
         arg = torch.empty(N, F_, dtype=torch.int32, device=x_.device)
-        _lib.launch("mmt_convpool_forward", x_, w_, b_, out, arg, ws, nbytes, N, W, D, F_)
+        _lib.launch(entry + "_forward", x_, w_, b_, out, arg, ws, nbytes, *dims)
         ctx.save_for_backward(x_, arg)
-        ctx.dims = (N, W, D, F_, nbytes)
+        ctx.call = (entry, dims, tuple(w_.shape), nbytes)
         ctx.mark_non_differentiable(arg)
         ctx.set_materialize_grads(False)        # no zeros tensor for the index output's "gradient" (that would be a library fill kernel)
         return out, arg
@@ -929,72 +930,28 @@ class _ConvPoolFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, _darg):
         x_, arg = ctx.saved_tensors
-        N, W, D, F_, nbytes = ctx.dims
+        entry, dims, wshape, nbytes = ctx.call
         if dout is None:
-            return None, None, None
+            return None, None, None, None
         g = _f32c(dout)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
-        dw, db = torch.empty(F_, D, 2, dtype=torch.float32, device=g.device), torch.empty(F_, dtype=torch.float32, device=g.device)
-        _lib.launch("mmt_convpool_backward", x_, g, arg, dw, db, ws, nbytes, N, W, D, F_)
-        return None, dw, db
+        dw, db = torch.empty(wshape, dtype=torch.float32, device=g.device), torch.empty(wshape[0], dtype=torch.float32, device=g.device)
+        _lib.launch(entry + "_backward", x_, g, arg, dw, db, ws, nbytes, *dims)
+        return None, dw, db, None
 
 
 def conv_maxpool(x, weight, bias):
     """x (N,W,D) windows, weight (F,D,2), bias (F) -> (out (N,F), argmax positions (N,F) int32)."""
-    return _ConvPoolFn.apply(x, weight, bias)
+    return _ConvPoolFn.apply(x, weight, bias, "conv_maxpool")
 
 
 CONV_K_MAX = 5      # csrc/convk.h CK_MAXK
 
 
-class _ConvPoolKFn(torch.autograd.Function):
-    """_ConvPoolFn with K = weight.shape[2] taps, 1 <= K <= 5, on the K-tap kernels (csrc/convk.h, mmt_convpool_k_*).  Same contract:
-    x (N,W,D) is input data, the index output is not differentiable."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        _lib.require_hip(x, weight, bias)
-        if x.requires_grad:
-            raise NotImplementedError("conv_maxpool_k: the windows are input data; a gradient w.r.t. them is not implemented "
-                                      "(the reference never asks for one)")
-        x_, w_, b_ = _f32c(x), _f32c(weight), _f32c(bias)
-        N, W, D = x_.shape
-        if w_.dim() != 3 or w_.shape[1] != D:
-            raise NotImplementedError("conv_maxpool_k: weight must be (F, D, K) = nn.Conv1d(D, F, kernel_size=K).weight, got %s"
-                                      % (tuple(w_.shape),))
-        F_, K = w_.shape[0], w_.shape[2]
-        nbytes = _lib.load().mmt_convpool_k_workspace_bytes(N, W, D, F_, K)
-        if nbytes == 0:             # refused: the launch with nothing to run raises the library's own message
-            _lib.launch("mmt_convpool_k_forward", None, None, None, None, None, None, 0, N, W, D, F_, K)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x_.device)
-        out = torch.empty(N, F_, dtype=torch.float32, device=x_.device)
-        arg = torch.empty(N, F_, dtype=torch.int32, device=x_.device)
-        _lib.launch("mmt_convpool_k_forward", x_, w_, b_, out, arg, ws, nbytes, N, W, D, F_, K)
-        ctx.save_for_backward(x_, arg)
-        ctx.dims = (N, W, D, F_, K, nbytes)
-        ctx.mark_non_differentiable(arg)
-        ctx.set_materialize_grads(False)
-        return out, arg
-
-    @staticmethod
-    def backward(ctx, dout, _darg):
-        x_, arg = ctx.saved_tensors
-        N, W, D, F_, K, nbytes = ctx.dims
-        if dout is None:
-            return None, None, None
-        g = _f32c(dout)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
-        dw, db = torch.empty(F_, D, K, dtype=torch.float32, device=g.device), torch.empty(F_, dtype=torch.float32, device=g.device)
-        _lib.launch("mmt_convpool_k_backward", x_, g, arg, dw, db, ws, nbytes, N, W, D, F_, K)
-        return None, dw, db
-
-
 def conv_maxpool_k(x, weight, bias):
     """x (N,W,D) windows, weight (F,D,K) with 1 <= K <= 5, bias (F) -> (out (N,F), argmax positions (N,F) int32 in [0, W-K]).
     K = 2 is ``conv_maxpool`` itself (the product has one 2-tap path); the other sizes run the K-tap kernels."""
-    if weight.dim() == 3 and weight.shape[2] == 2:
-        return _ConvPoolFn.apply(x, weight, bias)
-    return _ConvPoolKFn.apply(x, weight, bias)
+    return _ConvPoolFn.apply(x, weight, bias, "conv_maxpool_k")
 
 
 def _mem_scan_fwd(apre, chat, Wm, W2, b2, T, B, dropout_p, seed):

@@ -543,8 +543,8 @@ def lstm_fb_scan(gxc, w_p, W_hh, W1, b1, w2, b2, h0=None, c0=None, p_init=0.0, r
 
 # ------------------------------------------------------------------------------------------------ window encoder
 def conv_plan(N, W, D, F):
-    """What mmt_convpool_forward / _backward launch for (N, W, D, F): a mirror of carve_conv and of the forward's channel dispatch
-    (csrc/api.hip).  nsplit window splits of `wins` windows (the last one `last` windows), npairs window pairs in the fullest split,
+    """What mmt_convpool_forward / _backward launch for (N, W, D, F): a mirror of carve_conv at K = 2, ktap = false, and of the forward's
+    channel dispatch (csrc/api.hip).  nsplit window splits of `wins` windows (the last one `last` windows), npairs window pairs in the fullest split,
     nrt row tiles per window, one_rt the backward instance, fwd the forward launches as (CT, channel blocks, c_first)."""
     up = lambda a, m: -(-a // m) * m  # noqa: E731
     FPAD, DPB = up(F, 256), up(D, 128)

@@ -53,8 +53,8 @@ def conv_maxpool(x, w, b, arg=None, rounding=True):
 
 
 def conv_plan(N, W, D, F, K):
-    """What mmt_convpool_k_forward / _backward launch for (N, W, D, F, K): a mirror of carve_conv_k and of the forward's channel dispatch
-    (csrc/api.hip).  The backward's grid carries the tap, so `blocks` counts it; fwd lists the forward launches as (K, CT, channel
+    """What mmt_convpool_k_forward / _backward launch for (N, W, D, F, K): a mirror of carve_conv with ktap = true and of the forward's
+    channel dispatch (csrc/api.hip).  The backward's grid carries the tap, so `blocks` counts it; fwd lists the forward launches as (K, CT, channel
     blocks, c_first); one_rt is the backward instance (at most 32 conv positions)."""
     up = lambda a, m: -(-a // m) * m  # noqa: E731
     FPAD, DPB = up(F, 256), up(D, 128)

@@ -533,7 +533,7 @@ def test_window_encoder_without_rounding_is_the_oracle(drop):
         assert _rel(pa[k].grad, pb[k].grad) <= 1e-12, k
 
 
-# The plan of every conv case of tests/test_gpu_bf16_frontend.py, from reading carve_conv and mmt_convpool_forward (csrc/api.hip):
+# The plan of every conv case of tests/test_gpu_bf16_frontend.py, from reading carve_conv (K = 2, ktap = false) and mmt_convpool_forward (csrc/api.hip):
 # (wins, pairs in the fullest split, splits, windows of the last split, ONE_RT, row tiles, forward launches (CT, blocks, c_first))
 _PLANS = {
     (3001, 10, 88, 256): (6, 3, 501, 1, True, 1, [(4, 1, 0)]),
