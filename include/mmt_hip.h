@@ -8,10 +8,19 @@
  *   - every pointer is a DEVICE pointer unless named host_*; tensors are contiguous fp32 in the
  *     reference's own layouts: activations (B,T,d) row-major, mask (B,T,1) float {0,1} (a window is
  *     blanked where mask == 0, multiTransformer.py:30), nn.Linear weights (out,in);
- *   - the library allocates nothing: the caller passes a workspace of *_workspace_bytes() bytes that
- *     MUST be zero-filled when first created and may then be reused for calls of the same shape
- *     (pad regions are never written; saved-for-backward tensors live in it between a forward and its
- *     backward);
+ *   - the library allocates nothing: the caller passes a workspace of *_workspace_bytes() bytes, under
+ *     one of two contracts, named at each entry's workspace query:
+ *       "zero once": the workspace MUST be zero-filled when first created and may then be reused, without
+ *         clearing, by any later call of the same entry family and the same shape arguments, whatever
+ *         else differs (inputs, a NaN among them, mask, key lengths, plain / _keys / _causal form,
+ *         dropout probability, seed by value or device-resident).  Pad regions are never written, so
+ *         they stay zero; every other word a call reads it has written itself (or, in a backward, its
+ *         forward has: saved-for-backward tensors live in the workspace between the two).  This is the
+ *         contract of every entry that says nothing else;
+ *       "any contents": every word used is written first by a kernel of the same call, so the memory
+ *         may come uninitialised: mmt_lstm_scan_*, mmt_mfn_mem_scan_*, mmt_convpool_*,
+ *         mmt_convpool_k_* and mmt_local_attn_backward.
+ *     tests/test_gpu_workspace_state.py holds both, bit for bit;
  *   - all work is enqueued on `stream` (a hipStream_t); nothing synchronises, so calls are capturable
  *     into a hipGraph;
  *   - return 0 on success, non-zero MMT_E* on error with a message in mmt_last_error() (thread local).
@@ -58,6 +67,8 @@ int mmt_profile_collect(float* total_ms, int* launches);
  * followed by the stack's norm.{a_2,b_2}.  mmt_encoder_param_count() gives its length.
  * Eval-mode (dropout = identity) when dropout_p == 0; see mmt_encoder_forward's `dropout_p`, `seed`. */
 size_t mmt_encoder_param_count(int d, int f, int n_layers);
+/* workspace: zero once; reusable for the same (B, T, d, h, f, n_layers) and the same kind (train / eval, below) by every form of the
+ * entry (plain, _keys, _causal, _devseed). */
 size_t mmt_encoder_workspace_bytes(int B, int T, int d, int h, int f, int n_layers);
 /* ... for calls with dropout_p == 0 only (eval mode): without the attention-dropout bit masks (2 x n_layers x B*h x Tp^2/4 bytes, the
  * last region of the full workspace: an eval workspace is a prefix of a train one).  A forward and its backward take the same kind. */
@@ -109,6 +120,7 @@ int mmt_layernorm_backward(const float* dy, const float* x, const float* a_2, co
  * dropout_p, seed: the reference's nn.Dropout on p_attn (:32-33) in train mode (0 = eval / dropout=None); the decisions are
  * drawn by the forward into the workspace and re-read by the backward (same dropout_p and seed must be passed); they are
  * dropout stream 0 of mmt_debug_dropout_mask. */
+/* workspace: zero once; reusable for the same (B, T, d, h) and the same kind (train / eval) by the plain, _keys and _causal forms. */
 size_t mmt_sdpa_workspace_bytes(int B, int T, int d, int h);
 size_t mmt_sdpa_workspace_bytes_eval(int B, int T, int d, int h);      /* dropout_p == 0 calls: without the dropout bit masks */
 int mmt_sdpa_forward(const float* q, const float* k, const float* v, const float* mask, float* ctx,
@@ -215,6 +227,7 @@ int mmt_encoder_backward_causal_devseed(const float* dy, const float* x, const f
  * Replaces nn.Linear (+ F.relu) call sites of the path: PositionwiseFeedForward (:15-20), the four
  * attention projections (:43,55,65), embeds and read-out MLPs (:270,296,340-342,400-402).
  * x (M,K), W (N,K), b (N) or NULL, y (M,N), all fp32; act: 0 none, 1 ReLU, 2 tanh, 3 sigmoid; rowscale (M) or NULL. */
+/* workspace: zero once; reusable for the same (M, K, N), with or without dropout, rowscale and bias, for any act. */
 size_t mmt_linear_workspace_bytes(int M, int K, int N);
 int mmt_linear_forward(const float* x, const float* W, const float* b, const float* rowscale, float* y,
                        void* workspace, size_t workspace_bytes, int M, int K, int N, int act, mmt_stream_t stream);
@@ -283,6 +296,8 @@ int mmt_error_accumulate(const uint32_t* word, uint32_t* accum, mmt_stream_t str
  * if a scan for H > 128 (four workgroups per sequence exchanging h through memory) timed out waiting for a partner
  * workgroup — e.g. another process held the CUs.  The outputs are then INVALID.  Nothing synchronises here: read the word
  * after the stream has drained (the Python wrapper does, functional.check_device_errors()). */
+/* workspace: any contents (every word used is written first; the error block and the exchange granules are cleared by a kernel of
+ * the call). */
 size_t mmt_lstm_scan_workspace_bytes(int H);
 int mmt_lstm_scan_forward(const float* gx, const float* W_rec, const float* h0, const float* c0,
                           float* h_all, float* c_all, float* acts, void* workspace, size_t workspace_bytes,
@@ -305,6 +320,8 @@ int mmt_lstm_scan_backward(const float* dh_all, const float* dc_all, const float
  * Limits: 2 <= L <= 4, H % 4 == 0, H <= 128, B <= 512; anything else returns MMT_EINVAL (the workspace query returns 0) with the limit
  * named in mmt_last_error().  One workgroup scans its sequences alone: no device error word.  bf16 MFMA operands, fp32 accumulation
  * and cell state, as mmt_lstm_scan_*. */
+/* workspace: zero once; reusable for the same (H, L) with any T and B, by the forward and the backward (each prepares its own weight
+ * fragments; nothing is kept in it between the two). */
 size_t mmt_lstm_stack_workspace_bytes(int H, int L);
 int mmt_lstm_stack_scan_forward(const float* gx0, const float* P, const float* bias, const float* h0, const float* c0,
                                 float* h_all, float* c_all, float* acts, void* workspace, size_t workspace_bytes,
@@ -326,6 +343,7 @@ int mmt_lstm_stack_scan_backward(const float* dh_top, const float* P, const floa
  * Limits: H % 4 == 0, 4 <= H <= 128, E % 4 == 0, 4 <= E <= 128, B <= 512: MMT_EUNSUPPORTED with the limit named in mmt_last_error()
  * (the workspace query returns 0); T or B < 1, null pointers: MMT_EINVAL.  One workgroup scans its sequences alone: no device error
  * word.  bf16 MFMA operands (h, W_hh, W1; backward: dG, du), everything else and every sum fp32. */
+/* workspace: zero once; reusable for the same (H, E) with any T and B, by the forward and the backward (as the stacked scan's). */
 size_t mmt_lstm_fb_scan_workspace_bytes(int H, int E);
 int mmt_lstm_fb_scan_forward(const float* gxc, const float* w_p, const float* W_hh, const float* W1, const float* b1,
                              const float* w2, const float* b2, const float* h0, const float* c0, float p_init,
@@ -382,6 +400,7 @@ int mmt_ar_combine_backward(const float* dout, const float* mask, const float* h
  * gamma{1,2}_fc2; chat (T,B,128) = cHat.  Outputs mem_all (T,B,128) and u_all (T,B,128), g_all (T,B,256) kept
  * for the backward.  mem_dim must be 128 and h_gamma 64 (the reference's constants, :133,140-141).
  * dropout_p / seed: gamma{1,2}_dropout on relu(fc1) in train mode (0 = eval). */
+/* workspace: any contents (every word used is written first). */
 size_t mmt_mfn_mem_scan_workspace_bytes(void);
 int mmt_mfn_mem_scan_forward(const float* apre, const float* chat, const float* Wm, const float* W2, const float* b2,
                              float* mem_all, float* u_all, float* g_all, void* workspace, size_t workspace_bytes,
@@ -403,6 +422,8 @@ int mmt_mfn_mem_scan_backward(const float* dmem_all, const float* chat, const fl
  * x fp32 (N, W, D) contiguous: N = B*T windows (the reference loops over the batch; windows are independent), D % 4 == 0,
  * W >= 2.  weight fp32 (F, D, 2) in nn.Conv1d's layout, bias (F).  out fp32 (N, F); argmax int32 (N, F): the conv position
  * of the maximum (first one on ties), saved for the backward.  Kernel size 2 (the reference's constant, :82); other sizes: mmt_convpool_k_*. */
+/* workspace: any contents (every word used is written first: the padded weights by the forward's first kernel, the backward's
+ * partial sums by its first). */
 size_t mmt_convpool_workspace_bytes(int N, int W, int D, int F);
 int mmt_convpool_forward(const float* x, const float* weight, const float* bias, float* out, int32_t* argmax,
                          void* workspace, size_t workspace_bytes, int N, int W, int D, int F, mmt_stream_t stream);
@@ -419,6 +440,7 @@ int mmt_convpool_backward(const float* x, const float* dout, const int32_t* argm
  * D % 4 != 0: MMT_EUNSUPPORTED.  The workspace query returns 0 for a refused shape, with mmt_last_error() set.  Same numerics
  * as the 2-tap entries (bf16 operands, fp32 accumulation, bias after the pool, no atomics); K = 2 is accepted but runs other
  * kernels than mmt_convpool_* (the Python layer keeps k = 2 on those). */
+/* workspace: any contents (every word used is written first), as mmt_convpool_*. */
 size_t mmt_convpool_k_workspace_bytes(int N, int W, int D, int F, int K);
 int mmt_convpool_k_forward(const float* x, const float* weight, const float* bias, float* out, int32_t* argmax,
                            void* workspace, size_t workspace_bytes, int N, int W, int D, int F, int K, mmt_stream_t stream);

@@ -215,7 +215,19 @@ class WorkspacePool:
 
     The kernels rely on pad regions of a workspace staying zero; they never write them, so a buffer
     can be reused for the same shape without clearing.  A buffer is held by the autograd node between
-    forward and backward and handed back afterwards.  Lanes: the side streams on which the per-modality
+    forward and backward and handed back afterwards.
+
+    Two users of one buffer share its key: device, stream lane, size and tag, i.e. the call site and
+    its shape arguments (and, for the encoder stack and sdpa, train or eval).  Everything else may
+    differ between them and must not show in the later one's result: the input values (one batch
+    with a NaN or an Inf leaves them in the buffer), the mask and the key lengths, the plain / keyed /
+    causal form of the attention, the dropout probability, the seed and its kind (by value or a
+    DeviceSeed), which optional operands are given (bias, rowscale, h0 / c0), and, where the tag
+    carries no T and B (the stacked and the feedback LSTM scans), those as well.  A kernel sequence
+    therefore stores every word it later reads, whether or not the row, the key tile or the causal
+    tile it belongs to is blanked, and masks by select, never by multiplying with 0
+    (tests/test_gpu_workspace_state.py compares a call on a fresh pool with the same call on the
+    buffers another user has just handed back, bit for bit).  Lanes: the side streams on which the per-modality
     encoders of the MFT run concurrently are registered in SIDE_LANES and each owns its buffers; every
     other stream (the caller's, a hipGraph capture stream) is lane 0 with the usual in-order semantics.
     So concurrent streams are never handed a workspace another stream's kernels may still be using, and a

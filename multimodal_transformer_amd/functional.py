@@ -91,6 +91,13 @@ def _check_causal(op, key_lengths, causal):
     return bool(causal)
 
 
+# Workspaces of the entries that take memory with any contents (include/mmt_hip.h: mmt_lstm_scan_*, mmt_mfn_mem_scan_*, mmt_convpool_*,
+# mmt_convpool_k_*): every word their kernels read is written first by a kernel of the same call, so they come from the caching
+# allocator as they are, neither pooled nor cleared.  One function, so that a test can hand those entries memory it has filled.
+def _scratch(nbytes, device):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
 # Pool workspaces held from forward to backward (_lib.WorkspacePool): the Functions that keep one use these two.
 def _hold(ctx, *ws):
     """Forward: keep the workspaces for the backward if an input needs a gradient (-> True), else hand them back to the pool at once."""
@@ -582,7 +589,7 @@ class _LstmScanFn(torch.autograd.Function):
         if W_.shape != (4 * H, H):
             raise ValueError("lstm_scan: W_rec must be (4H,H) = (%d,%d), got %s" % (4 * H, H, tuple(W_.shape)))
         nbytes = _lib.load().mmt_lstm_scan_workspace_bytes(H)
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=gx_.device)
+        ws = _scratch(nbytes, gx_.device)
         h_all = torch.empty(T, B, H, dtype=torch.float32, device=gx_.device)
         c_all = torch.empty_like(h_all)
         acts = torch.empty(T, B, 4 * H, dtype=torch.float32, device=gx_.device)
@@ -599,7 +606,7 @@ class _LstmScanFn(torch.autograd.Function):
         T, B, H, nbytes = ctx.dims
         dev = h_all.device
         dh_, dc_ = _f32c(dh_all), _f32c(dc_all)
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        ws = _scratch(nbytes, dev)
         dgx = torch.empty(T, B, 4 * H, dtype=torch.float32, device=dev)
         dh0, dc0 = (torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(2))
         _lib.launch("mmt_lstm_scan_backward", dh_, dc_, W_, c0_, c_all, acts, dgx, dh0, dc0, ws, nbytes, T, B, H)
@@ -917,7 +924,7 @@ class _ConvPoolFn(torch.autograd.Function):
         nbytes = getattr(_lib.load(), entry + "_workspace_bytes")(*dims)
         if nbytes == 0:             # refused: the launch with nothing to run raises the library's own message
             _lib.launch(entry + "_forward", None, None, None, None, None, None, 0, *dims)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x_.device)
+        ws = _scratch(nbytes, x_.device)
         out = torch.empty(N, F_, dtype=torch.float32, device=x_.device)
         arg = torch.empty(N, F_, dtype=torch.int32, device=x_.device)
         _lib.launch(entry + "_forward", x_, w_, b_, out, arg, ws, nbytes, *dims)
@@ -934,7 +941,7 @@ class _ConvPoolFn(torch.autograd.Function):
         if dout is None:
             return None, None, None, None
         g = _f32c(dout)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
+        ws = _scratch(nbytes, g.device)
         dw, db = torch.empty(wshape, dtype=torch.float32, device=g.device), torch.empty(wshape[0], dtype=torch.float32, device=g.device)
         _lib.launch(entry + "_backward", x_, g, arg, dw, db, ws, nbytes, *dims)
         return None, dw, db, None
@@ -958,7 +965,7 @@ def _mem_scan_fwd(apre, chat, Wm, W2, b2, T, B, dropout_p, seed):
     """The MFN memory recurrence on contiguous fp32 tensors with rows t*B + b -> (mem_all, u_all, g_all), shaped like apre's rows."""
     MD, HG = W2.shape[1], W2.shape[2]
     nbytes = _lib.load().mmt_mfn_mem_scan_workspace_bytes()
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=apre.device)
+    ws = _scratch(nbytes, apre.device)
     rows = apre.shape[:-1]
     mem_all, u_all, g_all = _new(*rows, MD, like=apre), _new(*rows, 2 * HG, like=apre), _new(*rows, 2 * MD, like=apre)
     _launch_seeded("mmt_mfn_mem_scan_forward", seed, apre, chat, Wm, W2, b2, mem_all, u_all, g_all, ws, nbytes, T, B, MD, HG, dropout_p)
@@ -971,7 +978,7 @@ def _mem_scan_bwd(dmem, chat, Wm, W2, mem_all, u_all, g_all, T, B, dropout_p):
     MD, HG = W2.shape[1], W2.shape[2]
     M = T * B
     nbytes = _lib.load().mmt_mfn_mem_scan_workspace_bytes()
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dmem.device)
+    ws = _scratch(nbytes, dmem.device)
     dchat, dapre, dz = torch.empty_like(chat), torch.empty_like(u_all), torch.empty_like(g_all)
     _lib.launch("mmt_mfn_mem_scan_backward", dmem, chat, mem_all, u_all, g_all, Wm, W2, dchat, dapre, dz, ws, nbytes, T, B, MD, HG,
                 dropout_p)

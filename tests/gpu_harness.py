@@ -1,5 +1,6 @@
 """What the GPU test files share: the old-style tolerances, the `dev` fixture, the measures of the bf16-faithful tier (tests/bf16_ref.py),
-the child-process runner for tests whose environment switches are read once per process, and the harvest of device kernel names.
+the child-process runner for tests whose environment switches are read once per process, the harvest of device kernel names, and
+the workspace-state helpers (fills for memory of any contents, the recorder of the pool's traffic: tests/test_gpu_workspace_state.py).
 
 A plain module, not a conftest: it defines no pytest hooks, and a test file imports what it uses by name, the fixtures included.  The
 test files keep their cases, their bounds and their comparisons.  Importing this module must not initialise the GPU: the children of
@@ -193,3 +194,145 @@ def library_kernels(names):
     """kernels that are not ours: ATen element-wise / reduction / copy / cat kernels, rocBLAS / hipBLASLt / MIOpen GEMMs"""
     bad = ("at::", "at_cuda", "elementwise", "Cijk_", "rocblas", "hipblas", "miopen", "MIOpen", "CatArray", "reduce_kernel", "vectorized_")
     return sorted(set(n for n in names if any(b in n for b in bad)))
+
+
+# ------------------------------------------------------------------------------------------------ workspace state
+# What tests/test_gpu_workspace_state.py runs every case through: a workspace's past must not show in a result.  Entries that take
+# memory with any contents get it filled (FilledScratch, FilledPoolGet) and must give the same bits for every fill; entries under
+# "zero once, then reuse for the same shape" get the buffer another call has just used (PoolRecorder proves that they did) and must
+# give the bits of a run on a fresh pool.  tests/test_gpu_harness_cpu.py drives all of it with CPU tensors and a fake pool.
+FILLS = ("zeros", "ones", "bf16_inf")      # 0x00 bytes; 0xFF bytes: a NaN in fp32 and in bf16; 16-bit words 0x7F80: +Inf in bf16 (Inf x 0 = NaN)
+
+
+def fill_bytes(buf, fill):
+    """Fill a contiguous uint8 tensor in place with one of FILLS -> buf.  The 16-bit pattern is little-endian from byte 0 (allocations
+    are at least 2-byte aligned)."""
+    assert buf.dtype == torch.uint8 and buf.dim() == 1 and fill in FILLS, (buf.dtype, buf.shape, fill)
+    if fill == "zeros":
+        buf.fill_(0x00)
+    elif fill == "ones":
+        buf.fill_(0xFF)
+    else:
+        buf[0::2] = 0x80
+        buf[1::2] = 0x7F
+    return buf
+
+
+class FilledScratch:
+    """Stands in for functional._scratch: the same allocation, filled with `fill`; counts its calls (a case asserts that its forward
+    and its backward each made one, so that it cannot pass without the substitution having reached the entry)."""
+
+    def __init__(self, fill):
+        self.fill, self.calls = fill, 0
+
+    def __call__(self, nbytes, device):
+        self.calls += 1
+        return fill_bytes(torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device), self.fill)
+
+    def took(self):
+        """the calls since the last look"""
+        n, self.calls = self.calls, 0
+        return n
+
+
+class FilledPoolGet:
+    """Stands in for a pool's get (`real`: the unwrapped one): buffers whose tag starts with `tag0` are filled with `fill` before they
+    are handed out (only for an entry that documents "any contents": today mmt_local_attn_backward); counts them."""
+
+    def __init__(self, real, fill, tag0):
+        self.real, self.fill, self.tag0, self.calls = real, fill, tag0, 0
+
+    def __call__(self, nbytes, device, tag=None):
+        buf = self.real(nbytes, device, tag=tag)
+        if tag is not None and tag[0] == self.tag0:
+            self.calls += 1
+            fill_bytes(buf, self.fill)
+        return buf
+
+
+class PoolRecorder:
+    """Wraps get / put / clear of a WorkspacePool and keeps, per phase ("fresh", "dirtier", "probe"), which buffers were handed out and
+    handed back, by data_ptr.  A buffer handed out counts as reused when it was handed back since the last clear() — it then sits alive in
+    the free list, so no new allocation can have its address — and the phase that handed it back is kept with it.  The buffers a phase
+    handed back stay referenced here, so their bytes can be compared later (assert_dirtied)."""
+
+    def __init__(self, pool, monkeypatch):
+        self.pool, self._get, self._put, self._clear = pool, pool.get, pool.put, pool.clear
+        self.current, self.log, self._returned, self._tags = None, {}, {}, {}
+        monkeypatch.setattr(pool, "get", self.get)
+        monkeypatch.setattr(pool, "put", self.put)
+        monkeypatch.setattr(pool, "clear", self.clear)
+
+    def phase(self, name):
+        self.current = name
+        self.log[name] = {"got": [], "put": [], "bufs": {}}
+
+    def get(self, nbytes, device, tag=None):
+        buf = self._get(nbytes, device, tag=tag)
+        self._tags[buf.data_ptr()] = tag
+        if self.current is not None:
+            self.log[self.current]["got"].append((buf.data_ptr(), tag, self._returned.pop(buf.data_ptr(), None)))
+        return buf
+
+    def put(self, buf):
+        self._put(buf)
+        self._returned[buf.data_ptr()] = self.current
+        if self.current is not None:
+            self.log[self.current]["put"].append(buf.data_ptr())
+            self.log[self.current]["bufs"][buf.data_ptr()] = (self._tags.get(buf.data_ptr()), buf)
+
+    def clear(self):
+        self._clear()
+        self._returned.clear()
+
+    def _got(self, phase, tags):
+        return [g for g in self.log.get(phase, {"got": []})["got"] if tags is None or (g[1] is not None and g[1][0] in tags)]
+
+    def contents(self, phase, tags=None):
+        """[(tag, buffer)] the phase handed back, each buffer once, in the order of its first return"""
+        return [tb for tb in self.log[phase]["bufs"].values() if tags is None or (tb[0] is not None and tb[0][0] in tags)]
+
+    def assert_dirtied(self, clean="fresh", dirtier="dirtier", tags=None):
+        """The dirtier left other bytes than the clean run in at least one buffer of a tag both used: a dirtier that leaves a workspace
+        as the probe itself leaves it shows nothing -> how many buffers differ."""
+        left = {}
+        for tag, buf in self.contents(clean, tags):
+            left.setdefault(tag, []).append(buf)
+        n = sum(1 for tag, buf in self.contents(dirtier, tags)
+                if tag in left and not any(b.numel() == buf.numel() and torch.equal(b, buf) for b in left[tag]))
+        assert n > 0, "the dirtier left every workspace as the clean run leaves it: the case checks nothing"
+        return n
+
+    def assert_fresh(self, phase="fresh", tags=None):
+        """Every buffer the phase was handed is a new allocation or one the phase itself had handed back -> how many it was handed."""
+        got = self._got(phase, tags)
+        assert got, "the %s run was handed no workspace%s" % (phase, "" if tags is None else " tagged %s" % sorted(tags))
+        for ptr, tag, src in got:
+            assert src in (None, phase), "the %s run was handed a used workspace (%s, handed back in phase %r)" % (phase, tag, src)
+        return len(got)
+
+    def assert_reused(self, dirtier="dirtier", probe="probe", tags=None):
+        """The probe was handed at least one buffer (with a tag in `tags`, if given), and every one of them is a buffer the dirtier had
+        handed back -> how many distinct buffers that were."""
+        got = self._got(probe, tags)
+        assert got, "the dirty probe was handed no workspace%s" % ("" if tags is None else " tagged %s" % sorted(tags))
+        dirty = set(self.log.get(dirtier, {"put": []})["put"])
+        for ptr, tag, src in got:
+            assert src is not None, "the dirty probe was handed a new workspace for %s: nothing was reused" % (tag,)
+            assert ptr in dirty, "the dirty probe was handed a workspace for %s that the dirtier had not used" % (tag,)
+        return len({g[0] for g in got})
+
+
+def same_bits(tag, a, b, failures):
+    """a, b: {name: tensor or None} of two runs of one call: the same names, every tensor finite and torch.equal to its twin."""
+    assert list(a) == list(b), (tag, list(a), list(b))
+    for n in a:
+        if a[n] is None or b[n] is None:
+            if a[n] is not b[n]:
+                failures.append("%s %s: one run returned None" % (tag, n))
+            continue
+        if not (bool(torch.isfinite(a[n]).all()) and bool(torch.isfinite(b[n]).all())):
+            failures.append("%s %s: not finite" % (tag, n))
+        elif not torch.equal(a[n], b[n]):
+            d = (a[n].double() - b[n].double()).abs()
+            failures.append("%s %s: %d of %d entries differ (max %.3e)" % (tag, n, int((d > 0).sum()), d.numel(), float(d.max())))
