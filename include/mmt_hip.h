@@ -223,6 +223,35 @@ int mmt_encoder_backward_causal_devseed(const float* dy, const float* x, const f
                                         int B, int T, int d, int h, int f, int n_layers, float eps,
                                         float dropout_p, mmt_stream_t stream);
 
+/* ---- A causal encoder stack, one window at a time (opt-in; eval mode, forward only).
+ * Replaces Encoder.forward(x, mask)[:, t] with causal attention on               transformer/MFT/multiTransformer.py:73-76
+ *                                                                             (departs from :27-31 as the causal entries above do)
+ * for t = 0, 1, 2, ... of one recording per batch row, without recomputing the prefix: the state keeps, per layer, the bf16 K and V of
+ * the windows seen so far (exactly the operands the batch kernels consume).  One step is ONE launch for the whole stack and the final
+ * LayerNorm, one workgroup per sequence, no communication between workgroups: a sequence's result does not depend on its batch.
+ * Numerics: the batch path's rounding sites (bf16 operands of every product, fp32 sums, biases, residuals, LayerNorm) with one
+ * difference, the softmax reference point: the row's own exact maximum, where the batch kernel keeps a lazily moved maximum per
+ * 32-query tile (csrc/encoder_step.h).  Two equally faithful roundings: rows agree to about 1.5e-3 rel-L2.
+ * `state`: mmt_encoder_stream_bytes() bytes, ANY CONTENTS: every word a step reads was written by mmt_encoder_stream_prepare or by an
+ * earlier step of this recording.  A new recording starts by passing t = 0 again; nothing needs clearing.
+ * Limits: d % h == 0, d % 4 == 0, f % 4 == 0, d_k <= 64, d <= 512, f <= 2048, 1 <= n_layers <= 16, 1 <= capacity <= 4096,
+ * h * (d_k rounded up to 8) <= 2048: anything else is MMT_EUNSUPPORTED with the limit named in mmt_last_error(), at the size query
+ * (which then returns 0); non-positive sizes and null pointers: MMT_EINVAL. */
+/* (Encoder.forward, :73-76; departs from :27-31) */
+size_t mmt_encoder_stream_bytes(int B, int capacity, int d, int h, int f, int n_layers);
+/* One launch: the weight matrices of `params` (mmt_encoder_param_count() floats, the layout above) to bf16 in the step kernel's layout,
+ * at the front of the state.  Does not touch the cache.  Call it again after the parameters change.
+ * (Encoder.forward, :73-76; departs from :27-31) */
+int mmt_encoder_stream_prepare(const float* params, void* state, size_t state_bytes,
+                               int B, int capacity, int d, int h, int f, int n_layers, mmt_stream_t stream);
+/* x_t (B,d) -> y_t (B,d) at position t; mask_t (B) float {0,1} or NULL: a blanked window is uniform over its t + 1 keys, and its K_t
+ * and V_t are appended like any other.  `params`: the same buffer prepare saw (biases and LayerNorm weights are read from it in fp32).
+ * t is passed by value; t < 0 or t >= capacity returns MMT_EINVAL before any launch.  Steps of one recording must be enqueued in
+ * order t = 0, 1, ... on one stream.                                           (Encoder.forward, :73-76; departs from :27-31) */
+int mmt_encoder_stream_step(const float* x_t, const float* mask_t, const float* params, float* y_t,
+                            void* state, size_t state_bytes, int t, int B, int capacity, int d, int h, int f, int n_layers,
+                            float eps, mmt_stream_t stream);
+
 /* ---- Fused affine map  y = act(x W^T + b) [* rowscale] on bf16 MFMA.
  * Replaces nn.Linear (+ F.relu) call sites of the path: PositionwiseFeedForward (:15-20), the four
  * attention projections (:43,55,65), embeds and read-out MLPs (:270,296,340-342,400-402).

@@ -56,6 +56,10 @@ SIGNATURES = {
     "mmt_encoder_backward_causal": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _U64, _P]),
     "mmt_encoder_forward_causal_devseed": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _P, _P]),
     "mmt_encoder_backward_causal_devseed": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _P]),
+    # one window of a causal stack per launch: (B, capacity, d, h, f, n_layers) behind the state and, for a step, the position t
+    "mmt_encoder_stream_bytes": (_SZ, [_I] * 6),
+    "mmt_encoder_stream_prepare": (_I, [_P, _P, _SZ] + [_I] * 6 + [_P]),
+    "mmt_encoder_stream_step": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 7 + [_F, _P]),
     "mmt_linear_workspace_bytes": (_SZ, [_I] * 3),
     "mmt_linear_forward": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),
     "mmt_linear_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),

@@ -1547,6 +1547,78 @@ def mfn_gate(hs, cs, params, gamma_dropout=0.0, gamma_seed=0, out_dropout=0.0, o
                             *hs, *cs, *params)
 
 
+# A causal encoder stack, one window per call (include/mmt_hip.h mmt_encoder_stream_*): eval mode, forward only.  The state (prepared
+# bf16 weights, then the K/V cache) takes memory with any contents, so it comes from _scratch.
+def encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers):
+    """Bytes of the stream state of this shape; ValueError, naming the limit, for a shape outside the step kernel's domain."""
+    lib = _lib.load()
+    nbytes = lib.mmt_encoder_stream_bytes(int(B), int(capacity), int(d), int(h), int(d_ff), int(n_layers))
+    if nbytes == 0:
+        raise ValueError("encoder stream: %s" % (lib.mmt_last_error() or b"?").decode())
+    return nbytes
+
+
+def encoder_stream_state(B, capacity, d, h, d_ff, n_layers, device):
+    """An unprepared stream state on ``device`` (uint8; any contents)."""
+    return _scratch(encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers), device)
+
+
+def _stream_params(op, flat_params, d, d_ff, n_layers):
+    if flat_params.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("%s: forward only, no autograd (parameters that require grad: call it under torch.no_grad())" % op)
+    p_ = _f32c(flat_params)
+    need = _lib.load().mmt_encoder_param_count(d, d_ff, n_layers)
+    if p_.numel() != need:
+        raise ValueError("%s: flat parameter buffer has %d elements, expected %d" % (op, p_.numel(), need))
+    return p_
+
+
+def _stream_state(op, state, nbytes, device):
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < nbytes:
+        raise ValueError("%s: state must be a contiguous uint8 tensor of at least %d bytes (encoder_stream_state)" % (op, nbytes))
+    if state.device != device:
+        raise ValueError("%s: state is on %s, the operands on %s" % (op, state.device, device))
+
+
+def encoder_stream_prepare(flat_params, state, B, capacity, d, h, d_ff, n_layers):
+    """Write the bf16 weights of ``flat_params`` into the front of ``state`` (one launch; the cache is not touched).  Again after the
+    parameters change."""
+    _lib.require_hip(flat_params, state)
+    nbytes = encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers)
+    p_ = _stream_params("encoder_stream_prepare", flat_params, d, d_ff, n_layers)
+    _stream_state("encoder_stream_prepare", state, nbytes, p_.device)
+    _lib.launch("mmt_encoder_stream_prepare", p_, state, state.numel(), int(B), int(capacity), int(d), int(h), int(d_ff), int(n_layers))
+
+
+def encoder_stream_step(x_t, mask_t, flat_params, state, t, h, d_ff, n_layers, capacity, eps=1e-6):
+    """Row t of a causal encoder stack: x_t (B,d), mask_t (B) or None -> y_t (B,d) = Encoder.forward(x, mask)[:, t] with causal attention
+    on (transformer/MFT/multiTransformer.py:73-76; departs from :27-31), from the K/V cache in ``state`` (encoder_stream_state, prepared
+    by encoder_stream_prepare), to which this window's keys and values are appended.  Steps of a recording run in order t = 0, 1, ...;
+    t is passed by value.  One launch.  Forward only: an input that requires grad raises NotImplementedError."""
+    op = "encoder_stream_step"
+    if any(isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled() for a in (x_t, mask_t)):
+        raise NotImplementedError("%s: forward only, no autograd (an input requires grad)" % op)
+    if not isinstance(x_t, torch.Tensor) or x_t.dim() != 2 or x_t.dtype != torch.float32:
+        raise ValueError("%s: x_t must be a float32 (B,d) tensor, got %s %s"
+                         % (op, getattr(x_t, "dtype", type(x_t).__name__), tuple(getattr(x_t, "shape", ()))))
+    B, d = x_t.shape
+    if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != x_t.device):
+        raise ValueError("%s: mask_t must hold one entry per sequence (B = %d) on %s" % (op, B, x_t.device))
+    t, capacity = int(t), int(capacity)
+    if not 0 <= t < capacity:
+        raise ValueError("%s: position t = %d outside [0, capacity = %d): open a stream with a larger capacity" % (op, t, capacity))
+    _lib.require_hip(x_t, flat_params, state)
+    nbytes = encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers)
+    p_ = _stream_params(op, flat_params, d, d_ff, n_layers)
+    _stream_state(op, state, nbytes, x_t.device)
+    x_ = _f32c(x_t)
+    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
+    y = torch.empty_like(x_)
+    _lib.launch("mmt_encoder_stream_step", x_, m_, p_, y, state, state.numel(), t, B, capacity, d, int(h), int(d_ff), int(n_layers),
+                float(eps))
+    return y
+
+
 def check_device_errors():
     """Synchronise and raise if an asynchronous kernel reported an error through its device error word (mmt_hip.h)."""
     _lib.ERRORS.check()

@@ -110,6 +110,41 @@ class _FrontEnd(nn.Module):
         return outs
 
 
+class _FrontEndStream:
+    """``stream()`` of the MultiCNNTransformer wrappers: ``step({mod: (B, W, d_raw)}, mask_t)`` -> the (B,1) prediction of that window.
+    The window encoder runs on a T = 1 batch (``_encode``), then the fusion layer where the model has one, then the sequence model's
+    own step (``multiTransformer._SequenceStream``).  ``reset()`` starts a new recording."""
+
+    def __init__(self, model, batch, capacity):
+        if model.training:
+            raise ValueError("%s.stream: the model is in train mode; streaming is eval-mode inference (call .eval())" % type(model).__name__)
+        self.model, self.batch = model, int(batch)
+        self.seq = model.Transformer.stream(batch, capacity)
+
+    t = property(lambda self: self.seq.t)
+    capacity = property(lambda self: self.seq.capacity)
+
+    def reset(self):
+        self.seq.reset()
+
+    def step(self, inputs, mask_t=None):
+        m, B = self.model, self.batch
+        for mod in m.mods:
+            x = inputs[mod]
+            if x.dim() != 3 or x.shape[0] != B:
+                raise ValueError("%s stream step: inputs[%r] must have the shape (%d, W, d_raw), got %s"
+                                 % (type(m).__name__, mod, B, tuple(x.shape)))
+        with torch.no_grad():
+            outs = m._encode({mod: inputs[mod].unsqueeze(1) for mod in m.mods})           # {mod: (B,1,F_mod)}
+            if len(m.mods) > 1:
+                x = F_hip.cat_cols([outs[mod] for mod in m.mods])
+                if getattr(m, "fusionLayer", None) is not None:
+                    x = F_hip.linear(x, m.fusionLayer.weight.detach(), m.fusionLayer.bias.detach(), act=2)   # tanh, SFT/models.py:138
+            else:
+                x = outs[m.mods[0]]
+            return self.seq.step(x.reshape(B, -1), mask_t)
+
+
 class MultiCNNTransformer(_FrontEnd):
     """SFT: transformer/SFT/models.py:81-142."""
 
@@ -133,6 +168,10 @@ class MultiCNNTransformer(_FrontEnd):
             return self.Transformer(fused, mask, length)
         return self.Transformer(outs[self.mods[0]], mask, length)
 
+    def stream(self, batch, capacity):
+        """This model as an online predictor (``_FrontEndStream``): eval mode, ``causal_attention(model)`` on."""
+        return _FrontEndStream(self, batch, capacity)
+
 
 class MultiCNNTransformerMFT(_FrontEnd):
     """MFT: transformer/MFT/models.py:81-138 (``embed_dims`` replaces the fixed window embed sizes; no fusion layer)."""
@@ -155,6 +194,14 @@ class MultiCNNTransformerMFT(_FrontEnd):
             return self.Transformer(outs, mask, length)
         return self.Transformer(outs[self.mods[0]], mask, length)
 
+    def stream(self, batch, capacity):
+        """One modality: the UniTransformer's stream behind the window encoder.  More: NotImplementedError (the MFN gate)."""
+        if len(self.mods) > 1:
+            raise NotImplementedError("MultiCNNTransformerMFT.stream: with more than one modality the sequence model is the MFT, whose "
+                                      "MFN gate (per-modality LSTM cells and the delta-memory) needs a stepping state of its own; not "
+                                      "implemented (a single-modality model streams)")
+        return _FrontEndStream(self, batch, capacity)
+
 
 class MultiCNNTransformerB2(_FrontEnd):
     """B2-Trans: transformer/B2-Trans/models.py:81-134 (single modality; the fusion layer is commented out there)."""
@@ -172,6 +219,10 @@ class MultiCNNTransformerB2(_FrontEnd):
         if len(outs) > 1:
             return self.Transformer(F_hip.cat_cols([outs[m] for m in self.mods]), mask, length)
         return self.Transformer(outs[self.mods[0]], mask, length)
+
+    def stream(self, batch, capacity):
+        """This model as an online predictor (``_FrontEndStream``): eval mode, ``causal_attention(model)`` on."""
+        return _FrontEndStream(self, batch, capacity)
 
 
 class MultiCNNTransformerB3(_FrontEnd):

@@ -340,6 +340,28 @@ class Encoder(nn.Module):
                                           flat=self._flat_storage(ps) if x.is_cuda else None, nsplit=k, key_lengths=kl,
                                           causal=causal)
 
+    def stream(self, batch, capacity):
+        """Open an ``EncoderStream``: this stack as an online predictor for ``batch`` recordings of up to ``capacity`` windows, one
+        window per ``step`` against a K/V cache instead of a forward over the whole prefix.  Eval mode, forward only; every layer must
+        attend causally (``causal_attention(model)``).  Raises ValueError, before any launch, for anything else."""
+        name = type(self).__name__
+        if self.training:
+            raise ValueError("%s.stream: the encoder is in train mode; streaming is eval-mode inference (call .eval())" % name)
+        if not self._fusable():
+            raise ValueError("%s.stream: the stack is not the standard composition the fused kernels run (EncoderLayer of "
+                             "MultiHeadedAttention and PositionwiseFeedForward with one width, h, d_ff and attention mode in every "
+                             "layer, keep_attention off): use such a stack" % name)
+        l0 = self.layers[0].self_attn
+        if l0.mask_keys:
+            raise ValueError("%s.stream: mask_keys is set; a stream attends its own past only, which already keeps it from any padding "
+                             "(mask_padded_keys(model, False))" % name)
+        if not l0.causal:
+            raise ValueError("%s.stream: the layers do not attend causally, so window t depends on later windows and cannot be "
+                             "predicted online: call causal_attention(model) (and train the model that way)" % name)
+        if self.norm.a_2.device.type != "cuda":
+            raise ValueError("%s.stream: the encoder is on %s; move it to a HIP device (there is no CPU path)" % (name, self.norm.a_2.device))
+        return EncoderStream(self, batch, capacity)
+
     sub_batch_streams = 1        # set to 2: the batch runs as two halves on two HIP streams (functional._SPLIT_STREAMS); opt-in
     sub_batch_min_windows = 8192
 
@@ -352,6 +374,129 @@ class Encoder(nn.Module):
         if not x.is_cuda or k < 2 or x.shape[0] < 2 or x.shape[0] * x.shape[1] < self.sub_batch_min_windows or _lib.on_side_lane(x.device):
             return 1
         return min(k, x.shape[0])
+
+
+class EncoderStream:
+    """A causal ``Encoder`` run one window at a time (``Encoder.stream``): ``step(x_t)`` returns the row that the encoder's batch
+    forward gives at position ``t`` of the windows stepped so far, in ONE kernel launch (csrc/encoder_step.h), and advances ``t``.
+    The state is the bf16 copy of the weight matrices and the bf16 K / V of every layer for ``batch`` x ``capacity`` windows.
+
+    ``reset()`` starts a new recording: it sets ``t`` back to 0 and neither clears nor re-reads anything.  ``refresh()`` converts the
+    weights again: call it after the encoder's parameters changed (biases and LayerNorm weights are read live).  Rows agree with the
+    batch forward to the distance between two roundings of the same arithmetic (about 1.5e-3 rel-L2), not bit for bit."""
+
+    def __init__(self, encoder, batch, capacity):
+        l0 = encoder.layers[0]
+        self.encoder = encoder
+        self.batch, self.capacity, self.t = int(batch), int(capacity), 0
+        self.d, self.h, self.d_ff, self.n_layers = l0.size, l0.self_attn.h, l0.feed_forward.w_1.weight.shape[0], len(encoder.layers)
+        self.eps = encoder.norm.eps
+        self.device = encoder.norm.a_2.device
+        if self.batch < 1 or self.capacity < 1:
+            raise ValueError("Encoder.stream: batch and capacity must be at least 1, got %d and %d" % (self.batch, self.capacity))
+        self._dims = (self.batch, self.capacity, self.d, self.h, self.d_ff, self.n_layers)
+        self.state = F_hip.encoder_stream_state(*self._dims, self.device)        # ValueError naming the limit for an unsupported shape
+        self.refresh()
+
+    def refresh(self):
+        """Convert the encoder's current weight matrices into the state (one launch); the cache and ``t`` stay."""
+        ps = self.encoder.flat_parameters()
+        flat = self.encoder._flat_storage(ps)
+        if flat is None:
+            flat = torch.cat([q.detach().reshape(-1) for q in ps]).float()
+        self._flat = flat.detach()
+        F_hip.encoder_stream_prepare(self._flat, self.state, *self._dims)
+
+    def reset(self):
+        self.t = 0
+
+    def step(self, x_t, mask_t=None):
+        """x_t (B,d) or (B,1,d) float32 on the encoder's device, mask_t (B), (B,1) or (B,1,1) or None -> the same shape as x_t."""
+        if self.t >= self.capacity:
+            raise ValueError("EncoderStream.step: the stream is full (t = capacity = %d): reset() starts a new recording, "
+                             "Encoder.stream(batch, capacity) opens a longer one" % self.capacity)
+        if not isinstance(x_t, torch.Tensor) or x_t.dtype != torch.float32 or x_t.device != self.device:
+            raise ValueError("EncoderStream.step: x_t must be a float32 tensor on %s, got %s on %s"
+                             % (self.device, getattr(x_t, "dtype", type(x_t).__name__), getattr(x_t, "device", None)))
+        if tuple(x_t.shape) not in ((self.batch, self.d), (self.batch, 1, self.d)):
+            raise ValueError("EncoderStream.step: x_t must have the shape (%d,%d) or (%d,1,%d), got %s"
+                             % (self.batch, self.d, self.batch, self.d, tuple(x_t.shape)))
+        if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != self.batch or mask_t.device != self.device):
+            raise ValueError("EncoderStream.step: mask_t must hold one entry per sequence (%d) on %s" % (self.batch, self.device))
+        y = F_hip.encoder_stream_step(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.t, self.h, self.d_ff,
+                                      self.n_layers, self.capacity, self.eps)
+        self.t += 1
+        return y.view(x_t.shape)
+
+
+def _stream_model_checks(model):
+    if model.training:
+        raise ValueError("%s.stream: the model is in train mode; streaming is eval-mode inference (call .eval())" % type(model).__name__)
+
+
+class _SequenceStream:
+    """``stream()`` of UniFullTransformer, UniTransformer and NLPTransformer: ``step(x_t (B, window_embed_size), mask_t)`` -> the (B,1)
+    prediction of that window, what the model's eval forward gives at [:, t] with causal attention on.  Around the encoder step it runs
+    the kernels the batch forward runs: the embed affine map and the two read-out maps, and for the LSTM decoder one scan of T = 1
+    with the carried (h, c).  ``reset()`` starts a new recording."""
+
+    def __init__(self, model, batch, capacity):
+        _stream_model_checks(model)
+        self.model, self.batch = model, int(batch)
+        dec = getattr(model, "decoder", None)
+        if dec is not None and dec.num_layers != 1:
+            raise NotImplementedError("%s.stream: a decoder with n_layers = %d; the stepping state of the stacked scan is not implemented "
+                                      "(n_layers == 1 streams)" % (type(model).__name__, dec.num_layers))
+        self.enc = model.encoder.stream(batch, capacity)
+        self._dec = None
+        if dec is not None:
+            with torch.no_grad():
+                Wx, W_rec, Whh, bias = F_hip.decoder_pack(dec.weight_ih_l0, dec.weight_hh_l0, dec.bias_ih_l0, dec.bias_hh_l0)
+                self._dec = tuple(z.detach() for z in (Wx, W_rec, bias, F_hip.linear(model.dec_h0, Whh),
+                                                       F_hip.broadcast_rows(model.dec_c0, self.batch)))
+        self._h = self._c = None
+
+    t = property(lambda self: self.enc.t)
+    capacity = property(lambda self: self.enc.capacity)
+
+    def reset(self):
+        self.enc.reset()
+        self._h = self._c = None
+
+    @staticmethod
+    def _affine(x, layer, act=0, rowscale=None):
+        # detached views of the live parameters: an autograd node that sees a tensor requiring grad keeps its pool workspace for a
+        # backward that never comes, and the next call would get a new one (an allocation and a zero fill per step)
+        return F_hip.linear(x, layer.weight.detach(), layer.bias.detach(), act=act, rowscale=rowscale)
+
+    def _embed(self, x_t):
+        m = self.model
+        if isinstance(m.embed, nn.Sequential):                    # NLPTransformer: Dropout (identity in eval) -> Linear -> ReLU
+            return self._affine(x_t, m.embed[1], act=1)
+        return self._affine(x_t, m.embed)
+
+    def step(self, x_t, mask_t=None):
+        m, B = self.model, self.batch
+        if not isinstance(x_t, torch.Tensor) or x_t.dim() != 2 or x_t.shape[0] != B:
+            raise ValueError("%s stream step: x_t must have the shape (%d, window_embed_size), got %s"
+                             % (type(m).__name__, B, tuple(getattr(x_t, "shape", ()))))
+        if self.enc.t >= self.enc.capacity:
+            raise ValueError("%s stream step: the stream is full (t = capacity = %d)" % (type(m).__name__, self.enc.capacity))
+        if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B):
+            raise ValueError("%s stream step: mask_t must hold one entry per sequence (%d)" % (type(m).__name__, B))
+        with torch.no_grad():
+            first = self.enc.t == 0
+            r = None if mask_t is None else mask_t.float().reshape(B)
+            e = self.enc.step(self._embed(x_t), r)
+            if self._dec is not None:
+                Wx, W_rec, bias, row0, c0 = self._dec
+                gx = F_hip.linear(e.view(1, B, -1), Wx, bias)                    # (1,B,4d)
+                if first:
+                    gx = F_hip.add_row0(gx, row0)                                # step 0 sees h0 W_hh^T, as _decode
+                h_all, c_all = F_hip.lstm_scan(gx, W_rec, None if first else self._h, c0 if first else self._c)
+                self._h, self._c = h_all[0], c_all[0]
+                e = self._h
+            return self._affine(self._affine(e, m.out[0], act=1), m.out[2], rowscale=r)
 
 
 def _encoder(embed_dim, h, d_ff, dropout, N):
@@ -570,6 +715,11 @@ class UniTransformer(nn.Module, _DecoderMixin):
         e = F_hip.linear(inputs, self.embed.weight, self.embed.bias)
         return self._decode(self.encoder(e, mask), mask)
 
+    def stream(self, batch, capacity):
+        """This model as an online predictor: ``.step(x_t (B, window_embed_size), mask_t)`` -> the (B,1) prediction of window t
+        (``_SequenceStream``).  Eval mode, ``causal_attention(model)`` on; ValueError / NotImplementedError before any launch."""
+        return _SequenceStream(self, batch, capacity)
+
 
 class UniFullTransformer(nn.Module):
     """B2-Trans model (transformer/B2-Trans/multiTransformer.py:378-420): Linear embed -> Encoder -> MLP -> mask."""
@@ -588,6 +738,11 @@ class UniFullTransformer(nn.Module):
         enc = self.encoder(F_hip.linear(inputs, self.embed.weight, self.embed.bias), mask)
         hid = F_hip.linear(enc, self.out[0].weight, self.out[0].bias, act=1)
         return F_hip.linear(hid, self.out[2].weight, self.out[2].bias, rowscale=mask.float().reshape(-1))
+
+    def stream(self, batch, capacity):
+        """This model as an online predictor: ``.step(x_t (B, window_embed_size), mask_t)`` -> the (B,1) prediction of window t
+        (``_SequenceStream``).  Eval mode, ``causal_attention(model)`` on; ValueError / NotImplementedError before any launch."""
+        return _SequenceStream(self, batch, capacity)
 
 
 class NLPTransformer(nn.Module, _DecoderMixin):
@@ -612,3 +767,8 @@ class NLPTransformer(nn.Module, _DecoderMixin):
         seed = _lib.next_dropout_seed(inputs.device, 5, holder=self) if p_in > 0.0 else 0
         e = F_hip.linear(inputs, self.embed[1].weight, self.embed[1].bias, act=1, in_dropout=p_in, seed=seed)
         return self._decode(self.encoder(e, mask), mask)
+
+    def stream(self, batch, capacity):
+        """This model as an online predictor: ``.step(x_t (B, window_embed_size), mask_t)`` -> the (B,1) prediction of window t
+        (``_SequenceStream``).  Eval mode, ``causal_attention(model)`` on; ValueError / NotImplementedError before any launch."""
+        return _SequenceStream(self, batch, capacity)
