@@ -270,7 +270,8 @@ __device__ __forceinline__ void attn_fwd_body(
             // move the reference to the new running max (first tile: from 0 to the tile max, with o = l = 0)
             tmax = fmaxf(tmax, __shfl_xor(tmax, 32));  // finite: every tile holds >= 1 real key in one of the halves
             const float dlt = (kt == 0) ? tmax : fmaxf(tmax, 0.f);
-            const float alpha = fast_exp2(-dlt);
+            // alpha <= 1: a first tile whose maximum is below -128 would give 2^(-dlt) = inf, and o = l = 0 times inf is NaN
+            const float alpha = fast_exp2(-fmaxf(dlt, 0.f));
             mrun += dlt;
             lrun *= alpha;
 #pragma unroll
