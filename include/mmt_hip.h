@@ -252,6 +252,35 @@ int mmt_encoder_stream_step(const float* x_t, const float* mask_t, const float* 
                             void* state, size_t state_bytes, int t, int B, int capacity, int d, int h, int f, int n_layers,
                             float eps, mmt_stream_t stream);
 
+/* ---- The MFN gate, one window at a time (opt-in; eval mode, forward only).
+ * Replaces one iteration t of MFN.forward's loop                               transformer/MFT/multiTransformer.py:200-247
+ * (per-modality LSTMCell, cStar, the attention over the cell states, the memory candidate, both gates, the memory update and the
+ * read-out MLP) for t = 0, 1, 2, ... of one recording per batch row: the state carries (h_m, c_m, mem) between the calls.  One step
+ * is ONE launch, one workgroup per sequence, no communication between workgroups: a sequence's result does not depend on its batch.
+ * Numerics: the batch path's rounding sites exactly (the left operand of every product and every weight bf16; sums, biases,
+ * activations, softmax, the carried state and everything stored fp32); no site depends on a tile (csrc/mfn_step.h).
+ * nmods modalities (1..4) with input widths in_dims[m] (multiples of 4, <= 512) and LSTM hidden sizes hidden[m] (multiples of 4,
+ * their sum <= 256), both HOST arrays of nmods ints; the gate's other sizes are fixed: mem_dim 128, gamma hidden 64, att1 hidden 128,
+ * att2 hidden 256, read-out hidden 64; 1 <= output_dim <= 256.  Anything else is MMT_EUNSUPPORTED with the limit named in
+ * mmt_last_error(), at the size query (which then returns 0); non-positive sizes, null pointers and t < 0: MMT_EINVAL, before any launch.
+ * `state`: mmt_mfn_stream_bytes() bytes, ANY CONTENTS: every word a step reads was written by mmt_mfn_stream_prepare or by the step
+ * before it in this recording.  A new recording starts by passing t = 0 again; nothing needs clearing. */
+/* (MFN.forward, :200-247) */
+size_t mmt_mfn_stream_bytes(int B, int nmods, const int* in_dims, const int* hidden, int output_dim);
+/* One launch: every parameter into the state, weights to bf16 in the step kernel's layout, biases in fp32 (b_ih + b_hh summed).
+ * lstm_params: a HOST array of 4 * nmods device pointers, per modality weight_ih (4H,D), weight_hh (4H,H), bias_ih, bias_hh of its
+ * nn.LSTMCell; gate_params: a HOST array of 20 device pointers, weight then bias of att1_fc1, att1_fc2, att2_fc1, att2_fc2, gamma1_fc1,
+ * gamma1_fc2, gamma2_fc1, gamma2_fc2, out_fc1, out_fc2.  Does not touch the carried state.  Call it again after a parameter changes:
+ * a step reads the biases from the state too.                                  (MFN.__init__ / forward, :118-180, :200-247) */
+int mmt_mfn_stream_prepare(const float* const* lstm_params, const float* const* gate_params, void* state, size_t state_bytes,
+                           int B, int nmods, const int* in_dims, const int* hidden, int output_dim, mmt_stream_t stream);
+/* x_t: a HOST array of nmods device pointers, x_t[m] (B, in_dims[m]) -> y_t (B, output_dim) at position t; mask_t (B) float or NULL
+ * multiplies the output row (MultiTransformer.forward's `* mask`, :310); the state advances under a blanked window as it does in
+ * the batch path.  t is passed by value; step t reads copy t & 1 of the carried state and writes the other, so steps of one
+ * recording must be enqueued in order t = 0, 1, ... on one stream.              (MFN.forward, :200-247; :310) */
+int mmt_mfn_stream_step(const float* const* x_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,
+                        int t, int B, int nmods, const int* in_dims, const int* hidden, int output_dim, mmt_stream_t stream);
+
 /* ---- Fused affine map  y = act(x W^T + b) [* rowscale] on bf16 MFMA.
  * Replaces nn.Linear (+ F.relu) call sites of the path: PositionwiseFeedForward (:15-20), the four
  * attention projections (:43,55,65), embeds and read-out MLPs (:270,296,340-342,400-402).

@@ -60,6 +60,10 @@ SIGNATURES = {
     "mmt_encoder_stream_bytes": (_SZ, [_I] * 6),
     "mmt_encoder_stream_prepare": (_I, [_P, _P, _SZ] + [_I] * 6 + [_P]),
     "mmt_encoder_stream_step": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 7 + [_F, _P]),
+    # one window of the MFN gate per launch: (B, nmods, in_dims, hidden, output_dim), the two arrays host int32; pointer lists host arrays
+    "mmt_mfn_stream_bytes": (_SZ, [_I, _I, _P, _P, _I]),
+    "mmt_mfn_stream_prepare": (_I, [_P, _P, _P, _SZ, _I, _I, _P, _P, _I, _P]),
+    "mmt_mfn_stream_step": (_I, [_P, _P, _P, _P, _SZ, _I, _I, _I, _P, _P, _I, _P]),
     "mmt_linear_workspace_bytes": (_SZ, [_I] * 3),
     "mmt_linear_forward": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),
     "mmt_linear_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),

@@ -1,0 +1,222 @@
+// One window of the MFN gate per launch: mfn_step_kernel advances the per-modality LSTM cells, the attention over the cell states, the
+// delta-memory and the read-out by one position t for each of B sequences (transformer/MFT/multiTransformer.py:200-247 for one t),
+// carrying (h_m, c_m, mem) in a stream state (layout and limits: mfn_step_plan.h).  Its output row is what MFN.forward in eval mode
+// gives at [:, t] of the windows stepped so far.
+//
+// Shape of the kernel, as encoder_step.h: grid = B, one workgroup of 256 threads per sequence; workgroups share nothing and never
+// communicate, so a sequence's result does not depend on the batch it is stepped in.  Every product is step_matvec (step_common.h)
+// over prepared bf16 weights, the row lives in LDS between the stages, and the stages are a chain of dependent round trips.
+//
+// Arithmetic: the batch path's, row for row (functional._MfnGateFn and the scans it runs between): the left operand of every product
+// is rounded to bf16 (x_m, h_prev, cStar, relu(att1_fc1), attended, relu(att2_fc1), mem_prev, u, [h ; mem], relu(out_fc1)), every weight
+// is bf16, and sums, biases, the activations (sigmoid_f / tanh_f of scan_common.h), the softmax, c, h, mem and everything stored are
+// fp32.  No site depends on a tile, so the same reference serves the step and the batch path (tests/mfn_stream_ref.py).
+//
+// State discipline.  Step t reads copy t & 1 of (h, c, mem) and writes copy (t + 1) & 1: nothing written in a launch is read back in
+// it.  At t == 0 no word of either copy is read (zeros stand for the state, by branch, not by multiplying), so a state of any bit
+// pattern cannot reach a result and a new recording needs no launch.  Every address comes from (b < B, t & 1) and the plan's offsets
+// alone: t is a launch argument checked by the host, and the kernel returns at once when t < 0.  No address is derived from device data.
+#pragma once
+#include "common.h"
+#include "scan_common.h"                 // sigmoid_f, tanh_f
+#include "step_common.h"
+#include "mfn_step_plan.h"
+
+static_assert(MMT_MFN_STEP_THREADS == MMT_STEP_THREADS, "step_matvec is written for one workgroup size");
+
+struct MfnStepParams {
+    const float* x[MMT_MFN_STEP_MAX_MODS];     // (B, D_m) each
+    const float* mask;                         // (B) or nullptr
+    float* y;                                  // (B, output_dim)
+    char* state;
+    int t, B;
+    MfnStepPlan pl;
+};
+
+// mmt_mfn_stream_prepare: blockIdx.y = job.  A matrix job lays `rows` rows of a row-major fp32 source (leading dimension ld, columns
+// col0 .. col0 + K) into rows row0 .. of a prepared [KP / 8][nout][8] bf16 matrix; a vector job copies n floats (the sum of two
+// sources where a second is given) behind float dst0 of its destination.  Grid-stride over the destination.
+#define MMT_MFN_PREP_MATS 20
+#define MMT_MFN_PREP_VECS 14
+struct MfnPrepMat { const float* src; size_t dst; int ld, col0, rows, K, KP, nout, row0; };
+struct MfnPrepVec { const float* a; const float* b; size_t dst; int n, dst0; };
+struct MfnPrepParams {
+    char* state;
+    int nmat, nvec;
+    MfnPrepMat mat[MMT_MFN_PREP_MATS];
+    MfnPrepVec vec[MMT_MFN_PREP_VECS];
+};
+
+__global__ __launch_bounds__(256) void mfn_step_prep_kernel(const MfnPrepParams P) {
+    const int job = blockIdx.y;
+    const size_t first = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    if (job < P.nmat) {
+        const MfnPrepMat& J = P.mat[job];
+        bf16* dst = reinterpret_cast<bf16*>(P.state + J.dst);
+        const size_t total = (size_t)J.rows * J.KP;
+        for (size_t i = first; i < total; i += stride) {
+            const int j = (int)(i & 7);
+            const size_t r = i >> 3;
+            const int n = (int)(r % J.rows), k = (int)(r / J.rows) * 8 + j;
+            dst[((size_t)(k >> 3) * J.nout + J.row0 + n) * 8 + j] = k < J.K ? (bf16)J.src[(size_t)n * J.ld + J.col0 + k] : (bf16)0.f;
+        }
+    } else if (job - P.nmat < P.nvec) {
+        const MfnPrepVec& J = P.vec[job - P.nmat];
+        float* dst = reinterpret_cast<float*>(P.state + J.dst) + J.dst0;
+        for (size_t i = first; i < (size_t)J.n; i += stride) dst[i] = J.b ? J.a[i] + J.b[i] : J.a[i];
+    }
+}
+
+// maximum over the workgroup's 256 threads, the same value in every thread; red: 4 floats of LDS.  Two barriers.
+__device__ __forceinline__ float step_block_max(float v, float* red) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    __syncthreads();                                   // the previous use of red is over
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+__global__ __launch_bounds__(MMT_MFN_STEP_THREADS) void mfn_step_kernel(const MfnStepParams P) {
+    constexpr int MD = MMT_MFN_STEP_MD, HG = MMT_MFN_STEP_HG, SHM = MMT_MFN_STEP_MAX_SH;
+    __shared__ __attribute__((aligned(16))) float xs[MMT_MFN_STEP_MAX_MODS * MMT_MFN_STEP_MAX_IN];     // bf16(x_m), padded rows
+    __shared__ __attribute__((aligned(16))) float hs[SHM + 8 * MMT_MFN_STEP_MAX_MODS];                 // bf16(h_prev of m), padded rows
+    __shared__ __attribute__((aligned(16))) float pre[4 * SHM];                                        // gate pre-activations, [m][i f g o][H_m]
+    __shared__ __attribute__((aligned(16))) float cs[2 * SHM];                                         // cStar, fp32
+    __shared__ __attribute__((aligned(16))) float csr[2 * SHM];                                        // bf16(cStar)
+    __shared__ __attribute__((aligned(16))) float lg[2 * SHM];                                         // att1's logits
+    __shared__ __attribute__((aligned(16))) float at[2 * SHM];                                         // bf16(attended)
+    __shared__ __attribute__((aligned(16))) float a1[MMT_MFN_STEP_ATT1];                               // bf16(relu(att1_fc1))
+    __shared__ __attribute__((aligned(16))) float a2[MMT_MFN_STEP_ATT2];                               // bf16(relu(att2_fc1))
+    __shared__ __attribute__((aligned(16))) float memf[MD];                                            // mem_prev, fp32
+    __shared__ __attribute__((aligned(16))) float memr[MD];                                            // bf16(mem_prev)
+    __shared__ __attribute__((aligned(16))) float us[2 * HG];                                          // apre, then bf16(u)
+    __shared__ __attribute__((aligned(16))) float chat[MD];
+    __shared__ __attribute__((aligned(16))) float g1[MD];
+    __shared__ __attribute__((aligned(16))) float last[SHM + MD + 8];                                  // bf16([h of every modality ; mem])
+    __shared__ __attribute__((aligned(16))) float hid[MMT_MFN_STEP_OUTH];                              // bf16(relu(out_fc1))
+    __shared__ float red[4];
+
+    const int t = P.t;
+    if (t < 0) return;                                                           // the host refuses such a call
+    const MfnStepPlan& L = P.pl;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int SH = L.SH, A = L.A, nm = L.nm;
+    const bool first = t == 0;                                                   // uniform: no word of the state is read
+    float* dyn = reinterpret_cast<float*>(P.state + L.dyn_off);
+    const float* st_in = dyn + ((size_t)(t & 1) * P.B + b) * L.seq_floats;
+    float* st_out = dyn + ((size_t)((t & 1) ^ 1) * P.B + b) * L.seq_floats;
+    auto W = [&](size_t off) { return reinterpret_cast<const bf16*>(P.state + off); };
+    auto Bv = [&](size_t off) { return reinterpret_cast<const float*>(P.state + off); };
+
+    // the cell unit of this thread: modality mu, unit ju of it
+    int mu = 0;
+    for (int m = 1; m < nm; ++m) mu = tid >= L.hoff[m] ? m : mu;
+    const bool unit = tid < SH;
+    const int ju = tid - L.hoff[mu], Hu = L.H[mu];
+
+    // 0. stage x_m, h_prev and mem_prev (rounded where they feed a product); c_prev of this thread's unit stays in a register
+    float cprev = 0.f;
+    if (!first && unit) cprev = st_in[SH + tid];
+    for (int m = 0; m < nm; ++m) {
+        const int D = L.D[m], H = L.H[m];
+        const float* xr = P.x[m] + (size_t)b * D;
+        for (int k = tid; k < L.KPD[m]; k += MMT_MFN_STEP_THREADS) xs[L.xoff[m] + k] = k < D ? step_bf16_round(xr[k]) : 0.f;
+        for (int k = tid; k < L.KPH[m]; k += MMT_MFN_STEP_THREADS) {
+            float v = 0.f;
+            if (!first && k < H) v = step_bf16_round(st_in[L.hoff[m] + k]);
+            hs[L.hpoff[m] + k] = v;
+        }
+    }
+    if (tid < MD) {
+        float v = 0.f;
+        if (!first) v = st_in[2 * SH + tid];
+        memf[tid] = v; memr[tid] = step_bf16_round(v);
+    }
+    for (int k = L.KL + tid; k < L.KPL; k += MMT_MFN_STEP_THREADS) last[k] = 0.f;           // the pad of the read-out's input
+    __syncthreads();
+
+    // 1. LSTM cells (:207-208): pre = bf16(x) W_ih^T + (b_ih + b_hh) + bf16(h_prev) W_hh^T; a row has the same owner in both products
+    for (int m = 0; m < nm; ++m) {
+        float* pm = pre + 4 * L.hoff[m];
+        const float* bias = Bv(L.blstm[m]);
+        step_matvec(W(L.wih[m]), xs + L.xoff[m], L.KPD[m], 4 * L.H[m], [&](int n, float acc) { pm[n] = acc + bias[n]; });
+        if (!first) step_matvec(W(L.whh[m]), hs + L.hpoff[m], L.KPH[m], 4 * L.H[m], [&](int n, float acc) { pm[n] += acc; });
+    }
+    __syncthreads();
+    if (unit) {
+        const float* pm = pre + 4 * L.hoff[mu];
+        const float ig = sigmoid_f(pm[ju]), fg = sigmoid_f(pm[Hu + ju]), gg = tanh_f(pm[2 * Hu + ju]), og = sigmoid_f(pm[3 * Hu + ju]);
+        const float c = fg * cprev + ig * gg;
+        const float h = og * tanh_f(c);
+        st_out[tid] = h; st_out[SH + tid] = c;
+        // 2. cStar = [c_prev of every modality ; c_new of every modality] (:212-217)
+        cs[tid] = cprev; cs[SH + tid] = c;
+        csr[tid] = step_bf16_round(cprev); csr[SH + tid] = step_bf16_round(c);
+        last[tid] = step_bf16_round(h);
+    }
+    __syncthreads();
+
+    // 3. attention over the A features (:218-219), softmax_mul_fwd_kernel's formula
+    {
+        const float* b1 = Bv(L.b[MFN_B_A11]);
+        step_matvec(W(L.w[MFN_W_A11]), csr, A, MMT_MFN_STEP_ATT1, [&](int n, float acc) { a1[n] = step_bf16_round(fmaxf(acc + b1[n], 0.f)); });
+        __syncthreads();
+        const float* b2 = Bv(L.b[MFN_B_A12]);
+        step_matvec(W(L.w[MFN_W_A12]), a1, MMT_MFN_STEP_ATT1, A, [&](int n, float acc) { lg[n] = acc + b2[n]; });
+        __syncthreads();
+        float mx = -INFINITY;
+        for (int n = tid; n < A; n += MMT_MFN_STEP_THREADS) mx = fmaxf(mx, lg[n]);
+        mx = step_block_max(mx, red);
+        float sum = 0.f;
+        for (int n = tid; n < A; n += MMT_MFN_STEP_THREADS) sum += __expf(lg[n] - mx);
+        sum = step_block_sum(sum, red);
+        const float inv = 1.0f / sum;
+        for (int n = tid; n < A; n += MMT_MFN_STEP_THREADS) at[n] = step_bf16_round((__expf(lg[n] - mx) * inv) * cs[n]);
+        __syncthreads();
+    }
+
+    // 4. att2_fc1 and the gates' first layers (:220-223): all three read bf16(attended) or bf16(mem_prev) only
+    {
+        const float* b21 = Bv(L.b[MFN_B_A21]);
+        step_matvec(W(L.w[MFN_W_A21]), at, A, MMT_MFN_STEP_ATT2, [&](int n, float acc) { a2[n] = step_bf16_round(fmaxf(acc + b21[n], 0.f)); });
+        const float* bg = Bv(L.b[MFN_B_G1]);
+        step_matvec(W(L.w[MFN_W_WA]), at, A, 2 * HG, [&](int n, float acc) {                 // apre; with mem = 0 it is already u's argument
+            const float v = acc + bg[n];
+            us[n] = first ? step_bf16_round(fmaxf(v, 0.f)) : v;
+        });
+        if (!first)                                                                          // the same owner per row as the product above
+            step_matvec(W(L.w[MFN_W_WM]), memr, MD, 2 * HG, [&](int n, float acc) { us[n] = step_bf16_round(fmaxf(us[n] + acc, 0.f)); });
+        __syncthreads();
+    }
+
+    // 5. chat (:220), the gates (:222-223) and the memory (:224)
+    {
+        const float* b22 = Bv(L.b[MFN_B_A22]);
+        step_matvec(W(L.w[MFN_W_A22]), a2, MMT_MFN_STEP_ATT2, MD, [&](int n, float acc) { chat[n] = tanh_f(acc + b22[n]); });
+        const float* bz1 = Bv(L.b[MFN_B_G21]);
+        step_matvec(W(L.w[MFN_W_W21]), us, HG, MD, [&](int n, float acc) { g1[n] = sigmoid_f(acc + bz1[n]); });
+        __syncthreads();
+        const float* bz2 = Bv(L.b[MFN_B_G22]);
+        step_matvec(W(L.w[MFN_W_W22]), us + HG, HG, MD, [&](int n, float acc) {
+            const float mem = g1[n] * memf[n] + sigmoid_f(acc + bz2[n]) * chat[n];
+            st_out[2 * SH + n] = mem;
+            last[SH + n] = step_bf16_round(mem);
+        });
+        __syncthreads();
+    }
+
+    // 6. read-out (:241-247) and the window's mask
+    {
+        const float* bo1 = Bv(L.b[MFN_B_O1]);
+        step_matvec(W(L.w[MFN_W_O1]), last, L.KPL, MMT_MFN_STEP_OUTH, [&](int n, float acc) { hid[n] = step_bf16_round(fmaxf(acc + bo1[n], 0.f)); });
+        __syncthreads();
+        const float* bo2 = Bv(L.b[MFN_B_O2]);
+        const bool masked = P.mask != nullptr;
+        const float mk = masked ? P.mask[b] : 1.f;
+        step_matvec(W(L.w[MFN_W_O2]), hid, MMT_MFN_STEP_OUTH, L.OD, [&](int n, float acc) {
+            const float v = acc + bo2[n];
+            P.y[(size_t)b * L.OD + n] = masked ? v * mk : v;
+        });
+    }
+}

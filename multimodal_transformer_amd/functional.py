@@ -1619,6 +1619,107 @@ def encoder_stream_step(x_t, mask_t, flat_params, state, t, h, d_ff, n_layers, c
     return y
 
 
+# The MFN gate, one window per call (include/mmt_hip.h mmt_mfn_stream_*): eval mode, forward only.  The state (prepared bf16 weights,
+# fp32 biases, two copies of the carried (h, c, mem)) takes memory with any contents, so it comes from _scratch.
+_MFN_GATE_SHAPES = "att1_fc1 (128, A), att1_fc2 (A, 128), att2_fc1 (256, A), att2_fc2 (128, 256), gamma{1,2}_fc1 (64, A + 128), " \
+                   "gamma{1,2}_fc2 (128, 64), out_fc1 (64, sum H + 128), out_fc2 (output_dim, 64), A = 2 sum H"
+
+
+def _mfn_dims(in_dims, hidden):
+    in_dims, hidden = [int(v) for v in in_dims], [int(v) for v in hidden]
+    if len(in_dims) != len(hidden):
+        raise ValueError("mfn stream: %d input widths for %d hidden sizes" % (len(in_dims), len(hidden)))
+    n = len(in_dims)
+    return n, (ctypes.c_int * max(n, 1))(*in_dims), (ctypes.c_int * max(n, 1))(*hidden), in_dims, hidden
+
+
+def mfn_stream_bytes(B, in_dims, hidden, output_dim):
+    """Bytes of the MFN stream state for ``B`` sequences, modalities of input widths ``in_dims`` and LSTM hidden sizes ``hidden``;
+    ValueError, naming the limit, for a shape outside the step kernel's domain."""
+    lib = _lib.load()
+    n, cd, ch, _, _ = _mfn_dims(in_dims, hidden)
+    nbytes = lib.mmt_mfn_stream_bytes(int(B), n, cd, ch, int(output_dim))
+    if nbytes == 0:
+        raise ValueError((lib.mmt_last_error() or b"mfn stream: ?").decode())
+    return nbytes
+
+
+def mfn_stream_state(B, in_dims, hidden, output_dim, device):
+    """An unprepared MFN stream state on ``device`` (uint8; any contents)."""
+    return _scratch(mfn_stream_bytes(B, in_dims, hidden, output_dim), device)
+
+
+def _mfn_stream_state(op, state, nbytes, device):
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < nbytes:
+        raise ValueError("%s: state must be a contiguous uint8 tensor of at least %d bytes (mfn_stream_state)" % (op, nbytes))
+    if state.device != device:
+        raise ValueError("%s: state is on %s, the operands on %s" % (op, state.device, device))
+
+
+def mfn_stream_prepare(lstm_params, gate_params, state, B, in_dims, hidden, output_dim):
+    """Convert and copy every parameter of an MFN into ``state`` (one launch; the carried state is not touched): ``lstm_params`` per
+    modality (weight_ih, weight_hh, bias_ih, bias_hh) of its LSTMCell, ``gate_params`` the 20 gate tensors in ``_MfnGateFn``'s order.
+    Again after any parameter changes: a step reads the biases from the state too."""
+    op = "mfn_stream_prepare"
+    lstm = [q for cell in lstm_params for q in cell]
+    gate = list(gate_params)
+    if any(q.requires_grad and torch.is_grad_enabled() for q in lstm + gate):
+        raise NotImplementedError("%s: forward only, no autograd (parameters that require grad: pass detached tensors or call it under "
+                                  "torch.no_grad())" % op)
+    n, cd, ch, D, H = _mfn_dims(in_dims, hidden)
+    nbytes = mfn_stream_bytes(B, D, H, output_dim)
+    SH, MD, HG = sum(H), 128, 64
+    A = 2 * SH
+    want = [s for d, h in zip(D, H) for s in ((4 * h, d), (4 * h, h), (4 * h,), (4 * h,))]
+    if len(lstm) != 4 * n or [tuple(q.shape) for q in lstm] != want:
+        raise ValueError("%s: the LSTM cells' parameters have the shapes %s, expected %s" % (op, [tuple(q.shape) for q in lstm], want))
+    want = [(128, A), (128,), (A, 128), (A,), (256, A), (256,), (MD, 256), (MD,), (HG, A + MD), (HG,), (MD, HG), (MD,),
+            (HG, A + MD), (HG,), (MD, HG), (MD,), (64, SH + MD), (64,), (int(output_dim), 64), (int(output_dim),)]
+    if [tuple(q.shape) for q in gate] != want:
+        raise ValueError("%s: the gate's sizes are fixed in the step kernel (%s); got %s"
+                         % (op, _MFN_GATE_SHAPES, [tuple(q.shape) for q in gate]))
+    _lib.require_hip(state, *lstm, *gate)
+    _mfn_stream_state(op, state, nbytes, lstm[0].device)
+    keep = [_f32c(q) for q in lstm + gate]                                 # alive until the launch is enqueued
+    pl = (ctypes.c_void_p * len(lstm))(*[q.data_ptr() for q in keep[:len(lstm)]])
+    pg = (ctypes.c_void_p * 20)(*[q.data_ptr() for q in keep[len(lstm):]])
+    _lib.launch("mmt_mfn_stream_prepare", pl, pg, state, state.numel(), int(B), n, cd, ch, int(output_dim))
+
+
+def mfn_stream_step(xs, mask_t, state, t, in_dims, hidden, output_dim):
+    """Window t of an MFN gate: xs, per modality x_t (B, in_dims[m]); mask_t (B) or None -> y_t (B, output_dim) = MFN.forward(...)[:, t]
+    in eval mode, times mask_t (transformer/MFT/multiTransformer.py:200-247, :310), from the (h, c, mem) carried in ``state``
+    (mfn_stream_state, prepared by mfn_stream_prepare), which this call advances.  Steps of a recording run in order t = 0, 1, ...;
+    t is passed by value.  One launch.  Forward only: an input that requires grad raises NotImplementedError."""
+    op = "mfn_stream_step"
+    xs = list(xs)
+    if any(isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled() for a in xs + [mask_t]):
+        raise NotImplementedError("%s: forward only, no autograd (an input requires grad)" % op)
+    n, cd, ch, D, H = _mfn_dims(in_dims, hidden)
+    if len(xs) != n:
+        raise ValueError("%s: %d inputs for %d modalities" % (op, len(xs), n))
+    for x, d in zip(xs, D):
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] != d or x.shape[0] != xs[0].shape[0] \
+                or x.device != xs[0].device:
+            raise ValueError("%s: every x_t must be a float32 (B, %d) tensor on one device, got %s %s on %s"
+                             % (op, d, getattr(x, "dtype", type(x).__name__), tuple(getattr(x, "shape", ())), getattr(x, "device", None)))
+    B, dev = xs[0].shape[0], xs[0].device
+    if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != dev):
+        raise ValueError("%s: mask_t must hold one entry per sequence (B = %d) on %s" % (op, B, dev))
+    t = int(t)
+    if t < 0:
+        raise ValueError("%s: position t = %d is negative" % (op, t))
+    _lib.require_hip(*xs, state)
+    nbytes = mfn_stream_bytes(B, D, H, output_dim)
+    _mfn_stream_state(op, state, nbytes, dev)
+    keep = [_f32c(x) for x in xs]
+    px = (ctypes.c_void_p * n)(*[x.data_ptr() for x in keep])
+    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
+    y = torch.empty(B, int(output_dim), dtype=torch.float32, device=dev)
+    _lib.launch("mmt_mfn_stream_step", px, m_, y, state, state.numel(), t, B, n, cd, ch, int(output_dim))
+    return y
+
+
 def check_device_errors():
     """Synchronise and raise if an asynchronous kernel reported an error through its device error word (mmt_hip.h)."""
     _lib.ERRORS.check()

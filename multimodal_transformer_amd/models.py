@@ -113,7 +113,8 @@ class _FrontEnd(nn.Module):
 class _FrontEndStream:
     """``stream()`` of the MultiCNNTransformer wrappers: ``step({mod: (B, W, d_raw)}, mask_t)`` -> the (B,1) prediction of that window.
     The window encoder runs on a T = 1 batch (``_encode``), then the fusion layer where the model has one, then the sequence model's
-    own step (``multiTransformer._SequenceStream``).  ``reset()`` starts a new recording."""
+    own step (``multiTransformer._SequenceStream``; the MFT and B3-MFN take the per-modality rows as a dict:
+    ``multiTransformer._GateStream``).  ``reset()`` starts a new recording."""
 
     def __init__(self, model, batch, capacity):
         if model.training:
@@ -136,6 +137,8 @@ class _FrontEndStream:
                                  % (type(m).__name__, mod, B, tuple(x.shape)))
         with torch.no_grad():
             outs = m._encode({mod: inputs[mod].unsqueeze(1) for mod in m.mods})           # {mod: (B,1,F_mod)}
+            if getattr(self.seq, "takes_modalities", False):                              # the MFT and B3-MFN: no fusion, one row per modality
+                return self.seq.step({mod: outs[mod].reshape(B, -1) for mod in m.mods}, mask_t)
             if len(m.mods) > 1:
                 x = F_hip.cat_cols([outs[mod] for mod in m.mods])
                 if getattr(m, "fusionLayer", None) is not None:
@@ -202,6 +205,14 @@ class MultiCNNTransformerMFT(_FrontEnd):
                                       "implemented (a single-modality model streams)")
         return _FrontEndStream(self, batch, capacity)
 
+    def stream_modalities(self, batch, capacity):
+        """More than one modality: the MFT's stream (``MultiTransformer.stream``) behind the window encoder, ``step({mod: (B, W, d_raw)},
+        mask_t)`` -> (B,1).  Eval mode, ``causal_attention(model)`` on.  One modality: ValueError, ``stream`` serves that model."""
+        if len(self.mods) < 2:
+            raise ValueError("MultiCNNTransformerMFT.stream_modalities: with one modality the sequence model is the UniTransformer, not "
+                             "the MFT: call stream(batch, capacity)")
+        return _FrontEndStream(self, batch, capacity)
+
 
 class MultiCNNTransformerB2(_FrontEnd):
     """B2-Trans: transformer/B2-Trans/models.py:81-134 (single modality; the fusion layer is commented out there)."""
@@ -245,6 +256,14 @@ class MultiCNNTransformerB3(_FrontEnd):
         if len(self.mods) > 1:
             return self.Transformer(outs, mask, length)
         return self.Transformer(outs[self.mods[0]], mask, length)
+
+    def stream(self, batch, capacity=None):
+        """This model as an online predictor (``_FrontEndStream``): eval mode.  More than one modality: B3-MFN has no attention, so no
+        cache, no length limit and no need for ``causal_attention``.  One modality: the UniTransformer's stream, which needs both."""
+        if len(self.mods) < 2 and capacity is None:
+            raise ValueError("MultiCNNTransformerB3.stream: with one modality the sequence model is the UniTransformer, whose K/V cache "
+                             "needs a capacity (windows per recording)")
+        return _FrontEndStream(self, batch, capacity)
 
 
 class _LocalAttnLSTM(nn.Module):

@@ -588,6 +588,135 @@ class MFN(nn.Module):
         out = F_hip.mfn_gate(hs, cs, self._gate_params(), pg, seed_g, po, seed_o)          # (T,B,output_dim)
         return F_hip.batch_major(out, mask)
 
+    def stream(self, batch):
+        """Open an ``MFNStream``: this gate as an online predictor for ``batch`` recordings, one window per ``step`` with the carried
+        (h, c, mem) instead of a forward over the whole prefix.  Eval mode, forward only; no attention, so no length limit.  Raises
+        ValueError, before any launch, for anything else."""
+        if self.training:
+            raise ValueError("MFN.stream: the gate is in train mode; streaming is eval-mode inference (call .eval())")
+        dev = self.out_fc2.weight.device
+        if dev.type != "cuda":
+            raise ValueError("MFN.stream: the gate is on %s; move it to a HIP device (there is no CPU path)" % dev)
+        return MFNStream(self, batch)
+
+
+class MFNStream:
+    """An ``MFN`` gate run one window at a time (``MFN.stream``): ``step({mod: (B, dims[mod])}, mask_t)`` returns the (B, output_dim)
+    row that the gate's eval forward gives at position ``t`` of the windows stepped so far (times ``mask_t``), in ONE kernel launch
+    (csrc/mfn_step.h), and advances ``t``.  The state holds the bf16 copy of every weight matrix, the fp32 biases and two copies of
+    the carried (h, c, mem) of ``batch`` sequences.
+
+    ``reset()`` starts a new recording: it sets ``t`` back to 0 and neither clears nor re-reads anything.  ``refresh()`` converts
+    and copies the parameters again: call it after ANY parameter of the gate changed.  Unlike ``EncoderStream``, which reads biases
+    and LayerNorm weights live, the biases here are copies made at ``refresh()`` (``b_ih + b_hh`` already summed): the step kernel
+    reads nothing but its inputs and the state.  Rows have the batch path's rounding sites exactly and agree with it to fp32
+    summation order."""
+
+    def __init__(self, mfn, batch):
+        self.mfn, self.batch, self.t = mfn, int(batch), 0
+        self.mods = list(mfn.mods)
+        self.in_dims = [mfn.lstm[m].input_size for m in self.mods]
+        self.hidden = [mfn.lstm[m].hidden_size for m in self.mods]
+        self.output_dim = mfn.out_fc2.out_features
+        self.device = mfn.out_fc2.weight.device
+        if self.batch < 1:
+            raise ValueError("MFN.stream: batch must be at least 1, got %d" % self.batch)
+        self.state = F_hip.mfn_stream_state(self.batch, self.in_dims, self.hidden, self.output_dim, self.device)   # ValueError naming the limit
+        self.refresh()
+
+    def refresh(self):
+        """Convert and copy the gate's current parameters, biases included, into the state (one launch); (h, c, mem) and ``t`` stay."""
+        cells = [tuple(q.detach() for q in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)) for c in (self.mfn.lstm[m] for m in self.mods)]
+        F_hip.mfn_stream_prepare(cells, [q.detach() for q in self.mfn._gate_params()], self.state, self.batch, self.in_dims, self.hidden,
+                                 self.output_dim)
+
+    def reset(self):
+        self.t = 0
+
+    def step(self, inputs, mask_t=None):
+        """inputs {mod: (B, dims[mod]) float32 on the gate's device}, mask_t (B), (B,1) or (B,1,1) or None -> (B, output_dim)."""
+        xs = _modality_rows("MFNStream.step", inputs, self.mods, self.in_dims, self.batch, self.device, mask_t)
+        y = F_hip.mfn_stream_step(xs, mask_t, self.state, self.t, self.in_dims, self.hidden, self.output_dim)
+        self.t += 1
+        return y
+
+
+def _modality_rows(op, inputs, mods, widths, B, device, mask_t):
+    """The checks of a per-modality step, all before any launch -> the rows in the order of ``mods``."""
+    if not isinstance(inputs, dict) or any(m not in inputs for m in mods):
+        raise ValueError("%s: inputs must be a dict with a row for every modality %s, got %s"
+                         % (op, mods, sorted(inputs) if isinstance(inputs, dict) else type(inputs).__name__))
+    for m, d in zip(mods, widths):
+        x = inputs[m]
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != device:
+            raise ValueError("%s: inputs[%r] must be a float32 tensor on %s, got %s on %s"
+                             % (op, m, device, getattr(x, "dtype", type(x).__name__), getattr(x, "device", None)))
+        if tuple(x.shape) != (B, d):
+            raise ValueError("%s: inputs[%r] must have the shape (%d,%d), got %s" % (op, m, B, d, tuple(x.shape)))
+    if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != device):
+        raise ValueError("%s: mask_t must hold one entry per sequence (%d) on %s" % (op, B, device))
+    return [inputs[m] for m in mods]
+
+
+class _GateStream:
+    """``stream()`` of MultiTransformer (the MFT) and MultiTransformerB3: ``step({mod: (B, window_embed_size[mod])}, mask_t)`` -> the
+    (B,1) prediction of that window, what the model's eval forward gives at [:, t] (the MFT: with causal attention on).  Per modality
+    the embed affine map and, in the MFT, the encoder's step; then ONE launch for the whole MFN gate (``MFNStream``).  ``reset()``
+    starts a new recording.
+
+    ``modality_streams`` (an attribute; on for the MFT, off for B3-MFN): the per-modality launches run on ``_MOD_STREAMS`` as in the
+    batch forward, joined in front of the gate's launch.  Kept where it measured faster at B = 32 on the AVL models at the reference
+    sizes.  The MFT: 311 us forked against 560 us on one stream at t = 0, 574 us against 1225 us at t = 499: an encoder
+    step at d = 256, N = 6 is long enough for the fork and join to pay.  B3-MFN, whose modalities only run their embed: 181 us forked
+    against 126 us on one stream.  ``MMT_MODALITY_STREAMS=0`` serialises the MFT's step too."""
+
+    takes_modalities = True          # models._FrontEndStream hands such a stream the per-modality dict
+
+    def __init__(self, model, batch, capacity):
+        _stream_model_checks(model)
+        self.model, self.batch = model, int(batch)
+        self.mods = list(model.mods)
+        self.widths = [model.embed[m].in_features for m in self.mods]
+        stacks = getattr(model, "transformer", None)
+        if stacks is not None and capacity is None:
+            raise ValueError("%s.stream: the encoders' K/V cache needs a capacity (windows per recording)" % type(model).__name__)
+        self.encs = None if stacks is None else {m: stacks[m].stream(batch, capacity) for m in self.mods}      # their refusals pass through
+        self.gate = model.mfn.stream(batch)
+        self.device = self.gate.device
+        self.modality_streams = self.encs is not None
+
+    t = property(lambda self: self.gate.t)
+    capacity = property(lambda self: None if self.encs is None else self.encs[self.mods[0]].capacity)
+
+    def reset(self):
+        self.gate.reset()
+        for e in (self.encs or {}).values():
+            e.reset()
+
+    def refresh(self):
+        self.gate.refresh()
+        for e in (self.encs or {}).values():
+            e.refresh()
+
+    def step(self, inputs, mask_t=None):
+        m, B = self.model, self.batch
+        op = "%s stream step" % type(m).__name__
+        xs = _modality_rows(op, inputs, self.mods, self.widths, B, self.device, mask_t)
+        if self.encs is not None and self.t >= self.capacity:
+            raise ValueError("%s: the stream is full (t = capacity = %d)" % (op, self.capacity))
+        with torch.no_grad():
+            r = None if mask_t is None else mask_t.float().reshape(B)
+            rows = {}
+            fork = self.modality_streams and len(self.mods) > 1
+            main, streams = _MOD_STREAMS.begin(self.device, len(self.mods)) if fork else (None, [None] * len(self.mods))
+            for mod, x, st in zip(self.mods, xs, streams):
+                with torch.cuda.stream(st):                                # None: the caller's stream
+                    e = _SequenceStream._affine(x, m.embed[mod])
+                    rows[mod] = e if self.encs is None else self.encs[mod].step(e, r)
+            if fork:
+                _MOD_STREAMS.end(main, streams, list(rows.values()))
+            return self.gate.step(rows, r)
+
 
 class MultiTransformer(nn.Module):
     """MFT sequence model (transformer/MFT/multiTransformer.py:250-313): per-modality Linear embed ->
@@ -627,6 +756,11 @@ class MultiTransformer(nn.Module):
         _MOD_STREAMS.end(main, streams, list(gate_in.values()))
         return self.mfn._gate(gate_in, mask)                         # ... * mask (:310) in the gate's last pass
 
+    def stream(self, batch, capacity):
+        """The MFT as an online predictor: ``.step({mod: (B, window_embed_size[mod])}, mask_t)`` -> the (B,1) prediction of window t
+        (``_GateStream``).  Eval mode, ``causal_attention(model)`` on; the encoders' own refusals pass through, before any launch."""
+        return _GateStream(self, batch, capacity)
+
 
 class MultiTransformerB3(nn.Module):
     """B3-MFN sequence model (transformer/B3-MFN/multiTransformer.py:250-307): the MFT model without its encoder stacks — per-modality
@@ -654,6 +788,12 @@ class MultiTransformerB3(nn.Module):
                 gate_in[mod] = F_hip.time_major(e)                    # the reference's permute(1,0,2), :294
         _MOD_STREAMS.end(main, streams, list(gate_in.values()))
         return self.mfn._gate(gate_in, mask)                         # ... * mask (:304) in the gate's last pass
+
+    def stream(self, batch, capacity=None):
+        """B3-MFN as an online predictor: ``.step({mod: (B, window_embed_size[mod])}, mask_t)`` -> the (B,1) prediction of window t
+        (``_GateStream``).  Eval mode.  No attention, so no cache: ``capacity`` is accepted and ignored, a recording has no length
+        limit, and ``causal_attention`` is not needed."""
+        return _GateStream(self, batch, capacity)
 
 
 class _DecoderMixin:
