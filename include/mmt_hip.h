@@ -281,6 +281,26 @@ int mmt_mfn_stream_prepare(const float* const* lstm_params, const float* const* 
 int mmt_mfn_stream_step(const float* const* x_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,
                         int t, int B, int nmods, const int* in_dims, const int* hidden, int output_dim, mmt_stream_t stream);
 
+/* ---- Slots: the positioned forms of both steps (opt-in).  The position of every sequence lives in DEVICE memory, `pos` (B ints), and
+ * the kernel reads it, runs that window and advances it itself, so a step carries no host-side position: it can be captured into a
+ * hipGraph and replayed, and the sequences of a batch may start and end at different calls.  Per sequence b (csrc/step_slots.h):
+ *   pos[b] < 0                  idle: y_t[b] is written as zeros; nothing else is written, pos[b] stays
+ *   0 <= pos[b] < limit         the step above at t = pos[b], bit for bit; then, if advance != 0, pos[b] = pos[b] + 1
+ *   pos[b] >= limit, INT_MAX    full: as idle, and pos[b] stays, so the host can see it
+ * A slot is seated by storing 0 to pos[b] and released by storing a negative value, between launches on the step's stream; at
+ * position 0 no carried state and no cache row is read, so nothing else is needed.  No host-side check of the positions: the check is
+ * the kernel's.  Plans, state layout, *_bytes and *_prepare are those above, and one state serves both forms.  A null `pos` is
+ * MMT_EINVAL before any launch; every refusal of the step above passes through. */
+/* The encoder step at t = pos[b]; the limit is `capacity`.                    (Encoder.forward, :73-76; departs from :27-31) */
+int mmt_encoder_stream_step_slots(const float* x_t, const float* mask_t, const float* params, float* y_t,
+                                  void* state, size_t state_bytes, int* pos, int advance,
+                                  int B, int capacity, int d, int h, int f, int n_layers, float eps, mmt_stream_t stream);
+/* The MFN gate step at t = pos[b]: copy pos[b] & 1 of the carried state is read and the other written, per sequence.  limit <= 0: no
+ * limit (a gate has no cache); a gate behind encoders passes their capacity.   (MFN.forward, :200-247; :310) */
+int mmt_mfn_stream_step_slots(const float* const* x_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,
+                              int* pos, int limit, int advance,
+                              int B, int nmods, const int* in_dims, const int* hidden, int output_dim, mmt_stream_t stream);
+
 /* ---- Fused affine map  y = act(x W^T + b) [* rowscale] on bf16 MFMA.
  * Replaces nn.Linear (+ F.relu) call sites of the path: PositionwiseFeedForward (:15-20), the four
  * attention projections (:43,55,65), embeds and read-out MLPs (:270,296,340-342,400-402).

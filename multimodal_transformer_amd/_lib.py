@@ -64,6 +64,9 @@ SIGNATURES = {
     "mmt_mfn_stream_bytes": (_SZ, [_I, _I, _P, _P, _I]),
     "mmt_mfn_stream_prepare": (_I, [_P, _P, _P, _SZ, _I, _I, _P, _P, _I, _P]),
     "mmt_mfn_stream_step": (_I, [_P, _P, _P, _P, _SZ, _I, _I, _I, _P, _P, _I, _P]),
+    # slots: the position of each sequence in device memory, int32 (B,), and `advance` (the gate: `limit` in front of it) for the host's t
+    "mmt_encoder_stream_step_slots": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _I] + [_I] * 6 + [_F, _P]),
+    "mmt_mfn_stream_step_slots": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
     "mmt_linear_workspace_bytes": (_SZ, [_I] * 3),
     "mmt_linear_forward": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),
     "mmt_linear_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),

@@ -24,10 +24,20 @@
 // behind position t cannot reach a result.  Every cache address comes from (b, layer, head, j <= t < capacity) alone: t and capacity
 // are launch arguments checked by the host, and the kernel returns at once when t is outside [0, capacity).  No address is derived
 // from device data.
+//
+// The positioned form, encoder_step_slots_kernel: the same body (a compile-time switch, as attn.h's plain / keys / causal), with the
+// position of each sequence read from device memory, int pos[B] (step_slots.h).  Workgroup b reads p = pos[b] once, before anything
+// else, makes it wave-uniform (readfirstlane: the sweeps' trip counts stay scalar, as with t a launch argument) and decodes it.  An idle
+// or full slot is skipped: its row of y is written as zeros and nothing else, no cache row, no pos.  Otherwise the body runs with t = p,
+// and if `advance` is set one thread stores p + 1 to pos[b] after the last stage.  No other workgroup reads pos[b], so both contracts
+// above hold: nothing written in a launch is read back in it, and workgroups do not communicate.  The last sentence of the cache
+// discipline changes for this form: every address derived from pos[b] passes slot_decode first, with the limit (capacity) taken from
+// the launch arguments, so such an address is that of a row j <= t < capacity exactly as above.
 #pragma once
 #include "common.h"
 #include "encoder_step_plan.h"
 #include "step_common.h"          // step_bf16_round, step_block_sum, step_matvec
+#include "step_slots.h"           // slot_decode
 
 struct EncStepParams {
     const float* x;            // (B, d)
@@ -86,7 +96,9 @@ __device__ __forceinline__ void step_ln_stats(const float* xs, int d, float eps,
 
 #define MMT_STEP_KEYS_INFLIGHT 4       // keys a lane has in flight in an attention sweep
 
-__global__ __launch_bounds__(MMT_STEP_THREADS) void encoder_step_kernel(const EncStepParams P) {
+// SLOTS false: t = P.t (pos and advance unused).  SLOTS true: t = slot_decode(pos[b], capacity), P.t unused.
+template <bool SLOTS>
+__device__ __forceinline__ void encoder_step_body(const EncStepParams& P, int* pos, int advance) {
     __shared__ __attribute__((aligned(16))) float xs[MMT_STEP_MAX_D];            // the residual row, fp32
     __shared__ __attribute__((aligned(16))) float ns[MMT_STEP_MAX_D];            // bf16(LayerNorm) / the merged bf16 context, as floats
     __shared__ __attribute__((aligned(16))) float hs[MMT_STEP_MAX_F];            // bf16(relu(hid))
@@ -95,10 +107,23 @@ __global__ __launch_bounds__(MMT_STEP_THREADS) void encoder_step_kernel(const En
     __shared__ __attribute__((aligned(16))) float vs[MMT_STEP_MAX_HDKP];
     __shared__ float red[4];
 
-    const int t = P.t;
-    if (t < 0 || t >= P.capacity) return;                                        // the host refuses such a call; never index the cache with it
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x;
+    int t;
+    // Where p + 1 goes after the last stage (null: nowhere).  Thread 0 parks the address in LDS and fetches it back itself at the end:
+    // held in SGPRs across the whole body, which already spills ~220 of them to VGPR lanes, it cost the kernel a private segment.
+    __shared__ int* next;
+    if (SLOTS && tid == 0) next = advance != 0 ? pos + b : nullptr;
+    if (SLOTS) {
+        t = slot_decode(__builtin_amdgcn_readfirstlane(pos[b]), P.capacity);     // the one read of pos[b]; uniform, so t lives in an SGPR
+        if (t == MMT_SLOT_SKIP) {                                                // idle or full: a zero row and nothing else
+            for (int n = tid; n < P.d; n += MMT_STEP_THREADS) P.y[(size_t)b * P.d + n] = 0.f;
+            return;
+        }
+    } else {
+        t = P.t;
+        if (t < 0 || t >= P.capacity) return;                                    // the host refuses such a call; never index the cache with it
+    }
     const int d = P.d, h = P.h, f = P.f, dk = P.dk, dkp = P.dkp, nchunk = P.nchunk, KPd = P.KPd, KPf = P.KPf;
     const bool blank = P.mask != nullptr && P.mask[b] == 0.f;
 
@@ -265,4 +290,14 @@ __global__ __launch_bounds__(MMT_STEP_THREADS) void encoder_step_kernel(const En
     const float* fb = P.params + P.pl.final_b;
     for (int n = tid; n < d; n += MMT_STEP_THREADS)
         P.y[(size_t)b * d + n] = fa[n] * ((xs[n] - mean) * rstd) + fb[n];
+    if (SLOTS && tid == 0) {
+        int* const w = next;
+        if (w != nullptr) *w = t + 1;                                            // t < capacity <= 4096: no overflow.  Read by the next launch only
+    }
+}
+
+__global__ __launch_bounds__(MMT_STEP_THREADS) void encoder_step_kernel(const EncStepParams P) { encoder_step_body<false>(P, nullptr, 0); }
+
+__global__ __launch_bounds__(MMT_STEP_THREADS) void encoder_step_slots_kernel(const EncStepParams P, int* pos, int advance) {
+    encoder_step_body<true>(P, pos, advance);
 }

@@ -16,11 +16,20 @@
 // it.  At t == 0 no word of either copy is read (zeros stand for the state, by branch, not by multiplying), so a state of any bit
 // pattern cannot reach a result and a new recording needs no launch.  Every address comes from (b < B, t & 1) and the plan's offsets
 // alone: t is a launch argument checked by the host, and the kernel returns at once when t < 0.  No address is derived from device data.
+//
+// The positioned form, mfn_step_slots_kernel: the same body (a compile-time switch), with the position of each sequence read from
+// device memory, int pos[B] (step_slots.h).  Workgroup b reads p = pos[b] once, before anything else, makes it wave-uniform
+// (readfirstlane) and decodes it against the launch argument `limit` (<= 0: none).  An idle or full slot is skipped: its row of y is
+// written as zeros and nothing else, no carried state, no pos.  Otherwise the body runs with t = p: copy p & 1 is read and the other
+// written, per sequence, and if `advance` is set one thread stores p + 1 to pos[b] after the last stage.  No other workgroup reads
+// pos[b], so both contracts above hold.  The last sentence of the state discipline changes for this form: every address derived from
+// pos[b] passes slot_decode first, with the limit taken from the launch arguments; what it lets through only selects the copy, p & 1.
 #pragma once
 #include "common.h"
 #include "scan_common.h"                 // sigmoid_f, tanh_f
 #include "step_common.h"
 #include "mfn_step_plan.h"
+#include "step_slots.h"                  // slot_decode
 
 static_assert(MMT_MFN_STEP_THREADS == MMT_STEP_THREADS, "step_matvec is written for one workgroup size");
 
@@ -77,7 +86,9 @@ __device__ __forceinline__ float step_block_max(float v, float* red) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-__global__ __launch_bounds__(MMT_MFN_STEP_THREADS) void mfn_step_kernel(const MfnStepParams P) {
+// SLOTS false: t = P.t (pos, limit and advance unused).  SLOTS true: t = slot_decode(pos[b], limit), P.t unused.
+template <bool SLOTS>
+__device__ __forceinline__ void mfn_step_body(const MfnStepParams& P, int* pos, int limit, int advance) {
     constexpr int MD = MMT_MFN_STEP_MD, HG = MMT_MFN_STEP_HG, SHM = MMT_MFN_STEP_MAX_SH;
     __shared__ __attribute__((aligned(16))) float xs[MMT_MFN_STEP_MAX_MODS * MMT_MFN_STEP_MAX_IN];     // bf16(x_m), padded rows
     __shared__ __attribute__((aligned(16))) float hs[SHM + 8 * MMT_MFN_STEP_MAX_MODS];                 // bf16(h_prev of m), padded rows
@@ -97,10 +108,19 @@ __global__ __launch_bounds__(MMT_MFN_STEP_THREADS) void mfn_step_kernel(const Mf
     __shared__ __attribute__((aligned(16))) float hid[MMT_MFN_STEP_OUTH];                              // bf16(relu(out_fc1))
     __shared__ float red[4];
 
-    const int t = P.t;
-    if (t < 0) return;                                                           // the host refuses such a call
     const MfnStepPlan& L = P.pl;
     const int tid = threadIdx.x, b = blockIdx.x;
+    int t;
+    if (SLOTS) {
+        t = slot_decode(__builtin_amdgcn_readfirstlane(pos[b]), limit);          // the one read of pos[b]; uniform, so t lives in an SGPR
+        if (t == MMT_SLOT_SKIP) {                                                // idle or full: a zero row and nothing else
+            for (int n = tid; n < L.OD; n += MMT_MFN_STEP_THREADS) P.y[(size_t)b * L.OD + n] = 0.f;
+            return;
+        }
+    } else {
+        t = P.t;
+        if (t < 0) return;                                                       // the host refuses such a call
+    }
     const int SH = L.SH, A = L.A, nm = L.nm;
     const bool first = t == 0;                                                   // uniform: no word of the state is read
     float* dyn = reinterpret_cast<float*>(P.state + L.dyn_off);
@@ -219,4 +239,11 @@ __global__ __launch_bounds__(MMT_MFN_STEP_THREADS) void mfn_step_kernel(const Mf
             P.y[(size_t)b * L.OD + n] = masked ? v * mk : v;
         });
     }
+    if (SLOTS && advance != 0 && tid == 0) pos[b] = t + 1;                       // t < INT_MAX by slot_decode: no overflow.  Read by the next launch only
+}
+
+__global__ __launch_bounds__(MMT_MFN_STEP_THREADS) void mfn_step_kernel(const MfnStepParams P) { mfn_step_body<false>(P, nullptr, 0, 0); }
+
+__global__ __launch_bounds__(MMT_MFN_STEP_THREADS) void mfn_step_slots_kernel(const MfnStepParams P, int* pos, int limit, int advance) {
+    mfn_step_body<true>(P, pos, limit, advance);
 }

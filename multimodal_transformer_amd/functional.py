@@ -1590,12 +1590,8 @@ def encoder_stream_prepare(flat_params, state, B, capacity, d, h, d_ff, n_layers
     _lib.launch("mmt_encoder_stream_prepare", p_, state, state.numel(), int(B), int(capacity), int(d), int(h), int(d_ff), int(n_layers))
 
 
-def encoder_stream_step(x_t, mask_t, flat_params, state, t, h, d_ff, n_layers, capacity, eps=1e-6):
-    """Row t of a causal encoder stack: x_t (B,d), mask_t (B) or None -> y_t (B,d) = Encoder.forward(x, mask)[:, t] with causal attention
-    on (transformer/MFT/multiTransformer.py:73-76; departs from :27-31), from the K/V cache in ``state`` (encoder_stream_state, prepared
-    by encoder_stream_prepare), to which this window's keys and values are appended.  Steps of a recording run in order t = 0, 1, ...;
-    t is passed by value.  One launch.  Forward only: an input that requires grad raises NotImplementedError."""
-    op = "encoder_stream_step"
+def _encoder_step_inputs(op, x_t, mask_t):
+    """The checks of an encoder step's inputs that need no device -> (B, d)."""
     if any(isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled() for a in (x_t, mask_t)):
         raise NotImplementedError("%s: forward only, no autograd (an input requires grad)" % op)
     if not isinstance(x_t, torch.Tensor) or x_t.dim() != 2 or x_t.dtype != torch.float32:
@@ -1604,6 +1600,25 @@ def encoder_stream_step(x_t, mask_t, flat_params, state, t, h, d_ff, n_layers, c
     B, d = x_t.shape
     if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != x_t.device):
         raise ValueError("%s: mask_t must hold one entry per sequence (B = %d) on %s" % (op, B, x_t.device))
+    return B, d
+
+
+def _stream_positions(op, positions, B, device):
+    """``positions`` of a slots step: the int32 (B) tensor the kernel reads and advances in place, so nothing may stand in for it."""
+    if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32 or tuple(positions.shape) != (B,) \
+            or not positions.is_contiguous() or positions.device != device:
+        raise ValueError("%s: positions must be a contiguous int32 (%d,) tensor on %s (the kernel advances it in place), got %s %s on %s"
+                         % (op, B, device, getattr(positions, "dtype", type(positions).__name__),
+                            tuple(getattr(positions, "shape", ())), getattr(positions, "device", None)))
+
+
+def encoder_stream_step(x_t, mask_t, flat_params, state, t, h, d_ff, n_layers, capacity, eps=1e-6):
+    """Row t of a causal encoder stack: x_t (B,d), mask_t (B) or None -> y_t (B,d) = Encoder.forward(x, mask)[:, t] with causal attention
+    on (transformer/MFT/multiTransformer.py:73-76; departs from :27-31), from the K/V cache in ``state`` (encoder_stream_state, prepared
+    by encoder_stream_prepare), to which this window's keys and values are appended.  Steps of a recording run in order t = 0, 1, ...;
+    t is passed by value.  One launch.  Forward only: an input that requires grad raises NotImplementedError."""
+    op = "encoder_stream_step"
+    B, d = _encoder_step_inputs(op, x_t, mask_t)
     t, capacity = int(t), int(capacity)
     if not 0 <= t < capacity:
         raise ValueError("%s: position t = %d outside [0, capacity = %d): open a stream with a larger capacity" % (op, t, capacity))
@@ -1616,6 +1631,28 @@ def encoder_stream_step(x_t, mask_t, flat_params, state, t, h, d_ff, n_layers, c
     y = torch.empty_like(x_)
     _lib.launch("mmt_encoder_stream_step", x_, m_, p_, y, state, state.numel(), t, B, capacity, d, int(h), int(d_ff), int(n_layers),
                 float(eps))
+    return y
+
+
+def encoder_stream_step_slots(x_t, mask_t, flat_params, state, positions, h, d_ff, n_layers, capacity, eps=1e-6, advance=True):
+    """``encoder_stream_step`` with the position of every sequence in device memory (csrc/step_slots.h): ``positions`` int32 (B), read by
+    the kernel.  Row b is the row of ``encoder_stream_step`` at t = positions[b], bit for bit, where 0 <= positions[b] < capacity, and
+    zeros, with nothing else written, where the slot is idle (negative) or full (>= capacity).  ``advance``: the kernel adds 1 to the
+    position of every slot it ran.  No position crosses the host, so the call can be captured into a graph; the capacity check is the
+    kernel's.  One launch."""
+    op = "encoder_stream_step_slots"
+    B, d = _encoder_step_inputs(op, x_t, mask_t)
+    _stream_positions(op, positions, B, x_t.device)
+    capacity = int(capacity)
+    _lib.require_hip(x_t, flat_params, state)
+    nbytes = encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers)
+    p_ = _stream_params(op, flat_params, d, d_ff, n_layers)
+    _stream_state(op, state, nbytes, x_t.device)
+    x_ = _f32c(x_t)
+    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
+    y = torch.empty_like(x_)
+    _lib.launch("mmt_encoder_stream_step_slots", x_, m_, p_, y, state, state.numel(), positions, int(bool(advance)), B, capacity, d, int(h),
+                int(d_ff), int(n_layers), float(eps))
     return y
 
 
@@ -1686,12 +1723,8 @@ def mfn_stream_prepare(lstm_params, gate_params, state, B, in_dims, hidden, outp
     _lib.launch("mmt_mfn_stream_prepare", pl, pg, state, state.numel(), int(B), n, cd, ch, int(output_dim))
 
 
-def mfn_stream_step(xs, mask_t, state, t, in_dims, hidden, output_dim):
-    """Window t of an MFN gate: xs, per modality x_t (B, in_dims[m]); mask_t (B) or None -> y_t (B, output_dim) = MFN.forward(...)[:, t]
-    in eval mode, times mask_t (transformer/MFT/multiTransformer.py:200-247, :310), from the (h, c, mem) carried in ``state``
-    (mfn_stream_state, prepared by mfn_stream_prepare), which this call advances.  Steps of a recording run in order t = 0, 1, ...;
-    t is passed by value.  One launch.  Forward only: an input that requires grad raises NotImplementedError."""
-    op = "mfn_stream_step"
+def _mfn_step_inputs(op, xs, mask_t, in_dims, hidden):
+    """The checks of a gate step's inputs that need no device -> (xs, n, cd, ch, D, H, B, device)."""
     xs = list(xs)
     if any(isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled() for a in xs + [mask_t]):
         raise NotImplementedError("%s: forward only, no autograd (an input requires grad)" % op)
@@ -1706,6 +1739,16 @@ def mfn_stream_step(xs, mask_t, state, t, in_dims, hidden, output_dim):
     B, dev = xs[0].shape[0], xs[0].device
     if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != dev):
         raise ValueError("%s: mask_t must hold one entry per sequence (B = %d) on %s" % (op, B, dev))
+    return xs, n, cd, ch, D, H, B, dev
+
+
+def mfn_stream_step(xs, mask_t, state, t, in_dims, hidden, output_dim):
+    """Window t of an MFN gate: xs, per modality x_t (B, in_dims[m]); mask_t (B) or None -> y_t (B, output_dim) = MFN.forward(...)[:, t]
+    in eval mode, times mask_t (transformer/MFT/multiTransformer.py:200-247, :310), from the (h, c, mem) carried in ``state``
+    (mfn_stream_state, prepared by mfn_stream_prepare), which this call advances.  Steps of a recording run in order t = 0, 1, ...;
+    t is passed by value.  One launch.  Forward only: an input that requires grad raises NotImplementedError."""
+    op = "mfn_stream_step"
+    xs, n, cd, ch, D, H, B, dev = _mfn_step_inputs(op, xs, mask_t, in_dims, hidden)
     t = int(t)
     if t < 0:
         raise ValueError("%s: position t = %d is negative" % (op, t))
@@ -1717,6 +1760,27 @@ def mfn_stream_step(xs, mask_t, state, t, in_dims, hidden, output_dim):
     m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
     y = torch.empty(B, int(output_dim), dtype=torch.float32, device=dev)
     _lib.launch("mmt_mfn_stream_step", px, m_, y, state, state.numel(), t, B, n, cd, ch, int(output_dim))
+    return y
+
+
+def mfn_stream_step_slots(xs, mask_t, state, positions, in_dims, hidden, output_dim, limit=None, advance=True):
+    """``mfn_stream_step`` with the position of every sequence in device memory (csrc/step_slots.h): ``positions`` int32 (B), read by the
+    kernel.  Row b is the row of ``mfn_stream_step`` at t = positions[b], bit for bit (copy positions[b] & 1 of the carried state read,
+    the other written), where the slot is seated, and zeros, with nothing else written, where it is idle (negative) or full
+    (>= ``limit``; None: no limit).  ``advance``: the kernel adds 1 to the position of every slot it ran.  No position crosses the host,
+    so the call can be captured into a graph.  One launch."""
+    op = "mfn_stream_step_slots"
+    xs, n, cd, ch, D, H, B, dev = _mfn_step_inputs(op, xs, mask_t, in_dims, hidden)
+    _stream_positions(op, positions, B, dev)
+    _lib.require_hip(*xs, state)
+    nbytes = mfn_stream_bytes(B, D, H, output_dim)
+    _mfn_stream_state(op, state, nbytes, dev)
+    keep = [_f32c(x) for x in xs]
+    px = (ctypes.c_void_p * n)(*[x.data_ptr() for x in keep])
+    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
+    y = torch.empty(B, int(output_dim), dtype=torch.float32, device=dev)
+    _lib.launch("mmt_mfn_stream_step_slots", px, m_, y, state, state.numel(), positions, 0 if limit is None else int(limit),
+                int(bool(advance)), B, n, cd, ch, int(output_dim))
     return y
 
 

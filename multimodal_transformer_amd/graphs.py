@@ -75,3 +75,40 @@ def capture_step(step, warmup=2, graph=None, **graph_kwargs):
     with torch.cuda.graph(g, **graph_kwargs):
         out = step()
     return g, out
+
+
+class StreamGraph:
+    """One step of a slots stream as a replayable graph (``capture_stream``).  ``inputs`` (a tensor, or a dict of tensors per modality)
+    and ``mask`` (a tensor or None) are the static buffers the captured launches read: ``copy_`` the next window into them, call
+    ``replay()``, read ``output`` (overwritten by every replay).  Seating, releasing and reading ``stream.positions`` happen between
+    replays, as ordinary operations on the current stream."""
+
+    def __init__(self, graph, stream, inputs, mask, output):
+        self.graph, self.stream, self.inputs, self.mask, self.output = graph, stream, inputs, mask, output
+
+    def replay(self):
+        self.graph.replay()
+        return self.output
+
+
+def capture_stream(stream, inputs, mask=None):
+    """Capture ``stream.step(inputs, mask)`` of a slots stream (``Encoder.slot_stream``, ``MFN.slot_stream``, ``slot_stream`` of the MFT,
+    of B3-MFN and of their wrappers) -> ``StreamGraph``.  ``inputs`` / ``mask`` give the shapes (and the first contents) of the static
+    buffers.  A stream that keeps its position on the host is refused before anything is launched: that ``t`` would be frozen into
+    the graph.  The warm-up and the captured call themselves run with every slot idle, so they touch no cache row and no carried
+    state; the positions are put back afterwards, and nothing of the stream has changed."""
+    if not getattr(stream, "slots", False):
+        raise ValueError("capture_stream: %s keeps its position t on the host, and a captured step would replay that one t for ever: "
+                         "open the stream with slot_stream(...), whose positions live on the device" % type(stream).__name__)
+    def fresh(v):
+        return v.detach().clone(memory_format=torch.contiguous_format)
+
+    static_in = {k: fresh(v) for k, v in inputs.items()} if isinstance(inputs, dict) else fresh(inputs)
+    static_mask = None if mask is None else fresh(mask)
+    saved = stream.positions.clone()
+    stream.positions.fill_(-1)
+    try:
+        graph, out = capture_step(lambda: stream.step(static_in, static_mask))
+    finally:
+        stream.positions.copy_(saved)
+    return StreamGraph(graph, stream, static_in, static_mask, out)

@@ -116,14 +116,26 @@ class _FrontEndStream:
     own step (``multiTransformer._SequenceStream``; the MFT and B3-MFN take the per-modality rows as a dict:
     ``multiTransformer._GateStream``).  ``reset()`` starts a new recording."""
 
-    def __init__(self, model, batch, capacity):
+    def __init__(self, model, batch, capacity, slots=False):
         if model.training:
             raise ValueError("%s.stream: the model is in train mode; streaming is eval-mode inference (call .eval())" % type(model).__name__)
         self.model, self.batch = model, int(batch)
-        self.seq = model.Transformer.stream(batch, capacity)
+        self.seq = model.Transformer.slot_stream(batch, capacity) if slots else model.Transformer.stream(batch, capacity)
 
-    t = property(lambda self: self.seq.t)
+    t = property(lambda self: self.seq.t)                   # a slots stream: AttributeError naming .positions
     capacity = property(lambda self: self.seq.capacity)
+    # with slots (``slot_stream``): the members of multiTransformer._Slots, those of the sequence model's stream
+    slots = property(lambda self: self.seq.slots)
+    positions = property(lambda self: self.seq.positions)
+
+    def seat(self, indices):
+        self.seq.seat(indices)
+
+    def release(self, indices):
+        self.seq.release(indices)
+
+    def full(self):
+        return self.seq.full()
 
     def reset(self):
         self.seq.reset()
@@ -175,6 +187,10 @@ class MultiCNNTransformer(_FrontEnd):
         """This model as an online predictor (``_FrontEndStream``): eval mode, ``causal_attention(model)`` on."""
         return _FrontEndStream(self, batch, capacity)
 
+    def slot_stream(self, batch, capacity):
+        """Not implemented: the sequence model keeps host-side state per recording (its own ``slot_stream`` says why)."""
+        return self.Transformer.slot_stream(batch, capacity)
+
 
 class MultiCNNTransformerMFT(_FrontEnd):
     """MFT: transformer/MFT/models.py:81-138 (``embed_dims`` replaces the fixed window embed sizes; no fusion layer)."""
@@ -213,6 +229,12 @@ class MultiCNNTransformerMFT(_FrontEnd):
                              "the MFT: call stream(batch, capacity)")
         return _FrontEndStream(self, batch, capacity)
 
+    def slot_stream(self, batch, capacity):
+        """``stream_modalities(batch, capacity)`` with slots: sequences are seated and released independently (``.positions``,
+        ``.seat``, ``.release``, ``.full``: multiTransformer._Slots), and a step can be captured into a graph
+        (``graphs.capture_stream``).  One modality: NotImplementedError, the UniTransformer keeps host-side state per recording."""
+        return _FrontEndStream(self, batch, capacity, slots=True)
+
 
 class MultiCNNTransformerB2(_FrontEnd):
     """B2-Trans: transformer/B2-Trans/models.py:81-134 (single modality; the fusion layer is commented out there)."""
@@ -234,6 +256,10 @@ class MultiCNNTransformerB2(_FrontEnd):
     def stream(self, batch, capacity):
         """This model as an online predictor (``_FrontEndStream``): eval mode, ``causal_attention(model)`` on."""
         return _FrontEndStream(self, batch, capacity)
+
+    def slot_stream(self, batch, capacity):
+        """Not implemented: the sequence model keeps host-side state per recording (its own ``slot_stream`` says why)."""
+        return self.Transformer.slot_stream(batch, capacity)
 
 
 class MultiCNNTransformerB3(_FrontEnd):
@@ -264,6 +290,12 @@ class MultiCNNTransformerB3(_FrontEnd):
             raise ValueError("MultiCNNTransformerB3.stream: with one modality the sequence model is the UniTransformer, whose K/V cache "
                              "needs a capacity (windows per recording)")
         return _FrontEndStream(self, batch, capacity)
+
+    def slot_stream(self, batch, capacity=None):
+        """``stream(batch)`` with slots: sequences are seated and released independently (``.positions``, ``.seat``, ``.release``,
+        ``.full``: multiTransformer._Slots), and a step can be captured into a graph (``graphs.capture_stream``).  One modality:
+        NotImplementedError, the UniTransformer keeps host-side state per recording."""
+        return _FrontEndStream(self, batch, capacity, slots=True)
 
 
 class _LocalAttnLSTM(nn.Module):

@@ -362,6 +362,12 @@ class Encoder(nn.Module):
             raise ValueError("%s.stream: the encoder is on %s; move it to a HIP device (there is no CPU path)" % (name, self.norm.a_2.device))
         return EncoderStream(self, batch, capacity)
 
+    def slot_stream(self, batch, capacity, positions=None):
+        """``stream(batch, capacity)`` with slots (``EncoderSlotStream``): the position of every sequence lives on the device, so the
+        sequences are seated and released independently and a step can be captured into a graph (``graphs.capture_stream``).  The same
+        refusals, before any launch."""
+        return EncoderSlotStream(self.stream(batch, capacity), positions)
+
     sub_batch_streams = 1        # set to 2: the batch runs as two halves on two HIP streams (functional._SPLIT_STREAMS); opt-in
     sub_batch_min_windows = 8192
 
@@ -385,10 +391,14 @@ class EncoderStream:
     weights again: call it after the encoder's parameters changed (biases and LayerNorm weights are read live).  Rows agree with the
     batch forward to the distance between two roundings of the same arithmetic (about 1.5e-3 rel-L2), not bit for bit."""
 
+    slots = False                    # True in EncoderSlotStream: positions on the device instead of ``t``
+
     def __init__(self, encoder, batch, capacity):
         l0 = encoder.layers[0]
         self.encoder = encoder
-        self.batch, self.capacity, self.t = int(batch), int(capacity), 0
+        self.batch, self.capacity = int(batch), int(capacity)
+        if not self.slots:
+            self.t = 0
         self.d, self.h, self.d_ff, self.n_layers = l0.size, l0.self_attn.h, l0.feed_forward.w_1.weight.shape[0], len(encoder.layers)
         self.eps = encoder.norm.eps
         self.device = encoder.norm.a_2.device
@@ -415,6 +425,13 @@ class EncoderStream:
         if self.t >= self.capacity:
             raise ValueError("EncoderStream.step: the stream is full (t = capacity = %d): reset() starts a new recording, "
                              "Encoder.stream(batch, capacity) opens a longer one" % self.capacity)
+        self._check_step(x_t, mask_t)
+        y = F_hip.encoder_stream_step(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.t, self.h, self.d_ff,
+                                      self.n_layers, self.capacity, self.eps)
+        self.t += 1
+        return y.view(x_t.shape)
+
+    def _check_step(self, x_t, mask_t):
         if not isinstance(x_t, torch.Tensor) or x_t.dtype != torch.float32 or x_t.device != self.device:
             raise ValueError("EncoderStream.step: x_t must be a float32 tensor on %s, got %s on %s"
                              % (self.device, getattr(x_t, "dtype", type(x_t).__name__), getattr(x_t, "device", None)))
@@ -423,15 +440,81 @@ class EncoderStream:
                              % (self.batch, self.d, self.batch, self.d, tuple(x_t.shape)))
         if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != self.batch or mask_t.device != self.device):
             raise ValueError("EncoderStream.step: mask_t must hold one entry per sequence (%d) on %s" % (self.batch, self.device))
-        y = F_hip.encoder_stream_step(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.t, self.h, self.d_ff,
-                                      self.n_layers, self.capacity, self.eps)
-        self.t += 1
+
+
+_INT_MAX = 2 ** 31 - 1
+
+
+def _slot_positions(op, positions, batch, device):
+    """The positions of a slots stream: a new int32 (batch) tensor, every slot idle, or the one a composite stream shares."""
+    if positions is None:
+        return torch.full((batch,), -1, dtype=torch.int32, device=device)
+    if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32 or tuple(positions.shape) != (batch,) \
+            or not positions.is_contiguous() or positions.device != device:
+        raise ValueError("%s: positions must be a contiguous int32 (%d,) tensor on %s" % (op, batch, device))
+    return positions
+
+
+class _Slots:
+    """What every slots stream has instead of ``t``: ``positions``, int32 (batch) on the device, read and advanced by the step kernels
+    (csrc/step_slots.h).  A slot is idle (-1, as opened), seated (0 <= position < capacity: its next window) or full (>= capacity).  A
+    step gives an idle or full slot a zero row and touches nothing of it.  ``seat`` / ``release`` / ``reset`` are ordinary device
+    operations on the current stream, between steps (or between the replays of a captured step); none of them synchronises."""
+
+    slots = True
+
+    @property
+    def t(self):
+        raise AttributeError("a slots stream has no single position t: every sequence has its own, see .positions (int32 on the device)")
+
+    def _index(self, indices):
+        return torch.as_tensor(indices, dtype=torch.long, device=self.positions.device).reshape(-1)
+
+    def seat(self, indices):
+        """Start a new recording in these slots: their positions become 0.  Nothing is cleared; nothing needs to be."""
+        self.positions.index_fill_(0, self._index(indices), 0)
+
+    def release(self, indices):
+        """Make these slots idle: their positions become -1."""
+        self.positions.index_fill_(0, self._index(indices), -1)
+
+    def reset(self):
+        """Seat every slot."""
+        self.positions.zero_()
+
+    def full(self):
+        """bool (batch) on the device: the slots whose recording has used the whole capacity (no synchronisation)."""
+        return self.positions >= (_INT_MAX if self.capacity is None else self.capacity)
+
+
+class EncoderSlotStream(_Slots, EncoderStream):
+    """``EncoderStream`` with slots (``Encoder.slot_stream``; members: ``_Slots``).  ``step(x_t, mask_t)`` is ONE launch of
+    encoder_step_slots_kernel: row b is what an ``EncoderStream`` of that recording alone gives at window ``positions[b]``, bit for bit
+    (the same kernel body, one workgroup per sequence), and the kernel advances the positions of the slots it ran.  No position crosses
+    the host, so there is no "full" error: a full slot gets a zero row, and ``full()`` shows it."""
+
+    def __init__(self, opened, positions=None):
+        self.__dict__.update({k: v for k, v in opened.__dict__.items() if k != "t"})     # the state and the weights of the stream just opened
+        self.positions = _slot_positions("Encoder.slot_stream", positions, self.batch, self.device)
+
+    def step(self, x_t, mask_t=None, advance=True):
+        """As ``EncoderStream.step``.  ``advance=False`` leaves the positions (a composite stream advances them once, in its last launch)."""
+        self._check_step(x_t, mask_t)
+        y = F_hip.encoder_stream_step_slots(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.positions, self.h,
+                                            self.d_ff, self.n_layers, self.capacity, self.eps, advance=advance)
         return y.view(x_t.shape)
 
 
 def _stream_model_checks(model):
     if model.training:
         raise ValueError("%s.stream: the model is in train mode; streaming is eval-mode inference (call .eval())" % type(model).__name__)
+
+
+def _no_slot_stream(model):
+    raise NotImplementedError("%s.slot_stream: this model's stream keeps host-side state per recording (one position t for the batch; "
+                              "with an LSTM decoder also the carried (h, c) and the first row h0 W_hh, chosen on the host at t == 0), so "
+                              "its sequences cannot be seated independently; slots serve Encoder, MFN, MultiTransformer and MultiTransformerB3 "
+                              "(and their wrappers).  Use stream(batch, capacity)" % type(model).__name__)
 
 
 class _SequenceStream:
@@ -599,6 +682,12 @@ class MFN(nn.Module):
             raise ValueError("MFN.stream: the gate is on %s; move it to a HIP device (there is no CPU path)" % dev)
         return MFNStream(self, batch)
 
+    def slot_stream(self, batch, limit=None, positions=None):
+        """``stream(batch)`` with slots (``MFNSlotStream``): the position of every sequence lives on the device, so the sequences are
+        seated and released independently and a step can be captured into a graph (``graphs.capture_stream``).  ``limit``: windows per
+        recording after which a slot is full (None: none, a gate has no cache).  The same refusals, before any launch."""
+        return MFNSlotStream(self.stream(batch), limit, positions)
+
 
 class MFNStream:
     """An ``MFN`` gate run one window at a time (``MFN.stream``): ``step({mod: (B, dims[mod])}, mask_t)`` returns the (B, output_dim)
@@ -612,8 +701,12 @@ class MFNStream:
     reads nothing but its inputs and the state.  Rows have the batch path's rounding sites exactly and agree with it to fp32
     summation order."""
 
+    slots = False                    # True in MFNSlotStream: positions on the device instead of ``t``
+
     def __init__(self, mfn, batch):
-        self.mfn, self.batch, self.t = mfn, int(batch), 0
+        self.mfn, self.batch = mfn, int(batch)
+        if not self.slots:
+            self.t = 0
         self.mods = list(mfn.mods)
         self.in_dims = [mfn.lstm[m].input_size for m in self.mods]
         self.hidden = [mfn.lstm[m].hidden_size for m in self.mods]
@@ -639,6 +732,25 @@ class MFNStream:
         y = F_hip.mfn_stream_step(xs, mask_t, self.state, self.t, self.in_dims, self.hidden, self.output_dim)
         self.t += 1
         return y
+
+
+class MFNSlotStream(_Slots, MFNStream):
+    """``MFNStream`` with slots (``MFN.slot_stream``; members: ``_Slots``, ``capacity`` is the ``limit``).  ``step(inputs, mask_t)`` is
+    ONE launch of mfn_step_slots_kernel: row b is what an ``MFNStream`` of that recording alone gives at window ``positions[b]``, bit
+    for bit (copy ``positions[b] & 1`` of the carried state is read and the other written, per sequence), and the kernel advances the
+    positions of the slots it ran."""
+
+    def __init__(self, opened, limit=None, positions=None):
+        self.__dict__.update({k: v for k, v in opened.__dict__.items() if k != "t"})     # the state of the stream just opened
+        self.capacity = None if limit is None else int(limit)
+        if self.capacity is not None and self.capacity < 1:
+            raise ValueError("MFN.slot_stream: limit must be at least 1 (or None), got %d" % self.capacity)
+        self.positions = _slot_positions("MFN.slot_stream", positions, self.batch, self.device)
+
+    def step(self, inputs, mask_t=None, advance=True):
+        xs = _modality_rows("MFNStream.step", inputs, self.mods, self.in_dims, self.batch, self.device, mask_t)
+        return F_hip.mfn_stream_step_slots(xs, mask_t, self.state, self.positions, self.in_dims, self.hidden, self.output_dim,
+                                           limit=self.capacity, advance=advance)
 
 
 def _modality_rows(op, inputs, mods, widths, B, device, mask_t):
@@ -671,6 +783,7 @@ class _GateStream:
     against 126 us on one stream.  ``MMT_MODALITY_STREAMS=0`` serialises the MFT's step too."""
 
     takes_modalities = True          # models._FrontEndStream hands such a stream the per-modality dict
+    slots = False                    # True in _GateSlotStream
 
     def __init__(self, model, batch, capacity):
         _stream_model_checks(model)
@@ -684,6 +797,13 @@ class _GateStream:
         self.gate = model.mfn.stream(batch)
         self.device = self.gate.device
         self.modality_streams = self.encs is not None
+        if self.slots:
+            # ONE positions tensor: the encoders read it (advance off, on the modality streams as before), the gate's launch, which runs
+            # behind the join, advances it.  The gate's limit is the encoders' capacity, so a full slot is skipped by every launch.
+            self.positions = _slot_positions("%s.slot_stream" % type(model).__name__, None, self.batch, self.device)
+            if self.encs is not None:
+                self.encs = {m: EncoderSlotStream(e, self.positions) for m, e in self.encs.items()}
+            self.gate = MFNSlotStream(self.gate, self.capacity, self.positions)
 
     t = property(lambda self: self.gate.t)
     capacity = property(lambda self: None if self.encs is None else self.encs[self.mods[0]].capacity)
@@ -691,7 +811,7 @@ class _GateStream:
     def reset(self):
         self.gate.reset()
         for e in (self.encs or {}).values():
-            e.reset()
+            e.reset()                # a slots stream: the one shared tensor, zeroed again (idempotent)
 
     def refresh(self):
         self.gate.refresh()
@@ -702,7 +822,7 @@ class _GateStream:
         m, B = self.model, self.batch
         op = "%s stream step" % type(m).__name__
         xs = _modality_rows(op, inputs, self.mods, self.widths, B, self.device, mask_t)
-        if self.encs is not None and self.t >= self.capacity:
+        if not self.slots and self.encs is not None and self.t >= self.capacity:
             raise ValueError("%s: the stream is full (t = capacity = %d)" % (op, self.capacity))
         with torch.no_grad():
             r = None if mask_t is None else mask_t.float().reshape(B)
@@ -712,10 +832,36 @@ class _GateStream:
             for mod, x, st in zip(self.mods, xs, streams):
                 with torch.cuda.stream(st):                                # None: the caller's stream
                     e = _SequenceStream._affine(x, m.embed[mod])
-                    rows[mod] = e if self.encs is None else self.encs[mod].step(e, r)
+                    if self.encs is None:
+                        rows[mod] = e
+                    elif self.slots:
+                        rows[mod] = self.encs[mod].step(e, r, advance=False)
+                    else:
+                        rows[mod] = self.encs[mod].step(e, r)
             if fork:
                 _MOD_STREAMS.end(main, streams, list(rows.values()))
-            return self.gate.step(rows, r)
+            return self.gate.step(rows, r, advance=self._advance) if self.slots else self.gate.step(rows, r)
+
+
+class _GateSlotStream(_Slots, _GateStream):
+    """``slot_stream()`` of MultiTransformer and MultiTransformerB3: ``_GateStream`` with slots (members: ``_Slots``).  It owns ONE
+    ``positions`` tensor, which its encoder streams and its gate share: the encoders' launches read it, the gate's launch, the last of
+    the step, advances it.  A step launches what the ``_GateStream`` step launches, with the positioned kernels in place of the two step
+    kernels, and row b is what a ``_GateStream`` of that recording alone gives at window ``positions[b]``."""
+
+    _advance = True
+
+    def reset(self):
+        _Slots.reset(self)
+
+    def step(self, inputs, mask_t=None, advance=True):
+        """As ``_GateStream.step``.  ``advance=False``: the gate's launch leaves the positions, so the same windows can be stepped again
+        (a measurement at a fixed position; a recording advances)."""
+        self._advance = bool(advance)
+        try:
+            return _GateStream.step(self, inputs, mask_t)
+        finally:
+            self._advance = True
 
 
 class MultiTransformer(nn.Module):
@@ -761,6 +907,11 @@ class MultiTransformer(nn.Module):
         (``_GateStream``).  Eval mode, ``causal_attention(model)`` on; the encoders' own refusals pass through, before any launch."""
         return _GateStream(self, batch, capacity)
 
+    def slot_stream(self, batch, capacity):
+        """``stream(batch, capacity)`` with slots (``_GateSlotStream``): sequences are seated and released independently, and a step can
+        be captured into a graph (``graphs.capture_stream``).  The same refusals, before any launch."""
+        return _GateSlotStream(self, batch, capacity)
+
 
 class MultiTransformerB3(nn.Module):
     """B3-MFN sequence model (transformer/B3-MFN/multiTransformer.py:250-307): the MFT model without its encoder stacks — per-modality
@@ -794,6 +945,10 @@ class MultiTransformerB3(nn.Module):
         (``_GateStream``).  Eval mode.  No attention, so no cache: ``capacity`` is accepted and ignored, a recording has no length
         limit, and ``causal_attention`` is not needed."""
         return _GateStream(self, batch, capacity)
+
+    def slot_stream(self, batch, capacity=None):
+        """``stream(batch)`` with slots (``_GateSlotStream``); ``capacity`` is accepted and ignored, a slot is never full."""
+        return _GateSlotStream(self, batch, None)
 
 
 class _DecoderMixin:
@@ -860,6 +1015,10 @@ class UniTransformer(nn.Module, _DecoderMixin):
         (``_SequenceStream``).  Eval mode, ``causal_attention(model)`` on; ValueError / NotImplementedError before any launch."""
         return _SequenceStream(self, batch, capacity)
 
+    def slot_stream(self, batch, capacity):
+        """Not implemented for this model (``_no_slot_stream`` says why)."""
+        _no_slot_stream(self)
+
 
 class UniFullTransformer(nn.Module):
     """B2-Trans model (transformer/B2-Trans/multiTransformer.py:378-420): Linear embed -> Encoder -> MLP -> mask."""
@@ -883,6 +1042,10 @@ class UniFullTransformer(nn.Module):
         """This model as an online predictor: ``.step(x_t (B, window_embed_size), mask_t)`` -> the (B,1) prediction of window t
         (``_SequenceStream``).  Eval mode, ``causal_attention(model)`` on; ValueError / NotImplementedError before any launch."""
         return _SequenceStream(self, batch, capacity)
+
+    def slot_stream(self, batch, capacity):
+        """Not implemented for this model (``_no_slot_stream`` says why)."""
+        _no_slot_stream(self)
 
 
 class NLPTransformer(nn.Module, _DecoderMixin):
@@ -912,3 +1075,7 @@ class NLPTransformer(nn.Module, _DecoderMixin):
         """This model as an online predictor: ``.step(x_t (B, window_embed_size), mask_t)`` -> the (B,1) prediction of window t
         (``_SequenceStream``).  Eval mode, ``causal_attention(model)`` on; ValueError / NotImplementedError before any launch."""
         return _SequenceStream(self, batch, capacity)
+
+    def slot_stream(self, batch, capacity):
+        """Not implemented for this model (``_no_slot_stream`` says why)."""
+        _no_slot_stream(self)
