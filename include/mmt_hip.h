@@ -301,6 +301,39 @@ int mmt_mfn_stream_step_slots(const float* const* x_t, const float* mask_t, floa
                               int* pos, int limit, int advance,
                               int B, int nmods, const int* in_dims, const int* hidden, int output_dim, mmt_stream_t stream);
 
+/* ---- The LSTM decoder and the read-out, one window at a time (opt-in; eval mode, forward only).
+ * Replaces one iteration t of the decoder loop and the read-out MLP            transformer/SFT/multiTransformer.py:463-483
+ * (nn.LSTM(2d, d, n_layers) fed [o_{t-1} ; enc_t] with o the top layer's output, o_{-1} = 0 and (dec_h0, dec_c0) the initial state;
+ * then Linear(d, h_dim) -> ReLU -> Linear(h_dim, 1) -> * mask) for t = 0, 1, 2, ... of one recording per batch row: the state carries
+ * (h, c) of every layer between the calls.  n_layers == 0: the read-out alone (transformer/B2-Trans/multiTransformer.py:400-402).
+ * One step is ONE launch, one workgroup per sequence, no communication between workgroups: a sequence's result does not depend on its
+ * batch.  Numerics: the batch path's rounding sites exactly (the left operand of every product and every weight bf16; sums, biases,
+ * activations, the carried state and everything stored fp32); no site depends on a tile (csrc/decoder_step.h).
+ * Limits: d % 4 == 0, 4 <= d <= 512, 1 <= h_dim <= 512, 0 <= n_layers <= 4, B >= 1: anything else is MMT_EUNSUPPORTED with the limit
+ * named in mmt_last_error(), at the size query (which then returns 0); non-positive sizes, null pointers, t < 0 and a state of fewer
+ * than mmt_decoder_stream_bytes() bytes: MMT_EINVAL, before any launch.
+ * `state`: mmt_decoder_stream_bytes() bytes, ANY CONTENTS: every word a step reads was written by mmt_decoder_stream_prepare or by the
+ * step before it in this recording.  A new recording starts by passing t = 0 again; nothing needs clearing. */
+/* (_decode, :463-483) */
+size_t mmt_decoder_stream_bytes(int B, int d, int h_dim, int n_layers);
+/* One launch: every parameter into the state, weights to bf16 in the step kernel's layout (n_layers == 1: W_ih[:, :d] + W_hh summed
+ * in fp32 and rounded once), vectors in fp32 (b_ih + b_hh summed).  lstm_params: a HOST array of 4 * n_layers device pointers, per
+ * layer weight_ih (4d, 2d for layer 0, else d), weight_hh (4d, d), bias_ih, bias_hh; dec_h0, dec_c0 (n_layers, d); all three may be
+ * NULL when n_layers == 0.  W1 (h_dim, d), b1, W2 (1, h_dim), b2: the read-out.  Does not touch the carried state.  Call it again
+ * after a parameter changes.                                                   (__init__ / _decode, :444-452, :463-483) */
+int mmt_decoder_stream_prepare(const float* const* lstm_params, const float* dec_h0, const float* dec_c0,
+                               const float* W1, const float* b1, const float* W2, const float* b2, void* state, size_t state_bytes,
+                               int B, int d, int h_dim, int n_layers, mmt_stream_t stream);
+/* e_t (B, d), the encoder's row of this window -> y_t (B, 1) at position t; mask_t (B) float or NULL multiplies the output row; the
+ * state advances under a blanked window as it does in the batch path.  t is passed by value; step t reads copy t & 1 of the carried
+ * state and writes the other, so steps of one recording must be enqueued in order t = 0, 1, ... on one stream.   (_decode, :463-483) */
+int mmt_decoder_stream_step(const float* e_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,
+                            int t, int B, int d, int h_dim, int n_layers, mmt_stream_t stream);
+/* The positioned form (the slots contract above): the step at t = pos[b]; copy pos[b] & 1 of the carried state is read and the other
+ * written, per sequence.  limit <= 0: no limit; behind an encoder step its capacity.                            (_decode, :463-483) */
+int mmt_decoder_stream_step_slots(const float* e_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,
+                                  int* pos, int limit, int advance, int B, int d, int h_dim, int n_layers, mmt_stream_t stream);
+
 /* ---- Fused affine map  y = act(x W^T + b) [* rowscale] on bf16 MFMA.
  * Replaces nn.Linear (+ F.relu) call sites of the path: PositionwiseFeedForward (:15-20), the four
  * attention projections (:43,55,65), embeds and read-out MLPs (:270,296,340-342,400-402).
@@ -313,6 +346,15 @@ int mmt_linear_forward(const float* x, const float* W, const float* b, const flo
 int mmt_linear_backward(const float* dy, const float* x, const float* W, const float* y, const float* rowscale,
                         float* dx, float* dW, float* db,
                         void* workspace, size_t workspace_bytes, int M, int K, int N, int act, mmt_stream_t stream);
+
+/* ... with W and b prepared once (forward only; a stream's embed, whose weights do not change between steps): `prepared`,
+ * mmt_linear_prepared_bytes(K, N) bytes, any contents, receives from mmt_linear_prepare (two launches) what mmt_linear_forward lays into
+ * its workspace at every call, the padded bf16 W and the padded fp32 bias (b may be NULL: zeros).  mmt_linear_forward_prepared is then
+ * ONE launch, the row GEMM alone on the same operands: the same bits as mmt_linear_forward.  Prepare again after W or b changed. */
+size_t mmt_linear_prepared_bytes(int K, int N);
+int mmt_linear_prepare(const float* W, const float* b, void* prepared, size_t prepared_bytes, int K, int N, mmt_stream_t stream);
+int mmt_linear_forward_prepared(const float* x, const void* prepared, size_t prepared_bytes, const float* rowscale, float* y,
+                                int M, int K, int N, int act, mmt_stream_t stream);
 
 /* ... with train-mode dropout fused in: on the INPUT (x -> drop(x) while the A tile is staged: the `Dropout(0.1) -> Linear -> ReLU` embed of
  * NLPTransformer, transformer/SFT/multiTransformer.py:431-433,461) and / or behind the ReLU (act must be 1: MFN's out_dropout on

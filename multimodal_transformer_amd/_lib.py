@@ -67,9 +67,17 @@ SIGNATURES = {
     # slots: the position of each sequence in device memory, int32 (B,), and `advance` (the gate: `limit` in front of it) for the host's t
     "mmt_encoder_stream_step_slots": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _I] + [_I] * 6 + [_F, _P]),
     "mmt_mfn_stream_step_slots": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
+    # one window of the LSTM decoder and the read-out per launch: (B, d, h_dim, n_layers); lstm_params a host array of device pointers
+    "mmt_decoder_stream_bytes": (_SZ, [_I] * 4),
+    "mmt_decoder_stream_prepare": (_I, [_P] * 8 + [_SZ] + [_I] * 4 + [_P]),
+    "mmt_decoder_stream_step": (_I, [_P, _P, _P, _P, _SZ] + [_I] * 5 + [_P]),
+    "mmt_decoder_stream_step_slots": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _I] + [_I] * 4 + [_P]),
     "mmt_linear_workspace_bytes": (_SZ, [_I] * 3),
     "mmt_linear_forward": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),
     "mmt_linear_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),
+    "mmt_linear_prepared_bytes": (_SZ, [_I, _I]),
+    "mmt_linear_prepare": (_I, [_P, _P, _P, _SZ, _I, _I, _P]),
+    "mmt_linear_forward_prepared": (_I, [_P, _P, _SZ, _P, _P] + [_I] * 4 + [_P]),
     "mmt_linear_dropout_forward": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_F, _F, _U64, _P, _P]),
     "mmt_linear_dropout_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_F, _F, _U64, _I, _P]),
     "mmt_copy2d": (_I, [_P, _I, _P]),

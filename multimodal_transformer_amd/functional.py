@@ -1784,6 +1784,164 @@ def mfn_stream_step_slots(xs, mask_t, state, positions, in_dims, hidden, output_
     return y
 
 
+# The affine map with its operands prepared once (include/mmt_hip.h mmt_linear_prepare / mmt_linear_forward_prepared): forward only.
+def linear_prepare(W, b, prepared=None):
+    """The padded bf16 copy of ``W`` (N, K) and the padded bias ``b`` (N) or None, as ``linear`` lays them into its workspace at every
+    call -> a uint8 tensor for ``linear_prepared`` (``prepared``: one of this shape to write again), which carries its (K, N): the
+    padded layout alone does not tell two shapes of one padded size apart.  Two launches."""
+    if any(q is not None and q.requires_grad and torch.is_grad_enabled() for q in (W, b)):
+        raise NotImplementedError("linear_prepare: forward only, no autograd (pass detached tensors or call it under torch.no_grad())")
+    if not isinstance(W, torch.Tensor) or W.dim() != 2 or (b is not None and tuple(b.shape) != (W.shape[0],)):
+        raise ValueError("linear_prepare: W must be (N, K) and b (N) or None")
+    N, K = W.shape
+    if K % 4:
+        raise ValueError("linear_prepare: in_features %d must be a multiple of 4" % K)
+    _lib.require_hip(W, b, prepared)
+    nbytes = _lib.load().mmt_linear_prepared_bytes(K, N)
+    if prepared is None:
+        prepared = _scratch(nbytes, W.device)
+    elif prepared.dtype != torch.uint8 or not prepared.is_contiguous() or prepared.numel() < nbytes or prepared.device != W.device:
+        raise ValueError("linear_prepare: prepared must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, W.device))
+    W_, b_ = _f32c(W), _f32c(b)
+    prepared._mmt_linear_kn = None                                         # not valid for any shape while it is rewritten
+    _lib.launch("mmt_linear_prepare", W_, b_, prepared, prepared.numel(), K, N)
+    prepared._mmt_linear_kn = (K, N)
+    return prepared
+
+
+def linear_prepared(x, prepared, N, act=0, rowscale=None):
+    """``linear(x, W, b, act, rowscale)`` of x (M, K) with (W, b) given as ``linear_prepare(W, b)``: ONE launch, the row GEMM alone on
+    the same operands, so the same bits.  Forward only."""
+    if any(isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled() for a in (x, rowscale)):
+        raise NotImplementedError("linear_prepared: forward only, no autograd (an input requires grad)")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError("linear_prepared: x must be a float32 (M, K) tensor")
+    M, K = x.shape
+    N = int(N)
+    if rowscale is not None and rowscale.numel() != M:
+        raise ValueError("linear_prepared: rowscale must hold one entry per row (%d)" % M)
+    _lib.require_hip(x, prepared, rowscale)
+    nbytes = _lib.load().mmt_linear_prepared_bytes(K, N)
+    if not isinstance(prepared, torch.Tensor) or prepared.dtype != torch.uint8 or prepared.numel() < nbytes or prepared.device != x.device:
+        raise ValueError("linear_prepared: prepared must be linear_prepare's tensor for (N, K) = (%d, %d) on %s" % (N, K, x.device))
+    if getattr(prepared, "_mmt_linear_kn", None) != (K, N):
+        raise ValueError("linear_prepared: prepared was laid out for (K, N) = %s, the call is for (%d, %d) (the tensor linear_prepare "
+                         "returned carries its shape; a view or a copy of it does not)" % (getattr(prepared, "_mmt_linear_kn", None), K, N))
+    x_, r_ = _f32c(x), _f32c(rowscale)
+    y = torch.empty(M, N, dtype=torch.float32, device=x.device)
+    _lib.launch("mmt_linear_forward_prepared", x_, prepared, prepared.numel(), r_, y, M, K, N, int(act))
+    return y
+
+
+# The LSTM decoder and the read-out, one window per call (include/mmt_hip.h mmt_decoder_stream_*): eval mode, forward only.  The state
+# (prepared bf16 weights, fp32 vectors, two copies of the carried (h, c) of every layer) takes memory with any contents: _scratch.
+def decoder_stream_bytes(B, d, h_dim, n_layers):
+    """Bytes of the decoder stream state for ``B`` sequences, embed_dim ``d``, read-out width ``h_dim`` and ``n_layers`` LSTM layers
+    (0: the read-out alone); ValueError, naming the limit, for a shape outside the step kernel's domain."""
+    lib = _lib.load()
+    nbytes = lib.mmt_decoder_stream_bytes(int(B), int(d), int(h_dim), int(n_layers))
+    if nbytes == 0:
+        raise ValueError((lib.mmt_last_error() or b"decoder stream: ?").decode())
+    return nbytes
+
+
+def decoder_stream_state(B, d, h_dim, n_layers, device):
+    """An unprepared decoder stream state on ``device`` (uint8; any contents)."""
+    return _scratch(decoder_stream_bytes(B, d, h_dim, n_layers), device)
+
+
+def _decoder_stream_state(op, state, nbytes, device):
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < nbytes:
+        raise ValueError("%s: state must be a contiguous uint8 tensor of at least %d bytes (decoder_stream_state)" % (op, nbytes))
+    if state.device != device:
+        raise ValueError("%s: state is on %s, the operands on %s" % (op, state.device, device))
+
+
+def decoder_stream_prepare(lstm_params, dec_h0, dec_c0, out_params, state, B, d, h_dim, n_layers):
+    """Convert and copy every parameter of a decoder into ``state`` (one launch; the carried state is not touched): ``lstm_params`` per
+    layer (weight_ih, weight_hh, bias_ih, bias_hh) of its nn.LSTM(2d, d, n_layers), ``dec_h0`` / ``dec_c0`` (n_layers, 1, d) or
+    (n_layers, d) (all three empty / None when n_layers == 0), ``out_params`` (W1 (h_dim, d), b1, W2 (1, h_dim), b2) of the read-out.
+    Again after any parameter changes: a step reads every one of them from the state."""
+    op = "decoder_stream_prepare"
+    L, d, h_dim = int(n_layers), int(d), int(h_dim)
+    lstm = [q for layer in (lstm_params or []) for q in layer]
+    out = list(out_params)
+    init = [dec_h0, dec_c0] if L else []
+    if any(q is not None and q.requires_grad and torch.is_grad_enabled() for q in lstm + out + init):
+        raise NotImplementedError("%s: forward only, no autograd (parameters that require grad: pass detached tensors or call it under "
+                                  "torch.no_grad())" % op)
+    nbytes = decoder_stream_bytes(B, d, h_dim, L)
+    want = [s for l in range(L) for s in ((4 * d, 2 * d if l == 0 else d), (4 * d, d), (4 * d,), (4 * d,))]
+    if [tuple(q.shape) for q in lstm] != want:
+        raise ValueError("%s: the LSTM's parameters have the shapes %s, expected %s (nn.LSTM(2d, d, n_layers))"
+                         % (op, [tuple(q.shape) for q in lstm], want))
+    if any(q is None or q.numel() != L * d for q in init):
+        raise ValueError("%s: dec_h0 and dec_c0 must hold n_layers x d = %d values each" % (op, L * d))
+    want = [(h_dim, d), (h_dim,), (1, h_dim), (1,)]
+    if [tuple(q.shape) for q in out] != want:
+        raise ValueError("%s: the read-out's parameters have the shapes %s, expected %s" % (op, [tuple(q.shape) for q in out], want))
+    _lib.require_hip(state, *lstm, *out, *init)
+    _decoder_stream_state(op, state, nbytes, out[0].device)
+    keep = [_f32c(q) for q in lstm + init + out]                           # alive until the launch is enqueued
+    pl = (ctypes.c_void_p * max(len(lstm), 1))(*[q.data_ptr() for q in keep[:len(lstm)]]) if L else None
+    h0, c0 = (keep[len(lstm)], keep[len(lstm) + 1]) if L else (None, None)
+    W1, b1, W2, b2 = keep[len(lstm) + len(init):]
+    _lib.launch("mmt_decoder_stream_prepare", pl, h0, c0, W1, b1, W2, b2, state, state.numel(), int(B), d, h_dim, L)
+
+
+def _decoder_step_inputs(op, e_t, mask_t, d):
+    """The checks of a decoder step's inputs that need no device -> (B, device)."""
+    if any(isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled() for a in (e_t, mask_t)):
+        raise NotImplementedError("%s: forward only, no autograd (an input requires grad)" % op)
+    if not isinstance(e_t, torch.Tensor) or e_t.dim() != 2 or e_t.dtype != torch.float32 or e_t.shape[1] != int(d):
+        raise ValueError("%s: e_t must be a float32 (B, %d) tensor, got %s %s"
+                         % (op, int(d), getattr(e_t, "dtype", type(e_t).__name__), tuple(getattr(e_t, "shape", ()))))
+    B, dev = e_t.shape[0], e_t.device
+    if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != dev):
+        raise ValueError("%s: mask_t must hold one entry per sequence (B = %d) on %s" % (op, B, dev))
+    return B, dev
+
+
+def decoder_stream_step(e_t, mask_t, state, t, d, h_dim, n_layers):
+    """Window t of the LSTM decoder and the read-out: e_t (B, d), the encoder's row of this window; mask_t (B) or None -> y_t (B, 1) =
+    what ``_DecoderMixin._decode`` gives at [:, t] in eval mode, times mask_t (transformer/SFT/multiTransformer.py:463-483), from the
+    (h, c) of every layer carried in ``state`` (decoder_stream_state, prepared by decoder_stream_prepare), which this call advances.
+    Steps of a recording run in order t = 0, 1, ...; t is passed by value.  One launch.  Forward only."""
+    op = "decoder_stream_step"
+    B, dev = _decoder_step_inputs(op, e_t, mask_t, d)
+    t = int(t)
+    if t < 0:
+        raise ValueError("%s: position t = %d is negative" % (op, t))
+    _lib.require_hip(e_t, state)
+    nbytes = decoder_stream_bytes(B, d, h_dim, n_layers)
+    _decoder_stream_state(op, state, nbytes, dev)
+    e_ = _f32c(e_t)
+    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
+    y = torch.empty(B, 1, dtype=torch.float32, device=dev)
+    _lib.launch("mmt_decoder_stream_step", e_, m_, y, state, state.numel(), t, B, int(d), int(h_dim), int(n_layers))
+    return y
+
+
+def decoder_stream_step_slots(e_t, mask_t, state, positions, d, h_dim, n_layers, limit=None, advance=True):
+    """``decoder_stream_step`` with the position of every sequence in device memory (csrc/step_slots.h): ``positions`` int32 (B), read
+    by the kernel.  Row b is the row of ``decoder_stream_step`` at t = positions[b], bit for bit (copy positions[b] & 1 of the carried
+    state read, the other written), where the slot is seated, and zero, with nothing else written, where it is idle (negative) or full
+    (>= ``limit``; None: no limit).  ``advance``: the kernel adds 1 to the position of every slot it ran.  No position crosses the host,
+    so the call can be captured into a graph.  One launch."""
+    op = "decoder_stream_step_slots"
+    B, dev = _decoder_step_inputs(op, e_t, mask_t, d)
+    _stream_positions(op, positions, B, dev)
+    _lib.require_hip(e_t, state)
+    nbytes = decoder_stream_bytes(B, d, h_dim, n_layers)
+    _decoder_stream_state(op, state, nbytes, dev)
+    e_ = _f32c(e_t)
+    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
+    y = torch.empty(B, 1, dtype=torch.float32, device=dev)
+    _lib.launch("mmt_decoder_stream_step_slots", e_, m_, y, state, state.numel(), positions, 0 if limit is None else int(limit),
+                int(bool(advance)), B, int(d), int(h_dim), int(n_layers))
+    return y
+
+
 def check_device_errors():
     """Synchronise and raise if an asynchronous kernel reported an error through its device error word (mmt_hip.h)."""
     _lib.ERRORS.check()

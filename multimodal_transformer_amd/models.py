@@ -116,11 +116,14 @@ class _FrontEndStream:
     own step (``multiTransformer._SequenceStream``; the MFT and B3-MFN take the per-modality rows as a dict:
     ``multiTransformer._GateStream``).  ``reset()`` starts a new recording."""
 
-    def __init__(self, model, batch, capacity, slots=False):
+    def __init__(self, model, batch, capacity, slots=False, device=False):
         if model.training:
             raise ValueError("%s.stream: the model is in train mode; streaming is eval-mode inference (call .eval())" % type(model).__name__)
         self.model, self.batch = model, int(batch)
-        self.seq = model.Transformer.slot_stream(batch, capacity) if slots else model.Transformer.stream(batch, capacity)
+        if device:                                           # ``device_stream``: the sequence model's stream with its state on the device
+            self.seq = model.Transformer.device_stream(batch, capacity)
+        else:
+            self.seq = model.Transformer.slot_stream(batch, capacity) if slots else model.Transformer.stream(batch, capacity)
 
     t = property(lambda self: self.seq.t)                   # a slots stream: AttributeError naming .positions
     capacity = property(lambda self: self.seq.capacity)
@@ -139,6 +142,15 @@ class _FrontEndStream:
 
     def reset(self):
         self.seq.reset()
+
+    def refresh(self):
+        """Convert the sequence model's current parameters again, where its stream keeps converted copies (the MFT, the B3-MFN and every
+        ``device_stream``; the window encoder itself reads the live parameters)."""
+        if not hasattr(self.seq, "refresh"):                 # multiTransformer._SequenceStream packs the decoder's weights when it is opened
+            raise NotImplementedError("%s.stream: the stream of %s has no refresh() (it packs the decoder's weights once, when it is "
+                                      "opened): open a new stream after a parameter changed, or use device_stream, whose refresh() "
+                                      "follows it" % (type(self.model).__name__, type(self.model.Transformer).__name__))
+        self.seq.refresh()
 
     def step(self, inputs, mask_t=None):
         m, B = self.model, self.batch
@@ -191,6 +203,11 @@ class MultiCNNTransformer(_FrontEnd):
         """Not implemented: the sequence model keeps host-side state per recording (its own ``slot_stream`` says why)."""
         return self.Transformer.slot_stream(batch, capacity)
 
+    def device_stream(self, batch, capacity):
+        """``stream(batch, capacity)`` with the sequence model's whole per-recording state on the device (its ``device_stream``): sequences
+        are seated and released independently, and a step can be captured into a graph (``graphs.capture_stream``)."""
+        return _FrontEndStream(self, batch, capacity, device=True)
+
 
 class MultiCNNTransformerMFT(_FrontEnd):
     """MFT: transformer/MFT/models.py:81-138 (``embed_dims`` replaces the fixed window embed sizes; no fusion layer)."""
@@ -235,6 +252,15 @@ class MultiCNNTransformerMFT(_FrontEnd):
         (``graphs.capture_stream``).  One modality: NotImplementedError, the UniTransformer keeps host-side state per recording."""
         return _FrontEndStream(self, batch, capacity, slots=True)
 
+    def device_stream(self, batch, capacity):
+        """One modality: the UniTransformer's ``device_stream`` behind the window encoder (its whole per-recording state on the device:
+        sequences are seated and released independently, a step can be captured).  More: NotImplementedError, ``slot_stream`` serves
+        the MFT."""
+        if len(self.mods) > 1:
+            raise NotImplementedError("MultiCNNTransformerMFT.device_stream: with more than one modality the sequence model is the MFT, whose slots "
+                                      "stream is slot_stream(batch, capacity)")
+        return _FrontEndStream(self, batch, capacity, device=True)
+
 
 class MultiCNNTransformerB2(_FrontEnd):
     """B2-Trans: transformer/B2-Trans/models.py:81-134 (single modality; the fusion layer is commented out there)."""
@@ -260,6 +286,11 @@ class MultiCNNTransformerB2(_FrontEnd):
     def slot_stream(self, batch, capacity):
         """Not implemented: the sequence model keeps host-side state per recording (its own ``slot_stream`` says why)."""
         return self.Transformer.slot_stream(batch, capacity)
+
+    def device_stream(self, batch, capacity):
+        """``stream(batch, capacity)`` with the sequence model's whole per-recording state on the device (its ``device_stream``): sequences
+        are seated and released independently, and a step can be captured into a graph (``graphs.capture_stream``)."""
+        return _FrontEndStream(self, batch, capacity, device=True)
 
 
 class MultiCNNTransformerB3(_FrontEnd):
@@ -296,6 +327,18 @@ class MultiCNNTransformerB3(_FrontEnd):
         ``.full``: multiTransformer._Slots), and a step can be captured into a graph (``graphs.capture_stream``).  One modality:
         NotImplementedError, the UniTransformer keeps host-side state per recording."""
         return _FrontEndStream(self, batch, capacity, slots=True)
+
+    def device_stream(self, batch, capacity=None):
+        """One modality: the UniTransformer's ``device_stream`` behind the window encoder (its whole per-recording state on the device:
+        sequences are seated and released independently, a step can be captured).  More: NotImplementedError, ``slot_stream`` serves
+        the B3-MFN."""
+        if len(self.mods) > 1:
+            raise NotImplementedError("MultiCNNTransformerB3.device_stream: with more than one modality the sequence model is the B3-MFN, whose slots "
+                                      "stream is slot_stream(batch)")
+        if capacity is None:
+            raise ValueError("MultiCNNTransformerB3.device_stream: with one modality the sequence model is the UniTransformer, whose K/V "
+                             "cache needs a capacity (windows per recording)")
+        return _FrontEndStream(self, batch, capacity, device=True)
 
 
 class _LocalAttnLSTM(nn.Module):

@@ -514,7 +514,8 @@ def _no_slot_stream(model):
     raise NotImplementedError("%s.slot_stream: this model's stream keeps host-side state per recording (one position t for the batch; "
                               "with an LSTM decoder also the carried (h, c) and the first row h0 W_hh, chosen on the host at t == 0), so "
                               "its sequences cannot be seated independently; slots serve Encoder, MFN, MultiTransformer and MultiTransformerB3 "
-                              "(and their wrappers).  Use stream(batch, capacity)" % type(model).__name__)
+                              "(and their wrappers).  Use stream(batch, capacity), or device_stream(batch, capacity), which keeps that "
+                              "state on the device and seats sequences independently" % type(model).__name__)
 
 
 class _SequenceStream:
@@ -580,6 +581,72 @@ class _SequenceStream:
                 self._h, self._c = h_all[0], c_all[0]
                 e = self._h
             return self._affine(self._affine(e, m.out[0], act=1), m.out[2], rowscale=r)
+
+
+class _SequenceSlotStream(_Slots):
+    """``device_stream()`` of UniFullTransformer, UniTransformer and NLPTransformer: a stream whose whole per-recording state lives on the
+    device (members: ``_Slots``).  ``step(x_t (B, window_embed_size), mask_t)`` -> the (B,1) prediction of that window, in THREE launches:
+    the embed affine map, the encoder's positioned step (``EncoderSlotStream``, advance off) and ONE launch of decoder_step_slots_kernel
+    (csrc/decoder_step.h) for the LSTM decoder and the read-out, which advances the positions.  The decoder's carried (h, c) of every
+    layer sits in ``state`` beside the bf16 copy of its weights; at position 0 the kernel takes dec_h0 / dec_c0 instead of it, so
+    ``seat`` is all a new recording needs, and decoders of up to 4 layers are served (0: the read-out alone).  It owns ONE ``positions``
+    tensor, which its encoder stream shares.  Row b is what this stream opened for that recording alone gives at window
+    ``positions[b]``, bit for bit; no position crosses the host, so a step can be captured (``graphs.capture_stream``).
+
+    ``refresh()`` converts the parameters again: call it after any of them changed (the decoder step reads every one from ``state``)."""
+
+    def __init__(self, model, batch, capacity):
+        name = type(model).__name__
+        if model.training:
+            raise ValueError("%s.device_stream: the model is in train mode; streaming is eval-mode inference (call .eval())" % name)
+        self.model, self.batch = model, int(batch)
+        dec = getattr(model, "decoder", None)
+        self.n_layers = 0 if dec is None else dec.num_layers
+        self.d, self.h_dim = model.out[0].in_features, model.out[0].out_features
+        self._dims = (self.batch, self.d, self.h_dim, self.n_layers)
+        if self.batch >= 1:
+            F_hip.decoder_stream_bytes(*self._dims)                              # ValueError naming the limit, before anything is opened
+        opened = model.encoder.stream(batch, capacity)                           # the encoder's refusals pass through
+        self.device = opened.device
+        self.positions = _slot_positions("%s.device_stream" % name, None, self.batch, self.device)
+        self.enc = EncoderSlotStream(opened, self.positions)
+        self.state = F_hip.decoder_stream_state(*self._dims, self.device)
+        embed = model.embed
+        self._embed, self._embed_act = (embed[1], 1) if isinstance(embed, nn.Sequential) else (embed, 0)     # NLPTransformer: Dropout -> Linear -> ReLU
+        self._embed_prep = None          # the embed's padded bf16 weight and bias, laid out once: its step is the row GEMM alone
+        self.refresh()
+
+    capacity = property(lambda self: self.enc.capacity)
+
+    def refresh(self):
+        """Convert the model's current parameters into the states (the encoder's and the decoder's preparation launch and the embed's
+        two); the carried state, the cache and the positions stay."""
+        m, dec = self.model, getattr(self.model, "decoder", None)
+        self.enc.refresh()
+        self._embed_prep = F_hip.linear_prepare(self._embed.weight.detach(), self._embed.bias.detach(), self._embed_prep)
+        lstm =[[getattr(dec, "%s_l%d" % (n, l)).detach() for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+                for l in range(self.n_layers)]
+        h0, c0 = (m.dec_h0.detach(), m.dec_c0.detach()) if self.n_layers else (None, None)
+        out = [q.detach() for q in (m.out[0].weight, m.out[0].bias, m.out[2].weight, m.out[2].bias)]
+        F_hip.decoder_stream_prepare(lstm, h0, c0, out, self.state, *self._dims)
+
+    def step(self, x_t, mask_t=None, advance=True):
+        """``advance=False``: the decoder's launch leaves the positions, so the same windows can be stepped again (a measurement at a
+        fixed position; a recording advances)."""
+        m, B = self.model, self.batch
+        op = "%s device_stream step" % type(m).__name__
+        if not isinstance(x_t, torch.Tensor) or x_t.dtype != torch.float32 or x_t.device != self.device:
+            raise ValueError("%s: x_t must be a float32 tensor on %s, got %s on %s"
+                             % (op, self.device, getattr(x_t, "dtype", type(x_t).__name__), getattr(x_t, "device", None)))
+        if tuple(x_t.shape) != (B, self._embed.in_features):
+            raise ValueError("%s: x_t must have the shape (%d,%d), got %s" % (op, B, self._embed.in_features, tuple(x_t.shape)))
+        if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != self.device):
+            raise ValueError("%s: mask_t must hold one entry per sequence (%d) on %s" % (op, B, self.device))
+        with torch.no_grad():
+            r = None if mask_t is None else mask_t.float().reshape(B)
+            e = self.enc.step(F_hip.linear_prepared(x_t, self._embed_prep, self.d, act=self._embed_act), r, advance=False)
+            return F_hip.decoder_stream_step_slots(e, r, self.state, self.positions, self.d, self.h_dim, self.n_layers,
+                                                   limit=self.capacity, advance=advance)
 
 
 def _encoder(embed_dim, h, d_ff, dropout, N):
@@ -951,6 +1018,17 @@ class MultiTransformerB3(nn.Module):
         return _GateSlotStream(self, batch, None)
 
 
+class _DeviceStreamMixin:
+    """``device_stream`` of UniTransformer, UniFullTransformer and NLPTransformer."""
+
+    def device_stream(self, batch, capacity):
+        """This model as an online predictor whose whole per-recording state lives on the device (``_SequenceSlotStream``): sequences
+        are seated and released independently (``.positions``, ``.seat``, ``.release``, ``.full``), a step is three launches and can be
+        captured into a graph (``graphs.capture_stream``).  Eval mode, ``causal_attention(model)`` on, a decoder of at most 4 layers;
+        ValueError before any launch."""
+        return _SequenceSlotStream(self, batch, capacity)
+
+
 class _DecoderMixin:
     """Autoregressive LSTM decoder + MLP shared by UniTransformer and NLPTransformer
     (transformer/SFT/multiTransformer.py:463-483).  One layer: step t feeds [o_{t-1}; enc_t] with o = h, so
@@ -990,7 +1068,7 @@ class _DecoderMixin:
         return F_hip.batch_major(F_hip.linear(hid, self.out[2].weight, self.out[2].bias), mask)
 
 
-class UniTransformer(nn.Module, _DecoderMixin):
+class UniTransformer(nn.Module, _DecoderMixin, _DeviceStreamMixin):
     """Single-modality model (transformer/MFT/multiTransformer.py:315-376): Linear embed -> Encoder -> LSTM decoder -> MLP."""
 
     def __init__(self, window_embed_size, embed_dim=256, h_dim=128, N=6, d_ff=128, h=8, dropout=0.1, n_layers=1,
@@ -1016,11 +1094,11 @@ class UniTransformer(nn.Module, _DecoderMixin):
         return _SequenceStream(self, batch, capacity)
 
     def slot_stream(self, batch, capacity):
-        """Not implemented for this model (``_no_slot_stream`` says why)."""
+        """Not implemented for this model (``_no_slot_stream`` says why): ``device_stream`` is the stream with slots."""
         _no_slot_stream(self)
 
 
-class UniFullTransformer(nn.Module):
+class UniFullTransformer(nn.Module, _DeviceStreamMixin):
     """B2-Trans model (transformer/B2-Trans/multiTransformer.py:378-420): Linear embed -> Encoder -> MLP -> mask."""
 
     def __init__(self, window_embed_size, embed_dim=256, h_dim=128, N=6, d_ff=128, h=8, dropout=0.1, n_layers=1,
@@ -1044,11 +1122,11 @@ class UniFullTransformer(nn.Module):
         return _SequenceStream(self, batch, capacity)
 
     def slot_stream(self, batch, capacity):
-        """Not implemented for this model (``_no_slot_stream`` says why)."""
+        """Not implemented for this model (``_no_slot_stream`` says why): ``device_stream`` is the stream with slots."""
         _no_slot_stream(self)
 
 
-class NLPTransformer(nn.Module, _DecoderMixin):
+class NLPTransformer(nn.Module, _DecoderMixin, _DeviceStreamMixin):
     """SFT model (transformer/SFT/multiTransformer.py:422-484): Dropout(0.1) -> Linear -> ReLU embed,
     Encoder, LSTM decoder, MLP, mask."""
 
@@ -1077,5 +1155,5 @@ class NLPTransformer(nn.Module, _DecoderMixin):
         return _SequenceStream(self, batch, capacity)
 
     def slot_stream(self, batch, capacity):
-        """Not implemented for this model (``_no_slot_stream`` says why)."""
+        """Not implemented for this model (``_no_slot_stream`` says why): ``device_stream`` is the stream with slots."""
         _no_slot_stream(self)
