@@ -48,46 +48,6 @@ struct DecStepParams {
     DecStepPlan pl;
 };
 
-// mmt_decoder_stream_prepare: blockIdx.y = job.  A matrix job lays the `rows` x K block at column col0 of a row-major fp32 source
-// (leading dimension ld; plus the block at column col2 of a second source, leading dimension ld2, where one is given: summed in fp32,
-// rounded once) into a prepared [KP / 8][rows][8] bf16 matrix; a vector job copies n floats (the sum of two sources where a second is
-// given).  Grid-stride over the destination.
-#define MMT_DEC_PREP_MATS (3 + 2 * MMT_DEC_STEP_MAX_L)
-#define MMT_DEC_PREP_VECS (4 + MMT_DEC_STEP_MAX_L)
-struct DecPrepMat { const float* src; const float* src2; size_t dst; int ld, col0, ld2, col2, rows, K, KP; };
-struct DecPrepVec { const float* a; const float* b; size_t dst; int n; };
-struct DecPrepParams {
-    char* state;
-    int nmat, nvec;
-    DecPrepMat mat[MMT_DEC_PREP_MATS];
-    DecPrepVec vec[MMT_DEC_PREP_VECS];
-};
-
-__global__ __launch_bounds__(256) void decoder_step_prep_kernel(const DecPrepParams P) {
-    const int job = blockIdx.y;
-    const size_t first = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-    if (job < P.nmat) {
-        const DecPrepMat& J = P.mat[job];
-        bf16* dst = reinterpret_cast<bf16*>(P.state + J.dst);
-        const size_t total = (size_t)J.rows * J.KP;
-        for (size_t i = first; i < total; i += stride) {
-            const int j = (int)(i & 7);
-            const size_t r = i >> 3;
-            const int n = (int)(r % J.rows), k = (int)(r / J.rows) * 8 + j;
-            float v = 0.f;
-            if (k < J.K) {
-                v = J.src[(size_t)n * J.ld + J.col0 + k];
-                if (J.src2) v += J.src2[(size_t)n * J.ld2 + J.col2 + k];
-            }
-            dst[((size_t)(k >> 3) * J.rows + n) * 8 + j] = (bf16)v;
-        }
-    } else if (job - P.nmat < P.nvec) {
-        const DecPrepVec& J = P.vec[job - P.nmat];
-        float* dst = reinterpret_cast<float*>(P.state + J.dst);
-        for (size_t i = first; i < (size_t)J.n; i += stride) dst[i] = J.b ? J.a[i] + J.b[i] : J.a[i];
-    }
-}
-
 // SLOTS false: t = P.t (pos, limit and advance unused).  SLOTS true: t = slot_decode(pos[b], limit), P.t unused.
 template <bool SLOTS>
 __device__ __forceinline__ void decoder_step_body(const DecStepParams& P, int* pos, int limit, int advance) {

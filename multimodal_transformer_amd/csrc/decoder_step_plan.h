@@ -16,6 +16,7 @@
 //       step p reads copy p & 1 (at p == 0 nothing: dec_h0 / dec_c0 / zeros stand for it) and writes copy (p + 1) & 1.
 #pragma once
 #include <stddef.h>
+#include "step_prep.h"
 
 #define MMT_DEC_STEP_MAX_D 512            // embed_dim: the width of the encoder's row and of every LSTM layer
 #define MMT_DEC_STEP_MAX_HDIM 512         // hidden units of the read-out
@@ -65,4 +66,35 @@ static inline int decoder_step_plan(DecStepPlan& P, int B, int d, int h_dim, int
     P.dyn_floats = (size_t)2 * B * P.seq_floats;
     P.bytes = P.dyn_off + dec_step_align256(P.dyn_floats * 4);
     return MMT_DEC_STEP_OK;
+}
+
+// What mmt_decoder_stream_prepare writes, as the job table of step_prep_kernel (step_prep.h): every matrix and vector of the layout above
+// and no byte of the carried state.  lstm_params: per layer nn.LSTM's weight_ih_l (4d, 2d for l = 0, else d), weight_hh_l (4d, d),
+// bias_ih_l, bias_hh_l; dec_h0 / dec_c0 (L d) and lstm_params are not read when L == 0.
+static_assert(3 + 2 * MMT_DEC_STEP_MAX_L <= MMT_STEP_PREP_MATS && 4 + MMT_DEC_STEP_MAX_L <= MMT_STEP_PREP_VECS, "the table's capacities");
+static inline void decoder_step_prep_table(const DecStepPlan& S, const float* const* lstm_params, const float* dec_h0, const float* dec_c0,
+                                           const float* W1, const float* b1, const float* W2, const float* b2, StepPrepParams& P, size_t& most) {
+    P.nmat = P.nvec = 0;
+    most = 1;
+    const int L = S.L, d = S.d, G = 4 * S.d;
+    auto mat = [&](const float* src, int ld, int col0, const float* src2, int ld2, int col2, size_t dst, int rows, int K) {
+        step_prep_mat(P, most, src, ld, col0, src2, ld2, col2, dst, rows, K, rows);
+    };
+    for (int l = 0; l < L; ++l) {
+        const float* const* lp = lstm_params + 4 * l;
+        if (l == 0) {
+            mat(lp[0], 2 * d, d, nullptr, 0, 0, S.wx, G, d);                                  // Wx = W_ih[:, d:]
+            if (L == 1) mat(lp[0], 2 * d, 0, lp[1], d, 0, S.wa[0], G, d);                     // W_rec = W_ih[:, :d] + W_hh, as decoder_pack
+            else mat(lp[0], 2 * d, 0, nullptr, 0, 0, S.wa[0], G, d);                          // P_0's first half, as decoder_stack_pack
+        } else {
+            mat(lp[0], d, 0, nullptr, 0, 0, S.wa[l], G, d);
+        }
+        mat(lp[1], d, 0, nullptr, 0, 0, S.wb[l], G, d);
+        step_prep_vec(P, lp[2], lp[3], S.bl[l], G);
+    }
+    mat(W1, d, 0, nullptr, 0, 0, S.w1, S.hdim, d);
+    mat(W2, S.hdim, 0, nullptr, 0, 0, S.w2, 1, S.hdim);
+    step_prep_vec(P, b1, nullptr, S.b1, S.hdim);
+    step_prep_vec(P, b2, nullptr, S.b2, 1);
+    if (L) { step_prep_vec(P, dec_h0, nullptr, S.h0, L * d); step_prep_vec(P, dec_c0, nullptr, S.c0, L * d); }
 }

@@ -42,40 +42,6 @@ struct MfnStepParams {
     MfnStepPlan pl;
 };
 
-// mmt_mfn_stream_prepare: blockIdx.y = job.  A matrix job lays `rows` rows of a row-major fp32 source (leading dimension ld, columns
-// col0 .. col0 + K) into rows row0 .. of a prepared [KP / 8][nout][8] bf16 matrix; a vector job copies n floats (the sum of two
-// sources where a second is given) behind float dst0 of its destination.  Grid-stride over the destination.
-#define MMT_MFN_PREP_MATS 20
-#define MMT_MFN_PREP_VECS 14
-struct MfnPrepMat { const float* src; size_t dst; int ld, col0, rows, K, KP, nout, row0; };
-struct MfnPrepVec { const float* a; const float* b; size_t dst; int n, dst0; };
-struct MfnPrepParams {
-    char* state;
-    int nmat, nvec;
-    MfnPrepMat mat[MMT_MFN_PREP_MATS];
-    MfnPrepVec vec[MMT_MFN_PREP_VECS];
-};
-
-__global__ __launch_bounds__(256) void mfn_step_prep_kernel(const MfnPrepParams P) {
-    const int job = blockIdx.y;
-    const size_t first = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-    if (job < P.nmat) {
-        const MfnPrepMat& J = P.mat[job];
-        bf16* dst = reinterpret_cast<bf16*>(P.state + J.dst);
-        const size_t total = (size_t)J.rows * J.KP;
-        for (size_t i = first; i < total; i += stride) {
-            const int j = (int)(i & 7);
-            const size_t r = i >> 3;
-            const int n = (int)(r % J.rows), k = (int)(r / J.rows) * 8 + j;
-            dst[((size_t)(k >> 3) * J.nout + J.row0 + n) * 8 + j] = k < J.K ? (bf16)J.src[(size_t)n * J.ld + J.col0 + k] : (bf16)0.f;
-        }
-    } else if (job - P.nmat < P.nvec) {
-        const MfnPrepVec& J = P.vec[job - P.nmat];
-        float* dst = reinterpret_cast<float*>(P.state + J.dst) + J.dst0;
-        for (size_t i = first; i < (size_t)J.n; i += stride) dst[i] = J.b ? J.a[i] + J.b[i] : J.a[i];
-    }
-}
-
 // maximum over the workgroup's 256 threads, the same value in every thread; red: 4 floats of LDS.  Two barriers.
 __device__ __forceinline__ float step_block_max(float v, float* red) {
 #pragma unroll

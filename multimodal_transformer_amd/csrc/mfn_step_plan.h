@@ -12,6 +12,7 @@
 //       step t reads copy t & 1 (at t == 0 nothing: zeros stand for it) and writes copy (t + 1) & 1.
 #pragma once
 #include <stddef.h>
+#include "step_prep.h"
 
 #define MMT_MFN_STEP_MAX_MODS 4
 #define MMT_MFN_STEP_MAX_SH 256           // sum of the LSTM hidden sizes: one cell unit per thread
@@ -95,4 +96,40 @@ static inline int mfn_step_plan(MfnStepPlan& P, int B, int nmods, const int* in_
     P.dyn_floats = (size_t)2 * B * P.seq_floats;
     P.bytes = P.dyn_off + mfn_step_align256(P.dyn_floats * 4);
     return MMT_MFN_STEP_OK;
+}
+
+// What mmt_mfn_stream_prepare writes, as the job table of step_prep_kernel (step_prep.h): every matrix and vector of the layout above
+// and no byte of the carried state.  lstm_params: per modality nn.LSTMCell's weight_ih (4H,D), weight_hh (4H,H), bias_ih, bias_hh;
+// gate_params: att1_fc1.{w,b} att1_fc2 att2_fc1 att2_fc2 gamma1_fc1 gamma1_fc2 gamma2_fc1 gamma2_fc2 out_fc1 out_fc2 (_MfnGateFn's order).
+static_assert(MMT_STEP_PREP_MATS == 2 * MMT_MFN_STEP_MAX_MODS + 12 && MMT_STEP_PREP_VECS == MMT_MFN_STEP_MAX_MODS + 10, "the table's capacities");
+static inline void mfn_step_prep_table(const MfnStepPlan& S, const float* const* lstm_params, const float* const* gate_params,
+                                       StepPrepParams& P, size_t& most) {
+    P.nmat = P.nvec = 0;
+    most = 1;
+    auto mat = [&](const float* src, size_t dst, int ld, int col0, int rows, int K, int nout, int row0) {
+        step_prep_mat(P, most, src, ld, col0, nullptr, 0, 0, dst + (size_t)row0 * 8 * 2, rows, K, nout);
+    };
+    auto vec = [&](const float* a, const float* b, size_t dst, int n, int dst0) { step_prep_vec(P, a, b, dst + (size_t)4 * dst0, n); };
+    for (int m = 0; m < S.nm; ++m) {
+        const float* const* lp = lstm_params + 4 * m;
+        mat(lp[0], S.wih[m], S.D[m], 0, 4 * S.H[m], S.D[m], 4 * S.H[m], 0);
+        mat(lp[1], S.whh[m], S.H[m], 0, 4 * S.H[m], S.H[m], 4 * S.H[m], 0);
+        vec(lp[2], lp[3], S.blstm[m], 4 * S.H[m], 0);
+    }
+    const float* const* g = gate_params;
+    const int A = S.A, MD = MMT_MFN_STEP_MD, HG = MMT_MFN_STEP_HG;
+    mat(g[0], S.w[MFN_W_A11], A, 0, MMT_MFN_STEP_ATT1, A, MMT_MFN_STEP_ATT1, 0);   vec(g[1], nullptr, S.b[MFN_B_A11], MMT_MFN_STEP_ATT1, 0);
+    mat(g[2], S.w[MFN_W_A12], MMT_MFN_STEP_ATT1, 0, A, MMT_MFN_STEP_ATT1, A, 0);   vec(g[3], nullptr, S.b[MFN_B_A12], A, 0);
+    mat(g[4], S.w[MFN_W_A21], A, 0, MMT_MFN_STEP_ATT2, A, MMT_MFN_STEP_ATT2, 0);   vec(g[5], nullptr, S.b[MFN_B_A21], MMT_MFN_STEP_ATT2, 0);
+    mat(g[6], S.w[MFN_W_A22], MMT_MFN_STEP_ATT2, 0, MD, MMT_MFN_STEP_ATT2, MD, 0); vec(g[7], nullptr, S.b[MFN_B_A22], MD, 0);
+    for (int i = 0; i < 2; ++i) {                             // gamma{1,2}: fc1 = [attended part | memory part], gamma1's rows above gamma2's
+        const float* w1 = g[8 + 4 * i]; const float* b1 = g[9 + 4 * i]; const float* w2 = g[10 + 4 * i]; const float* b2 = g[11 + 4 * i];
+        mat(w1, S.w[MFN_W_WA], A + MD, 0, HG, A, 2 * HG, i * HG);
+        mat(w1, S.w[MFN_W_WM], A + MD, A, HG, MD, 2 * HG, i * HG);
+        vec(b1, nullptr, S.b[MFN_B_G1], HG, i * HG);
+        mat(w2, S.w[i ? MFN_W_W22 : MFN_W_W21], HG, 0, MD, HG, MD, 0);
+        vec(b2, nullptr, S.b[i ? MFN_B_G22 : MFN_B_G21], MD, 0);
+    }
+    mat(g[16], S.w[MFN_W_O1], S.KL, 0, MMT_MFN_STEP_OUTH, S.KL, MMT_MFN_STEP_OUTH, 0);    vec(g[17], nullptr, S.b[MFN_B_O1], MMT_MFN_STEP_OUTH, 0);
+    mat(g[18], S.w[MFN_W_O2], MMT_MFN_STEP_OUTH, 0, S.OD, MMT_MFN_STEP_OUTH, S.OD, 0);    vec(g[19], nullptr, S.b[MFN_B_O2], S.OD, 0);
 }

@@ -124,6 +124,12 @@ def _take_ws(ctx, op):
 # -3.5 % step time, 64 as 2 x 32: -11 %; 4 streams were no better than 2.  The pieces use seeds of their own (different dropout masks).
 _SPLIT_STREAMS = _lib.StreamFork()
 
+# Modality streams.  The modalities of the MFT are independent until the MFN gate: their embeds, encoder stacks and LSTM scans run on one HIP
+# stream each (the first on the caller's stream): one stack at the reference sizes fills only part of the 256 CUs, so concurrency, not a
+# faster kernel, is what is missing.  ``MMT_MODALITY_STREAMS=0`` serialises everything on one stream.  Here, not beside the models, so that
+# multiTransformer and streaming share the one object.
+_MOD_STREAMS = _lib.StreamFork("MMT_MODALITY_STREAMS")
+
 
 def _row_chunks(B, k):
     k = max(1, min(int(k), B))
@@ -1549,58 +1555,38 @@ def mfn_gate(hs, cs, params, gamma_dropout=0.0, gamma_seed=0, out_dropout=0.0, o
 
 # A causal encoder stack, one window per call (include/mmt_hip.h mmt_encoder_stream_*): eval mode, forward only.  The state (prepared
 # bf16 weights, then the K/V cache) takes memory with any contents, so it comes from _scratch.
-def encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers):
-    """Bytes of the stream state of this shape; ValueError, naming the limit, for a shape outside the step kernel's domain."""
+def _stream_bytes(entry, message, unknown, *dims):
+    """The size query ``entry`` of a stream family; where it returns 0 a ValueError with the library's reason."""
     lib = _lib.load()
-    nbytes = lib.mmt_encoder_stream_bytes(int(B), int(capacity), int(d), int(h), int(d_ff), int(n_layers))
+    nbytes = getattr(lib, entry)(*dims)
     if nbytes == 0:
-        raise ValueError("encoder stream: %s" % (lib.mmt_last_error() or b"?").decode())
+        raise ValueError(message % (lib.mmt_last_error() or unknown).decode())
     return nbytes
 
 
-def encoder_stream_state(B, capacity, d, h, d_ff, n_layers, device):
-    """An unprepared stream state on ``device`` (uint8; any contents)."""
-    return _scratch(encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers), device)
+def _forward_only(op, tensors, why="an input requires grad"):
+    """The streams are inference: nothing that requires grad while grad is enabled."""
+    if torch.is_grad_enabled() and any(isinstance(a, torch.Tensor) and a.requires_grad for a in tensors):
+        raise NotImplementedError("%s: forward only, no autograd (%s)" % (op, why))
 
 
-def _stream_params(op, flat_params, d, d_ff, n_layers):
-    if flat_params.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("%s: forward only, no autograd (parameters that require grad: call it under torch.no_grad())" % op)
-    p_ = _f32c(flat_params)
-    need = _lib.load().mmt_encoder_param_count(d, d_ff, n_layers)
-    if p_.numel() != need:
-        raise ValueError("%s: flat parameter buffer has %d elements, expected %d" % (op, p_.numel(), need))
-    return p_
+_PARAMS_GRAD = "parameters that require grad: pass detached tensors or call it under torch.no_grad()"
 
 
-def _stream_state(op, state, nbytes, device):
+def _step_mask(op, mask_t, B, device):
+    """``mask_t`` of a step: one entry per sequence on the inputs' device -> the (B) float32 argument, or None."""
+    if mask_t is None:
+        return None
+    if not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != device:
+        raise ValueError("%s: mask_t must hold one entry per sequence (B = %d) on %s" % (op, B, device))
+    return _f32c(mask_t).reshape(B)
+
+
+def _stream_state(op, state, nbytes, device, maker):
     if not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < nbytes:
-        raise ValueError("%s: state must be a contiguous uint8 tensor of at least %d bytes (encoder_stream_state)" % (op, nbytes))
+        raise ValueError("%s: state must be a contiguous uint8 tensor of at least %d bytes (%s)" % (op, nbytes, maker))
     if state.device != device:
         raise ValueError("%s: state is on %s, the operands on %s" % (op, state.device, device))
-
-
-def encoder_stream_prepare(flat_params, state, B, capacity, d, h, d_ff, n_layers):
-    """Write the bf16 weights of ``flat_params`` into the front of ``state`` (one launch; the cache is not touched).  Again after the
-    parameters change."""
-    _lib.require_hip(flat_params, state)
-    nbytes = encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers)
-    p_ = _stream_params("encoder_stream_prepare", flat_params, d, d_ff, n_layers)
-    _stream_state("encoder_stream_prepare", state, nbytes, p_.device)
-    _lib.launch("mmt_encoder_stream_prepare", p_, state, state.numel(), int(B), int(capacity), int(d), int(h), int(d_ff), int(n_layers))
-
-
-def _encoder_step_inputs(op, x_t, mask_t):
-    """The checks of an encoder step's inputs that need no device -> (B, d)."""
-    if any(isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled() for a in (x_t, mask_t)):
-        raise NotImplementedError("%s: forward only, no autograd (an input requires grad)" % op)
-    if not isinstance(x_t, torch.Tensor) or x_t.dim() != 2 or x_t.dtype != torch.float32:
-        raise ValueError("%s: x_t must be a float32 (B,d) tensor, got %s %s"
-                         % (op, getattr(x_t, "dtype", type(x_t).__name__), tuple(getattr(x_t, "shape", ()))))
-    B, d = x_t.shape
-    if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != x_t.device):
-        raise ValueError("%s: mask_t must hold one entry per sequence (B = %d) on %s" % (op, B, x_t.device))
-    return B, d
 
 
 def _stream_positions(op, positions, B, device):
@@ -1612,26 +1598,67 @@ def _stream_positions(op, positions, B, device):
                             tuple(getattr(positions, "shape", ())), getattr(positions, "device", None)))
 
 
+def encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers):
+    """Bytes of the stream state of this shape; ValueError, naming the limit, for a shape outside the step kernel's domain."""
+    return _stream_bytes("mmt_encoder_stream_bytes", "encoder stream: %s", b"?", int(B), int(capacity), int(d), int(h), int(d_ff), int(n_layers))
+
+
+def encoder_stream_state(B, capacity, d, h, d_ff, n_layers, device):
+    """An unprepared stream state on ``device`` (uint8; any contents)."""
+    return _scratch(encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers), device)
+
+
+def _stream_params(op, flat_params, d, d_ff, n_layers):
+    _forward_only(op, (flat_params,), "parameters that require grad: call it under torch.no_grad()")
+    p_ = _f32c(flat_params)
+    need = _lib.load().mmt_encoder_param_count(d, d_ff, n_layers)
+    if p_.numel() != need:
+        raise ValueError("%s: flat parameter buffer has %d elements, expected %d" % (op, p_.numel(), need))
+    return p_
+
+
+def encoder_stream_prepare(flat_params, state, B, capacity, d, h, d_ff, n_layers):
+    """Write the bf16 weights of ``flat_params`` into the front of ``state`` (one launch; the cache is not touched).  Again after the
+    parameters change."""
+    _lib.require_hip(flat_params, state)
+    nbytes = encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers)
+    p_ = _stream_params("encoder_stream_prepare", flat_params, d, d_ff, n_layers)
+    _stream_state("encoder_stream_prepare", state, nbytes, p_.device, "encoder_stream_state")
+    _lib.launch("mmt_encoder_stream_prepare", p_, state, state.numel(), int(B), int(capacity), int(d), int(h), int(d_ff), int(n_layers))
+
+
+def _encoder_step(op, x_t, mask_t, flat_params, state, h, d_ff, n_layers, capacity, eps, t=None, positions=None, advance=True):
+    """Both forms of the encoder step: the position is ``t``, by value, or ``positions`` on the device (the capacity is its limit)."""
+    _forward_only(op, (x_t, mask_t))
+    if not isinstance(x_t, torch.Tensor) or x_t.dim() != 2 or x_t.dtype != torch.float32:
+        raise ValueError("%s: x_t must be a float32 (B,d) tensor, got %s %s"
+                         % (op, getattr(x_t, "dtype", type(x_t).__name__), tuple(getattr(x_t, "shape", ()))))
+    B, d = x_t.shape
+    m_ = _step_mask(op, mask_t, B, x_t.device)
+    capacity = int(capacity)
+    if t is not None:
+        where = (int(t),)
+        if not 0 <= where[0] < capacity:
+            raise ValueError("%s: position t = %d outside [0, capacity = %d): open a stream with a larger capacity" % (op, where[0], capacity))
+    else:
+        _stream_positions(op, positions, B, x_t.device)
+        where = (positions, int(bool(advance)))
+    _lib.require_hip(x_t, flat_params, state)
+    nbytes = encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers)
+    p_ = _stream_params(op, flat_params, d, d_ff, n_layers)
+    _stream_state(op, state, nbytes, x_t.device, "encoder_stream_state")
+    x_ = _f32c(x_t)
+    y = torch.empty_like(x_)
+    _lib.launch("mmt_" + op, x_, m_, p_, y, state, state.numel(), *where, B, capacity, d, int(h), int(d_ff), int(n_layers), float(eps))
+    return y
+
+
 def encoder_stream_step(x_t, mask_t, flat_params, state, t, h, d_ff, n_layers, capacity, eps=1e-6):
     """Row t of a causal encoder stack: x_t (B,d), mask_t (B) or None -> y_t (B,d) = Encoder.forward(x, mask)[:, t] with causal attention
     on (transformer/MFT/multiTransformer.py:73-76; departs from :27-31), from the K/V cache in ``state`` (encoder_stream_state, prepared
     by encoder_stream_prepare), to which this window's keys and values are appended.  Steps of a recording run in order t = 0, 1, ...;
     t is passed by value.  One launch.  Forward only: an input that requires grad raises NotImplementedError."""
-    op = "encoder_stream_step"
-    B, d = _encoder_step_inputs(op, x_t, mask_t)
-    t, capacity = int(t), int(capacity)
-    if not 0 <= t < capacity:
-        raise ValueError("%s: position t = %d outside [0, capacity = %d): open a stream with a larger capacity" % (op, t, capacity))
-    _lib.require_hip(x_t, flat_params, state)
-    nbytes = encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers)
-    p_ = _stream_params(op, flat_params, d, d_ff, n_layers)
-    _stream_state(op, state, nbytes, x_t.device)
-    x_ = _f32c(x_t)
-    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
-    y = torch.empty_like(x_)
-    _lib.launch("mmt_encoder_stream_step", x_, m_, p_, y, state, state.numel(), t, B, capacity, d, int(h), int(d_ff), int(n_layers),
-                float(eps))
-    return y
+    return _encoder_step("encoder_stream_step", x_t, mask_t, flat_params, state, h, d_ff, n_layers, capacity, eps, t=int(t))
 
 
 def encoder_stream_step_slots(x_t, mask_t, flat_params, state, positions, h, d_ff, n_layers, capacity, eps=1e-6, advance=True):
@@ -1640,20 +1667,8 @@ def encoder_stream_step_slots(x_t, mask_t, flat_params, state, positions, h, d_f
     zeros, with nothing else written, where the slot is idle (negative) or full (>= capacity).  ``advance``: the kernel adds 1 to the
     position of every slot it ran.  No position crosses the host, so the call can be captured into a graph; the capacity check is the
     kernel's.  One launch."""
-    op = "encoder_stream_step_slots"
-    B, d = _encoder_step_inputs(op, x_t, mask_t)
-    _stream_positions(op, positions, B, x_t.device)
-    capacity = int(capacity)
-    _lib.require_hip(x_t, flat_params, state)
-    nbytes = encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers)
-    p_ = _stream_params(op, flat_params, d, d_ff, n_layers)
-    _stream_state(op, state, nbytes, x_t.device)
-    x_ = _f32c(x_t)
-    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
-    y = torch.empty_like(x_)
-    _lib.launch("mmt_encoder_stream_step_slots", x_, m_, p_, y, state, state.numel(), positions, int(bool(advance)), B, capacity, d, int(h),
-                int(d_ff), int(n_layers), float(eps))
-    return y
+    return _encoder_step("encoder_stream_step_slots", x_t, mask_t, flat_params, state, h, d_ff, n_layers, capacity, eps,
+                         positions=positions, advance=advance)
 
 
 # The MFN gate, one window per call (include/mmt_hip.h mmt_mfn_stream_*): eval mode, forward only.  The state (prepared bf16 weights,
@@ -1673,24 +1688,13 @@ def _mfn_dims(in_dims, hidden):
 def mfn_stream_bytes(B, in_dims, hidden, output_dim):
     """Bytes of the MFN stream state for ``B`` sequences, modalities of input widths ``in_dims`` and LSTM hidden sizes ``hidden``;
     ValueError, naming the limit, for a shape outside the step kernel's domain."""
-    lib = _lib.load()
     n, cd, ch, _, _ = _mfn_dims(in_dims, hidden)
-    nbytes = lib.mmt_mfn_stream_bytes(int(B), n, cd, ch, int(output_dim))
-    if nbytes == 0:
-        raise ValueError((lib.mmt_last_error() or b"mfn stream: ?").decode())
-    return nbytes
+    return _stream_bytes("mmt_mfn_stream_bytes", "%s", b"mfn stream: ?", int(B), n, cd, ch, int(output_dim))
 
 
 def mfn_stream_state(B, in_dims, hidden, output_dim, device):
     """An unprepared MFN stream state on ``device`` (uint8; any contents)."""
     return _scratch(mfn_stream_bytes(B, in_dims, hidden, output_dim), device)
-
-
-def _mfn_stream_state(op, state, nbytes, device):
-    if not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < nbytes:
-        raise ValueError("%s: state must be a contiguous uint8 tensor of at least %d bytes (mfn_stream_state)" % (op, nbytes))
-    if state.device != device:
-        raise ValueError("%s: state is on %s, the operands on %s" % (op, state.device, device))
 
 
 def mfn_stream_prepare(lstm_params, gate_params, state, B, in_dims, hidden, output_dim):
@@ -1700,9 +1704,7 @@ def mfn_stream_prepare(lstm_params, gate_params, state, B, in_dims, hidden, outp
     op = "mfn_stream_prepare"
     lstm = [q for cell in lstm_params for q in cell]
     gate = list(gate_params)
-    if any(q.requires_grad and torch.is_grad_enabled() for q in lstm + gate):
-        raise NotImplementedError("%s: forward only, no autograd (parameters that require grad: pass detached tensors or call it under "
-                                  "torch.no_grad())" % op)
+    _forward_only(op, lstm + gate, _PARAMS_GRAD)
     n, cd, ch, D, H = _mfn_dims(in_dims, hidden)
     nbytes = mfn_stream_bytes(B, D, H, output_dim)
     SH, MD, HG = sum(H), 128, 64
@@ -1716,18 +1718,17 @@ def mfn_stream_prepare(lstm_params, gate_params, state, B, in_dims, hidden, outp
         raise ValueError("%s: the gate's sizes are fixed in the step kernel (%s); got %s"
                          % (op, _MFN_GATE_SHAPES, [tuple(q.shape) for q in gate]))
     _lib.require_hip(state, *lstm, *gate)
-    _mfn_stream_state(op, state, nbytes, lstm[0].device)
+    _stream_state(op, state, nbytes, lstm[0].device, "mfn_stream_state")
     keep = [_f32c(q) for q in lstm + gate]                                 # alive until the launch is enqueued
     pl = (ctypes.c_void_p * len(lstm))(*[q.data_ptr() for q in keep[:len(lstm)]])
     pg = (ctypes.c_void_p * 20)(*[q.data_ptr() for q in keep[len(lstm):]])
     _lib.launch("mmt_mfn_stream_prepare", pl, pg, state, state.numel(), int(B), n, cd, ch, int(output_dim))
 
 
-def _mfn_step_inputs(op, xs, mask_t, in_dims, hidden):
-    """The checks of a gate step's inputs that need no device -> (xs, n, cd, ch, D, H, B, device)."""
+def _mfn_step(op, xs, mask_t, state, in_dims, hidden, output_dim, t=None, positions=None, limit=None, advance=True):
+    """Both forms of the gate step: the position is ``t``, by value, or ``positions`` on the device with their ``limit``."""
     xs = list(xs)
-    if any(isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled() for a in xs + [mask_t]):
-        raise NotImplementedError("%s: forward only, no autograd (an input requires grad)" % op)
+    _forward_only(op, xs + [mask_t])
     n, cd, ch, D, H = _mfn_dims(in_dims, hidden)
     if len(xs) != n:
         raise ValueError("%s: %d inputs for %d modalities" % (op, len(xs), n))
@@ -1737,9 +1738,22 @@ def _mfn_step_inputs(op, xs, mask_t, in_dims, hidden):
             raise ValueError("%s: every x_t must be a float32 (B, %d) tensor on one device, got %s %s on %s"
                              % (op, d, getattr(x, "dtype", type(x).__name__), tuple(getattr(x, "shape", ())), getattr(x, "device", None)))
     B, dev = xs[0].shape[0], xs[0].device
-    if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != dev):
-        raise ValueError("%s: mask_t must hold one entry per sequence (B = %d) on %s" % (op, B, dev))
-    return xs, n, cd, ch, D, H, B, dev
+    m_ = _step_mask(op, mask_t, B, dev)
+    if t is not None:
+        where = (int(t),)
+        if where[0] < 0:
+            raise ValueError("%s: position t = %d is negative" % (op, where[0]))
+    else:
+        _stream_positions(op, positions, B, dev)
+        where = (positions, 0 if limit is None else int(limit), int(bool(advance)))
+    _lib.require_hip(*xs, state)
+    nbytes = mfn_stream_bytes(B, D, H, output_dim)
+    _stream_state(op, state, nbytes, dev, "mfn_stream_state")
+    keep = [_f32c(x) for x in xs]
+    px = (ctypes.c_void_p * n)(*[x.data_ptr() for x in keep])
+    y = torch.empty(B, int(output_dim), dtype=torch.float32, device=dev)
+    _lib.launch("mmt_" + op, px, m_, y, state, state.numel(), *where, B, n, cd, ch, int(output_dim))
+    return y
 
 
 def mfn_stream_step(xs, mask_t, state, t, in_dims, hidden, output_dim):
@@ -1747,20 +1761,7 @@ def mfn_stream_step(xs, mask_t, state, t, in_dims, hidden, output_dim):
     in eval mode, times mask_t (transformer/MFT/multiTransformer.py:200-247, :310), from the (h, c, mem) carried in ``state``
     (mfn_stream_state, prepared by mfn_stream_prepare), which this call advances.  Steps of a recording run in order t = 0, 1, ...;
     t is passed by value.  One launch.  Forward only: an input that requires grad raises NotImplementedError."""
-    op = "mfn_stream_step"
-    xs, n, cd, ch, D, H, B, dev = _mfn_step_inputs(op, xs, mask_t, in_dims, hidden)
-    t = int(t)
-    if t < 0:
-        raise ValueError("%s: position t = %d is negative" % (op, t))
-    _lib.require_hip(*xs, state)
-    nbytes = mfn_stream_bytes(B, D, H, output_dim)
-    _mfn_stream_state(op, state, nbytes, dev)
-    keep = [_f32c(x) for x in xs]
-    px = (ctypes.c_void_p * n)(*[x.data_ptr() for x in keep])
-    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
-    y = torch.empty(B, int(output_dim), dtype=torch.float32, device=dev)
-    _lib.launch("mmt_mfn_stream_step", px, m_, y, state, state.numel(), t, B, n, cd, ch, int(output_dim))
-    return y
+    return _mfn_step("mfn_stream_step", xs, mask_t, state, in_dims, hidden, output_dim, t=int(t))
 
 
 def mfn_stream_step_slots(xs, mask_t, state, positions, in_dims, hidden, output_dim, limit=None, advance=True):
@@ -1769,19 +1770,7 @@ def mfn_stream_step_slots(xs, mask_t, state, positions, in_dims, hidden, output_
     the other written), where the slot is seated, and zeros, with nothing else written, where it is idle (negative) or full
     (>= ``limit``; None: no limit).  ``advance``: the kernel adds 1 to the position of every slot it ran.  No position crosses the host,
     so the call can be captured into a graph.  One launch."""
-    op = "mfn_stream_step_slots"
-    xs, n, cd, ch, D, H, B, dev = _mfn_step_inputs(op, xs, mask_t, in_dims, hidden)
-    _stream_positions(op, positions, B, dev)
-    _lib.require_hip(*xs, state)
-    nbytes = mfn_stream_bytes(B, D, H, output_dim)
-    _mfn_stream_state(op, state, nbytes, dev)
-    keep = [_f32c(x) for x in xs]
-    px = (ctypes.c_void_p * n)(*[x.data_ptr() for x in keep])
-    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
-    y = torch.empty(B, int(output_dim), dtype=torch.float32, device=dev)
-    _lib.launch("mmt_mfn_stream_step_slots", px, m_, y, state, state.numel(), positions, 0 if limit is None else int(limit),
-                int(bool(advance)), B, n, cd, ch, int(output_dim))
-    return y
+    return _mfn_step("mfn_stream_step_slots", xs, mask_t, state, in_dims, hidden, output_dim, positions=positions, limit=limit, advance=advance)
 
 
 # The affine map with its operands prepared once (include/mmt_hip.h mmt_linear_prepare / mmt_linear_forward_prepared): forward only.
@@ -1789,8 +1778,7 @@ def linear_prepare(W, b, prepared=None):
     """The padded bf16 copy of ``W`` (N, K) and the padded bias ``b`` (N) or None, as ``linear`` lays them into its workspace at every
     call -> a uint8 tensor for ``linear_prepared`` (``prepared``: one of this shape to write again), which carries its (K, N): the
     padded layout alone does not tell two shapes of one padded size apart.  Two launches."""
-    if any(q is not None and q.requires_grad and torch.is_grad_enabled() for q in (W, b)):
-        raise NotImplementedError("linear_prepare: forward only, no autograd (pass detached tensors or call it under torch.no_grad())")
+    _forward_only("linear_prepare", (W, b), "pass detached tensors or call it under torch.no_grad()")
     if not isinstance(W, torch.Tensor) or W.dim() != 2 or (b is not None and tuple(b.shape) != (W.shape[0],)):
         raise ValueError("linear_prepare: W must be (N, K) and b (N) or None")
     N, K = W.shape
@@ -1812,8 +1800,7 @@ def linear_prepare(W, b, prepared=None):
 def linear_prepared(x, prepared, N, act=0, rowscale=None):
     """``linear(x, W, b, act, rowscale)`` of x (M, K) with (W, b) given as ``linear_prepare(W, b)``: ONE launch, the row GEMM alone on
     the same operands, so the same bits.  Forward only."""
-    if any(isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled() for a in (x, rowscale)):
-        raise NotImplementedError("linear_prepared: forward only, no autograd (an input requires grad)")
+    _forward_only("linear_prepared", (x, rowscale))
     if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
         raise ValueError("linear_prepared: x must be a float32 (M, K) tensor")
     M, K = x.shape
@@ -1838,23 +1825,12 @@ def linear_prepared(x, prepared, N, act=0, rowscale=None):
 def decoder_stream_bytes(B, d, h_dim, n_layers):
     """Bytes of the decoder stream state for ``B`` sequences, embed_dim ``d``, read-out width ``h_dim`` and ``n_layers`` LSTM layers
     (0: the read-out alone); ValueError, naming the limit, for a shape outside the step kernel's domain."""
-    lib = _lib.load()
-    nbytes = lib.mmt_decoder_stream_bytes(int(B), int(d), int(h_dim), int(n_layers))
-    if nbytes == 0:
-        raise ValueError((lib.mmt_last_error() or b"decoder stream: ?").decode())
-    return nbytes
+    return _stream_bytes("mmt_decoder_stream_bytes", "%s", b"decoder stream: ?", int(B), int(d), int(h_dim), int(n_layers))
 
 
 def decoder_stream_state(B, d, h_dim, n_layers, device):
     """An unprepared decoder stream state on ``device`` (uint8; any contents)."""
     return _scratch(decoder_stream_bytes(B, d, h_dim, n_layers), device)
-
-
-def _decoder_stream_state(op, state, nbytes, device):
-    if not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < nbytes:
-        raise ValueError("%s: state must be a contiguous uint8 tensor of at least %d bytes (decoder_stream_state)" % (op, nbytes))
-    if state.device != device:
-        raise ValueError("%s: state is on %s, the operands on %s" % (op, state.device, device))
 
 
 def decoder_stream_prepare(lstm_params, dec_h0, dec_c0, out_params, state, B, d, h_dim, n_layers):
@@ -1867,9 +1843,7 @@ def decoder_stream_prepare(lstm_params, dec_h0, dec_c0, out_params, state, B, d,
     lstm = [q for layer in (lstm_params or []) for q in layer]
     out = list(out_params)
     init = [dec_h0, dec_c0] if L else []
-    if any(q is not None and q.requires_grad and torch.is_grad_enabled() for q in lstm + out + init):
-        raise NotImplementedError("%s: forward only, no autograd (parameters that require grad: pass detached tensors or call it under "
-                                  "torch.no_grad())" % op)
+    _forward_only(op, lstm + out + init, _PARAMS_GRAD)
     nbytes = decoder_stream_bytes(B, d, h_dim, L)
     want = [s for l in range(L) for s in ((4 * d, 2 * d if l == 0 else d), (4 * d, d), (4 * d,), (4 * d,))]
     if [tuple(q.shape) for q in lstm] != want:
@@ -1881,7 +1855,7 @@ def decoder_stream_prepare(lstm_params, dec_h0, dec_c0, out_params, state, B, d,
     if [tuple(q.shape) for q in out] != want:
         raise ValueError("%s: the read-out's parameters have the shapes %s, expected %s" % (op, [tuple(q.shape) for q in out], want))
     _lib.require_hip(state, *lstm, *out, *init)
-    _decoder_stream_state(op, state, nbytes, out[0].device)
+    _stream_state(op, state, nbytes, out[0].device, "decoder_stream_state")
     keep = [_f32c(q) for q in lstm + init + out]                           # alive until the launch is enqueued
     pl = (ctypes.c_void_p * max(len(lstm), 1))(*[q.data_ptr() for q in keep[:len(lstm)]]) if L else None
     h0, c0 = (keep[len(lstm)], keep[len(lstm) + 1]) if L else (None, None)
@@ -1889,17 +1863,28 @@ def decoder_stream_prepare(lstm_params, dec_h0, dec_c0, out_params, state, B, d,
     _lib.launch("mmt_decoder_stream_prepare", pl, h0, c0, W1, b1, W2, b2, state, state.numel(), int(B), d, h_dim, L)
 
 
-def _decoder_step_inputs(op, e_t, mask_t, d):
-    """The checks of a decoder step's inputs that need no device -> (B, device)."""
-    if any(isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled() for a in (e_t, mask_t)):
-        raise NotImplementedError("%s: forward only, no autograd (an input requires grad)" % op)
+def _decoder_step(op, e_t, mask_t, state, d, h_dim, n_layers, t=None, positions=None, limit=None, advance=True):
+    """Both forms of the decoder step: the position is ``t``, by value, or ``positions`` on the device with their ``limit``."""
+    _forward_only(op, (e_t, mask_t))
     if not isinstance(e_t, torch.Tensor) or e_t.dim() != 2 or e_t.dtype != torch.float32 or e_t.shape[1] != int(d):
         raise ValueError("%s: e_t must be a float32 (B, %d) tensor, got %s %s"
                          % (op, int(d), getattr(e_t, "dtype", type(e_t).__name__), tuple(getattr(e_t, "shape", ()))))
     B, dev = e_t.shape[0], e_t.device
-    if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != dev):
-        raise ValueError("%s: mask_t must hold one entry per sequence (B = %d) on %s" % (op, B, dev))
-    return B, dev
+    m_ = _step_mask(op, mask_t, B, dev)
+    if t is not None:
+        where = (int(t),)
+        if where[0] < 0:
+            raise ValueError("%s: position t = %d is negative" % (op, where[0]))
+    else:
+        _stream_positions(op, positions, B, dev)
+        where = (positions, 0 if limit is None else int(limit), int(bool(advance)))
+    _lib.require_hip(e_t, state)
+    nbytes = decoder_stream_bytes(B, d, h_dim, n_layers)
+    _stream_state(op, state, nbytes, dev, "decoder_stream_state")
+    e_ = _f32c(e_t)
+    y = torch.empty(B, 1, dtype=torch.float32, device=dev)
+    _lib.launch("mmt_" + op, e_, m_, y, state, state.numel(), *where, B, int(d), int(h_dim), int(n_layers))
+    return y
 
 
 def decoder_stream_step(e_t, mask_t, state, t, d, h_dim, n_layers):
@@ -1907,19 +1892,7 @@ def decoder_stream_step(e_t, mask_t, state, t, d, h_dim, n_layers):
     what ``_DecoderMixin._decode`` gives at [:, t] in eval mode, times mask_t (transformer/SFT/multiTransformer.py:463-483), from the
     (h, c) of every layer carried in ``state`` (decoder_stream_state, prepared by decoder_stream_prepare), which this call advances.
     Steps of a recording run in order t = 0, 1, ...; t is passed by value.  One launch.  Forward only."""
-    op = "decoder_stream_step"
-    B, dev = _decoder_step_inputs(op, e_t, mask_t, d)
-    t = int(t)
-    if t < 0:
-        raise ValueError("%s: position t = %d is negative" % (op, t))
-    _lib.require_hip(e_t, state)
-    nbytes = decoder_stream_bytes(B, d, h_dim, n_layers)
-    _decoder_stream_state(op, state, nbytes, dev)
-    e_ = _f32c(e_t)
-    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
-    y = torch.empty(B, 1, dtype=torch.float32, device=dev)
-    _lib.launch("mmt_decoder_stream_step", e_, m_, y, state, state.numel(), t, B, int(d), int(h_dim), int(n_layers))
-    return y
+    return _decoder_step("decoder_stream_step", e_t, mask_t, state, d, h_dim, n_layers, t=int(t))
 
 
 def decoder_stream_step_slots(e_t, mask_t, state, positions, d, h_dim, n_layers, limit=None, advance=True):
@@ -1928,18 +1901,7 @@ def decoder_stream_step_slots(e_t, mask_t, state, positions, d, h_dim, n_layers,
     state read, the other written), where the slot is seated, and zero, with nothing else written, where it is idle (negative) or full
     (>= ``limit``; None: no limit).  ``advance``: the kernel adds 1 to the position of every slot it ran.  No position crosses the host,
     so the call can be captured into a graph.  One launch."""
-    op = "decoder_stream_step_slots"
-    B, dev = _decoder_step_inputs(op, e_t, mask_t, d)
-    _stream_positions(op, positions, B, dev)
-    _lib.require_hip(e_t, state)
-    nbytes = decoder_stream_bytes(B, d, h_dim, n_layers)
-    _decoder_stream_state(op, state, nbytes, dev)
-    e_ = _f32c(e_t)
-    m_ = None if mask_t is None else _f32c(mask_t).reshape(B)
-    y = torch.empty(B, 1, dtype=torch.float32, device=dev)
-    _lib.launch("mmt_decoder_stream_step_slots", e_, m_, y, state, state.numel(), positions, 0 if limit is None else int(limit),
-                int(bool(advance)), B, int(d), int(h_dim), int(n_layers))
-    return y
+    return _decoder_step("decoder_stream_step_slots", e_t, mask_t, state, d, h_dim, n_layers, positions=positions, limit=limit, advance=advance)
 
 
 def check_device_errors():

@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import _lib, functional as F_hip
 from .multiTransformer import (MultiTransformer, MultiTransformerB3, NLPTransformer, UniFullTransformer, UniTransformer, _MOD_STREAMS,
-                               _hip_device)
+                               _hip_device, _stream_model_checks)
 
 
 class Highway(nn.Module):
@@ -113,21 +113,17 @@ class _FrontEnd(nn.Module):
 class _FrontEndStream:
     """``stream()`` of the MultiCNNTransformer wrappers: ``step({mod: (B, W, d_raw)}, mask_t)`` -> the (B,1) prediction of that window.
     The window encoder runs on a T = 1 batch (``_encode``), then the fusion layer where the model has one, then the sequence model's
-    own step (``multiTransformer._SequenceStream``; the MFT and B3-MFN take the per-modality rows as a dict:
-    ``multiTransformer._GateStream``).  ``reset()`` starts a new recording."""
+    own step (``streaming._SequenceStream``; the MFT and B3-MFN take the per-modality rows as a dict: ``streaming._GateStream``).  ``reset()`` starts a new recording."""
 
-    def __init__(self, model, batch, capacity, slots=False, device=False):
-        if model.training:
-            raise ValueError("%s.stream: the model is in train mode; streaming is eval-mode inference (call .eval())" % type(model).__name__)
+    def __init__(self, model, batch, capacity, method="stream"):
+        """``method``: the sequence model's method that opens its stream, "stream", "slot_stream" or "device_stream"."""
+        _stream_model_checks(model)
         self.model, self.batch = model, int(batch)
-        if device:                                           # ``device_stream``: the sequence model's stream with its state on the device
-            self.seq = model.Transformer.device_stream(batch, capacity)
-        else:
-            self.seq = model.Transformer.slot_stream(batch, capacity) if slots else model.Transformer.stream(batch, capacity)
+        self.seq = getattr(model.Transformer, method)(batch, capacity)
 
     t = property(lambda self: self.seq.t)                   # a slots stream: AttributeError naming .positions
     capacity = property(lambda self: self.seq.capacity)
-    # with slots (``slot_stream``): the members of multiTransformer._Slots, those of the sequence model's stream
+    # with slots (``slot_stream``): the members of streaming._Slots, those of the sequence model's stream
     slots = property(lambda self: self.seq.slots)
     positions = property(lambda self: self.seq.positions)
 
@@ -146,7 +142,7 @@ class _FrontEndStream:
     def refresh(self):
         """Convert the sequence model's current parameters again, where its stream keeps converted copies (the MFT, the B3-MFN and every
         ``device_stream``; the window encoder itself reads the live parameters)."""
-        if not hasattr(self.seq, "refresh"):                 # multiTransformer._SequenceStream packs the decoder's weights when it is opened
+        if not hasattr(self.seq, "refresh"):                 # streaming._SequenceStream packs the decoder's weights when it is opened
             raise NotImplementedError("%s.stream: the stream of %s has no refresh() (it packs the decoder's weights once, when it is "
                                       "opened): open a new stream after a parameter changed, or use device_stream, whose refresh() "
                                       "follows it" % (type(self.model).__name__, type(self.model.Transformer).__name__))
@@ -206,7 +202,7 @@ class MultiCNNTransformer(_FrontEnd):
     def device_stream(self, batch, capacity):
         """``stream(batch, capacity)`` with the sequence model's whole per-recording state on the device (its ``device_stream``): sequences
         are seated and released independently, and a step can be captured into a graph (``graphs.capture_stream``)."""
-        return _FrontEndStream(self, batch, capacity, device=True)
+        return _FrontEndStream(self, batch, capacity, "device_stream")
 
 
 class MultiCNNTransformerMFT(_FrontEnd):
@@ -248,9 +244,9 @@ class MultiCNNTransformerMFT(_FrontEnd):
 
     def slot_stream(self, batch, capacity):
         """``stream_modalities(batch, capacity)`` with slots: sequences are seated and released independently (``.positions``,
-        ``.seat``, ``.release``, ``.full``: multiTransformer._Slots), and a step can be captured into a graph
+        ``.seat``, ``.release``, ``.full``: streaming._Slots), and a step can be captured into a graph
         (``graphs.capture_stream``).  One modality: NotImplementedError, the UniTransformer keeps host-side state per recording."""
-        return _FrontEndStream(self, batch, capacity, slots=True)
+        return _FrontEndStream(self, batch, capacity, "slot_stream")
 
     def device_stream(self, batch, capacity):
         """One modality: the UniTransformer's ``device_stream`` behind the window encoder (its whole per-recording state on the device:
@@ -259,7 +255,7 @@ class MultiCNNTransformerMFT(_FrontEnd):
         if len(self.mods) > 1:
             raise NotImplementedError("MultiCNNTransformerMFT.device_stream: with more than one modality the sequence model is the MFT, whose slots "
                                       "stream is slot_stream(batch, capacity)")
-        return _FrontEndStream(self, batch, capacity, device=True)
+        return _FrontEndStream(self, batch, capacity, "device_stream")
 
 
 class MultiCNNTransformerB2(_FrontEnd):
@@ -290,7 +286,7 @@ class MultiCNNTransformerB2(_FrontEnd):
     def device_stream(self, batch, capacity):
         """``stream(batch, capacity)`` with the sequence model's whole per-recording state on the device (its ``device_stream``): sequences
         are seated and released independently, and a step can be captured into a graph (``graphs.capture_stream``)."""
-        return _FrontEndStream(self, batch, capacity, device=True)
+        return _FrontEndStream(self, batch, capacity, "device_stream")
 
 
 class MultiCNNTransformerB3(_FrontEnd):
@@ -324,9 +320,9 @@ class MultiCNNTransformerB3(_FrontEnd):
 
     def slot_stream(self, batch, capacity=None):
         """``stream(batch)`` with slots: sequences are seated and released independently (``.positions``, ``.seat``, ``.release``,
-        ``.full``: multiTransformer._Slots), and a step can be captured into a graph (``graphs.capture_stream``).  One modality:
+        ``.full``: streaming._Slots), and a step can be captured into a graph (``graphs.capture_stream``).  One modality:
         NotImplementedError, the UniTransformer keeps host-side state per recording."""
-        return _FrontEndStream(self, batch, capacity, slots=True)
+        return _FrontEndStream(self, batch, capacity, "slot_stream")
 
     def device_stream(self, batch, capacity=None):
         """One modality: the UniTransformer's ``device_stream`` behind the window encoder (its whole per-recording state on the device:
@@ -338,7 +334,7 @@ class MultiCNNTransformerB3(_FrontEnd):
         if capacity is None:
             raise ValueError("MultiCNNTransformerB3.device_stream: with one modality the sequence model is the UniTransformer, whose K/V "
                              "cache needs a capacity (windows per recording)")
-        return _FrontEndStream(self, batch, capacity, device=True)
+        return _FrontEndStream(self, batch, capacity, "device_stream")
 
 
 class _LocalAttnLSTM(nn.Module):

@@ -28,6 +28,11 @@ import torch.nn as nn
 
 from . import _lib
 from . import functional as F_hip
+from .functional import _MOD_STREAMS            # the one object, shared with streaming; models imports it from here
+# the models as online predictors: what stream() / slot_stream() / device_stream() below open
+from .streaming import (_INT_MAX, EncoderSlotStream, EncoderStream, MFNSlotStream, MFNStream, _GateSlotStream, _GateStream,
+                        _modality_rows, _no_slot_stream, _SequenceSlotStream, _SequenceStream, _slot_positions, _Slots,
+                        _stream_model_checks)
 
 
 def clones(module, N):
@@ -340,10 +345,8 @@ class Encoder(nn.Module):
                                           flat=self._flat_storage(ps) if x.is_cuda else None, nsplit=k, key_lengths=kl,
                                           causal=causal)
 
-    def stream(self, batch, capacity):
-        """Open an ``EncoderStream``: this stack as an online predictor for ``batch`` recordings of up to ``capacity`` windows, one
-        window per ``step`` against a K/V cache instead of a forward over the whole prefix.  Eval mode, forward only; every layer must
-        attend causally (``causal_attention(model)``).  Raises ValueError, before any launch, for anything else."""
+    def _stream_refusals(self):
+        """What ``stream`` and ``slot_stream`` refuse, before anything is allocated or launched."""
         name = type(self).__name__
         if self.training:
             raise ValueError("%s.stream: the encoder is in train mode; streaming is eval-mode inference (call .eval())" % name)
@@ -360,13 +363,20 @@ class Encoder(nn.Module):
                              "predicted online: call causal_attention(model) (and train the model that way)" % name)
         if self.norm.a_2.device.type != "cuda":
             raise ValueError("%s.stream: the encoder is on %s; move it to a HIP device (there is no CPU path)" % (name, self.norm.a_2.device))
+
+    def stream(self, batch, capacity):
+        """Open an ``EncoderStream``: this stack as an online predictor for ``batch`` recordings of up to ``capacity`` windows, one
+        window per ``step`` against a K/V cache instead of a forward over the whole prefix.  Eval mode, forward only; every layer must
+        attend causally (``causal_attention(model)``).  Raises ValueError, before any launch, for anything else."""
+        self._stream_refusals()
         return EncoderStream(self, batch, capacity)
 
     def slot_stream(self, batch, capacity, positions=None):
         """``stream(batch, capacity)`` with slots (``EncoderSlotStream``): the position of every sequence lives on the device, so the
         sequences are seated and released independently and a step can be captured into a graph (``graphs.capture_stream``).  The same
         refusals, before any launch."""
-        return EncoderSlotStream(self.stream(batch, capacity), positions)
+        self._stream_refusals()
+        return EncoderSlotStream(self, batch, capacity, positions)
 
     sub_batch_streams = 1        # set to 2: the batch runs as two halves on two HIP streams (functional._SPLIT_STREAMS); opt-in
     sub_batch_min_windows = 8192
@@ -382,282 +392,9 @@ class Encoder(nn.Module):
         return min(k, x.shape[0])
 
 
-class EncoderStream:
-    """A causal ``Encoder`` run one window at a time (``Encoder.stream``): ``step(x_t)`` returns the row that the encoder's batch
-    forward gives at position ``t`` of the windows stepped so far, in ONE kernel launch (csrc/encoder_step.h), and advances ``t``.
-    The state is the bf16 copy of the weight matrices and the bf16 K / V of every layer for ``batch`` x ``capacity`` windows.
-
-    ``reset()`` starts a new recording: it sets ``t`` back to 0 and neither clears nor re-reads anything.  ``refresh()`` converts the
-    weights again: call it after the encoder's parameters changed (biases and LayerNorm weights are read live).  Rows agree with the
-    batch forward to the distance between two roundings of the same arithmetic (about 1.5e-3 rel-L2), not bit for bit."""
-
-    slots = False                    # True in EncoderSlotStream: positions on the device instead of ``t``
-
-    def __init__(self, encoder, batch, capacity):
-        l0 = encoder.layers[0]
-        self.encoder = encoder
-        self.batch, self.capacity = int(batch), int(capacity)
-        if not self.slots:
-            self.t = 0
-        self.d, self.h, self.d_ff, self.n_layers = l0.size, l0.self_attn.h, l0.feed_forward.w_1.weight.shape[0], len(encoder.layers)
-        self.eps = encoder.norm.eps
-        self.device = encoder.norm.a_2.device
-        if self.batch < 1 or self.capacity < 1:
-            raise ValueError("Encoder.stream: batch and capacity must be at least 1, got %d and %d" % (self.batch, self.capacity))
-        self._dims = (self.batch, self.capacity, self.d, self.h, self.d_ff, self.n_layers)
-        self.state = F_hip.encoder_stream_state(*self._dims, self.device)        # ValueError naming the limit for an unsupported shape
-        self.refresh()
-
-    def refresh(self):
-        """Convert the encoder's current weight matrices into the state (one launch); the cache and ``t`` stay."""
-        ps = self.encoder.flat_parameters()
-        flat = self.encoder._flat_storage(ps)
-        if flat is None:
-            flat = torch.cat([q.detach().reshape(-1) for q in ps]).float()
-        self._flat = flat.detach()
-        F_hip.encoder_stream_prepare(self._flat, self.state, *self._dims)
-
-    def reset(self):
-        self.t = 0
-
-    def step(self, x_t, mask_t=None):
-        """x_t (B,d) or (B,1,d) float32 on the encoder's device, mask_t (B), (B,1) or (B,1,1) or None -> the same shape as x_t."""
-        if self.t >= self.capacity:
-            raise ValueError("EncoderStream.step: the stream is full (t = capacity = %d): reset() starts a new recording, "
-                             "Encoder.stream(batch, capacity) opens a longer one" % self.capacity)
-        self._check_step(x_t, mask_t)
-        y = F_hip.encoder_stream_step(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.t, self.h, self.d_ff,
-                                      self.n_layers, self.capacity, self.eps)
-        self.t += 1
-        return y.view(x_t.shape)
-
-    def _check_step(self, x_t, mask_t):
-        if not isinstance(x_t, torch.Tensor) or x_t.dtype != torch.float32 or x_t.device != self.device:
-            raise ValueError("EncoderStream.step: x_t must be a float32 tensor on %s, got %s on %s"
-                             % (self.device, getattr(x_t, "dtype", type(x_t).__name__), getattr(x_t, "device", None)))
-        if tuple(x_t.shape) not in ((self.batch, self.d), (self.batch, 1, self.d)):
-            raise ValueError("EncoderStream.step: x_t must have the shape (%d,%d) or (%d,1,%d), got %s"
-                             % (self.batch, self.d, self.batch, self.d, tuple(x_t.shape)))
-        if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != self.batch or mask_t.device != self.device):
-            raise ValueError("EncoderStream.step: mask_t must hold one entry per sequence (%d) on %s" % (self.batch, self.device))
-
-
-_INT_MAX = 2 ** 31 - 1
-
-
-def _slot_positions(op, positions, batch, device):
-    """The positions of a slots stream: a new int32 (batch) tensor, every slot idle, or the one a composite stream shares."""
-    if positions is None:
-        return torch.full((batch,), -1, dtype=torch.int32, device=device)
-    if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32 or tuple(positions.shape) != (batch,) \
-            or not positions.is_contiguous() or positions.device != device:
-        raise ValueError("%s: positions must be a contiguous int32 (%d,) tensor on %s" % (op, batch, device))
-    return positions
-
-
-class _Slots:
-    """What every slots stream has instead of ``t``: ``positions``, int32 (batch) on the device, read and advanced by the step kernels
-    (csrc/step_slots.h).  A slot is idle (-1, as opened), seated (0 <= position < capacity: its next window) or full (>= capacity).  A
-    step gives an idle or full slot a zero row and touches nothing of it.  ``seat`` / ``release`` / ``reset`` are ordinary device
-    operations on the current stream, between steps (or between the replays of a captured step); none of them synchronises."""
-
-    slots = True
-
-    @property
-    def t(self):
-        raise AttributeError("a slots stream has no single position t: every sequence has its own, see .positions (int32 on the device)")
-
-    def _index(self, indices):
-        return torch.as_tensor(indices, dtype=torch.long, device=self.positions.device).reshape(-1)
-
-    def seat(self, indices):
-        """Start a new recording in these slots: their positions become 0.  Nothing is cleared; nothing needs to be."""
-        self.positions.index_fill_(0, self._index(indices), 0)
-
-    def release(self, indices):
-        """Make these slots idle: their positions become -1."""
-        self.positions.index_fill_(0, self._index(indices), -1)
-
-    def reset(self):
-        """Seat every slot."""
-        self.positions.zero_()
-
-    def full(self):
-        """bool (batch) on the device: the slots whose recording has used the whole capacity (no synchronisation)."""
-        return self.positions >= (_INT_MAX if self.capacity is None else self.capacity)
-
-
-class EncoderSlotStream(_Slots, EncoderStream):
-    """``EncoderStream`` with slots (``Encoder.slot_stream``; members: ``_Slots``).  ``step(x_t, mask_t)`` is ONE launch of
-    encoder_step_slots_kernel: row b is what an ``EncoderStream`` of that recording alone gives at window ``positions[b]``, bit for bit
-    (the same kernel body, one workgroup per sequence), and the kernel advances the positions of the slots it ran.  No position crosses
-    the host, so there is no "full" error: a full slot gets a zero row, and ``full()`` shows it."""
-
-    def __init__(self, opened, positions=None):
-        self.__dict__.update({k: v for k, v in opened.__dict__.items() if k != "t"})     # the state and the weights of the stream just opened
-        self.positions = _slot_positions("Encoder.slot_stream", positions, self.batch, self.device)
-
-    def step(self, x_t, mask_t=None, advance=True):
-        """As ``EncoderStream.step``.  ``advance=False`` leaves the positions (a composite stream advances them once, in its last launch)."""
-        self._check_step(x_t, mask_t)
-        y = F_hip.encoder_stream_step_slots(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.positions, self.h,
-                                            self.d_ff, self.n_layers, self.capacity, self.eps, advance=advance)
-        return y.view(x_t.shape)
-
-
-def _stream_model_checks(model):
-    if model.training:
-        raise ValueError("%s.stream: the model is in train mode; streaming is eval-mode inference (call .eval())" % type(model).__name__)
-
-
-def _no_slot_stream(model):
-    raise NotImplementedError("%s.slot_stream: this model's stream keeps host-side state per recording (one position t for the batch; "
-                              "with an LSTM decoder also the carried (h, c) and the first row h0 W_hh, chosen on the host at t == 0), so "
-                              "its sequences cannot be seated independently; slots serve Encoder, MFN, MultiTransformer and MultiTransformerB3 "
-                              "(and their wrappers).  Use stream(batch, capacity), or device_stream(batch, capacity), which keeps that "
-                              "state on the device and seats sequences independently" % type(model).__name__)
-
-
-class _SequenceStream:
-    """``stream()`` of UniFullTransformer, UniTransformer and NLPTransformer: ``step(x_t (B, window_embed_size), mask_t)`` -> the (B,1)
-    prediction of that window, what the model's eval forward gives at [:, t] with causal attention on.  Around the encoder step it runs
-    the kernels the batch forward runs: the embed affine map and the two read-out maps, and for the LSTM decoder one scan of T = 1
-    with the carried (h, c).  ``reset()`` starts a new recording."""
-
-    def __init__(self, model, batch, capacity):
-        _stream_model_checks(model)
-        self.model, self.batch = model, int(batch)
-        dec = getattr(model, "decoder", None)
-        if dec is not None and dec.num_layers != 1:
-            raise NotImplementedError("%s.stream: a decoder with n_layers = %d; the stepping state of the stacked scan is not implemented "
-                                      "(n_layers == 1 streams)" % (type(model).__name__, dec.num_layers))
-        self.enc = model.encoder.stream(batch, capacity)
-        self._dec = None
-        if dec is not None:
-            with torch.no_grad():
-                Wx, W_rec, Whh, bias = F_hip.decoder_pack(dec.weight_ih_l0, dec.weight_hh_l0, dec.bias_ih_l0, dec.bias_hh_l0)
-                self._dec = tuple(z.detach() for z in (Wx, W_rec, bias, F_hip.linear(model.dec_h0, Whh),
-                                                       F_hip.broadcast_rows(model.dec_c0, self.batch)))
-        self._h = self._c = None
-
-    t = property(lambda self: self.enc.t)
-    capacity = property(lambda self: self.enc.capacity)
-
-    def reset(self):
-        self.enc.reset()
-        self._h = self._c = None
-
-    @staticmethod
-    def _affine(x, layer, act=0, rowscale=None):
-        # detached views of the live parameters: an autograd node that sees a tensor requiring grad keeps its pool workspace for a
-        # backward that never comes, and the next call would get a new one (an allocation and a zero fill per step)
-        return F_hip.linear(x, layer.weight.detach(), layer.bias.detach(), act=act, rowscale=rowscale)
-
-    def _embed(self, x_t):
-        m = self.model
-        if isinstance(m.embed, nn.Sequential):                    # NLPTransformer: Dropout (identity in eval) -> Linear -> ReLU
-            return self._affine(x_t, m.embed[1], act=1)
-        return self._affine(x_t, m.embed)
-
-    def step(self, x_t, mask_t=None):
-        m, B = self.model, self.batch
-        if not isinstance(x_t, torch.Tensor) or x_t.dim() != 2 or x_t.shape[0] != B:
-            raise ValueError("%s stream step: x_t must have the shape (%d, window_embed_size), got %s"
-                             % (type(m).__name__, B, tuple(getattr(x_t, "shape", ()))))
-        if self.enc.t >= self.enc.capacity:
-            raise ValueError("%s stream step: the stream is full (t = capacity = %d)" % (type(m).__name__, self.enc.capacity))
-        if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B):
-            raise ValueError("%s stream step: mask_t must hold one entry per sequence (%d)" % (type(m).__name__, B))
-        with torch.no_grad():
-            first = self.enc.t == 0
-            r = None if mask_t is None else mask_t.float().reshape(B)
-            e = self.enc.step(self._embed(x_t), r)
-            if self._dec is not None:
-                Wx, W_rec, bias, row0, c0 = self._dec
-                gx = F_hip.linear(e.view(1, B, -1), Wx, bias)                    # (1,B,4d)
-                if first:
-                    gx = F_hip.add_row0(gx, row0)                                # step 0 sees h0 W_hh^T, as _decode
-                h_all, c_all = F_hip.lstm_scan(gx, W_rec, None if first else self._h, c0 if first else self._c)
-                self._h, self._c = h_all[0], c_all[0]
-                e = self._h
-            return self._affine(self._affine(e, m.out[0], act=1), m.out[2], rowscale=r)
-
-
-class _SequenceSlotStream(_Slots):
-    """``device_stream()`` of UniFullTransformer, UniTransformer and NLPTransformer: a stream whose whole per-recording state lives on the
-    device (members: ``_Slots``).  ``step(x_t (B, window_embed_size), mask_t)`` -> the (B,1) prediction of that window, in THREE launches:
-    the embed affine map, the encoder's positioned step (``EncoderSlotStream``, advance off) and ONE launch of decoder_step_slots_kernel
-    (csrc/decoder_step.h) for the LSTM decoder and the read-out, which advances the positions.  The decoder's carried (h, c) of every
-    layer sits in ``state`` beside the bf16 copy of its weights; at position 0 the kernel takes dec_h0 / dec_c0 instead of it, so
-    ``seat`` is all a new recording needs, and decoders of up to 4 layers are served (0: the read-out alone).  It owns ONE ``positions``
-    tensor, which its encoder stream shares.  Row b is what this stream opened for that recording alone gives at window
-    ``positions[b]``, bit for bit; no position crosses the host, so a step can be captured (``graphs.capture_stream``).
-
-    ``refresh()`` converts the parameters again: call it after any of them changed (the decoder step reads every one from ``state``)."""
-
-    def __init__(self, model, batch, capacity):
-        name = type(model).__name__
-        if model.training:
-            raise ValueError("%s.device_stream: the model is in train mode; streaming is eval-mode inference (call .eval())" % name)
-        self.model, self.batch = model, int(batch)
-        dec = getattr(model, "decoder", None)
-        self.n_layers = 0 if dec is None else dec.num_layers
-        self.d, self.h_dim = model.out[0].in_features, model.out[0].out_features
-        self._dims = (self.batch, self.d, self.h_dim, self.n_layers)
-        if self.batch >= 1:
-            F_hip.decoder_stream_bytes(*self._dims)                              # ValueError naming the limit, before anything is opened
-        opened = model.encoder.stream(batch, capacity)                           # the encoder's refusals pass through
-        self.device = opened.device
-        self.positions = _slot_positions("%s.device_stream" % name, None, self.batch, self.device)
-        self.enc = EncoderSlotStream(opened, self.positions)
-        self.state = F_hip.decoder_stream_state(*self._dims, self.device)
-        embed = model.embed
-        self._embed, self._embed_act = (embed[1], 1) if isinstance(embed, nn.Sequential) else (embed, 0)     # NLPTransformer: Dropout -> Linear -> ReLU
-        self._embed_prep = None          # the embed's padded bf16 weight and bias, laid out once: its step is the row GEMM alone
-        self.refresh()
-
-    capacity = property(lambda self: self.enc.capacity)
-
-    def refresh(self):
-        """Convert the model's current parameters into the states (the encoder's and the decoder's preparation launch and the embed's
-        two); the carried state, the cache and the positions stay."""
-        m, dec = self.model, getattr(self.model, "decoder", None)
-        self.enc.refresh()
-        self._embed_prep = F_hip.linear_prepare(self._embed.weight.detach(), self._embed.bias.detach(), self._embed_prep)
-        lstm =[[getattr(dec, "%s_l%d" % (n, l)).detach() for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
-                for l in range(self.n_layers)]
-        h0, c0 = (m.dec_h0.detach(), m.dec_c0.detach()) if self.n_layers else (None, None)
-        out = [q.detach() for q in (m.out[0].weight, m.out[0].bias, m.out[2].weight, m.out[2].bias)]
-        F_hip.decoder_stream_prepare(lstm, h0, c0, out, self.state, *self._dims)
-
-    def step(self, x_t, mask_t=None, advance=True):
-        """``advance=False``: the decoder's launch leaves the positions, so the same windows can be stepped again (a measurement at a
-        fixed position; a recording advances)."""
-        m, B = self.model, self.batch
-        op = "%s device_stream step" % type(m).__name__
-        if not isinstance(x_t, torch.Tensor) or x_t.dtype != torch.float32 or x_t.device != self.device:
-            raise ValueError("%s: x_t must be a float32 tensor on %s, got %s on %s"
-                             % (op, self.device, getattr(x_t, "dtype", type(x_t).__name__), getattr(x_t, "device", None)))
-        if tuple(x_t.shape) != (B, self._embed.in_features):
-            raise ValueError("%s: x_t must have the shape (%d,%d), got %s" % (op, B, self._embed.in_features, tuple(x_t.shape)))
-        if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != self.device):
-            raise ValueError("%s: mask_t must hold one entry per sequence (%d) on %s" % (op, B, self.device))
-        with torch.no_grad():
-            r = None if mask_t is None else mask_t.float().reshape(B)
-            e = self.enc.step(F_hip.linear_prepared(x_t, self._embed_prep, self.d, act=self._embed_act), r, advance=False)
-            return F_hip.decoder_stream_step_slots(e, r, self.state, self.positions, self.d, self.h_dim, self.n_layers,
-                                                   limit=self.capacity, advance=advance)
-
-
 def _encoder(embed_dim, h, d_ff, dropout, N):
     return Encoder(EncoderLayer(embed_dim, MultiHeadedAttention(h, embed_dim), PositionwiseFeedForward(embed_dim, d_ff, dropout),
                                 dropout), N)
-
-
-# The modalities of the MFT are independent until the MFN gate: their embeds, encoder stacks and LSTM scans run on one HIP stream each
-# (the first on the caller's stream): one stack at the reference sizes fills only part of the 256 CUs, so concurrency, not a faster
-# kernel, is what is missing.  ``MMT_MODALITY_STREAMS=0`` serialises everything on one stream.
-_MOD_STREAMS = _lib.StreamFork("MMT_MODALITY_STREAMS")
 
 
 class MFN(nn.Module):
@@ -738,197 +475,27 @@ class MFN(nn.Module):
         out = F_hip.mfn_gate(hs, cs, self._gate_params(), pg, seed_g, po, seed_o)          # (T,B,output_dim)
         return F_hip.batch_major(out, mask)
 
-    def stream(self, batch):
-        """Open an ``MFNStream``: this gate as an online predictor for ``batch`` recordings, one window per ``step`` with the carried
-        (h, c, mem) instead of a forward over the whole prefix.  Eval mode, forward only; no attention, so no length limit.  Raises
-        ValueError, before any launch, for anything else."""
+    def _stream_refusals(self):
+        """What ``stream`` and ``slot_stream`` refuse, before anything is allocated or launched."""
         if self.training:
             raise ValueError("MFN.stream: the gate is in train mode; streaming is eval-mode inference (call .eval())")
         dev = self.out_fc2.weight.device
         if dev.type != "cuda":
             raise ValueError("MFN.stream: the gate is on %s; move it to a HIP device (there is no CPU path)" % dev)
+
+    def stream(self, batch):
+        """Open an ``MFNStream``: this gate as an online predictor for ``batch`` recordings, one window per ``step`` with the carried
+        (h, c, mem) instead of a forward over the whole prefix.  Eval mode, forward only; no attention, so no length limit.  Raises
+        ValueError, before any launch, for anything else."""
+        self._stream_refusals()
         return MFNStream(self, batch)
 
     def slot_stream(self, batch, limit=None, positions=None):
         """``stream(batch)`` with slots (``MFNSlotStream``): the position of every sequence lives on the device, so the sequences are
         seated and released independently and a step can be captured into a graph (``graphs.capture_stream``).  ``limit``: windows per
         recording after which a slot is full (None: none, a gate has no cache).  The same refusals, before any launch."""
-        return MFNSlotStream(self.stream(batch), limit, positions)
-
-
-class MFNStream:
-    """An ``MFN`` gate run one window at a time (``MFN.stream``): ``step({mod: (B, dims[mod])}, mask_t)`` returns the (B, output_dim)
-    row that the gate's eval forward gives at position ``t`` of the windows stepped so far (times ``mask_t``), in ONE kernel launch
-    (csrc/mfn_step.h), and advances ``t``.  The state holds the bf16 copy of every weight matrix, the fp32 biases and two copies of
-    the carried (h, c, mem) of ``batch`` sequences.
-
-    ``reset()`` starts a new recording: it sets ``t`` back to 0 and neither clears nor re-reads anything.  ``refresh()`` converts
-    and copies the parameters again: call it after ANY parameter of the gate changed.  Unlike ``EncoderStream``, which reads biases
-    and LayerNorm weights live, the biases here are copies made at ``refresh()`` (``b_ih + b_hh`` already summed): the step kernel
-    reads nothing but its inputs and the state.  Rows have the batch path's rounding sites exactly and agree with it to fp32
-    summation order."""
-
-    slots = False                    # True in MFNSlotStream: positions on the device instead of ``t``
-
-    def __init__(self, mfn, batch):
-        self.mfn, self.batch = mfn, int(batch)
-        if not self.slots:
-            self.t = 0
-        self.mods = list(mfn.mods)
-        self.in_dims = [mfn.lstm[m].input_size for m in self.mods]
-        self.hidden = [mfn.lstm[m].hidden_size for m in self.mods]
-        self.output_dim = mfn.out_fc2.out_features
-        self.device = mfn.out_fc2.weight.device
-        if self.batch < 1:
-            raise ValueError("MFN.stream: batch must be at least 1, got %d" % self.batch)
-        self.state = F_hip.mfn_stream_state(self.batch, self.in_dims, self.hidden, self.output_dim, self.device)   # ValueError naming the limit
-        self.refresh()
-
-    def refresh(self):
-        """Convert and copy the gate's current parameters, biases included, into the state (one launch); (h, c, mem) and ``t`` stay."""
-        cells = [tuple(q.detach() for q in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)) for c in (self.mfn.lstm[m] for m in self.mods)]
-        F_hip.mfn_stream_prepare(cells, [q.detach() for q in self.mfn._gate_params()], self.state, self.batch, self.in_dims, self.hidden,
-                                 self.output_dim)
-
-    def reset(self):
-        self.t = 0
-
-    def step(self, inputs, mask_t=None):
-        """inputs {mod: (B, dims[mod]) float32 on the gate's device}, mask_t (B), (B,1) or (B,1,1) or None -> (B, output_dim)."""
-        xs = _modality_rows("MFNStream.step", inputs, self.mods, self.in_dims, self.batch, self.device, mask_t)
-        y = F_hip.mfn_stream_step(xs, mask_t, self.state, self.t, self.in_dims, self.hidden, self.output_dim)
-        self.t += 1
-        return y
-
-
-class MFNSlotStream(_Slots, MFNStream):
-    """``MFNStream`` with slots (``MFN.slot_stream``; members: ``_Slots``, ``capacity`` is the ``limit``).  ``step(inputs, mask_t)`` is
-    ONE launch of mfn_step_slots_kernel: row b is what an ``MFNStream`` of that recording alone gives at window ``positions[b]``, bit
-    for bit (copy ``positions[b] & 1`` of the carried state is read and the other written, per sequence), and the kernel advances the
-    positions of the slots it ran."""
-
-    def __init__(self, opened, limit=None, positions=None):
-        self.__dict__.update({k: v for k, v in opened.__dict__.items() if k != "t"})     # the state of the stream just opened
-        self.capacity = None if limit is None else int(limit)
-        if self.capacity is not None and self.capacity < 1:
-            raise ValueError("MFN.slot_stream: limit must be at least 1 (or None), got %d" % self.capacity)
-        self.positions = _slot_positions("MFN.slot_stream", positions, self.batch, self.device)
-
-    def step(self, inputs, mask_t=None, advance=True):
-        xs = _modality_rows("MFNStream.step", inputs, self.mods, self.in_dims, self.batch, self.device, mask_t)
-        return F_hip.mfn_stream_step_slots(xs, mask_t, self.state, self.positions, self.in_dims, self.hidden, self.output_dim,
-                                           limit=self.capacity, advance=advance)
-
-
-def _modality_rows(op, inputs, mods, widths, B, device, mask_t):
-    """The checks of a per-modality step, all before any launch -> the rows in the order of ``mods``."""
-    if not isinstance(inputs, dict) or any(m not in inputs for m in mods):
-        raise ValueError("%s: inputs must be a dict with a row for every modality %s, got %s"
-                         % (op, mods, sorted(inputs) if isinstance(inputs, dict) else type(inputs).__name__))
-    for m, d in zip(mods, widths):
-        x = inputs[m]
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != device:
-            raise ValueError("%s: inputs[%r] must be a float32 tensor on %s, got %s on %s"
-                             % (op, m, device, getattr(x, "dtype", type(x).__name__), getattr(x, "device", None)))
-        if tuple(x.shape) != (B, d):
-            raise ValueError("%s: inputs[%r] must have the shape (%d,%d), got %s" % (op, m, B, d, tuple(x.shape)))
-    if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or mask_t.device != device):
-        raise ValueError("%s: mask_t must hold one entry per sequence (%d) on %s" % (op, B, device))
-    return [inputs[m] for m in mods]
-
-
-class _GateStream:
-    """``stream()`` of MultiTransformer (the MFT) and MultiTransformerB3: ``step({mod: (B, window_embed_size[mod])}, mask_t)`` -> the
-    (B,1) prediction of that window, what the model's eval forward gives at [:, t] (the MFT: with causal attention on).  Per modality
-    the embed affine map and, in the MFT, the encoder's step; then ONE launch for the whole MFN gate (``MFNStream``).  ``reset()``
-    starts a new recording.
-
-    ``modality_streams`` (an attribute; on for the MFT, off for B3-MFN): the per-modality launches run on ``_MOD_STREAMS`` as in the
-    batch forward, joined in front of the gate's launch.  Kept where it measured faster at B = 32 on the AVL models at the reference
-    sizes.  The MFT: 311 us forked against 560 us on one stream at t = 0, 574 us against 1225 us at t = 499: an encoder
-    step at d = 256, N = 6 is long enough for the fork and join to pay.  B3-MFN, whose modalities only run their embed: 181 us forked
-    against 126 us on one stream.  ``MMT_MODALITY_STREAMS=0`` serialises the MFT's step too."""
-
-    takes_modalities = True          # models._FrontEndStream hands such a stream the per-modality dict
-    slots = False                    # True in _GateSlotStream
-
-    def __init__(self, model, batch, capacity):
-        _stream_model_checks(model)
-        self.model, self.batch = model, int(batch)
-        self.mods = list(model.mods)
-        self.widths = [model.embed[m].in_features for m in self.mods]
-        stacks = getattr(model, "transformer", None)
-        if stacks is not None and capacity is None:
-            raise ValueError("%s.stream: the encoders' K/V cache needs a capacity (windows per recording)" % type(model).__name__)
-        self.encs = None if stacks is None else {m: stacks[m].stream(batch, capacity) for m in self.mods}      # their refusals pass through
-        self.gate = model.mfn.stream(batch)
-        self.device = self.gate.device
-        self.modality_streams = self.encs is not None
-        if self.slots:
-            # ONE positions tensor: the encoders read it (advance off, on the modality streams as before), the gate's launch, which runs
-            # behind the join, advances it.  The gate's limit is the encoders' capacity, so a full slot is skipped by every launch.
-            self.positions = _slot_positions("%s.slot_stream" % type(model).__name__, None, self.batch, self.device)
-            if self.encs is not None:
-                self.encs = {m: EncoderSlotStream(e, self.positions) for m, e in self.encs.items()}
-            self.gate = MFNSlotStream(self.gate, self.capacity, self.positions)
-
-    t = property(lambda self: self.gate.t)
-    capacity = property(lambda self: None if self.encs is None else self.encs[self.mods[0]].capacity)
-
-    def reset(self):
-        self.gate.reset()
-        for e in (self.encs or {}).values():
-            e.reset()                # a slots stream: the one shared tensor, zeroed again (idempotent)
-
-    def refresh(self):
-        self.gate.refresh()
-        for e in (self.encs or {}).values():
-            e.refresh()
-
-    def step(self, inputs, mask_t=None):
-        m, B = self.model, self.batch
-        op = "%s stream step" % type(m).__name__
-        xs = _modality_rows(op, inputs, self.mods, self.widths, B, self.device, mask_t)
-        if not self.slots and self.encs is not None and self.t >= self.capacity:
-            raise ValueError("%s: the stream is full (t = capacity = %d)" % (op, self.capacity))
-        with torch.no_grad():
-            r = None if mask_t is None else mask_t.float().reshape(B)
-            rows = {}
-            fork = self.modality_streams and len(self.mods) > 1
-            main, streams = _MOD_STREAMS.begin(self.device, len(self.mods)) if fork else (None, [None] * len(self.mods))
-            for mod, x, st in zip(self.mods, xs, streams):
-                with torch.cuda.stream(st):                                # None: the caller's stream
-                    e = _SequenceStream._affine(x, m.embed[mod])
-                    if self.encs is None:
-                        rows[mod] = e
-                    elif self.slots:
-                        rows[mod] = self.encs[mod].step(e, r, advance=False)
-                    else:
-                        rows[mod] = self.encs[mod].step(e, r)
-            if fork:
-                _MOD_STREAMS.end(main, streams, list(rows.values()))
-            return self.gate.step(rows, r, advance=self._advance) if self.slots else self.gate.step(rows, r)
-
-
-class _GateSlotStream(_Slots, _GateStream):
-    """``slot_stream()`` of MultiTransformer and MultiTransformerB3: ``_GateStream`` with slots (members: ``_Slots``).  It owns ONE
-    ``positions`` tensor, which its encoder streams and its gate share: the encoders' launches read it, the gate's launch, the last of
-    the step, advances it.  A step launches what the ``_GateStream`` step launches, with the positioned kernels in place of the two step
-    kernels, and row b is what a ``_GateStream`` of that recording alone gives at window ``positions[b]``."""
-
-    _advance = True
-
-    def reset(self):
-        _Slots.reset(self)
-
-    def step(self, inputs, mask_t=None, advance=True):
-        """As ``_GateStream.step``.  ``advance=False``: the gate's launch leaves the positions, so the same windows can be stepped again
-        (a measurement at a fixed position; a recording advances)."""
-        self._advance = bool(advance)
-        try:
-            return _GateStream.step(self, inputs, mask_t)
-        finally:
-            self._advance = True
+        self._stream_refusals()
+        return MFNSlotStream(self, batch, limit, positions)
 
 
 class MultiTransformer(nn.Module):

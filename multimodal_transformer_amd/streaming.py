@@ -1,0 +1,476 @@
+"""The models as online predictors, one window per ``step``: the stream classes behind ``stream()``, ``slot_stream()`` and
+``device_stream()`` of multiTransformer's models.  This project's own addition (the reference has no counterpart); DESIGN 4.5 - 4.8.
+
+A stream keeps its position in one of two places.  A host stream (``EncoderStream``, ``MFNStream``, ``_SequenceStream``, ``_GateStream``)
+has one ``t`` for the batch, a Python int passed to the step kernels by value.  A slots stream (``_Slots``: ``EncoderSlotStream``,
+``MFNSlotStream``, ``_SequenceSlotStream``, ``_GateSlotStream``) has ``positions``, one int32 per sequence on the device, read and advanced
+by the positioned kernels, so its sequences are seated and released independently and a step can be captured into a graph.  Each class
+decides that in its ``__init__`` and nowhere else.  The models refuse what cannot stream (``Encoder._stream_refusals``,
+``MFN._stream_refusals``) before they open one of these."""
+import torch
+
+from . import functional as F_hip
+
+_INT_MAX = 2 ** 31 - 1
+
+
+def _slot_positions(op, positions, batch, device):
+    """The positions of a slots stream: a new int32 (batch) tensor, every slot idle, or the one a composite stream shares."""
+    if positions is None:
+        return torch.full((batch,), -1, dtype=torch.int32, device=device)
+    if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32 or tuple(positions.shape) != (batch,) \
+            or not positions.is_contiguous() or positions.device != device:
+        raise ValueError("%s: positions must be a contiguous int32 (%d,) tensor on %s" % (op, batch, device))
+    return positions
+
+
+def _check_row(op, name, x, B, width, device, windowed=False):
+    """One input of a step: float32 on ``device`` (None: not asked for, the kernel behind converts) with the shape (B, width), or
+    (B, 1, width) too where ``windowed``.  Before any launch."""
+    if not isinstance(x, torch.Tensor) or (device is not None and (x.dtype != torch.float32 or x.device != device)):
+        raise ValueError("%s: %s must be a float32 tensor on %s, got %s on %s"
+                         % (op, name, device, getattr(x, "dtype", type(x).__name__), getattr(x, "device", None)))
+    if tuple(x.shape) != (B, width) and not (windowed and tuple(x.shape) == (B, 1, width)):
+        raise ValueError("%s: %s must have the shape (%d,%d)%s, got %s"
+                         % (op, name, B, width, " or (%d,1,%d)" % (B, width) if windowed else "", tuple(x.shape)))
+
+
+def _check_mask(op, mask_t, B, device):
+    if mask_t is not None and (not isinstance(mask_t, torch.Tensor) or mask_t.numel() != B or (device is not None and mask_t.device != device)):
+        raise ValueError("%s: mask_t must hold one entry per sequence (%d)%s" % (op, B, "" if device is None else " on %s" % device))
+
+
+def _stream_model_checks(model, method="stream"):
+    if model.training:
+        raise ValueError("%s.%s: the model is in train mode; streaming is eval-mode inference (call .eval())" % (type(model).__name__, method))
+
+
+class _Slots:
+    """What every slots stream has instead of ``t``: ``positions``, int32 (batch) on the device, read and advanced by the step kernels
+    (csrc/step_slots.h).  A slot is idle (-1, as opened), seated (0 <= position < capacity: its next window) or full (>= capacity).  A
+    step gives an idle or full slot a zero row and touches nothing of it.  ``seat`` / ``release`` / ``reset`` are ordinary device
+    operations on the current stream, between steps (or between the replays of a captured step); none of them synchronises."""
+
+    slots = True
+
+    @property
+    def t(self):
+        raise AttributeError("a slots stream has no single position t: every sequence has its own, see .positions (int32 on the device)")
+
+    def _index(self, indices):
+        return torch.as_tensor(indices, dtype=torch.long, device=self.positions.device).reshape(-1)
+
+    def seat(self, indices):
+        """Start a new recording in these slots: their positions become 0.  Nothing is cleared; nothing needs to be."""
+        self.positions.index_fill_(0, self._index(indices), 0)
+
+    def release(self, indices):
+        """Make these slots idle: their positions become -1."""
+        self.positions.index_fill_(0, self._index(indices), -1)
+
+    def reset(self):
+        """Seat every slot."""
+        self.positions.zero_()
+
+    def full(self):
+        """bool (batch) on the device: the slots whose recording has used the whole capacity (no synchronisation)."""
+        return self.positions >= (_INT_MAX if self.capacity is None else self.capacity)
+
+
+class EncoderStream:
+    """A causal ``Encoder`` run one window at a time (``Encoder.stream``): ``step(x_t)`` returns the row that the encoder's batch
+    forward gives at position ``t`` of the windows stepped so far, in ONE kernel launch (csrc/encoder_step.h), and advances ``t``.
+    The state is the bf16 copy of the weight matrices and the bf16 K / V of every layer for ``batch`` x ``capacity`` windows.
+
+    ``reset()`` starts a new recording: it sets ``t`` back to 0 and neither clears nor re-reads anything.  ``refresh()`` converts the
+    weights again: call it after the encoder's parameters changed (biases and LayerNorm weights are read live).  Rows agree with the
+    batch forward to the distance between two roundings of the same arithmetic (about 1.5e-3 rel-L2), not bit for bit."""
+
+    slots = False                    # True in EncoderSlotStream: positions on the device instead of ``t``
+
+    def __init__(self, encoder, batch, capacity):
+        self._shape(encoder, batch, capacity)
+        self.t = 0
+        self._allocate()
+
+    def _shape(self, encoder, batch, capacity):
+        """The members that describe the stream, and the refusals of its shape: nothing is allocated or launched."""
+        l0 = encoder.layers[0]
+        self.encoder = encoder
+        self.batch, self.capacity = int(batch), int(capacity)
+        self.d, self.h, self.d_ff, self.n_layers = l0.size, l0.self_attn.h, l0.feed_forward.w_1.weight.shape[0], len(encoder.layers)
+        self.eps = encoder.norm.eps
+        self.device = encoder.norm.a_2.device
+        if self.batch < 1 or self.capacity < 1:
+            raise ValueError("Encoder.stream: batch and capacity must be at least 1, got %d and %d" % (self.batch, self.capacity))
+        self._dims = (self.batch, self.capacity, self.d, self.h, self.d_ff, self.n_layers)
+        F_hip.encoder_stream_bytes(*self._dims)                                   # ValueError naming the limit for an unsupported shape
+
+    def _allocate(self):
+        self.state = F_hip.encoder_stream_state(*self._dims, self.device)
+        self.refresh()
+
+    def refresh(self):
+        """Convert the encoder's current weight matrices into the state (one launch); the cache and ``t`` stay."""
+        ps = self.encoder.flat_parameters()
+        flat = self.encoder._flat_storage(ps)
+        if flat is None:
+            flat = torch.cat([q.detach().reshape(-1) for q in ps]).float()
+        self._flat = flat.detach()
+        F_hip.encoder_stream_prepare(self._flat, self.state, *self._dims)
+
+    def reset(self):
+        self.t = 0
+
+    def step(self, x_t, mask_t=None):
+        """x_t (B,d) or (B,1,d) float32 on the encoder's device, mask_t (B), (B,1) or (B,1,1) or None -> the same shape as x_t."""
+        if self.t >= self.capacity:
+            raise ValueError("EncoderStream.step: the stream is full (t = capacity = %d): reset() starts a new recording, "
+                             "Encoder.stream(batch, capacity) opens a longer one" % self.capacity)
+        self._check_step(x_t, mask_t)
+        y = F_hip.encoder_stream_step(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.t, self.h, self.d_ff,
+                                      self.n_layers, self.capacity, self.eps)
+        self.t += 1
+        return y.view(x_t.shape)
+
+    def _check_step(self, x_t, mask_t):
+        _check_row("EncoderStream.step", "x_t", x_t, self.batch, self.d, self.device, windowed=True)
+        _check_mask("EncoderStream.step", mask_t, self.batch, self.device)
+
+
+class EncoderSlotStream(_Slots, EncoderStream):
+    """``EncoderStream`` with slots (``Encoder.slot_stream``; members: ``_Slots``).  ``step(x_t, mask_t)`` is ONE launch of
+    encoder_step_slots_kernel: row b is what an ``EncoderStream`` of that recording alone gives at window ``positions[b]``, bit for bit
+    (the same kernel body, one workgroup per sequence), and the kernel advances the positions of the slots it ran.  No position crosses
+    the host, so there is no "full" error: a full slot gets a zero row, and ``full()`` shows it."""
+
+    def __init__(self, encoder, batch, capacity, positions=None):
+        self._shape(encoder, batch, capacity)
+        self.positions = _slot_positions("Encoder.slot_stream", positions, self.batch, self.device)
+        self._allocate()
+
+    def step(self, x_t, mask_t=None, advance=True):
+        """As ``EncoderStream.step``.  ``advance=False`` leaves the positions (a composite stream advances them once, in its last launch)."""
+        self._check_step(x_t, mask_t)
+        y = F_hip.encoder_stream_step_slots(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.positions, self.h,
+                                            self.d_ff, self.n_layers, self.capacity, self.eps, advance=advance)
+        return y.view(x_t.shape)
+
+
+def _no_slot_stream(model):
+    raise NotImplementedError("%s.slot_stream: this model's stream keeps host-side state per recording (one position t for the batch; "
+                              "with an LSTM decoder also the carried (h, c) and the first row h0 W_hh, chosen on the host at t == 0), so "
+                              "its sequences cannot be seated independently; slots serve Encoder, MFN, MultiTransformer and MultiTransformerB3 "
+                              "(and their wrappers).  Use stream(batch, capacity), or device_stream(batch, capacity), which keeps that "
+                              "state on the device and seats sequences independently" % type(model).__name__)
+
+
+def _embed_of(model):
+    """(the embed's Linear, its activation) of a sequence model.  NLPTransformer: Dropout (identity in eval) -> Linear -> ReLU."""
+    embed = model.embed
+    return (embed[1], 1) if isinstance(embed, torch.nn.Sequential) else (embed, 0)
+
+
+class _SequenceStream:
+    """``stream()`` of UniFullTransformer, UniTransformer and NLPTransformer: ``step(x_t (B, window_embed_size), mask_t)`` -> the (B,1)
+    prediction of that window, what the model's eval forward gives at [:, t] with causal attention on.  Around the encoder step it runs
+    the kernels the batch forward runs: the embed affine map and the two read-out maps, and for the LSTM decoder one scan of T = 1
+    with the carried (h, c).  ``reset()`` starts a new recording."""
+
+    def __init__(self, model, batch, capacity):
+        _stream_model_checks(model)
+        self.model, self.batch = model, int(batch)
+        dec = getattr(model, "decoder", None)
+        if dec is not None and dec.num_layers != 1:
+            raise NotImplementedError("%s.stream: a decoder with n_layers = %d; the stepping state of the stacked scan is not implemented "
+                                      "(n_layers == 1 streams)" % (type(model).__name__, dec.num_layers))
+        self.enc = model.encoder.stream(batch, capacity)
+        self._embed, self._embed_act = _embed_of(model)
+        self._dec = None
+        if dec is not None:
+            with torch.no_grad():
+                Wx, W_rec, Whh, bias = F_hip.decoder_pack(dec.weight_ih_l0, dec.weight_hh_l0, dec.bias_ih_l0, dec.bias_hh_l0)
+                self._dec = tuple(z.detach() for z in (Wx, W_rec, bias, F_hip.linear(model.dec_h0, Whh),
+                                                       F_hip.broadcast_rows(model.dec_c0, self.batch)))
+        self._h = self._c = None
+
+    t = property(lambda self: self.enc.t)
+    capacity = property(lambda self: self.enc.capacity)
+
+    def reset(self):
+        self.enc.reset()
+        self._h = self._c = None
+
+    @staticmethod
+    def _affine(x, layer, act=0, rowscale=None):
+        # detached views of the live parameters: an autograd node that sees a tensor requiring grad keeps its pool workspace for a
+        # backward that never comes, and the next call would get a new one (an allocation and a zero fill per step)
+        return F_hip.linear(x, layer.weight.detach(), layer.bias.detach(), act=act, rowscale=rowscale)
+
+    def step(self, x_t, mask_t=None):
+        m, B = self.model, self.batch
+        op = "%s stream step" % type(m).__name__
+        _check_row(op, "x_t", x_t, B, self._embed.in_features, None)         # the embed is ``linear``, which converts what it is given
+        _check_mask(op, mask_t, B, None)
+        if self.enc.t >= self.enc.capacity:
+            raise ValueError("%s: the stream is full (t = capacity = %d)" % (op, self.enc.capacity))
+        with torch.no_grad():
+            first = self.enc.t == 0
+            r = None if mask_t is None else mask_t.float().reshape(B)
+            e = self.enc.step(self._affine(x_t, self._embed, act=self._embed_act), r)
+            if self._dec is not None:
+                Wx, W_rec, bias, row0, c0 = self._dec
+                gx = F_hip.linear(e.view(1, B, -1), Wx, bias)                    # (1,B,4d)
+                if first:
+                    gx = F_hip.add_row0(gx, row0)                                # step 0 sees h0 W_hh^T, as _decode
+                h_all, c_all = F_hip.lstm_scan(gx, W_rec, None if first else self._h, c0 if first else self._c)
+                self._h, self._c = h_all[0], c_all[0]
+                e = self._h
+            return self._affine(self._affine(e, m.out[0], act=1), m.out[2], rowscale=r)
+
+
+class _SequenceSlotStream(_Slots):
+    """``device_stream()`` of UniFullTransformer, UniTransformer and NLPTransformer: a stream whose whole per-recording state lives on the
+    device (members: ``_Slots``).  ``step(x_t (B, window_embed_size), mask_t)`` -> the (B,1) prediction of that window, in THREE launches:
+    the embed affine map, the encoder's positioned step (``EncoderSlotStream``, advance off) and ONE launch of decoder_step_slots_kernel
+    (csrc/decoder_step.h) for the LSTM decoder and the read-out, which advances the positions.  The decoder's carried (h, c) of every
+    layer sits in ``state`` beside the bf16 copy of its weights; at position 0 the kernel takes dec_h0 / dec_c0 instead of it, so
+    ``seat`` is all a new recording needs, and decoders of up to 4 layers are served (0: the read-out alone).  It owns ONE ``positions``
+    tensor, which its encoder stream shares.  Row b is what this stream opened for that recording alone gives at window
+    ``positions[b]``, bit for bit; no position crosses the host, so a step can be captured (``graphs.capture_stream``).
+
+    ``refresh()`` converts the parameters again: call it after any of them changed (the decoder step reads every one from ``state``)."""
+
+    def __init__(self, model, batch, capacity):
+        _stream_model_checks(model, "device_stream")
+        self.model, self.batch = model, int(batch)
+        dec = getattr(model, "decoder", None)
+        self.n_layers = 0 if dec is None else dec.num_layers
+        self.d, self.h_dim = model.out[0].in_features, model.out[0].out_features
+        self._dims = (self.batch, self.d, self.h_dim, self.n_layers)
+        if self.batch >= 1:
+            F_hip.decoder_stream_bytes(*self._dims)                              # ValueError naming the limit, before anything is opened
+        self.enc = model.encoder.slot_stream(batch, capacity)                    # the encoder's refusals pass through; it makes the positions
+        self.device, self.positions = self.enc.device, self.enc.positions
+        self.state = F_hip.decoder_stream_state(*self._dims, self.device)
+        self._embed, self._embed_act = _embed_of(model)
+        self._embed_prep = None          # the embed's padded bf16 weight and bias, laid out once: its step is the row GEMM alone
+        self.refresh()
+
+    capacity = property(lambda self: self.enc.capacity)
+
+    def refresh(self):
+        """Convert the model's current parameters into the states (the encoder's and the decoder's preparation launch and the embed's
+        two); the carried state, the cache and the positions stay."""
+        m, dec = self.model, getattr(self.model, "decoder", None)
+        self.enc.refresh()
+        self._embed_prep = F_hip.linear_prepare(self._embed.weight.detach(), self._embed.bias.detach(), self._embed_prep)
+        lstm = [[getattr(dec, "%s_l%d" % (n, l)).detach() for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+                for l in range(self.n_layers)]
+        h0, c0 = (m.dec_h0.detach(), m.dec_c0.detach()) if self.n_layers else (None, None)
+        out = [q.detach() for q in (m.out[0].weight, m.out[0].bias, m.out[2].weight, m.out[2].bias)]
+        F_hip.decoder_stream_prepare(lstm, h0, c0, out, self.state, *self._dims)
+
+    def step(self, x_t, mask_t=None, advance=True):
+        """``advance=False``: the decoder's launch leaves the positions, so the same windows can be stepped again (a measurement at a
+        fixed position; a recording advances)."""
+        B, op = self.batch, "%s device_stream step" % type(self.model).__name__
+        _check_row(op, "x_t", x_t, B, self._embed.in_features, self.device)
+        _check_mask(op, mask_t, B, self.device)
+        with torch.no_grad():
+            r = None if mask_t is None else mask_t.float().reshape(B)
+            e = self.enc.step(F_hip.linear_prepared(x_t, self._embed_prep, self.d, act=self._embed_act), r, advance=False)
+            return F_hip.decoder_stream_step_slots(e, r, self.state, self.positions, self.d, self.h_dim, self.n_layers,
+                                                   limit=self.capacity, advance=advance)
+
+
+class MFNStream:
+    """An ``MFN`` gate run one window at a time (``MFN.stream``): ``step({mod: (B, dims[mod])}, mask_t)`` returns the (B, output_dim)
+    row that the gate's eval forward gives at position ``t`` of the windows stepped so far (times ``mask_t``), in ONE kernel launch
+    (csrc/mfn_step.h), and advances ``t``.  The state holds the bf16 copy of every weight matrix, the fp32 biases and two copies of
+    the carried (h, c, mem) of ``batch`` sequences.
+
+    ``reset()`` starts a new recording: it sets ``t`` back to 0 and neither clears nor re-reads anything.  ``refresh()`` converts
+    and copies the parameters again: call it after ANY parameter of the gate changed.  Unlike ``EncoderStream``, which reads biases
+    and LayerNorm weights live, the biases here are copies made at ``refresh()`` (``b_ih + b_hh`` already summed): the step kernel
+    reads nothing but its inputs and the state.  Rows have the batch path's rounding sites exactly and agree with it to fp32
+    summation order."""
+
+    slots = False                    # True in MFNSlotStream: positions on the device instead of ``t``
+
+    def __init__(self, mfn, batch):
+        self._shape(mfn, batch)
+        self.t = 0
+        self._allocate()
+
+    def _shape(self, mfn, batch):
+        """The members that describe the stream, and the refusals of its shape: nothing is allocated or launched."""
+        self.mfn, self.batch = mfn, int(batch)
+        self.mods = list(mfn.mods)
+        self.in_dims = [mfn.lstm[m].input_size for m in self.mods]
+        self.hidden = [mfn.lstm[m].hidden_size for m in self.mods]
+        self.output_dim = mfn.out_fc2.out_features
+        self.device = mfn.out_fc2.weight.device
+        if self.batch < 1:
+            raise ValueError("MFN.stream: batch must be at least 1, got %d" % self.batch)
+        F_hip.mfn_stream_bytes(self.batch, self.in_dims, self.hidden, self.output_dim)        # ValueError naming the limit
+
+    def _allocate(self):
+        self.state = F_hip.mfn_stream_state(self.batch, self.in_dims, self.hidden, self.output_dim, self.device)
+        self.refresh()
+
+    def refresh(self):
+        """Convert and copy the gate's current parameters, biases included, into the state (one launch); (h, c, mem) and ``t`` stay."""
+        cells = [tuple(q.detach() for q in (c.weight_ih, c.weight_hh, c.bias_ih, c.bias_hh)) for c in (self.mfn.lstm[m] for m in self.mods)]
+        F_hip.mfn_stream_prepare(cells, [q.detach() for q in self.mfn._gate_params()], self.state, self.batch, self.in_dims, self.hidden,
+                                 self.output_dim)
+
+    def reset(self):
+        self.t = 0
+
+    def step(self, inputs, mask_t=None):
+        """inputs {mod: (B, dims[mod]) float32 on the gate's device}, mask_t (B), (B,1) or (B,1,1) or None -> (B, output_dim)."""
+        xs = _modality_rows("MFNStream.step", inputs, self.mods, self.in_dims, self.batch, self.device, mask_t)
+        y = F_hip.mfn_stream_step(xs, mask_t, self.state, self.t, self.in_dims, self.hidden, self.output_dim)
+        self.t += 1
+        return y
+
+
+class MFNSlotStream(_Slots, MFNStream):
+    """``MFNStream`` with slots (``MFN.slot_stream``; members: ``_Slots``, ``capacity`` is the ``limit``).  ``step(inputs, mask_t)`` is
+    ONE launch of mfn_step_slots_kernel: row b is what an ``MFNStream`` of that recording alone gives at window ``positions[b]``, bit
+    for bit (copy ``positions[b] & 1`` of the carried state is read and the other written, per sequence), and the kernel advances the
+    positions of the slots it ran."""
+
+    def __init__(self, mfn, batch, limit=None, positions=None):
+        self._shape(mfn, batch)
+        self.capacity = None if limit is None else int(limit)
+        if self.capacity is not None and self.capacity < 1:
+            raise ValueError("MFN.slot_stream: limit must be at least 1 (or None), got %d" % self.capacity)
+        self.positions = _slot_positions("MFN.slot_stream", positions, self.batch, self.device)
+        self._allocate()
+
+    def step(self, inputs, mask_t=None, advance=True):
+        xs = _modality_rows("MFNStream.step", inputs, self.mods, self.in_dims, self.batch, self.device, mask_t)
+        return F_hip.mfn_stream_step_slots(xs, mask_t, self.state, self.positions, self.in_dims, self.hidden, self.output_dim,
+                                           limit=self.capacity, advance=advance)
+
+
+def _modality_rows(op, inputs, mods, widths, B, device, mask_t):
+    """The checks of a per-modality step, all before any launch -> the rows in the order of ``mods``."""
+    if not isinstance(inputs, dict) or any(m not in inputs for m in mods):
+        raise ValueError("%s: inputs must be a dict with a row for every modality %s, got %s"
+                         % (op, mods, sorted(inputs) if isinstance(inputs, dict) else type(inputs).__name__))
+    for m, d in zip(mods, widths):
+        _check_row(op, "inputs[%r]" % m, inputs[m], B, d, device)
+    _check_mask(op, mask_t, B, device)
+    return [inputs[m] for m in mods]
+
+
+class _GateStream:
+    """``stream()`` of MultiTransformer (the MFT) and MultiTransformerB3: ``step({mod: (B, window_embed_size[mod])}, mask_t)`` -> the
+    (B,1) prediction of that window, what the model's eval forward gives at [:, t] (the MFT: with causal attention on).  Per modality
+    the embed affine map and, in the MFT, the encoder's step; then ONE launch for the whole MFN gate (``MFNStream``).  ``reset()``
+    starts a new recording.
+
+    ``modality_streams`` (an attribute; on for the MFT, off for B3-MFN): the per-modality launches run on ``_MOD_STREAMS`` as in the
+    batch forward, joined in front of the gate's launch.  Kept where it measured faster at B = 32 on the AVL models at the reference
+    sizes.  The MFT: 311 us forked against 560 us on one stream at t = 0, 574 us against 1225 us at t = 499: an encoder
+    step at d = 256, N = 6 is long enough for the fork and join to pay.  B3-MFN, whose modalities only run their embed: 181 us forked
+    against 126 us on one stream.  ``MMT_MODALITY_STREAMS=0`` serialises the MFT's step too."""
+
+    takes_modalities = True          # models._FrontEndStream hands such a stream the per-modality dict
+    slots = False                    # True in _GateSlotStream
+
+    def __init__(self, model, batch, capacity):
+        stacks = self._shape(model, batch, capacity)
+        self.encs = None if stacks is None else {m: stacks[m].stream(batch, capacity) for m in self.mods}      # their refusals pass through
+        self.gate = model.mfn.stream(batch)
+        self.device = self.gate.device
+
+    def _shape(self, model, batch, capacity):
+        """The members that describe the stream, and its own refusals -> the model's encoder stacks, or None (B3-MFN)."""
+        _stream_model_checks(model)
+        self.model, self.batch = model, int(batch)
+        self.mods = list(model.mods)
+        self.widths = [model.embed[m].in_features for m in self.mods]
+        stacks = getattr(model, "transformer", None)
+        if stacks is not None and capacity is None:
+            raise ValueError("%s.stream: the encoders' K/V cache needs a capacity (windows per recording)" % type(model).__name__)
+        self.modality_streams = stacks is not None
+        return stacks
+
+    t = property(lambda self: self.gate.t)
+    capacity = property(lambda self: None if self.encs is None else self.encs[self.mods[0]].capacity)
+
+    def reset(self):
+        self.gate.reset()
+        for e in (self.encs or {}).values():
+            e.reset()
+
+    def refresh(self):
+        self.gate.refresh()
+        for e in (self.encs or {}).values():
+            e.refresh()
+
+    def step(self, inputs, mask_t=None):
+        op = "%s stream step" % type(self.model).__name__
+        xs = _modality_rows(op, inputs, self.mods, self.widths, self.batch, self.device, mask_t)
+        if self.encs is not None and self.t >= self.capacity:
+            raise ValueError("%s: the stream is full (t = capacity = %d)" % (op, self.capacity))
+        return self._step(xs, mask_t, True)
+
+    def _encoder_step(self, enc, e, r):
+        return enc.step(e, r)
+
+    def _gate_step(self, rows, r, advance):
+        return self.gate.step(rows, r)           # a host stream always advances: its t is the recording's
+
+    def _step(self, xs, mask_t, advance):
+        """The step of both forms behind their checks: the per-modality launches, forked where that pays, then the gate's."""
+        m, B = self.model, self.batch
+        with torch.no_grad():
+            r = None if mask_t is None else mask_t.float().reshape(B)
+            rows = {}
+            fork = self.modality_streams and len(self.mods) > 1
+            main, streams = F_hip._MOD_STREAMS.begin(self.device, len(self.mods)) if fork else (None, [None] * len(self.mods))
+            for mod, x, st in zip(self.mods, xs, streams):
+                with torch.cuda.stream(st):                                # None: the caller's stream
+                    e = _SequenceStream._affine(x, m.embed[mod])
+                    rows[mod] = e if self.encs is None else self._encoder_step(self.encs[mod], e, r)
+            if fork:
+                F_hip._MOD_STREAMS.end(main, streams, list(rows.values()))
+            return self._gate_step(rows, r, advance)
+
+
+class _GateSlotStream(_Slots, _GateStream):
+    """``slot_stream()`` of MultiTransformer and MultiTransformerB3: ``_GateStream`` with slots (members: ``_Slots``).  It owns ONE
+    ``positions`` tensor, which its encoder streams and its gate share: the encoders' launches read it, the gate's launch, the last of
+    the step, advances it.  A step launches what the ``_GateStream`` step launches, with the positioned kernels in place of the two step
+    kernels, and row b is what a ``_GateStream`` of that recording alone gives at window ``positions[b]``."""
+
+    def __init__(self, model, batch, capacity):
+        stacks = self._shape(model, batch, capacity)
+        # ONE positions tensor: the first stream opened makes it and the others are handed it.  The encoders read it (advance off, on the
+        # modality streams as before), the gate's launch, which runs behind the join, advances it.  The gate's limit is the encoders'
+        # capacity, so a full slot is skipped by every launch.
+        self.positions = self.encs = None
+        if stacks is not None:
+            self.encs = {}
+            for mod in self.mods:
+                self.encs[mod] = stacks[mod].slot_stream(batch, capacity, self.positions)                      # their refusals pass through
+                self.positions = self.encs[mod].positions
+        self.gate = model.mfn.slot_stream(batch, capacity if stacks is not None else None, self.positions)
+        self.device, self.positions = self.gate.device, self.gate.positions
+
+    def step(self, inputs, mask_t=None, advance=True):
+        """As ``_GateStream.step``.  ``advance=False``: the gate's launch leaves the positions, so the same windows can be stepped again
+        (a measurement at a fixed position; a recording advances)."""
+        xs = _modality_rows("%s stream step" % type(self.model).__name__, inputs, self.mods, self.widths, self.batch, self.device, mask_t)
+        return self._step(xs, mask_t, bool(advance))
+
+    def _encoder_step(self, enc, e, r):
+        return enc.step(e, r, advance=False)
+
+    def _gate_step(self, rows, r, advance):
+        return self.gate.step(rows, r, advance=advance)

@@ -4,10 +4,14 @@ MFN.stream / MFNStream and the stream methods of MultiTransformer, MultiTransfor
 C boundary's size query and refusals.  No GPU: the library is loaded, nothing is launched."""
 import ctypes
 import inspect
+import os
+import shutil
+import subprocess
 
 import pytest
 import torch
 
+import conftest
 import mfn_stream_ref as S
 import oracle
 import recipe as R
@@ -250,3 +254,21 @@ def test_step_refusals_before_any_launch():
     lp, gp = (ctypes.c_void_p * 8)(*[4096] * 8), (ctypes.c_void_p * 20)(*[4096] * 20)
     assert lib.mmt_mfn_stream_prepare(lp, gp, fake, 16, *dims, None) == 3
     assert lib.mmt_mfn_stream_prepare(lp, (ctypes.c_void_p * 20)(*([4096] * 19 + [None])), fake, big, *dims, None) == MMT_EINVAL
+
+
+# ------------------------------------------------------------------------------------------------ the host check of the plan
+def test_mfn_step_plan_check_under_sanitizers(tmp_path):
+    """tools/mfn_step_plan_check.cpp, built with -fsanitize=address,undefined, walks the limits and their refused neighbours and, on
+    host buffers of the queried state sizes, the job table the preparation launches and what the step kernels address"""
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no C++ compiler on this machine")
+    exe = str(tmp_path / "mfn_step_plan_check")
+    src = os.path.join(conftest.ROOT, "tools", "mfn_step_plan_check.cpp")
+    build = subprocess.run([cxx, "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src],
+                           capture_output=True, text=True, timeout=300)
+    if build.returncode != 0 and "sanitize" in build.stderr + build.stdout and ("cannot find" in build.stderr or "unsupported" in build.stderr):
+        pytest.skip("this compiler has no sanitizer runtime: %s" % build.stderr[-300:])
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0 and "all checks passed" in run.stdout, (run.stdout[-2000:], run.stderr[-3000:])

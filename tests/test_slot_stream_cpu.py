@@ -122,6 +122,11 @@ def test_surface():
             assert callable(getattr(cls, name)), (cls.__name__, name)
         assert isinstance(inspect.getattr_static(cls, "t"), property)
     assert issubclass(MT.EncoderSlotStream, MT.EncoderStream) and issubclass(MT.MFNSlotStream, MT.MFNStream)
+    # the stream classes live in a module of their own; multiTransformer's names are those objects
+    for name in ("EncoderStream", "_Slots", "EncoderSlotStream", "_SequenceStream", "_SequenceSlotStream", "MFNStream", "MFNSlotStream",
+                 "_GateStream", "_GateSlotStream", "_modality_rows", "_slot_positions", "_INT_MAX", "_stream_model_checks", "_no_slot_stream"):
+        assert getattr(MT, name) is getattr(m.streaming, name), name
+    assert MT._MOD_STREAMS is F._MOD_STREAMS
     assert _params(graphs.capture_stream) == ["stream", "inputs", "mask"]
     for name in ("inputs", "mask", "output", "replay"):
         assert name in graphs.StreamGraph.__doc__ or hasattr(graphs.StreamGraph, name)

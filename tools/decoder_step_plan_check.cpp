@@ -1,9 +1,10 @@
 // Stand-alone host check of the one-window decoder step's limits and state layout (csrc/decoder_step_plan.h): no HIP, no GPU.
 //   c++ -std=c++17 -fsanitize=address,undefined -o tools/bin/decoder_step_plan_check tools/decoder_step_plan_check.cpp && tools/bin/decoder_step_plan_check
 // Walks the limits and their refused neighbours; for accepted shapes checks that the regions of the state are aligned, do not overlap
-// and sum to the reported size, and, on a host buffer of exactly that size, touches every element the preparation kernel writes and
-// both copies of the carried state for the first and last (b, layer), at the positions slot_decode lets through, so that an offset or
-// size mistake is an AddressSanitizer report.
+// and sum to the reported size, and, on a host buffer of exactly that size, walks the job table that mmt_decoder_stream_prepare launches
+// (decoder_step_prep_table, through step_prep_walk.h: every weight and vector byte written exactly once, none elsewhere) and touches both
+// copies of the carried state for the first and last (b, layer), at the positions slot_decode lets through, so that an offset or size
+// mistake is a failed check or an AddressSanitizer report.
 #include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,6 +13,7 @@
 #include <vector>
 #include "../multimodal_transformer_amd/csrc/decoder_step_plan.h"
 #include "../multimodal_transformer_amd/csrc/step_slots.h"
+#include "step_prep_walk.h"
 
 static int fails = 0;
 #define EXPECT(c) do { if (!(c)) { printf("FAILED %s (line %d)\n", #c, __LINE__); ++fails; } } while (0)
@@ -20,7 +22,7 @@ static bool accepted(int B, int d, int hd, int L) {
     return B >= 1 && d >= 4 && d <= 512 && d % 4 == 0 && hd >= 1 && hd <= 512 && L >= 0 && L <= 4;
 }
 
-struct Region { size_t off, len; };
+typedef PrepRegion Region;
 
 static void check_layout(int B, int d, int hd, int L, bool touch) {
     DecStepPlan P; const char* why = nullptr;
@@ -55,17 +57,18 @@ static void check_layout(int B, int d, int hd, int L, bool touch) {
     EXPECT(R.front().off == 0 && used == P.bytes && P.bytes >= end && P.bytes - end < 256);       // they sum to the size
     EXPECT(P.dyn_off % 256 == 0 && P.dyn_off + P.dyn_floats * 4 <= P.bytes);
     if (!touch) return;
-    std::vector<unsigned char> st(P.bytes);                                    // exactly the queried size
-    for (const Region& r : R) for (size_t i = 0; i < r.len; ++i) st[r.off + i] += 1;
-    bool once = true;
-    for (const Region& r : R) for (size_t i = 0; i < r.len; ++i) once = once && st[r.off + i] == 1;
-    EXPECT(once);                                                              // an overlap of two regions would read 2
-    // the addresses the kernels form: the last element of every prepared matrix ...
-    for (const Mat& m : M) {
-        unsigned short* w = reinterpret_cast<unsigned short*>(st.data() + m.off);
-        w[((size_t)(m.kp / 8 - 1) * m.rows + m.rows - 1) * 8 + 7] += 1;
-    }
-    // ... and both copies of the carried state for the first and last (b, layer), at every position slot_decode lets through
+    std::vector<unsigned char> st(P.bytes);                                    // exactly the queried size: counts the writes of a byte
+    // what the preparation writes: the table the entry launches, with sources that are never dereferenced
+    static const float some = 0.f;
+    const float* lp[4 * MMT_DEC_STEP_MAX_L];
+    for (const float*& q : lp) q = &some;
+    StepPrepParams T; size_t most = 0;
+    decoder_step_prep_table(P, lp, &some, &some, &some, &some, &some, &some, T, most);
+    EXPECT(T.nmat == (L ? 3 + 2 * L : 2) && T.nvec == (L ? 4 + L : 2));
+    if (L) R.pop_back();                                                       // the carried state: the last region, never prepared
+    fails += step_prep_walk(T, most, R, P.dyn_off, st.data());
+    for (size_t i = P.dyn_off; i < P.bytes; ++i) EXPECT(st[i] == 0);
+    // both copies of the carried state for the first and last (b, layer), at every position slot_decode lets through
     float* dyn = reinterpret_cast<float*>(st.data() + P.dyn_off);
     for (int p : {0, 1, 2, INT_MAX - 1, INT_MAX, -1, INT_MIN}) {
         const int t = slot_decode(p, 0);

@@ -1,14 +1,16 @@
 // Stand-alone host check of the one-window MFN gate step's limits and state layout (csrc/mfn_step_plan.h): no HIP, no GPU.
 //   c++ -std=c++17 -fsanitize=address,undefined -o tools/bin/mfn_step_plan_check tools/mfn_step_plan_check.cpp && tools/bin/mfn_step_plan_check
 // Walks the limits and their refused neighbours; for accepted shapes checks that the regions of the state are aligned, do not overlap
-// and sum to the reported size, and, on a host buffer of exactly that size, touches every element the preparation kernel writes and
-// every word of the carried state a step can address, so that an offset or size mistake is an AddressSanitizer report.
+// and sum to the reported size, and, on a host buffer of exactly that size, walks the job table that mmt_mfn_stream_prepare launches
+// (mfn_step_prep_table, through step_prep_walk.h: every weight and bias byte written exactly once, none elsewhere) and touches every word of
+// the carried state a step can address, so that an offset or size mistake is a failed check or an AddressSanitizer report.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
 #include "../multimodal_transformer_amd/csrc/mfn_step_plan.h"
+#include "step_prep_walk.h"
 
 static int fails = 0;
 #define EXPECT(c) do { if (!(c)) { printf("FAILED %s (line %d)\n", #c, __LINE__); ++fails; } } while (0)
@@ -24,7 +26,7 @@ static bool accepted(int B, int nm, const int* D, const int* H, int od) {
     return sh <= 256;
 }
 
-struct Region { size_t off, len; };
+typedef PrepRegion Region;
 
 static void check_layout(int B, int nm, const int* D, const int* H, int od, bool touch) {
     MfnStepPlan P; const char* why = nullptr;
@@ -66,22 +68,19 @@ static void check_layout(int B, int nm, const int* D, const int* H, int od, bool
     }
     EXPECT(R.front().off == 0 && used == P.bytes && P.bytes >= end && P.bytes - end < 256);       // they sum to the size
     if (!touch) return;
-    std::vector<unsigned char> st(P.bytes);                                    // exactly the queried size
-    for (const Region& r : R) for (size_t i = 0; i < r.len; ++i) st[r.off + i] += 1;
-    bool once = true;
-    for (const Region& r : R) for (size_t i = 0; i < r.len; ++i) once = once && st[r.off + i] == 1;
-    EXPECT(once);                                                              // an overlap of two regions would read 2
-    // the addresses the kernels form: the last element of a prepared matrix, and every word of either copy of the carried state
-    for (int m = 0; m < nm; ++m) {
-        unsigned short* w = reinterpret_cast<unsigned short*>(st.data() + P.wih[m]);
-        w[((size_t)(P.KPD[m] / 8 - 1) * 4 * H[m] + 4 * H[m] - 1) * 8 + 7] += 1;
-        w = reinterpret_cast<unsigned short*>(st.data() + P.whh[m]);
-        w[((size_t)(P.KPH[m] / 8 - 1) * 4 * H[m] + 4 * H[m] - 1) * 8 + 7] += 1;
-    }
-    for (int i = 0; i < MFN_W_COUNT; ++i) {
-        unsigned short* w = reinterpret_cast<unsigned short*>(st.data() + P.w[i]);
-        w[((size_t)(P.w_kp[i] / 8 - 1) * P.w_rows[i] + P.w_rows[i] - 1) * 8 + 7] += 1;
-    }
+    std::vector<unsigned char> st(P.bytes);                                    // exactly the queried size: counts the writes of a byte
+    // what the preparation writes: the table the entry launches, with sources that are never dereferenced
+    static const float some = 0.f;
+    const float* lp[4 * MMT_MFN_STEP_MAX_MODS]; const float* gp[20];
+    for (const float*& q : lp) q = &some;
+    for (const float*& q : gp) q = &some;
+    StepPrepParams T; size_t most = 0;
+    mfn_step_prep_table(P, lp, gp, T, most);
+    EXPECT(T.nmat == 2 * nm + 12 && T.nvec == nm + 10);
+    R.pop_back();                                                              // the carried state: the last region, never prepared
+    fails += step_prep_walk(T, most, R, P.dyn_off, st.data());
+    for (size_t i = P.dyn_off; i < P.bytes; ++i) EXPECT(st[i] == 0);
+    // every word of either copy of the carried state
     float* dyn = reinterpret_cast<float*>(st.data() + P.dyn_off);
     for (int t : {0, 1, 2, 2147483647}) for (int b : {0, B - 1}) {
         float* in = dyn + ((size_t)(t & 1) * B + b) * P.seq_floats;
