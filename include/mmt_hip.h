@@ -334,6 +334,35 @@ int mmt_decoder_stream_step(const float* e_t, const float* mask_t, float* y_t, v
 int mmt_decoder_stream_step_slots(const float* e_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,
                                   int* pos, int limit, int advance, int B, int d, int h_dim, int n_layers, mmt_stream_t stream);
 
+/* ---- The LSTM baseline, ONE WINDOW PER CALL (csrc/lstm_step.h): embed, attention MLP, the n_layers LSTM cells from zero states, the
+ * local attention over the last attn_len outputs with the softmax over the TAPS (mmt_local_attn_forward_taps) and the read-out MLP,
+ * eval mode.  This project's own addition; it steps models._LocalAttnLSTM with attend_over_taps on (MultiLSTM, MultiLSTMB1).
+ * One step is ONE launch, one workgroup per sequence, no communication between workgroups: a sequence's result does not depend on its
+ * batch.  Numerics: the batch path's rounding sites exactly (the left operand of every product and every weight bf16; sums, biases,
+ * activations, the softmax, the context, the carried state and everything stored fp32).
+ * Dimensions (B, in, E, H, n_layers, attn_len): input width 1..2048, embed_dim 1..512, h_dim 1..512, n_layers 1..4, attn_len 1..16,
+ * B >= 1: anything above a limit is MMT_EUNSUPPORTED with the limit named in mmt_last_error(), at the size query (which then returns
+ * 0); non-positive sizes, null pointers, t < 0 and a state of fewer than mmt_lstm_stream_bytes() bytes: MMT_EINVAL, before any launch.
+ * `state`: mmt_lstm_stream_bytes() bytes, ANY CONTENTS: every word a step reads was written by mmt_lstm_stream_prepare or by an earlier
+ * step of this recording (two copies of (h, c) of every layer and a ring of attn_len rows of m_t * h_top per sequence).  A new
+ * recording starts by passing t = 0 again; nothing needs clearing. */
+size_t mmt_lstm_stream_bytes(int B, int in, int E, int H, int n_layers, int attn_len);
+/* One launch: every parameter into the state, weights to bf16 in the step kernel's layout, vectors in fp32 (b_ih + b_hh summed).
+ * params: a HOST array of 10 + 4 * n_layers device pointers: embed (W (E, in), b), attn[0] (W (E, E), b), attn[2] (W (attn_len, E), b),
+ * per layer weight_ih (4H, E for layer 0, else H), weight_hh (4H, H), bias_ih, bias_hh, then the read-out (W (E, H), b, W (1, E), b).
+ * Does not touch the carried state or the ring.  Call it again after a parameter changes. */
+int mmt_lstm_stream_prepare(const float* const* params, void* state, size_t state_bytes,
+                            int B, int in, int E, int H, int n_layers, int attn_len, mmt_stream_t stream);
+/* x_t (B, in) -> y_t (B, 1) at position t; mask_t (B) float or NULL multiplies the top layer's output that enters the attention (now
+ * and as a later tap) and the output row; (h, c) advance under a blanked window as they do in the batch path.  t is passed by value;
+ * steps of one recording must be enqueued in order t = 0, 1, ... on one stream. */
+int mmt_lstm_stream_step(const float* x_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,
+                         int t, int B, int in, int E, int H, int n_layers, int attn_len, mmt_stream_t stream);
+/* The positioned form (the slots contract above): the step at t = pos[b], per sequence.  limit <= 0: no limit. */
+int mmt_lstm_stream_step_slots(const float* x_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,
+                               int* pos, int limit, int advance, int B, int in, int E, int H, int n_layers, int attn_len,
+                               mmt_stream_t stream);
+
 /* ---- Fused affine map  y = act(x W^T + b) [* rowscale] on bf16 MFMA.
  * Replaces nn.Linear (+ F.relu) call sites of the path: PositionwiseFeedForward (:15-20), the four
  * attention projections (:43,55,65), embeds and read-out MLPs (:270,296,340-342,400-402).
@@ -494,6 +523,13 @@ int mmt_local_attn_forward(const float* z, const float* h, const float* valid, f
 size_t mmt_local_attn_workspace_bytes(int B, int T, int H, int L);
 int mmt_local_attn_backward(const float* dctx, const float* attn, const float* h, const float* valid, float* dz, float* dh,
                             void* workspace, size_t workspace_bytes, int B, int T, int H, int L, mmt_stream_t stream);
+/* The second mode (models.attend_over_taps): a[b,t,:] = softmax over the L TAPS of row (b,t), all L of them (taps that reach before
+ * step 0 or onto a masked step take part and bring zero rows), so that ctx[b,t] depends on steps <= t alone.  Same arguments, layouts,
+ * limits, launches and workspace (mmt_local_attn_workspace_bytes) as the two entries above; dz = a (da - sum_i a da) per row. */
+int mmt_local_attn_forward_taps(const float* z, const float* h, const float* valid, float* ctx, float* attn,
+                                int B, int T, int H, int L, mmt_stream_t stream);
+int mmt_local_attn_backward_taps(const float* dctx, const float* attn, const float* h, const float* valid, float* dz, float* dh,
+                                 void* workspace, size_t workspace_bytes, int B, int T, int H, int L, mmt_stream_t stream);
 
 /* ---- Autoregressive read-out of the LSTM baseline MultiARLSTM: the teacher-forced sum and the free-running step loop
  *                                                             transformer/MFT/models.py:381-386 (teacher-forced), :388-397 (free-running),

@@ -72,6 +72,11 @@ SIGNATURES = {
     "mmt_decoder_stream_prepare": (_I, [_P] * 8 + [_SZ] + [_I] * 4 + [_P]),
     "mmt_decoder_stream_step": (_I, [_P, _P, _P, _P, _SZ] + [_I] * 5 + [_P]),
     "mmt_decoder_stream_step_slots": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _I] + [_I] * 4 + [_P]),
+    # one window of the LSTM baseline per launch: (B, in, E, H, n_layers, attn_len); params a host array of device pointers
+    "mmt_lstm_stream_bytes": (_SZ, [_I] * 6),
+    "mmt_lstm_stream_prepare": (_I, [_P, _P, _SZ] + [_I] * 6 + [_P]),
+    "mmt_lstm_stream_step": (_I, [_P, _P, _P, _P, _SZ] + [_I] * 7 + [_P]),
+    "mmt_lstm_stream_step_slots": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _I] + [_I] * 6 + [_P]),
     "mmt_linear_workspace_bytes": (_SZ, [_I] * 3),
     "mmt_linear_forward": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),
     "mmt_linear_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),
@@ -99,6 +104,8 @@ SIGNATURES = {
     "mmt_local_attn_forward": (_I, [_P] * 5 + [_I] * 4 + [_P]),
     "mmt_local_attn_workspace_bytes": (_SZ, [_I] * 4),
     "mmt_local_attn_backward": (_I, [_P] * 7 + [_SZ] + [_I] * 4 + [_P]),
+    "mmt_local_attn_forward_taps": (_I, [_P] * 5 + [_I] * 4 + [_P]),
+    "mmt_local_attn_backward_taps": (_I, [_P] * 7 + [_SZ] + [_I] * 4 + [_P]),
     "mmt_ar_combine_forward": (_I, [_P] * 4 + [_F] + [_P] * 2 + [_I] * 3 + [_P]),
     "mmt_ar_combine_backward": (_I, [_P] * 3 + [_I, _F] + [_P] * 2 + [_I] * 3 + [_P]),
     "mmt_mfn_mem_scan_workspace_bytes": (_SZ, []),

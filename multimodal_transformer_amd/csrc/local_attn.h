@@ -11,6 +11,16 @@
 //   da[b,t,i]  = [t>=i] valid[b,t-i] <dctx[b,t,:], h[t-i,b,:]>
 //   dz[b,t,i]  = a[b,t,i] (da[b,t,i] - sum_t' a[b,t',i] da[b,t',i])
 //
+// The second mode, TAPS (mmt_local_attn_*_taps; models.attend_over_taps, off by default): the softmax runs over the L taps of a row,
+// what the reference's comment describes and what an online predictor needs: row t then depends on steps <= t alone.
+//   a[b,t,i]   = exp(z[b,t,i] - m[b,t]) / s[b,t]      m, s: max and sum of exp over the L taps of ROW (b,t), summed in tap order.  All L
+//                                                     taps take part, also those that reach before step 0 or onto a masked step (their
+//                                                     rows of h are zeros, as above)
+//   dz[b,t,i]  = a[b,t,i] (da[b,t,i] - sum_i' a[b,t,i'] da[b,t,i'])
+//   ctx, dh, da as above.  One body per kernel, the mode a compile-time switch (local_attn_fwd_taps_kernel, local_attn_dz_taps_kernel
+//   beside the kernels of the time mode, which keep their names): the forward skips the column statistics, the dz kernel needs no
+//   reduction across threads.  la_row_softmax is the one expression of the row's softmax (lstm_step.h uses it too).
+//
 // fp32 throughout and no MFMA: at most 16 taps, nothing to contract.  The kernels stream h / ctx (forward) and h / dctx / dh (backward)
 // once per tile of MMT_LA_TT steps plus an (L-1)-step halo; the rows a tile re-reads for its other taps come from L1 / L2.
 // Layouts: z, a, dz (B,T,L); valid (B,T); h, dh (T,B,H) time-major as the LSTM scan has them; ctx, dctx (B,T,H) batch-major.
@@ -91,24 +101,43 @@ __device__ __forceinline__ void la_col_stats(const float* __restrict__ zb, int T
     __syncthreads();
 }
 
-// ctx (B,T,H) and a (B,T,L; written by the workgroups of column chunk 0) from z, h, valid.
-template <int V>
-__global__ __launch_bounds__(MMT_THREADS) void local_attn_fwd_kernel(const float* __restrict__ z, const float* __restrict__ h,
-                                                                     const float* __restrict__ valid, float* __restrict__ ctx,
-                                                                     float* __restrict__ attn, int B, int T, int H, int L) {
+// TAPS: a[i] = expf(z[i] - max) / sum over the L taps of one row, max and sum taken in tap-index order.
+__device__ __forceinline__ void la_row_softmax(const float* z, int L, float* a) {
+    float m = -INFINITY, s = 0.f;
+    for (int i = 0; i < L; ++i) m = fmaxf(m, z[i]);
+    for (int i = 0; i < L; ++i) s += expf(z[i] - m);
+    for (int i = 0; i < L; ++i) a[i] = expf(z[i] - m) / s;
+}
+
+// ctx (B,T,H) and a (B,T,L; written by the workgroups of column chunk 0) from z, h, valid.  TAPS: the softmax per row, no statistics.
+template <int V, bool TAPS>
+__device__ __forceinline__ void local_attn_fwd_body(const float* __restrict__ z, const float* __restrict__ h,
+                                                    const float* __restrict__ valid, float* __restrict__ ctx,
+                                                    float* __restrict__ attn, int B, int T, int H, int L) {
     typedef LaVec<V> Vec;
     __shared__ float s_max[MMT_LA_MAXL], s_sum[MMT_LA_MAXL], red[4 * MMT_LA_MAXL];
     __shared__ float a_s[MMT_LA_TT][MMT_LA_MAXL];
     __shared__ float v_s[MMT_LA_TT + MMT_LA_MAXL - 1];          // valid[b, t0-15 .. t0+TT-1]
     const int tid = threadIdx.x, b = blockIdx.z, t0 = blockIdx.x * MMT_LA_TT;
     const float* zb = z + (size_t)b * T * L;
-    la_col_stats(zb, T, L, s_max, s_sum, red);
-    for (int k = tid; k < MMT_LA_TT * L; k += MMT_THREADS) {
-        const int r = k / L, i = k - r * L, t = t0 + r;
-        if (t < T) {
-            const float a = expf(zb[(size_t)t * L + i] - s_max[i]) / s_sum[i];
-            a_s[r][i] = a;
-            if (blockIdx.y == 0) attn[((size_t)b * T + t) * L + i] = a;
+    if (TAPS) {
+        for (int r = tid; r < MMT_LA_TT; r += MMT_THREADS) {
+            const int t = t0 + r;
+            if (t < T) {
+                la_row_softmax(zb + (size_t)t * L, L, a_s[r]);
+                if (blockIdx.y == 0)
+                    for (int i = 0; i < L; ++i) attn[((size_t)b * T + t) * L + i] = a_s[r][i];
+            }
+        }
+    } else {
+        la_col_stats(zb, T, L, s_max, s_sum, red);
+        for (int k = tid; k < MMT_LA_TT * L; k += MMT_THREADS) {
+            const int r = k / L, i = k - r * L, t = t0 + r;
+            if (t < T) {
+                const float a = expf(zb[(size_t)t * L + i] - s_max[i]) / s_sum[i];
+                a_s[r][i] = a;
+                if (blockIdx.y == 0) attn[((size_t)b * T + t) * L + i] = a;
+            }
         }
     }
     for (int k = tid; k < MMT_LA_TT + MMT_LA_MAXL - 1; k += MMT_THREADS) {
@@ -132,6 +161,20 @@ __global__ __launch_bounds__(MMT_THREADS) void local_attn_fwd_kernel(const float
         }
         Vec::store(ctx + ((size_t)b * T + t) * H + col, acc);
     }
+}
+
+// The two instances of the forward's body: the time mode keeps the name (and so the code object) it always had.
+template <int V>
+__global__ __launch_bounds__(MMT_THREADS) void local_attn_fwd_kernel(const float* __restrict__ z, const float* __restrict__ h,
+                                                                     const float* __restrict__ valid, float* __restrict__ ctx,
+                                                                     float* __restrict__ attn, int B, int T, int H, int L) {
+    local_attn_fwd_body<V, false>(z, h, valid, ctx, attn, B, T, H, L);
+}
+template <int V>
+__global__ __launch_bounds__(MMT_THREADS) void local_attn_fwd_taps_kernel(const float* __restrict__ z, const float* __restrict__ h,
+                                                                          const float* __restrict__ valid, float* __restrict__ ctx,
+                                                                          float* __restrict__ attn, int B, int T, int H, int L) {
+    local_attn_fwd_body<V, true>(z, h, valid, ctx, attn, B, T, H, L);
 }
 
 // dh (T,B,H) and the per-chunk partials of da: da_part[chunk][b][t][i] (summed over the chunk's columns).
@@ -188,12 +231,30 @@ __global__ __launch_bounds__(MMT_THREADS) void local_attn_bwd_kernel(const float
 }
 
 // dz (B,T,L) = a (da - sum_t a da), da = the chunk partials summed in chunk order.  One workgroup per sequence.
-__global__ __launch_bounds__(MMT_THREADS) void local_attn_dz_kernel(const float* __restrict__ attn, const float* __restrict__ da_part,
-                                                                    float* __restrict__ dz, int B, int T, int L, int nchunks) {
+// TAPS: dz = a (da - sum_i a da) per row, the sum in tap order: a thread owns a row, nothing crosses threads.
+template <bool TAPS>
+__device__ __forceinline__ void local_attn_dz_body(const float* __restrict__ attn, const float* __restrict__ da_part,
+                                                   float* __restrict__ dz, int B, int T, int L, int nchunks) {
     __shared__ float red[4 * MMT_LA_MAXL], S[MMT_LA_MAXL];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, b = blockIdx.x;
     const size_t TL = (size_t)T * L;
     const float* ab = attn + b * TL;
+    if (TAPS) {
+        for (int t = tid; t < T; t += MMT_THREADS) {
+            float d[MMT_LA_MAXL], s = 0.f;
+#pragma unroll
+            for (int i = 0; i < MMT_LA_MAXL; ++i)
+                if (i < L) {
+                    d[i] = 0.f;
+                    for (int k = 0; k < nchunks; ++k) d[i] += da_part[((size_t)k * B + b) * TL + (size_t)t * L + i];
+                    s += ab[(size_t)t * L + i] * d[i];
+                }
+#pragma unroll
+            for (int i = 0; i < MMT_LA_MAXL; ++i)
+                if (i < L) dz[b * TL + (size_t)t * L + i] = ab[(size_t)t * L + i] * (d[i] - s);
+        }
+        return;
+    }
     float acc[MMT_LA_MAXL];
 #pragma unroll
     for (int i = 0; i < MMT_LA_MAXL; ++i) acc[i] = 0.f;
@@ -224,4 +285,13 @@ __global__ __launch_bounds__(MMT_THREADS) void local_attn_dz_kernel(const float*
                 dz[b * TL + (size_t)t * L + i] = ab[(size_t)t * L + i] * (d - S[i]);
             }
     }
+}
+
+__global__ __launch_bounds__(MMT_THREADS) void local_attn_dz_kernel(const float* __restrict__ attn, const float* __restrict__ da_part,
+                                                                    float* __restrict__ dz, int B, int T, int L, int nchunks) {
+    local_attn_dz_body<false>(attn, da_part, dz, B, T, L, nchunks);
+}
+__global__ __launch_bounds__(MMT_THREADS) void local_attn_dz_taps_kernel(const float* __restrict__ attn, const float* __restrict__ da_part,
+                                                                         float* __restrict__ dz, int B, int T, int L, int nchunks) {
+    local_attn_dz_body<true>(attn, da_part, dz, B, T, L, nchunks);
 }

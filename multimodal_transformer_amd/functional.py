@@ -538,13 +538,14 @@ def highway(x, Wp, bp, Wg, bg, dropout_p=0.0, seed=0, proj_act=0):
 
 
 class _LocalAttnFn(torch.autograd.Function):
-    """ctx = convolve(h * valid, softmax_t(z)): the local attention of the LSTM baselines (transformer/B1-LSTM/models.py:10-25,186-207).
+    """ctx = convolve(h * valid, softmax(z)): the local attention of the LSTM baselines (transformer/B1-LSTM/models.py:10-25,186-207).
     z (B,T,L) logits, h (T,B,H) LSTM outputs (time-major, as lstm_scan returns them), valid (B,T[,1]) prefix mask -> ctx (B,T,H).
-    The softmax runs over the TIME axis, padded steps included (the reference's nn.Softmax(dim=1) on 3-D logits); steps with
+    ``taps`` False: the softmax runs over the TIME axis, padded steps included (the reference's nn.Softmax(dim=1) on 3-D logits).
+    ``taps`` True (``models.attend_over_taps``): over the L taps of each row, so that row t depends on steps <= t alone.  Steps with
     valid == 0 contribute no h (pad_packed_sequence's zeros).  Gradients flow to z and h."""
 
     @staticmethod
-    def forward(ctx, z, h, valid):
+    def forward(ctx, z, h, valid, taps):
         _lib.require_hip(z, h, valid)
         z_, h_, v_ = _f32c(z), _f32c16(h), _f32c(valid)
         B, T, L = z_.shape
@@ -555,8 +556,9 @@ class _LocalAttnFn(torch.autograd.Function):
         H = h_.shape[2]
         out = torch.empty(B, T, H, dtype=torch.float32, device=z_.device)
         a = torch.empty(B, T, L, dtype=torch.float32, device=z_.device)
-        _lib.launch("mmt_local_attn_forward", z_, h_, v_, out, a, B, T, H, L)
+        _lib.launch("mmt_local_attn_forward_taps" if taps else "mmt_local_attn_forward", z_, h_, v_, out, a, B, T, H, L)
         ctx.save_for_backward(a, h_, v_)
+        ctx.taps = taps
         return out
 
     @staticmethod
@@ -568,14 +570,17 @@ class _LocalAttnFn(torch.autograd.Function):
         nbytes = _lib.load().mmt_local_attn_workspace_bytes(B, T, H, L)
         ws = _lib.POOL.get(nbytes, g.device, tag=("local_attn", B, T, H, L))
         dz, dh = torch.empty_like(a), torch.empty_like(h_)
-        _lib.launch("mmt_local_attn_backward", g, a, h_, v_, dz, dh, ws, nbytes, B, T, H, L)
+        _lib.launch("mmt_local_attn_backward_taps" if ctx.taps else "mmt_local_attn_backward", g, a, h_, v_, dz, dh, ws, nbytes, B, T, H, L)
         _lib.POOL.put(ws)
-        return dz, dh, None
+        return dz, dh, None, None
 
 
-def local_attention(z, h, valid):
-    """(B,T,L) logits, (T,B,H) LSTM outputs, (B,T[,1]) mask -> (B,T,H) context; see _LocalAttnFn."""
-    return _LocalAttnFn.apply(z, h, valid)
+def local_attention(z, h, valid, over="time"):
+    """(B,T,L) logits, (T,B,H) LSTM outputs, (B,T[,1]) mask -> (B,T,H) context; see _LocalAttnFn.  ``over``: what the softmax
+    normalises over, "time" (the reference's) or "taps" (``models.attend_over_taps``)."""
+    if over not in ("time", "taps"):
+        raise ValueError("local_attention: over must be \"time\" or \"taps\", got %r" % (over,))
+    return _LocalAttnFn.apply(z, h, valid, over == "taps")
 
 
 class _LstmScanFn(torch.autograd.Function):
@@ -1902,6 +1907,84 @@ def decoder_stream_step_slots(e_t, mask_t, state, positions, d, h_dim, n_layers,
     (>= ``limit``; None: no limit).  ``advance``: the kernel adds 1 to the position of every slot it ran.  No position crosses the host,
     so the call can be captured into a graph.  One launch."""
     return _decoder_step("decoder_stream_step_slots", e_t, mask_t, state, d, h_dim, n_layers, positions=positions, limit=limit, advance=advance)
+
+
+# The LSTM baseline, one window per call (include/mmt_hip.h mmt_lstm_stream_*): eval mode, forward only.  The state (prepared bf16
+# weights, fp32 vectors, two copies of the carried (h, c) of every layer, the ring of the local attention) takes memory with any
+# contents: _scratch.  dims = (in, E, H, n_layers, attn_len).
+def lstm_stream_bytes(B, in_dim, embed_dim, h_dim, n_layers, attn_len):
+    """Bytes of the LSTM stream state for ``B`` sequences; ValueError, naming the limit, for a shape outside the step kernel's domain."""
+    return _stream_bytes("mmt_lstm_stream_bytes", "%s", b"lstm stream: ?", int(B), int(in_dim), int(embed_dim), int(h_dim), int(n_layers),
+                         int(attn_len))
+
+
+def lstm_stream_state(B, in_dim, embed_dim, h_dim, n_layers, attn_len, device):
+    """An unprepared LSTM stream state on ``device`` (uint8; any contents)."""
+    return _scratch(lstm_stream_bytes(B, in_dim, embed_dim, h_dim, n_layers, attn_len), device)
+
+
+def lstm_stream_prepare(embed_params, attn_params, lstm_params, dec_params, state, B, in_dim, embed_dim, h_dim, n_layers, attn_len):
+    """Convert and copy every parameter of an LSTM baseline into ``state`` (one launch; the carried state and the ring are not touched):
+    ``embed_params`` (W (E, in), b), ``attn_params`` (W0 (E, E), b0, W2 (L, E), b2), ``lstm_params`` per layer (weight_ih, weight_hh,
+    bias_ih, bias_hh) of its nn.LSTM(E, H, n_layers), ``dec_params`` (W0 (E, H), b0, W2 (1, E), b2) of the read-out.  Again after any
+    parameter changes: a step reads every one of them from the state."""
+    op = "lstm_stream_prepare"
+    I, E, H, NL, L = int(in_dim), int(embed_dim), int(h_dim), int(n_layers), int(attn_len)
+    nbytes = lstm_stream_bytes(B, I, E, H, NL, L)
+    ps = list(embed_params) + list(attn_params) + [q for layer in lstm_params for q in layer] + list(dec_params)
+    _forward_only(op, ps, _PARAMS_GRAD)
+    want = [(E, I), (E,), (E, E), (E,), (L, E), (L,)]
+    want += [s for l in range(NL) for s in ((4 * H, E if l == 0 else H), (4 * H, H), (4 * H,), (4 * H,))]
+    want += [(E, H), (E,), (1, E), (1,)]
+    if [tuple(q.shape) for q in ps] != want:
+        raise ValueError("%s: the parameters have the shapes %s, expected %s" % (op, [tuple(q.shape) for q in ps], want))
+    _lib.require_hip(state, *ps)
+    _stream_state(op, state, nbytes, ps[0].device, "lstm_stream_state")
+    keep = [_f32c(q) for q in ps]                                          # alive until the launch is enqueued
+    table = (ctypes.c_void_p * len(keep))(*[q.data_ptr() for q in keep])
+    _lib.launch("mmt_lstm_stream_prepare", table, state, state.numel(), int(B), I, E, H, NL, L)
+
+
+def _lstm_step(op, x_t, mask_t, state, dims, t=None, positions=None, limit=None, advance=True):
+    """Both forms of the LSTM step: the position is ``t``, by value, or ``positions`` on the device with their ``limit``."""
+    dims = tuple(int(v) for v in dims)
+    _forward_only(op, (x_t, mask_t))
+    if not isinstance(x_t, torch.Tensor) or x_t.dim() != 2 or x_t.dtype != torch.float32 or x_t.shape[1] != dims[0]:
+        raise ValueError("%s: x_t must be a float32 (B, %d) tensor, got %s %s"
+                         % (op, dims[0], getattr(x_t, "dtype", type(x_t).__name__), tuple(getattr(x_t, "shape", ()))))
+    B, dev = x_t.shape[0], x_t.device
+    m_ = _step_mask(op, mask_t, B, dev)
+    if t is not None:
+        where = (int(t),)
+        if where[0] < 0:
+            raise ValueError("%s: position t = %d is negative" % (op, where[0]))
+    else:
+        _stream_positions(op, positions, B, dev)
+        where = (positions, 0 if limit is None else int(limit), int(bool(advance)))
+    _lib.require_hip(x_t, state)
+    nbytes = lstm_stream_bytes(B, *dims)
+    _stream_state(op, state, nbytes, dev, "lstm_stream_state")
+    x_ = _f32c(x_t)
+    y = torch.empty(B, 1, dtype=torch.float32, device=dev)
+    _lib.launch("mmt_" + op, x_, m_, y, state, state.numel(), *where, B, *dims)
+    return y
+
+
+def lstm_stream_step(x_t, mask_t, state, t, in_dim, embed_dim, h_dim, n_layers, attn_len):
+    """Window t of the LSTM baseline: x_t (B, in); mask_t (B) or None -> y_t (B, 1) = what ``_LocalAttnLSTM.forward`` gives at [:, t] in
+    eval mode with ``attend_over_taps`` on, from the (h, c) of every layer and the ring of the last attn_len outputs carried in ``state``
+    (lstm_stream_state, prepared by lstm_stream_prepare), which this call advances.  Steps of a recording run in order t = 0, 1, ...; t
+    is passed by value.  One launch.  Forward only."""
+    return _lstm_step("lstm_stream_step", x_t, mask_t, state, (in_dim, embed_dim, h_dim, n_layers, attn_len), t=int(t))
+
+
+def lstm_stream_step_slots(x_t, mask_t, state, positions, in_dim, embed_dim, h_dim, n_layers, attn_len, limit=None, advance=True):
+    """``lstm_stream_step`` with the position of every sequence in device memory (csrc/step_slots.h): ``positions`` int32 (B), read by
+    the kernel.  Row b is the row of ``lstm_stream_step`` at t = positions[b], bit for bit, where the slot is seated, and zero, with
+    nothing else written, where it is idle (negative) or full (>= ``limit``; None: no limit).  ``advance``: the kernel adds 1 to the
+    position of every slot it ran.  No position crosses the host, so the call can be captured into a graph.  One launch."""
+    return _lstm_step("lstm_stream_step_slots", x_t, mask_t, state, (in_dim, embed_dim, h_dim, n_layers, attn_len), positions=positions,
+                      limit=limit, advance=advance)
 
 
 def check_device_errors():

@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, functional as F_hip
+from .streaming import LSTMSlotStream, LSTMStream
 from .multiTransformer import (MultiTransformer, MultiTransformerB3, NLPTransformer, UniFullTransformer, UniTransformer, _MOD_STREAMS,
                                _hip_device, _stream_model_checks)
 
@@ -119,7 +120,11 @@ class _FrontEndStream:
         """``method``: the sequence model's method that opens its stream, "stream", "slot_stream" or "device_stream"."""
         _stream_model_checks(model)
         self.model, self.batch = model, int(batch)
-        self.seq = getattr(model.Transformer, method)(batch, capacity)
+        seq_model = getattr(model, "Transformer", None)
+        if seq_model is None:                                 # MultiCNNLSTM: the sequence model is .LSTM, which has no cache, so no capacity
+            self.seq = getattr(model.LSTM, method)(batch, capacity)
+        else:
+            self.seq = getattr(seq_model, method)(batch, capacity)
 
     t = property(lambda self: self.seq.t)                   # a slots stream: AttributeError naming .positions
     capacity = property(lambda self: self.seq.capacity)
@@ -145,7 +150,7 @@ class _FrontEndStream:
         if not hasattr(self.seq, "refresh"):                 # streaming._SequenceStream packs the decoder's weights when it is opened
             raise NotImplementedError("%s.stream: the stream of %s has no refresh() (it packs the decoder's weights once, when it is "
                                       "opened): open a new stream after a parameter changed, or use device_stream, whose refresh() "
-                                      "follows it" % (type(self.model).__name__, type(self.model.Transformer).__name__))
+                                      "follows it" % (type(self.model).__name__, type(self.seq).__name__))
         self.seq.refresh()
 
     def step(self, inputs, mask_t=None):
@@ -337,6 +342,22 @@ class MultiCNNTransformerB3(_FrontEnd):
         return _FrontEndStream(self, batch, capacity, "device_stream")
 
 
+def attend_over_taps(module, on=True):
+    """Set ``over_taps`` on every LSTM baseline (``_LocalAttnLSTM``: MultiLSTM, MultiLSTMB1, MultiEDLSTM, MultiARLSTM, and MultiCNNLSTM
+    through its ``.LSTM``) at or below ``module`` -> {qualified name: module}.  From the next forward on the local attention's softmax
+    normalises the L taps of each step (``functional.local_attention(..., over="taps")``), forward and backward, what the reference's
+    own comment describes, instead of each tap's column over all T steps of the padded batch (what its ``nn.Softmax(dim=1)`` computes).
+    The output at step t then depends on steps <= t alone and no longer on the padded length, which is what lets these models run as
+    online predictors (``stream`` / ``slot_stream``).  Outputs then differ from the reference's, by design; a model is trained with
+    the flag it is used with.  Off by default; ``attend_over_taps(module, False)`` restores the reference's semantics."""
+    found = {}
+    for name, m in module.named_modules():
+        if isinstance(m, _LocalAttnLSTM):
+            m.over_taps = bool(on)
+            found[name] = m
+    return found
+
+
 class _LocalAttnLSTM(nn.Module):
     """The LSTM baseline's sequence model, shared by both copies:
 
@@ -351,10 +372,12 @@ class _LocalAttnLSTM(nn.Module):
     pack_padded_sequence / pad_packed_sequence are not needed: the LSTM is causal, so the scan over all T steps gives the same h at
     real steps, and local_attention zeroes it at padded ones (outputs and gradients are those of the packed run).  The attention
     softmax normalises each of the L columns over all T steps of the padded batch (nn.Softmax(dim=1) on (B,T,L) logits), so outputs
-    at real steps depend on the padded length, as in the reference."""
+    at real steps depend on the padded length, as in the reference.  With ``attend_over_taps(model)`` on (``over_taps``) the softmax
+    normalises the L taps of each step instead, and the model can be stepped one window at a time (``stream`` / ``slot_stream``)."""
 
     _embed_p = 0.1
     _dec_dropout = None
+    over_taps = False                  # set by attend_over_taps(): the softmax over the taps of a step, not over time
 
     def __init__(self, window_embed_size, embed_dim, h_dim=256, n_layers=1, attn_len=5, device=torch.device("cuda:0")):
         super().__init__()
@@ -399,7 +422,7 @@ class _LocalAttnLSTM(nn.Module):
             gx = F_hip.linear(h_all, getattr(lstm, "weight_ih_l%d" % l),
                               F_hip.add2(getattr(lstm, "bias_ih_l%d" % l), getattr(lstm, "bias_hh_l%d" % l)))
             h_all, _ = F_hip.lstm_scan(gx, getattr(lstm, "weight_hh_l%d" % l), init(hb, l), init(cb, l))
-        return F_hip.local_attention(z, h_all, mask)
+        return F_hip.local_attention(z, h_all, mask, over="taps" if self.over_taps else "time")
 
     def forward(self, inputs, mask, lengths, target=None, output_feats=False):
         context = self._front(inputs, mask, lengths, self.lstm)
@@ -408,6 +431,28 @@ class _LocalAttnLSTM(nn.Module):
         seed_dec = _lib.next_dropout_seed(inputs.device, 8, holder=self) if p_dec > 0.0 else 0
         hid = F_hip.linear(context, dec0.weight, dec0.bias, act=1, out_dropout=p_dec, seed=seed_dec)
         return F_hip.linear(hid, last.weight, last.bias, rowscale=mask.float().reshape(-1))
+
+    def _stream_refusals(self, method):
+        """What cannot stream, before anything is opened or launched."""
+        _stream_model_checks(self, method)
+        if not self.over_taps:
+            raise ValueError("%s.%s: the local attention's softmax runs over time, so a step's output depends on every later window and "
+                             "on the padded length; streaming needs attend_over_taps(model) (models.attend_over_taps), which normalises "
+                             "the taps of each step instead" % (type(self).__name__, method))
+
+    def stream(self, batch, capacity=None):
+        """This model as an online predictor (``streaming.LSTMStream``): ``step(x_t (B, window_embed_size), mask_t)`` -> the (B,1)
+        prediction of that window in ONE launch (csrc/lstm_step.h).  Eval mode, ``attend_over_taps(model)`` on.  There is no cache, so
+        no capacity (the argument is accepted and ignored, for the wrappers' common call)."""
+        self._stream_refusals("stream")
+        return LSTMStream(self, batch)
+
+    def slot_stream(self, batch, limit=None):
+        """``stream(batch)`` with slots (``streaming.LSTMSlotStream``): sequences are seated and released independently (``.positions``,
+        ``.seat``, ``.release``, ``.full``: streaming._Slots), and a step can be captured into a graph (``graphs.capture_stream``).
+        ``limit``: windows per recording after which a slot counts as full (None: none)."""
+        self._stream_refusals("slot_stream")
+        return LSTMSlotStream(self, batch, limit)
 
 
 class MultiLSTM(_LocalAttnLSTM):
@@ -459,6 +504,12 @@ class MultiEDLSTM(_LocalAttnLSTM):
         self.device = _hip_device(device)
         self.to(self.device)
 
+    def stream(self, batch, capacity=None):
+        raise NotImplementedError("MultiEDLSTM.stream: the decoder LSTM with the read-out in its recurrence carries state of its own "
+                                  "(its (h, c) and the fed-back prediction); its step is not implemented (MultiLSTM and MultiLSTMB1 stream)")
+
+    slot_stream = stream
+
     def forward(self, inputs, mask, lengths, target=None, tgt_init=0.0):
         if self.n_layers != 1:
             raise NotImplementedError("MultiEDLSTM: n_layers = %d; the decoder scan with the read-out in its recurrence takes n_layers == 1"
@@ -505,6 +556,12 @@ class MultiARLSTM(_LocalAttnLSTM):
         self.device = _hip_device(device)
         self.to(self.device)
 
+    def stream(self, batch, capacity=None):
+        raise NotImplementedError("MultiARLSTM.stream: the autoregressive read-out carries state of its own (its last ar_order "
+                                  "predictions or targets); its step is not implemented (MultiLSTM and MultiLSTMB1 stream)")
+
+    slot_stream = stream
+
     def forward(self, inputs, mask, lengths, target=None, tgt_init=0.0):
         F_hip._ar_limits(self.ar_order)                 # both before any launch, with the limit named
         F_hip._scan_limits(self.h_dim, "MultiARLSTM")
@@ -542,3 +599,13 @@ class MultiCNNLSTM(_FrontEnd):
         outs = self._encode(inputs)
         x = F_hip.cat_cols([outs[m] for m in self.mods]) if len(self.mods) > 1 else outs[self.mods[0]]
         return self.LSTM(x, mask, length)
+
+    def stream(self, batch, capacity=None):
+        """This model as an online predictor (``_FrontEndStream``): the window encoder at T = 1, then the LSTM baseline's one-launch step.
+        Eval mode, ``attend_over_taps(model)`` on.  No cache, so no capacity."""
+        return _FrontEndStream(self, batch, None)
+
+    def slot_stream(self, batch, limit=None):
+        """``stream(batch)`` with slots: sequences are seated and released independently (``.positions``, ``.seat``, ``.release``,
+        ``.full``: streaming._Slots), and a step can be captured into a graph (``graphs.capture_stream``)."""
+        return _FrontEndStream(self, batch, limit, "slot_stream")

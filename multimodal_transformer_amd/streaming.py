@@ -1,12 +1,14 @@
 """The models as online predictors, one window per ``step``: the stream classes behind ``stream()``, ``slot_stream()`` and
-``device_stream()`` of multiTransformer's models.  This project's own addition (the reference has no counterpart); DESIGN 4.5 - 4.8.
+``device_stream()`` of multiTransformer's models and of the LSTM baselines in models.  This project's own addition (the reference has no
+counterpart); DESIGN 4.5 - 4.9.
 
-A stream keeps its position in one of two places.  A host stream (``EncoderStream``, ``MFNStream``, ``_SequenceStream``, ``_GateStream``)
-has one ``t`` for the batch, a Python int passed to the step kernels by value.  A slots stream (``_Slots``: ``EncoderSlotStream``,
-``MFNSlotStream``, ``_SequenceSlotStream``, ``_GateSlotStream``) has ``positions``, one int32 per sequence on the device, read and advanced
-by the positioned kernels, so its sequences are seated and released independently and a step can be captured into a graph.  Each class
-decides that in its ``__init__`` and nowhere else.  The models refuse what cannot stream (``Encoder._stream_refusals``,
-``MFN._stream_refusals``) before they open one of these."""
+A stream keeps its position in one of two places.  A host stream (``EncoderStream``, ``MFNStream``, ``LSTMStream``, ``_SequenceStream``,
+``_GateStream``) has one ``t`` for the batch, a Python int passed to the step kernels by value.  A slots stream (``_Slots``:
+``EncoderSlotStream``, ``MFNSlotStream``, ``LSTMSlotStream``, ``_SequenceSlotStream``, ``_GateSlotStream``) has ``positions``, one
+int32 per sequence on the device, read and advanced by the positioned kernels, so its sequences are seated and released independently
+and a step can be captured into a graph.  Each class decides that in its ``__init__`` and nowhere else.  The models refuse what cannot
+stream (``Encoder._stream_refusals``, ``MFN._stream_refusals``, ``models._LocalAttnLSTM._stream_refusals``) before they open one of
+these."""
 import torch
 
 from . import functional as F_hip
@@ -354,6 +356,84 @@ class MFNSlotStream(_Slots, MFNStream):
         xs = _modality_rows("MFNStream.step", inputs, self.mods, self.in_dims, self.batch, self.device, mask_t)
         return F_hip.mfn_stream_step_slots(xs, mask_t, self.state, self.positions, self.in_dims, self.hidden, self.output_dim,
                                            limit=self.capacity, advance=advance)
+
+
+class LSTMStream:
+    """An LSTM baseline (``MultiLSTM`` / ``MultiLSTMB1`` with ``models.attend_over_taps`` on) run one window at a time
+    (``MultiLSTM.stream``): ``step(x_t (B, window_embed_size), mask_t)`` returns the (B,1) row that the model's eval forward gives at
+    position ``t`` of the windows stepped so far, in ONE kernel launch (csrc/lstm_step.h), and advances ``t``.  The state holds the
+    bf16 copy of every weight matrix, the fp32 biases, two copies of the carried (h, c) of every layer and, per sequence, a ring of
+    the last attn_len masked outputs of the top layer.  There is no cache, so no capacity: a recording may be of any length.
+
+    ``reset()`` starts a new recording: it sets ``t`` back to 0 and neither clears nor re-reads anything.  ``refresh()`` converts and
+    copies the parameters again: call it after ANY parameter of the model changed (the step reads nothing but its inputs and the
+    state).  Rows have the batch path's rounding sites exactly."""
+
+    slots = False                    # True in LSTMSlotStream: positions on the device instead of ``t``
+    capacity = None
+
+    def __init__(self, model, batch):
+        self._shape(model, batch)
+        self.t = 0
+        self._allocate()
+
+    def _shape(self, model, batch):
+        """The members that describe the stream, and the refusals of its shape: nothing is allocated or launched."""
+        self.model, self.batch = model, int(batch)
+        self.device = model.embed[1].weight.device
+        self._dims = (model.embed[1].in_features, model.embed_dim, model.h_dim, model.n_layers, model.attn_len)
+        if self.batch < 1:
+            raise ValueError("%s.stream: batch must be at least 1, got %d" % (type(model).__name__, self.batch))
+        F_hip.lstm_stream_bytes(self.batch, *self._dims)                        # ValueError naming the limit
+
+    def _allocate(self):
+        self.state = F_hip.lstm_stream_state(self.batch, *self._dims, self.device)
+        self.refresh()
+
+    def refresh(self):
+        """Convert and copy the model's current parameters, biases included, into the state (one launch); (h, c), the ring and the
+        position(s) stay."""
+        m = self.model
+        lin = lambda layer: [layer.weight.detach(), layer.bias.detach()]            # noqa: E731
+        lstm = [[getattr(m.lstm, "%s_l%d" % (n, l)).detach() for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+                for l in range(m.n_layers)]
+        F_hip.lstm_stream_prepare(lin(m.embed[1]), lin(m.attn[0]) + lin(m.attn[2]), lstm, lin(m.decoder[0]) + lin(m.decoder[-1]),
+                                  self.state, self.batch, *self._dims)
+
+    def reset(self):
+        self.t = 0
+
+    def _check_step(self, x_t, mask_t):
+        op = "%s stream step" % type(self.model).__name__
+        _check_row(op, "x_t", x_t, self.batch, self._dims[0], self.device)
+        _check_mask(op, mask_t, self.batch, self.device)
+
+    def step(self, x_t, mask_t=None):
+        """x_t (B, window_embed_size) float32 on the model's device, mask_t (B), (B,1) or (B,1,1) or None -> (B,1)."""
+        self._check_step(x_t, mask_t)
+        y = F_hip.lstm_stream_step(x_t, mask_t, self.state, self.t, *self._dims)
+        self.t += 1
+        return y
+
+
+class LSTMSlotStream(_Slots, LSTMStream):
+    """``LSTMStream`` with slots (``MultiLSTM.slot_stream``; members: ``_Slots``, ``capacity`` is the ``limit``).  ``step(x_t, mask_t)`` is
+    ONE launch of lstm_step_slots_kernel: row b is what an ``LSTMStream`` of that recording alone gives at window ``positions[b]``, bit
+    for bit (copy ``positions[b] & 1`` of the carried state is read and the other written, per sequence), and the kernel advances the
+    positions of the slots it ran."""
+
+    def __init__(self, model, batch, limit=None, positions=None):
+        self._shape(model, batch)
+        self.capacity = None if limit is None else int(limit)
+        if self.capacity is not None and self.capacity < 1:
+            raise ValueError("%s.slot_stream: limit must be at least 1 (or None), got %d" % (type(model).__name__, self.capacity))
+        self.positions = _slot_positions("%s.slot_stream" % type(model).__name__, positions, self.batch, self.device)
+        self._allocate()
+
+    def step(self, x_t, mask_t=None, advance=True):
+        """As ``LSTMStream.step``.  ``advance=False`` leaves the positions, so the same windows can be stepped again."""
+        self._check_step(x_t, mask_t)
+        return F_hip.lstm_stream_step_slots(x_t, mask_t, self.state, self.positions, *self._dims, limit=self.capacity, advance=advance)
 
 
 def _modality_rows(op, inputs, mods, widths, B, device, mask_t):
