@@ -8,6 +8,36 @@
  *   - every pointer is a DEVICE pointer unless named host_*; tensors are contiguous fp32 in the
  *     reference's own layouts: activations (B,T,d) row-major, mask (B,T,1) float {0,1} (a window is
  *     blanked where mask == 0, multiTransformer.py:30), nn.Linear weights (out,in);
+ *   - the pointer contract.  Every tensor argument is CONTIGUOUS in the layout its entry names, of the element type its
+ *     declaration names (float = fp32, int32_t, double, uint64_t; a stream state and a workspace are bytes), and aligned to
+ *     that element type.  Nothing is read through a stride: a caller with a strided, transposed, expanded or non-fp32 tensor
+ *     makes a contiguous fp32 copy first (the Python binding's _f32c does).  Beyond that an argument is in one of three
+ *     classes:
+ *       (a) scalar access: any address aligned to the element type.  Every argument not listed under (b) or (c): masks,
+ *           row scales, key lengths, positions, weights and biases that are converted into a workspace (mmt_linear_* Wt / b,
+ *           every scan's W_rec / P / W_hh / W1 / Wm / W2, the conv weight and bias, the parameters given to a
+ *           *_stream_prepare), seed words, and every argument of mmt_sdpa_*, mmt_key_lengths, mmt_ar_combine_*,
+ *           mmt_lstm_stack_scan_*, mmt_lstm_fb_scan_*, mmt_softmax_mul_*, mmt_colsum, mmt_highway_*, mmt_adam_step,
+ *           mmt_ccc_forward, and x_t / e_t / mask_t / y_t / params of the stream steps;
+ *       (b) alignment selects the instantiation: a 16-byte aligned address (with leading dimensions and widths that are
+ *           multiples of 4) runs a kernel that moves four floats per lane, any other address the scalar one, which gives the
+ *           same values: every pointer of an mmt_copy2d segment, h / ctx / dctx / dh of mmt_local_attn_*, q / k of
+ *           mmt_attn_probs_forward*;
+ *       (c) 16-byte alignment is REQUIRED: a kernel of the entry moves 16 bytes per lane through the pointer.  The entry
+ *           returns MMT_EINVAL before any launch, and mmt_last_error() names the argument:
+ *             mmt_encoder_forward*: x, params, y;  mmt_encoder_backward*: dy, x, params, dx;
+ *             mmt_layernorm_forward: x, a_2, b_2, y;  mmt_layernorm_backward: dy, x, a_2, dx;
+ *             mmt_linear_forward / mmt_linear_dropout_forward: x, y;  mmt_linear_backward / mmt_linear_dropout_backward: dx;
+ *             mmt_linear_prepare: prepared;  mmt_linear_forward_prepared: x, prepared, y;
+ *             mmt_lstm_scan_forward: gx, h0, c0, h_all, c_all, acts;
+ *             mmt_lstm_scan_backward: dh_all, dc_all, c0, c_all, acts, dgx, dh0, dc0;
+ *             mmt_mfn_mem_scan_forward*: apre, chat, b2, mem_all, u_all, g_all;
+ *             mmt_mfn_mem_scan_backward: dmem_all, chat, mem_all, u_all, g_all, dchat, dapre, dz_all;
+ *             mmt_convpool_* and mmt_convpool_k_*: x;  mmt_mse_sum_forward: pred, target, dpred;
+ *             the `state` of every mmt_*_stream_prepare / _step / _step_slots (its pieces are laid out from its base and
+ *             a step reads the prepared weights and the K/V cache eight bf16 per lane).
+ *       An optional argument that is absent (a null pointer) passes.  A workspace is carved into 256-byte aligned pieces
+ *       from its base and is accessed 16 bytes wide: pass the base of an allocation (hipMalloc gives 256-byte alignment);
  *   - the library allocates nothing: the caller passes a workspace of *_workspace_bytes() bytes, under
  *     one of two contracts, named at each entry's workspace query:
  *       "zero once": the workspace MUST be zero-filled when first created and may then be reused, without

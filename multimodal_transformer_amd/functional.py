@@ -23,7 +23,9 @@ def _f32c(t):
 
 
 def _f32c16(t):
-    """contiguous fp32 AND 16-byte aligned (a contiguous view at an odd storage offset is not): for kernels that move four floats per lane"""
+    """contiguous fp32 AND 16-byte aligned (a contiguous view at an odd storage offset is not): for the arguments that an entry's kernels
+    move four floats per lane (include/mmt_hip.h, pointer contract, class (c): the entry refuses any other address).  An aligned
+    argument is passed as it is: no copy, no launch."""
     t = _f32c(t)
     return t.clone() if t is not None and t.data_ptr() % 16 else t
 
@@ -157,7 +159,7 @@ def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, s
     causal = _check_causal("encoder_stack", key_lengths, causal)
     lib = _lib.load()
     _lib.require_hip(x, mask, flat_params)
-    x_, m_, p_ = _f32c(x), _f32c(mask), _f32c(flat_params)
+    x_, m_, p_ = _f32c16(x), _f32c(mask), _f32c16(flat_params)
     B, T, d = x_.shape
     kl_ = _check_key_lengths("encoder_stack", key_lengths, B, x_.device)
     if m_.numel() != B * T:
@@ -199,7 +201,7 @@ def _encoder_bwd(ctx, dy):
     x_, m_, p_ = ctx.saved_tensors
     T, d, h, d_ff, n_layers, eps, dropout_p = ctx.cfg
     kl_ = ctx.key_lengths
-    dy_ = _f32c(dy)
+    dy_ = _f32c16(dy)
     dx = torch.empty_like(x_)
     dps = [torch.empty_like(p_) for _ in wss]       # fresh buffers per call: returned gradient views never alias later calls
     main, streams = _SPLIT_STREAMS.begin(x_.device, len(wss))
@@ -270,7 +272,7 @@ class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, a_2, b_2, eps):
         _lib.require_hip(x, a_2, b_2)
-        x_, a_, b_ = _f32c(x), _f32c(a_2), _f32c(b_2)
+        x_, a_, b_ = _f32c16(x), _f32c16(a_2), _f32c16(b_2)
         d = x_.shape[-1]
         M = x_.numel() // d
         y = torch.empty_like(x_)
@@ -285,7 +287,7 @@ class _LayerNormFn(torch.autograd.Function):
         x_, a_, stats = ctx.saved_tensors
         d = x_.shape[-1]
         M = x_.numel() // d
-        dy_ = _f32c(dy)
+        dy_ = _f32c16(dy)
         dx, da, db = torch.empty_like(x_), torch.empty_like(a_), torch.empty_like(a_)
         scratch = torch.empty(_lib.load().mmt_layernorm_scratch_floats(M, d), dtype=torch.float32, device=x_.device)
         _lib.launch("mmt_layernorm_backward", dy_, x_, a_, stats, dx, da, db, scratch, M, d, ctx.eps)
@@ -419,7 +421,7 @@ class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, b, rowscale, act, in_p, out_p, seed):
         _lib.require_hip(x, W, b, rowscale)
-        x_, W_, b_, r_ = _f32c(x), _f32c(W), _f32c(b), _f32c(rowscale)
+        x_, W_, b_, r_ = _f32c16(x), _f32c(W), _f32c(b), _f32c(rowscale)
         if r_ is not None and r_.numel() != x_.numel() // x_.shape[-1]:
             raise ValueError("linear: rowscale must have one entry per row")
         y, ws = _raw_linear_fwd(x_, W_, b_, act, r_, in_p, out_p, seed)
@@ -460,7 +462,7 @@ class _LinearPairFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W1, b1, W2, b2, act1, act2):
         _lib.require_hip(x, W1, b1, W2, b2)
-        x_, W1_, b1_, W2_, b2_ = _f32c(x), _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
+        x_, W1_, b1_, W2_, b2_ = _f32c16(x), _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
         y1, ws1 = _raw_linear_fwd(x_, W1_, b1_, act1)
         y2, ws2 = _raw_linear_fwd(x_, W2_, b2_, act2)
         ctx.cfg = (act1, act2, b1 is not None, b2 is not None)
@@ -501,7 +503,7 @@ class _HighwayFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, Wp, bp, Wg, bg, p, seed, proj_act):
         _lib.require_hip(x, Wp, bp, Wg, bg)
-        x_, Wp_, bp_, Wg_, bg_ = _f32c(x), _f32c(Wp), _f32c(bp), _f32c(Wg), _f32c(bg)
+        x_, Wp_, bp_, Wg_, bg_ = _f32c16(x), _f32c(Wp), _f32c(bp), _f32c(Wg), _f32c(bg)
         proj, wsp = _raw_linear_fwd(x_, Wp_, bp_, act=proj_act)
         gate, wsg = _raw_linear_fwd(x_, Wg_, bg_, act=3)
         out = torch.empty_like(x_)
@@ -594,7 +596,7 @@ class _LstmScanFn(torch.autograd.Function):
     def forward(ctx, gx, W_rec, h0, c0):
         ctx.set_materialize_grads(False)            # an unused output (the decoder never reads c_all) arrives as None, not as a zero fill
         _lib.require_hip(gx, W_rec, h0, c0)
-        gx_, W_, h0_, c0_ = _f32c(gx), _f32c(W_rec), _f32c(h0), _f32c(c0)
+        gx_, W_, h0_, c0_ = _f32c16(gx), _f32c(W_rec), _f32c16(h0), _f32c16(c0)
         T, B, H4 = gx_.shape
         H = H4 // 4
         if W_.shape != (4 * H, H):
@@ -616,7 +618,7 @@ class _LstmScanFn(torch.autograd.Function):
         W_, h0_, c0_, h_all, c_all, acts = ctx.saved_tensors
         T, B, H, nbytes = ctx.dims
         dev = h_all.device
-        dh_, dc_ = _f32c(dh_all), _f32c(dc_all)
+        dh_, dc_ = _f32c16(dh_all), _f32c16(dc_all)
         ws = _scratch(nbytes, dev)
         dgx = torch.empty(T, B, 4 * H, dtype=torch.float32, device=dev)
         dh0, dc0 = (torch.empty(B, H, dtype=torch.float32, device=dev) for _ in range(2))
@@ -924,7 +926,7 @@ class _ConvPoolFn(torch.autograd.Function):
         if x.requires_grad:
             raise NotImplementedError("%s: the windows are input data; a gradient w.r.t. them is not implemented "
                                       "(the reference never asks for one)" % op)
-        x_, w_, b_ = _f32c(x), _f32c(weight), _f32c(bias)
+        x_, w_, b_ = _f32c16(x), _f32c(weight), _f32c(bias)
         N, W, D = x_.shape
         k = "2" if op == "conv_maxpool" else "K"
         if w_.dim() != 3 or w_.shape[1] != D or (k == "2" and w_.shape[2] != 2):
@@ -1014,7 +1016,7 @@ class _MfnMemScanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, apre, chat, Wm, W2, b2, dropout_p, seed):
         _lib.require_hip(apre, chat, Wm, W2, b2)
-        a_, c_, Wm_, W2_, b2_ = _f32c(apre), _f32c(chat), _f32c(Wm), _f32c(W2), _f32c(b2)
+        a_, c_, Wm_, W2_, b2_ = _f32c16(apre), _f32c16(chat), _f32c(Wm), _f32c(W2), _f32c16(b2)
         T, B, U = a_.shape
         MD, HG = c_.shape[-1], W2_.shape[-1]
         if U != 2 * HG or Wm_.shape != (U, MD) or W2_.shape != (2, MD, HG) or b2_.shape != (2, MD):
@@ -1028,7 +1030,7 @@ class _MfnMemScanFn(torch.autograd.Function):
     def backward(ctx, dmem):
         c_, Wm_, W2_, mem_all, u_all, g_all = ctx.saved_tensors
         T, B = mem_all.shape[:2]
-        dapre, dchat, dWm, dW2, db2 = _mem_scan_bwd(_f32c(dmem), c_, Wm_, W2_, mem_all, u_all, g_all, T, B, ctx.dropout_p)
+        dapre, dchat, dWm, dW2, db2 = _mem_scan_bwd(_f32c16(dmem), c_, Wm_, W2_, mem_all, u_all, g_all, T, B, ctx.dropout_p)
         return dapre, dchat, dWm, dW2, db2, None, None
 
 
@@ -1592,6 +1594,9 @@ def _stream_state(op, state, nbytes, device, maker):
         raise ValueError("%s: state must be a contiguous uint8 tensor of at least %d bytes (%s)" % (op, nbytes, maker))
     if state.device != device:
         raise ValueError("%s: state is on %s, the operands on %s" % (op, state.device, device))
+    if state.data_ptr() % 16:           # a step reads the prepared weights (and the K/V cache) eight bf16 per lane, from pieces laid out from the base
+        raise ValueError("%s: state must start at a 16-byte aligned address (%s gives one; a view at an odd offset does not), got "
+                         "an address that is %d modulo 16" % (op, maker, state.data_ptr() % 16))
 
 
 def _stream_positions(op, positions, B, device):
@@ -1793,8 +1798,10 @@ def linear_prepare(W, b, prepared=None):
     nbytes = _lib.load().mmt_linear_prepared_bytes(K, N)
     if prepared is None:
         prepared = _scratch(nbytes, W.device)
-    elif prepared.dtype != torch.uint8 or not prepared.is_contiguous() or prepared.numel() < nbytes or prepared.device != W.device:
-        raise ValueError("linear_prepare: prepared must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, W.device))
+    elif prepared.dtype != torch.uint8 or not prepared.is_contiguous() or prepared.numel() < nbytes or prepared.device != W.device \
+            or prepared.data_ptr() % 16:
+        raise ValueError("linear_prepare: prepared must be a contiguous, 16-byte aligned uint8 tensor of at least %d bytes on %s"
+                         % (nbytes, W.device))
     W_, b_ = _f32c(W), _f32c(b)
     prepared._mmt_linear_kn = None                                         # not valid for any shape while it is rewritten
     _lib.launch("mmt_linear_prepare", W_, b_, prepared, prepared.numel(), K, N)
@@ -1819,7 +1826,7 @@ def linear_prepared(x, prepared, N, act=0, rowscale=None):
     if getattr(prepared, "_mmt_linear_kn", None) != (K, N):
         raise ValueError("linear_prepared: prepared was laid out for (K, N) = %s, the call is for (%d, %d) (the tensor linear_prepare "
                          "returned carries its shape; a view or a copy of it does not)" % (getattr(prepared, "_mmt_linear_kn", None), K, N))
-    x_, r_ = _f32c(x), _f32c(rowscale)
+    x_, r_ = _f32c16(x), _f32c(rowscale)
     y = torch.empty(M, N, dtype=torch.float32, device=x.device)
     _lib.launch("mmt_linear_forward_prepared", x_, prepared, prepared.numel(), r_, y, M, K, N, int(act))
     return y
