@@ -42,7 +42,7 @@
  *     one of two contracts, named at each entry's workspace query:
  *       "zero once": the workspace MUST be zero-filled when first created and may then be reused, without
  *         clearing, by any later call of the same entry family and the same shape arguments, whatever
- *         else differs (inputs, a NaN among them, mask, key lengths, plain / _keys / _causal form,
+ *         else differs (inputs, a NaN among them, mask, key lengths, plain / _keys / _causal / _band form,
  *         dropout probability, seed by value or device-resident).  Pad regions are never written, so
  *         they stay zero; every other word a call reads it has written itself (or, in a backward, its
  *         forward has: saved-for-backward tensors live in the workspace between the two).  This is the
@@ -98,7 +98,7 @@ int mmt_profile_collect(float* total_ms, int* launches);
  * Eval-mode (dropout = identity) when dropout_p == 0; see mmt_encoder_forward's `dropout_p`, `seed`. */
 size_t mmt_encoder_param_count(int d, int f, int n_layers);
 /* workspace: zero once; reusable for the same (B, T, d, h, f, n_layers) and the same kind (train / eval, below) by every form of the
- * entry (plain, _keys, _causal, _devseed). */
+ * entry (plain, _keys, _causal, _band, _devseed). */
 size_t mmt_encoder_workspace_bytes(int B, int T, int d, int h, int f, int n_layers);
 /* ... for calls with dropout_p == 0 only (eval mode): without the attention-dropout bit masks (2 x n_layers x B*h x Tp^2/4 bytes, the
  * last region of the full workspace: an eval workspace is a prefix of a train one).  A forward and its backward take the same kind. */
@@ -150,7 +150,7 @@ int mmt_layernorm_backward(const float* dy, const float* x, const float* a_2, co
  * dropout_p, seed: the reference's nn.Dropout on p_attn (:32-33) in train mode (0 = eval / dropout=None); the decisions are
  * drawn by the forward into the workspace and re-read by the backward (same dropout_p and seed must be passed); they are
  * dropout stream 0 of mmt_debug_dropout_mask. */
-/* workspace: zero once; reusable for the same (B, T, d, h) and the same kind (train / eval) by the plain, _keys and _causal forms. */
+/* workspace: zero once; reusable for the same (B, T, d, h) and the same kind (train / eval) by the plain, _keys, _causal and _band forms. */
 size_t mmt_sdpa_workspace_bytes(int B, int T, int d, int h);
 size_t mmt_sdpa_workspace_bytes_eval(int B, int T, int d, int h);      /* dropout_p == 0 calls: without the dropout bit masks */
 int mmt_sdpa_forward(const float* q, const float* k, const float* v, const float* mask, float* ctx,
@@ -252,6 +252,48 @@ int mmt_encoder_backward_causal_devseed(const float* dy, const float* x, const f
                                         void* workspace, size_t workspace_bytes,
                                         int B, int T, int d, int h, int f, int n_layers, float eps,
                                         float dropout_p, mmt_stream_t stream);
+
+/* ---- Banded causal self-attention (opt-in; sliding-window / local causal attention; departs from :27-31 as the causal entries do).
+ * Query t of a sequence sees keys max(0, t - span + 1) .. t of that sequence, span >= 1 windows, its own included: every other key scores
+ * -inf, its probability is exactly 0 and it gets no dK or dV from that query.  span = 1: a query sees itself only, in eval mode
+ * ctx[b, t] == bf16(v[b, t]).  span >= T is causal attention as a function, computed by the band kernels (agreement with the _causal
+ * entries is within tolerance, not bit for bit: the forward sweeps its key tiles downwards from the diagonal).  The query-row mask keeps
+ * its meaning: a blanked row t is uniform over its min(t + 1, span) visible keys and passes no gradient to q.  Dropout bits are drawn as
+ * for the plain entry, per position for the whole T x T block; bits outside the band are never read.  Each `_band` entry has the plain
+ * entry's signature with `int span` in front of the stream, and the plain entry's workspace (zero once, reusable for the same shape
+ * and kind by every form); span < 1 returns MMT_EINVAL.  The backward always runs as two kernels (dK/dV, dQ).  There is no form with
+ * key lengths, for the reason given for causal. */
+/* mmt_sdpa_forward / mmt_sdpa_backward, band                                  (attention(), :22-34; departs from :27-31) */
+int mmt_sdpa_forward_band(const float* q, const float* k, const float* v, const float* mask, float* ctx,
+                          void* workspace, size_t workspace_bytes, int B, int T, int d, int h,
+                          float dropout_p, uint64_t seed, int span, mmt_stream_t stream);
+int mmt_sdpa_backward_band(const float* dctx, const float* mask, float* dq, float* dk, float* dv,
+                           void* workspace, size_t workspace_bytes, int B, int T, int d, int h,
+                           float dropout_p, uint64_t seed, int span, mmt_stream_t stream);
+/* mmt_attn_probs_forward, band: entries outside columns max(0, t - span + 1) .. t of row t are exact zeros, a blanked query row t is
+ * 1/min(t + 1, span) on those columns                                         (p_attn, :22-34,59; departs from :27-31) */
+int mmt_attn_probs_forward_band(const float* q, const float* k, const float* mask, float* probs,
+                                int B, int T, int d, int h, float dropout_p, uint64_t seed, int span, mmt_stream_t stream);
+/* mmt_encoder_forward / mmt_encoder_backward and their device-seeded twins, band: every layer's self-attention has the same span
+ *                                                                             (Encoder.forward, :72-83; departs from :27-31) */
+int mmt_encoder_forward_band(const float* x, const float* mask, const float* params, float* y,
+                             void* workspace, size_t workspace_bytes,
+                             int B, int T, int d, int h, int f, int n_layers, float eps,
+                             float dropout_p, uint64_t seed, int span, mmt_stream_t stream);
+int mmt_encoder_backward_band(const float* dy, const float* x, const float* mask, const float* params,
+                              float* dx, float* dparams,
+                              void* workspace, size_t workspace_bytes,
+                              int B, int T, int d, int h, int f, int n_layers, float eps,
+                              float dropout_p, uint64_t seed, int span, mmt_stream_t stream);
+int mmt_encoder_forward_band_devseed(const float* x, const float* mask, const float* params, float* y,
+                                     void* workspace, size_t workspace_bytes,
+                                     int B, int T, int d, int h, int f, int n_layers, float eps,
+                                     float dropout_p, uint64_t* seed_state, int span, mmt_stream_t stream);
+int mmt_encoder_backward_band_devseed(const float* dy, const float* x, const float* mask, const float* params,
+                                      float* dx, float* dparams,
+                                      void* workspace, size_t workspace_bytes,
+                                      int B, int T, int d, int h, int f, int n_layers, float eps,
+                                      float dropout_p, int span, mmt_stream_t stream);
 
 /* ---- A causal encoder stack, one window at a time (opt-in; eval mode, forward only).
  * Replaces Encoder.forward(x, mask)[:, t] with causal attention on               transformer/MFT/multiTransformer.py:73-76

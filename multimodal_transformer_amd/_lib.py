@@ -56,6 +56,14 @@ SIGNATURES = {
     "mmt_encoder_backward_causal": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _U64, _P]),
     "mmt_encoder_forward_causal_devseed": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _P, _P]),
     "mmt_encoder_backward_causal_devseed": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _P]),
+    # band: the plain entry's arguments with `int span` in front of the stream
+    "mmt_sdpa_forward_band": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_F, _U64, _I, _P]),
+    "mmt_sdpa_backward_band": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_F, _U64, _I, _P]),
+    "mmt_attn_probs_forward_band": (_I, [_P, _P, _P, _P] + [_I] * 4 + [_F, _U64, _I, _P]),
+    "mmt_encoder_forward_band": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _U64, _I, _P]),
+    "mmt_encoder_backward_band": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _U64, _I, _P]),
+    "mmt_encoder_forward_band_devseed": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _P, _I, _P]),
+    "mmt_encoder_backward_band_devseed": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 6 + [_F, _F, _I, _P]),
     # one window of a causal stack per launch: (B, capacity, d, h, f, n_layers) behind the state and, for a step, the position t
     "mmt_encoder_stream_bytes": (_SZ, [_I] * 6),
     "mmt_encoder_stream_prepare": (_I, [_P, _P, _SZ] + [_I] * 6 + [_P]),
@@ -176,21 +184,26 @@ def require_hip(*tensors):
                                "(move the module and its inputs to a HIP device)" % t.device)
 
 
-def entry_name(name, keys=False, causal=False, devseed=False):
-    """The form of the C entry point ``name`` to call: ``name`` + {"", "_keys", "_causal"} + {"", "_devseed"} (include/mmt_hip.h)."""
+def entry_name(name, keys=False, causal=False, devseed=False, band=False):
+    """The form of the C entry point ``name`` to call: ``name`` + {"", "_keys", "_causal", "_band"} + {"", "_devseed"}
+    (include/mmt_hip.h).  ``band`` (a span is given) needs ``causal`` and selects ``_band`` in its place."""
     if keys and causal:
         raise ValueError("%s has no form with both key_lengths and causal=True" % name)
-    return name + ("_keys" if keys else "_causal" if causal else "") + ("_devseed" if devseed else "")
+    if band and not causal:
+        raise ValueError("%s has a form with a span only together with causal=True" % name)
+    return name + ("_keys" if keys else "_band" if band else "_causal" if causal else "") + ("_devseed" if devseed else "")
 
 
-def launch(name, *args, key_lengths=None, causal=False, devseed=False):
+def launch(name, *args, key_lengths=None, causal=False, devseed=False, span=None):
     """Call the C entry point ``name`` on the current stream (read now: StreamFork's ``torch.cuda.stream`` blocks rely on it).  A tensor
     goes as its data_ptr(), None as a null pointer, every other argument unchanged; a non-zero return code raises.
     ``key_lengths`` (an int32 (B,) device tensor): call the entry's ``_keys`` form, which takes that tensor behind the stream.
     ``causal``: call the entry's ``_causal`` form, which takes the entry's own arguments (with ``key_lengths``: raises).
+    ``span`` (an int >= 1, with ``causal``): call the entry's ``_band`` form, which takes the span in front of the stream.
     ``devseed``: call the device-seeded twin of that form (DeviceSeed), whose seed argument, if it takes one, is among ``args``."""
-    name = entry_name(name, key_lengths is not None, causal, devseed)
-    argv = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args] + [torch.cuda.current_stream().cuda_stream]
+    name = entry_name(name, key_lengths is not None, causal, devseed, span is not None)
+    argv = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    argv += ([] if span is None else [int(span)]) + [torch.cuda.current_stream().cuda_stream]
     if key_lengths is not None:
         argv.append(key_lengths.data_ptr())
     check(getattr(load(), name)(*argv))
@@ -247,7 +260,7 @@ class WorkspacePool:
     its shape arguments (and, for the encoder stack and sdpa, train or eval).  Everything else may
     differ between them and must not show in the later one's result: the input values (one batch
     with a NaN or an Inf leaves them in the buffer), the mask and the key lengths, the plain / keyed /
-    causal form of the attention, the dropout probability, the seed and its kind (by value or a
+    causal / band form of the attention and its span, the dropout probability, the seed and its kind (by value or a
     DeviceSeed), which optional operands are given (bias, rowscale, h0 / c0), and, where the tag
     carries no T and B (the stacked and the feedback LSTM scans), those as well.  A kernel sequence
     therefore stores every word it later reads, whether or not the row, the key tile or the causal

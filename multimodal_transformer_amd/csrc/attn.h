@@ -20,6 +20,24 @@
 // (key > query, or key >= T, masked by a select), and behind it the wave only keeps staging for the workgroup, whose sweep ends at
 // the diagonal of its last query tile.  The dK/dV kernel, whose waves own key tiles, mirrors that: idle in front of the diagonal.
 //
+// Band (opt-in, the *_band_kernel entries, one more argument `int span` >= 1): query t sees keys max(0, t-span+1) .. t of
+// its sequence — causal with a lower edge.  MODE's fourth value.  The visible key tiles of query tile qt are band_lo_tile(qt) .. qt, the
+// query tiles that see key tile kt are kt .. band_hi_tile(kt); a workgroup stages from the lowest tile of its first wave to the highest
+// of its last, and a wave is idle (staging and the barrier only) outside its own range.  At most three tiles of a wave are partial — the
+// diagonal, and the two on the far edge — and they coincide when span <= 32.  Every working tile of a band runs ONE body, EDGE, whose
+// select is (unsigned)(query - key) < span, with the query clamped to T-1 in the key-sweeping kernels (key <= query < T then needs no
+// test of its own, and a row >= T, never stored, keeps finite values) and `query < T` tested beside it in the dK/dV kernel; in a tile
+// between the edges the select passes everything.  Straight-line code behind the MFMA, always a select, never a multiplier.  A second
+// instantiation for the tiles between (the full body, chosen per tile in the sweep loop) saves those tiles three vector instructions
+// per score but costs the forward 13-40 VGPRs and dK/dV 8-24, a wave per SIMD in 7 of the 18 instances (DESIGN.md 4.10 has both
+// tables): the one body was kept, as attn_probs_causal chose for the same reason.
+// FIRST-TILE RULE: in a lower-edge tile a row may have no visible key at all (span 64, row 31, key tile qt-2), and the forward's first
+// tile sets the running maximum to the tile maximum whatever its sign: -inf there, and the sweep would form -inf - (-inf).  So the band
+// forward sweeps its key tiles DOWNWARDS from the diagonal: the first working tile is the one in which every row sees its own key and
+// has a finite maximum; a later all-masked row has tile maximum -inf, never moves the reference (fmaxf(-inf, 0) = 0) and contributes
+// P = 2^-inf = 0.  The rest of the rule is unchanged.  dQ and dK/dV have no running state and sweep upwards.  The plain, keyed and
+// causal kernels keep their ascending sweep and their bits.
+//
 // Scores are kept in the log2 domain: the producer stores Q' = (x Wq^T + bq) * log2(e)/sqrt(d_k), so
 // P = 2^(S' - L) with L = rowmax + log2(rowsum) saved per query for the backward pass.
 #pragma once
@@ -120,11 +138,16 @@ __device__ __forceinline__ int attn_key_len(const int* __restrict__ key_lengths,
     return __builtin_amdgcn_readfirstlane(min(max(key_lengths[b], 1), T));
 }
 
-enum AttnMode { ATTN_PLAIN = 0, ATTN_KEYS = 1, ATTN_CAUSAL = 2 };
-// tags of the tile bodies: the hot tile, the tile that holds the tail of the swept axis, the tile on the causal diagonal
+enum AttnMode { ATTN_PLAIN = 0, ATTN_KEYS = 1, ATTN_CAUSAL = 2, ATTN_BAND = 3 };
+// tags of the tile bodies: the hot tile, the tile that holds the tail of the swept axis, the tile on the causal diagonal, a partial tile
+// of a band (its diagonal and its far edge; the band kernels run it on every tile)
 using TileFull = std::integral_constant<int, 0>;
 using TileTail = std::integral_constant<int, 1>;
 using TileDiag = std::integral_constant<int, 2>;
+using TileEdge = std::integral_constant<int, 3>;
+// band: the lowest key tile that a query of tile qt sees, the highest query tile that sees a key of tile kt (span <= T: no overflow)
+__device__ __forceinline__ int band_lo_tile(int qt, int span) { return max(0, (32 * qt - span + 1) >> 5); }
+__device__ __forceinline__ int band_hi_tile(int kt, int span, int nt) { return min(nt - 1, (32 * kt + 30 + span) >> 5); }
 
 struct AttnBlock { int bx, bh; bool valid; };
 __device__ __forceinline__ AttnBlock attn_block(int nx, int nbh) {
@@ -155,8 +178,8 @@ __device__ __forceinline__ void attn_fwd_body(
         const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
         bf16* __restrict__ ctx, float* __restrict__ lse,
         int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
-        const int* __restrict__ key_lengths) {
-    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL;
+        const int* __restrict__ key_lengths, int span) {
+    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL, BAND = MODE == ATTN_BAND;
     constexpr int KS = DKP / 16;
     constexpr int DKB = DKP < 32 ? DKP : 32;           // feature rows of this launch's output block
     constexpr bool ONES = (DKP == 16) && !DROP;        // row sums through the MFMA
@@ -179,13 +202,18 @@ __device__ __forceinline__ void attn_fwd_body(
     // keys that exist for this sequence and the tiles that hold them: (T, nt), or the sequence's key length and its tiles;
     // causal: the workgroup's sweep ends at the diagonal of its last query tile
     const int Tk = KEYS ? attn_key_len(key_lengths, b, T) : T;
-    const int nk = KEYS ? (Tk + 31) >> 5 : CAUSAL ? min(nt, ab.bx * 4 + 4) : nt;
+    const int nk = KEYS ? (Tk + 31) >> 5 : (CAUSAL || BAND) ? min(nt, ab.bx * 4 + 4) : nt;
+    // band: the workgroup sweeps DOWNWARDS from tile nk-1 to kw0, this wave works in qt .. klo of them; sp: the span, at most T
+    const int sp = BAND ? min(span, T) : 0;
+    const int kw0 = BAND ? band_lo_tile(ab.bx * 4, sp) : 0, klo = BAND ? band_lo_tile(qtc, sp) : 0;
+    const int kfirst = BAND ? nk - 1 : 0;               // the first tile staged
+    const int qrel = BAND ? min(qtc * 32 + r, T - 1) : 0;      // band: this lane's query, clamped (a row >= T, never stored, acts as row T-1)
     const bf16* Qb = Qr + (size_t)bh * fragR_elems(Tp, DKP);
     const bf16* Kb = Kr + (size_t)bh * fragR_elems(Tp, DKP);
     const bf16* Vb = Vr + (size_t)bh * fragR_elems(Tp, DKP) + (size_t)fb * 4 * 256;      // feature group 4 fb of tile 0
     // dropout: this lane's 16-bit words of the wave's row of mask blocks (attn_mask.h, LQ layout), one per key tile, fetched a tile ahead
     const uint16_t* mrow = maskQ + ((size_t)bh * nt + qtc) * nt * 64 + lane;
-    uint32_t mw = DROP ? mrow[0] : 0u;
+    uint32_t mw = DROP ? mrow[BAND ? (size_t)qtc * 64 : 0] : 0u;      // band: the wave's first working tile is its diagonal one
 
     TileStager<2, (PK + PV + MMT_THREADS - 1) / MMT_THREADS> stg;
     {
@@ -193,7 +221,7 @@ __device__ __forceinline__ void attn_fwd_body(
         const int pieces[2] = {PK, PV}, strides[2] = {32 * DKP, 32 * DKP}, lds0[2] = {0, PK}, pad[2] = {0, MMT_TR_OCT - 32};
         stg.init(base, pieces, strides, lds0, pad, threadIdx.x);
     }
-    stg.load(0);
+    stg.load(kfirst);
     zeros[threadIdx.x] = (bf16)0.f;
     // transposing-read role of this lane in the V tile: its feature row r = 16 g1 + (lane & 15) is delivered by the hardware; the
     // address it SUPPLIES is that of window q = (lane >> 2) & 3 of a 4-window block, features 16 g1 + 4 pp .. + 3, pp = lane & 3.
@@ -208,7 +236,7 @@ __device__ __forceinline__ void attn_fwd_body(
     bf16x8 ones;
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones[j] = (bf16)1.0f;
-    stg.store(stage[0]);
+    stg.store(stage[kfirst & 1]);
     __syncthreads();
 
     f32x16 o;
@@ -226,14 +254,17 @@ __device__ __forceinline__ void attn_fwd_body(
     //@ prologue
     auto body = [&](auto tile_tag, int kt) {
         constexpr bool TAIL = (int)decltype(tile_tag)::value == 1, DIAG = (int)decltype(tile_tag)::value == 2;
+        constexpr bool EDGE = (int)decltype(tile_tag)::value == 3;
         // the workgroup stages one tile ahead: compile-time off in the last tile of a plain or keyed sweep; causal: the wave's
-        // diagonal tile is not the workgroup's last one unless the wave owns the last query tile
-        const bool more = CAUSAL ? kt + 1 < nk : !TAIL;
+        // diagonal tile is not the workgroup's last one unless the wave owns the last query tile; band: the next tile is the one below
+        const bool more = BAND ? kt > kw0 : CAUSAL ? kt + 1 < nk : !TAIL;
+        const int knext = BAND ? kt - 1 : kt + 1;
         //@ loop_top
-        progress_prio(kt, nk);
+        progress_prio(BAND ? qt - kt : kt, BAND ? qt - klo + 1 : nk);
         const uint32_t tw = mw;                          // this tile's keep bits
-        if (DROP && !TAIL && !DIAG) mw = mrow[(size_t)(kt + 1) * 64];
-        if (more) stg.load(kt + 1);                     // next tile in flight behind this tile's arithmetic
+        if (BAND) { if (DROP && kt > klo) mw = mrow[(size_t)(kt - 1) * 64]; }
+        else if (DROP && !TAIL && !DIAG) mw = mrow[(size_t)(kt + 1) * 64];
+        if (more) stg.load(knext);                      // next tile in flight behind this tile's arithmetic
         const bf16* sk = stage[kt & 1];
         const bf16* sv = vpad ? zeros : sk + PK * 8 + voff;
         // S' - m straight out of the MFMA: the accumulator init is a register set that holds -m for the whole sweep and is rewritten
@@ -260,16 +291,21 @@ __device__ __forceinline__ void attn_fwd_body(
 #pragma unroll                                          // visible to every query of the tile, so every row keeps a finite maximum
             for (int i = 0; i < 16; ++i) s[i] = (acc32_row(i, hh) <= r && kt * 32 + acc32_row(i, hh) < T) ? s[i] : -INFINITY;
         }
+        if (EDGE) {                                     // band: keys query-span+1 .. query exist.  On the diagonal (the first tile of the
+#pragma unroll                                          // downward sweep) every row sees its own key; on the far edge a row may see none
+            for (int i = 0; i < 16; ++i) s[i] = ((unsigned)(qrel - kt * 32 - acc32_row(i, hh)) < (unsigned)sp) ? s[i] : -INFINITY;
+        }
         // (no inline asm here: hipcc's hazard recognizer does not count an asm statement as a reader of MFMA results)
         float tmax = fmaxf(fmaxf(s[0], s[1]), s[2]);
 #pragma unroll
         for (int i = 3; i < 15; i += 2) tmax = fmaxf(fmaxf(tmax, s[i]), s[i + 1]);
         tmax = fmaxf(tmax, s[15]);                      // over this lane's 16 keys; the other half of the wave holds the query's other 16
         //@ qk_max
-        if (kt == 0 || __any(tmax > MMT_RESCALE_THR)) {      // __any looks at both halves: no exchange on the common path
+        const int kone = BAND ? qt : 0;                 // the wave's first working tile
+        if (kt == kone || __any(tmax > MMT_RESCALE_THR)) {        // __any looks at both halves: no exchange on the common path
             // move the reference to the new running max (first tile: from 0 to the tile max, with o = l = 0)
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32));  // finite: every tile holds >= 1 real key in one of the halves
-            const float dlt = (kt == 0) ? tmax : fmaxf(tmax, 0.f);
+            tmax = fmaxf(tmax, __shfl_xor(tmax, 32));  // finite: every tile holds >= 1 real key in one of the halves (band: in the first
+            const float dlt = (kt == kone) ? tmax : fmaxf(tmax, 0.f);      // tile; -inf in a later one leaves the reference where it is)
             // alpha <= 1: a first tile whose maximum is below -128 would give 2^(-dlt) = inf, and o = l = 0 times inf is NaN
             const float alpha = fast_exp2(-fmaxf(dlt, 0.f));
             mrun += dlt;
@@ -298,7 +334,7 @@ __device__ __forceinline__ void attn_fwd_body(
             o = mfma32(va, pack8(s, s2), o);
         }
         //@ pv
-        if (more) stg.store(stage[(kt + 1) & 1]);
+        if (more) stg.store(stage[knext & 1]);
         //@ stage_wait
         __syncthreads();        // stage[(kt+1)&1] was last read at tile kt-1, i.e. before the previous barrier
         //@ barrier
@@ -312,6 +348,19 @@ __device__ __forceinline__ void attn_fwd_body(
         for (int kt = live ? qt + 1 : 0; kt < nk; ++kt) {
             if (kt + 1 < nk) { stg.load(kt + 1); stg.store(stage[(kt + 1) & 1]); }
             __syncthreads();
+        }
+    } else if constexpr (BAND) {
+        // downwards: idle above the wave's diagonal, the EDGE body from it to the wave's lowest tile, idle below
+        auto idle = [&](int kt) {
+            if (kt > kw0) { stg.load(kt - 1); stg.store(stage[(kt - 1) & 1]); }
+            __syncthreads();
+        };
+        int kt = nk - 1;
+        for (; kt > (live ? qt : kw0 - 1); --kt) idle(kt);
+        if (live) {
+            for (; kt >= klo; --kt) body(TileEdge{}, kt);
+            __builtin_amdgcn_s_setprio(0);
+            for (; kt >= kw0; --kt) idle(kt);
         }
     } else {
         for (int kt = 0; kt < nk - 1; ++kt) body(TileFull{}, kt);
@@ -344,7 +393,7 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_kernel(
         const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
         bf16* __restrict__ ctx, float* __restrict__ lse,
         int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
-    attn_fwd_body<DKP, DROP, ATTN_PLAIN>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, nullptr);
+    attn_fwd_body<DKP, DROP, ATTN_PLAIN>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, nullptr, 0);
 }
 // ... with key lengths: sequence b attends keys < key_lengths[b]
 template <int DKP, bool DROP>
@@ -353,7 +402,7 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_keys_kernel(
         bf16* __restrict__ ctx, float* __restrict__ lse,
         int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
         const int* __restrict__ key_lengths) {
-    attn_fwd_body<DKP, DROP, ATTN_KEYS>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, key_lengths);
+    attn_fwd_body<DKP, DROP, ATTN_KEYS>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, key_lengths, 0);
 }
 // ... causal: query t attends keys <= t
 template <int DKP, bool DROP>
@@ -361,7 +410,15 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_causal_kernel(
         const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
         bf16* __restrict__ ctx, float* __restrict__ lse,
         int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
-    attn_fwd_body<DKP, DROP, ATTN_CAUSAL>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, nullptr);
+    attn_fwd_body<DKP, DROP, ATTN_CAUSAL>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, nullptr, 0);
+}
+// ... band: query t attends keys max(0, t - span + 1) .. t
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_band_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
+        bf16* __restrict__ ctx, float* __restrict__ lse,
+        int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb, int span) {
+    attn_fwd_body<DKP, DROP, ATTN_BAND>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, nullptr, span);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -376,8 +433,8 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
         const float* __restrict__ lse, const float* __restrict__ delta,
         bf16* __restrict__ dkv, int lddkv,      // row-major [M][lddkv]; dK at column HD, dV at 2*HD
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb,
-        const int* __restrict__ key_lengths) {
-    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL;
+        const int* __restrict__ key_lengths, int span) {
+    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL, BAND = MODE == ATTN_BAND;
     constexpr int KS = DKP / 16;
     constexpr int DKB = DKP < 32 ? DKP : 32;
     // pieces: R-layout tile (in LDS with its 8-feature groups 576 bytes apart: the products that contract over the queries read
@@ -413,8 +470,12 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
     const size_t offR = (size_t)bh * fragR_elems(Tp, DKP);
     const bf16 *Krb = Kr + offR, *Vrb = Vr + offR;
     const uint16_t* mrow = maskK + ((size_t)bh * nt + ktc) * nt * 64 + lane;      // LK layout: this lane's word of one block per query tile
-    const int q0 = CAUSAL ? ab.bx * 4 : 0;              // first query tile of the workgroup's sweep (causal: no earlier query sees its keys)
-    uint32_t mw = DROP ? mrow[(size_t)(CAUSAL ? ktc : 0) * 64] : 0u;      // causal: the wave's first working tile is its diagonal one
+    const int q0 = (CAUSAL || BAND) ? ab.bx * 4 : 0;    // first query tile of the workgroup's sweep (causal: no earlier query sees its keys)
+    // band: the wave works in query tiles kt .. qhi, the workgroup's sweep ends behind the last tile of its last live wave (nq == nt otherwise)
+    const int sp = BAND ? min(span, T) : 0;
+    const int qhi = BAND ? band_hi_tile(ktc, sp, nt) : nt - 1;
+    const int nq = BAND ? band_hi_tile(min(nt - 1, ab.bx * 4 + 3), sp, nt) + 1 : nt;
+    uint32_t mw = DROP ? mrow[(size_t)((CAUSAL || BAND) ? ktc : 0) * 64] : 0u;      // causal: the wave's first working tile is its diagonal one
     const uint32_t scale_bits = __builtin_bit_cast(uint32_t, drop_scale);
 
     TileStager<4, (TOTAL + MMT_THREADS - 1) / MMT_THREADS> stg;
@@ -446,7 +507,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
     const int g1 = (lane >> 4) & 1, tq = (lane >> 2) & 3, tpp = lane & 3;
     const int toff = (((ONEACC ? 0 : 4 * fb + 2 * g1) + (tpp >> 1)) * MMT_TR_OCT + 4 * hh + tq) * 8 + 4 * (tpp & 1);
     // (causal: a key >= T is seen by queries >= T only, which the DIAG body masks)
-    const bool key_tail = CAUSAL ? false : KEYS ? (ktc * 32 + 32 > Tk) : (ktc == nt - 1) && (T & 31);
+    const bool key_tail = (CAUSAL || BAND) ? false : KEYS ? (ktc * 32 + 32 > Tk) : (ktc == nt - 1) && (T & 31);
     const bool key_ok = (ktc * 32 + r) < Tk;
     stg.store(stage[0]);                                // (q0 is a multiple of 4: tile qt sits in stage[qt & 1] in every mode)
     __syncthreads();
@@ -467,8 +528,9 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
     const float kmul = (key_tail && !key_ok) ? 0.f : 1.f;
     auto body = [&](auto tile_tag, int qt) {
         constexpr bool QTAIL = (int)decltype(tile_tag)::value == 1, DIAG = (int)decltype(tile_tag)::value == 2;
-        const bool more = qt + 1 < nt;                  // scalar, loop-invariant except at the very last tile
-        progress_prio(qt - q0, nt - q0);
+        constexpr bool EDGE = (int)decltype(tile_tag)::value == 3;
+        const bool more = qt + 1 < nq;                  // scalar, loop-invariant except at the very last tile
+        progress_prio(BAND ? qt - kt : qt - q0, BAND ? qhi - kt + 1 : nq - q0);
         const uint32_t tw = mw;
         if (DROP && more) mw = mrow[(size_t)(qt + 1) * 64];
         if (more) stg.load(qt + 1);
@@ -499,6 +561,8 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
             if (QTAIL) pv = (qt * 32 + acc32_row(j, hh) < T) ? pv : 0.f;      // queries >= T do not exist
             // qt == kt: neither do queries in front of the key (a select: L of such a query is from ITS keys, 2^(S' - L) may be inf)
             if (DIAG) pv = (acc32_row(j, hh) >= r && qt * 32 + acc32_row(j, hh) < T) ? pv : 0.f;
+            // band: only queries key .. key+span-1 below T see the key (a select, for the same reason)
+            if (EDGE) pv = ((unsigned)((qt - kt) * 32 + acc32_row(j, hh) - r) < (unsigned)sp && qt * 32 + acc32_row(j, hh) < T) ? pv : 0.f;
             s[j] = pv;
         }
         if (key_tail) {                                 // wave-uniform, loop-invariant: only the last key tile's wave pays
@@ -543,6 +607,20 @@ __device__ __forceinline__ void attn_bwd_dkv_body(
             for (int qt = kt + 1; qt < nt - 1; ++qt) body(TileFull{}, qt);
             if (kt < nt - 1) { if (T & 31) body(TileTail{}, nt - 1); else body(TileFull{}, nt - 1); }
         }
+    } else if constexpr (BAND) {
+        // idle in front of the diagonal, the EDGE body from it to the wave's last query tile (it masks the query tail too), idle behind
+        // it.  No key tile is without queries.
+        auto idle = [&](int qt) {
+            if (qt + 1 < nq) { stg.load(qt + 1); stg.store(stage[(qt + 1) & 1]); }
+            __syncthreads();
+        };
+        int qt = q0;
+        for (; qt < (live ? kt : nq); ++qt) idle(qt);
+        if (live) {
+            for (; qt <= qhi; ++qt) body(TileEdge{}, qt);
+            __builtin_amdgcn_s_setprio(0);
+            for (; qt < nq; ++qt) idle(qt);
+        }
     } else {
         for (int qt = 0; qt < nt - 1; ++qt) body(TileFull{}, qt);
         if (T & 31) body(TileTail{}, nt - 1); else body(TileFull{}, nt - 1);
@@ -573,7 +651,7 @@ __global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_k
         const float* __restrict__ lse, const float* __restrict__ delta,
         bf16* __restrict__ dkv, int lddkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb) {
-    attn_bwd_dkv_body<DKP, DROP, ATTN_PLAIN>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, nullptr);
+    attn_bwd_dkv_body<DKP, DROP, ATTN_PLAIN>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, nullptr, 0);
 }
 // ... with key lengths: dK = dV = 0 for keys >= key_lengths[b]
 template <int DKP, bool DROP>
@@ -583,7 +661,7 @@ __global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_k
         bf16* __restrict__ dkv, int lddkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb,
         const int* __restrict__ key_lengths) {
-    attn_bwd_dkv_body<DKP, DROP, ATTN_KEYS>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, key_lengths);
+    attn_bwd_dkv_body<DKP, DROP, ATTN_KEYS>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, key_lengths, 0);
 }
 // ... causal: key t gets dK, dV from queries >= t
 template <int DKP, bool DROP>
@@ -592,7 +670,16 @@ __global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_c
         const float* __restrict__ lse, const float* __restrict__ delta,
         bf16* __restrict__ dkv, int lddkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb) {
-    attn_bwd_dkv_body<DKP, DROP, ATTN_CAUSAL>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, nullptr);
+    attn_bwd_dkv_body<DKP, DROP, ATTN_CAUSAL>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, nullptr, 0);
+}
+// ... band: key t gets dK, dV from queries t .. t + span - 1
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, DKP == 16 ? 4 : 2) void attn_bwd_dkv_band_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr, const bf16* __restrict__ dOr,
+        const float* __restrict__ lse, const float* __restrict__ delta,
+        bf16* __restrict__ dkv, int lddkv,
+        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskK, float drop_scale, int fb, int span) {
+    attn_bwd_dkv_body<DKP, DROP, ATTN_BAND>(Qr, Kr, Vr, dOr, lse, delta, dkv, lddkv, h, T, nt, nbh, maskK, drop_scale, fb, nullptr, span);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -607,8 +694,8 @@ __device__ __forceinline__ void attn_bwd_dq_body(
         const float* __restrict__ rowmask, float scale,
         bf16* __restrict__ dqkv, int lddqkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
-        const int* __restrict__ key_lengths) {
-    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL;
+        const int* __restrict__ key_lengths, int span) {
+    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL, BAND = MODE == ATTN_BAND;
     constexpr int KS = DKP / 16;
     constexpr int DKB = DKP < 32 ? DKP : 32;
     constexpr int PR = DKP * 4, PRL = (DKP / 8) * MMT_TR_OCT;      // K tile padded in LDS: K^T fragments by transposing reads
@@ -623,11 +710,15 @@ __device__ __forceinline__ void attn_bwd_dq_body(
     const int bh = ab.bh, b = bh / h, head = bh - b * h;
     const int Tp = nt * 32;
     const int Tk = KEYS ? attn_key_len(key_lengths, b, T) : T;          // keys that exist for this sequence, and their tiles
-    const int nk = KEYS ? (Tk + 31) >> 5 : CAUSAL ? min(nt, ab.bx * 4 + 4) : nt;      // causal: up to the diagonal of the last query tile
+    const int nk = KEYS ? (Tk + 31) >> 5 : (CAUSAL || BAND) ? min(nt, ab.bx * 4 + 4) : nt;      // causal: up to the diagonal of the last query tile
+    // band: the workgroup sweeps upwards from tile k0, this wave works in klo .. qt of them
+    const int sp = BAND ? min(span, T) : 0;
+    const int k0 = BAND ? band_lo_tile(ab.bx * 4, sp) : 0, klo = BAND ? band_lo_tile(qtc, sp) : 0;
+    const int qrel = BAND ? min(qtc * 32 + r, T - 1) : 0;      // band: this lane's query, clamped (attn_fwd_body)
     const size_t offR = (size_t)bh * fragR_elems(Tp, DKP);
     const bf16 *Qrb = Qr + offR, *dOrb = dOr + offR;
     const uint16_t* mrow = maskQ + ((size_t)bh * nt + qtc) * nt * 64 + lane;      // LQ layout
-    uint32_t mw = DROP ? mrow[0] : 0u;
+    uint32_t mw = DROP ? mrow[BAND ? (size_t)klo * 64 : 0] : 0u;
     const uint32_t scale_bits = __builtin_bit_cast(uint32_t, drop_scale);
 
     TileStager<2, (2 * PR + MMT_THREADS - 1) / MMT_THREADS> stg;
@@ -636,7 +727,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(
         const int pieces[2] = {PR, PR}, strides[2] = {32 * DKP, 32 * DKP}, lds0[2] = {0, PRL}, pad[2] = {MMT_TR_OCT - 32, 0};
         stg.init(base, pieces, strides, lds0, pad, threadIdx.x);
     }
-    stg.load(0);
+    stg.load(k0);
     // transposing-read role (see attn_fwd_kernel): feature row 32 fb + r of K^T; slot j <-> key 16 s2 + 8 (j >> 2) + 4 hh + (j & 3).
     // d_k = 16: the lanes of rows >= 16 (nobody reads their dQ^T rows) fetch what lanes r - 16 fetch.
     const int g1 = (lane >> 4) & 1, tq = (lane >> 2) & 3, tpp = lane & 3;
@@ -653,16 +744,18 @@ __device__ __forceinline__ void attn_bwd_dq_body(
     f32x16 dq;
 #pragma unroll
     for (int j = 0; j < 16; ++j) dq[j] = 0.f;
-    stg.store(stage[0]);
+    stg.store(stage[k0 & 1]);
     __syncthreads();
 
     // Tile body without conditional code between MFMAs and their consumers (see attn_fwd_kernel); key tail peeled.
     auto body = [&](auto tile_tag, int kt) {
         constexpr bool TAIL = (int)decltype(tile_tag)::value == 1, DIAG = (int)decltype(tile_tag)::value == 2;
+        constexpr bool EDGE = (int)decltype(tile_tag)::value == 3;
         const bool more = kt + 1 < nk;
-        progress_prio(kt, nk);
+        progress_prio(BAND ? kt - klo : kt, BAND ? qt - klo + 1 : nk);
         const uint32_t tw = mw;
-        if (DROP && more && !DIAG) mw = mrow[(size_t)(kt + 1) * 64];
+        if (BAND) { if (DROP && kt < qt) mw = mrow[(size_t)(kt + 1) * 64]; }
+        else if (DROP && more && !DIAG) mw = mrow[(size_t)(kt + 1) * 64];
         if (more) stg.load(kt + 1);
         const bf16* sk = stage[kt & 1];
         const bf16* sv = sk + PRL * 8;
@@ -685,6 +778,8 @@ __device__ __forceinline__ void attn_bwd_dq_body(
             if (TAIL) pv = (kt * 32 + acc32_row(j, hh) < Tk) ? pv : 0.f;      // keys >= T (>= the key length) do not exist
             // kt == qt: neither do keys behind the query (a select: L is from the visible keys, 2^(S' - L) of a later key may be inf)
             if (DIAG) pv = (acc32_row(j, hh) <= r && kt * 32 + acc32_row(j, hh) < T) ? pv : 0.f;
+            // band: only keys query-span+1 .. query exist (a select, for the same reason)
+            if (EDGE) pv = ((unsigned)(qrel - kt * 32 - acc32_row(j, hh)) < (unsigned)sp) ? pv : 0.f;
             s[j] = pv;
         }
         if (DROP) {
@@ -710,6 +805,19 @@ __device__ __forceinline__ void attn_bwd_dq_body(
         for (int kt = live ? qt + 1 : 0; kt < nk; ++kt) {
             if (kt + 1 < nk) { stg.load(kt + 1); stg.store(stage[(kt + 1) & 1]); }
             __syncthreads();
+        }
+    } else if constexpr (BAND) {
+        // idle below the wave's lowest tile, the EDGE body from it to the diagonal, idle above
+        auto idle = [&](int kt) {
+            if (kt + 1 < nk) { stg.load(kt + 1); stg.store(stage[(kt + 1) & 1]); }
+            __syncthreads();
+        };
+        int kt = k0;
+        for (; kt < (live ? klo : nk); ++kt) idle(kt);
+        if (live) {
+            for (; kt <= qt; ++kt) body(TileEdge{}, kt);
+            __builtin_amdgcn_s_setprio(0);
+            for (; kt < nk; ++kt) idle(kt);
         }
     } else {
         for (int kt = 0; kt < nk - 1; ++kt) body(TileFull{}, kt);
@@ -737,7 +845,7 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_kernel(
         const float* __restrict__ rowmask, float scale,
         bf16* __restrict__ dqkv, int lddqkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
-    attn_bwd_dq_body<DKP, DROP, ATTN_PLAIN>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, nullptr);
+    attn_bwd_dq_body<DKP, DROP, ATTN_PLAIN>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, nullptr, 0);
 }
 // ... with key lengths: the sweep ends at key_lengths[b]
 template <int DKP, bool DROP>
@@ -748,7 +856,7 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_keys_kernel(
         bf16* __restrict__ dqkv, int lddqkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb,
         const int* __restrict__ key_lengths) {
-    attn_bwd_dq_body<DKP, DROP, ATTN_KEYS>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, key_lengths);
+    attn_bwd_dq_body<DKP, DROP, ATTN_KEYS>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, key_lengths, 0);
 }
 // ... causal: the sweep of a query tile ends at its diagonal
 template <int DKP, bool DROP>
@@ -758,7 +866,17 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_causal_kernel(
         const float* __restrict__ rowmask, float scale,
         bf16* __restrict__ dqkv, int lddqkv,
         int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
-    attn_bwd_dq_body<DKP, DROP, ATTN_CAUSAL>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, nullptr);
+    attn_bwd_dq_body<DKP, DROP, ATTN_CAUSAL>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, nullptr, 0);
+}
+// ... band: the sweep of a query tile runs from its far edge to its diagonal
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_bwd_dq_band_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
+        const bf16* __restrict__ dOr, const float* __restrict__ lse, const float* __restrict__ delta,
+        const float* __restrict__ rowmask, float scale,
+        bf16* __restrict__ dqkv, int lddqkv,
+        int h, int T, int nt, int nbh, const uint16_t* __restrict__ maskQ, float drop_scale, int fb, int span) {
+    attn_bwd_dq_body<DKP, DROP, ATTN_BAND>(Qr, Kr, Vr, dOr, lse, delta, rowmask, scale, dqkv, lddqkv, h, T, nt, nbh, maskQ, drop_scale, fb, nullptr, span);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -30,6 +30,12 @@
 // the tiles above the diagonal are written as exact zeros.  The diagonal is a select on a wave-uniform flag inside the one tile
 // body, still straight-line code: a second instantiation of the body, as attn.h has, doubles the keep-bit generator and brings the
 // d_k = 64 train instance to 256 VGPRs with scratch.
+//
+// Band (attn_probs_band_kernel; attn.h): both sweeps of query tile qt run key tiles band_lo_tile(qt) .. qt, a key outside query-span+1 ..
+// query scores MASKED — one select in the one tile body, on every tile of the sweep (the kernel is bound by its stores) — and the
+// tiles on BOTH sides of the band are written as exact zeros.  A (lane, query) pair whose first tiles hold no visible key carries
+// m = MASKED, which is finite: the first visible score wipes what it had summed (2^(MASKED - s) == 0), and one that never sees a key
+// weighs 0 in the merge.  The keep bits of a sweep that starts in the middle of a 64-tile group are drawn at its first tile.
 #pragma once
 #include "common.h"
 #include "attn_mask.h"
@@ -63,8 +69,8 @@ __device__ __forceinline__ bf16x8 probs_frag(const float* __restrict__ row, int 
 template <int DKP, bool DROP, int MODE>
 __device__ __forceinline__ void attn_probs_body(
         const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
-        int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop, const int* __restrict__ key_lengths) {
-    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL;
+        int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop, const int* __restrict__ key_lengths, int span) {
+    constexpr bool KEYS = MODE == ATTN_KEYS, CAUSAL = MODE == ATTN_CAUSAL, BAND = MODE == ATTN_BAND;
     constexpr int KS = DKP / 16;
     __shared__ uint32_t patch[DROP ? 4 * 64 * MMT_PROBS_PATCH_ROW : 1];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -75,7 +81,9 @@ __device__ __forceinline__ void attn_probs_body(
     if (qt >= nt) return;                               // waves share nothing: no barrier below
     const int bh = ab.bh, b = bh / h, head = bh - b * h;
     const int Tk = KEYS ? attn_key_len(key_lengths, b, T) : T;          // keys that exist for this sequence, and their tiles
-    const int nk = KEYS ? (Tk + 31) >> 5 : CAUSAL ? qt + 1 : nt;       // causal: up to the diagonal tile
+    const int nk = KEYS ? (Tk + 31) >> 5 : (CAUSAL || BAND) ? qt + 1 : nt;       // causal: up to the diagonal tile
+    const int sp = BAND ? min(span, T) : 0;
+    const int k0 = BAND ? band_lo_tile(qt, sp) : 0;                    // band: from the tile of the first query's first key
 
     // A operand: Q' of query r of the tile (a query >= T reads row T-1 and is never stored), features 16 s + 8 hh .. + 7
     bf16x8 qf[KS];
@@ -102,7 +110,11 @@ __device__ __forceinline__ void attn_probs_body(
 #pragma unroll
         for (int ss = 0; ss < KS; ++ss) s = mfma32(qf[ss], kf[ss], s);
         const bool kok = kt * 32 + r < Tk;
-        if constexpr (CAUSAL) {                         // on the diagonal tile key r is visible to the queries >= r only
+        if constexpr (BAND) {                           // key r of the tile is visible to the queries key .. key + span - 1
+            const int rel = (qt - kt) * 32 - r;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s[i] = (kok && (unsigned)(rel + acc32_row(i, hh)) < (unsigned)sp) ? s[i] : MMT_PROBS_MASKED;
+        } else if constexpr (CAUSAL) {                  // on the diagonal tile key r is visible to the queries >= r only
             const bool diag = kt == qt;
 #pragma unroll
             for (int i = 0; i < 16; ++i) s[i] = (kok && (!diag || r <= acc32_row(i, hh))) ? s[i] : MMT_PROBS_MASKED;
@@ -118,8 +130,8 @@ __device__ __forceinline__ void attn_probs_body(
 #pragma unroll
     for (int i = 0; i < 16; ++i) { m[i] = MMT_PROBS_MASKED; l[i] = 0.f; }
     bf16x8 kf[KS], kn[KS];
-    kfrag(0, kf);
-    for (int kt = 0; kt < nk; ++kt) {
+    kfrag(k0, kf);
+    for (int kt = k0; kt < nk; ++kt) {
         kfrag(min(kt + 1, nk - 1), kn);                 // next tile in flight behind this tile's arithmetic (the last one re-reads itself)
         const f32x16 s = scores(kf, kt);
 #pragma unroll
@@ -132,7 +144,8 @@ __device__ __forceinline__ void attn_probs_body(
         for (int s2 = 0; s2 < KS; ++s2) kf[s2] = kn[s2];
     }
     // merge the 32 lanes of a half: m <- row max, l <- (1/(1-p)) / row sum.  A lane that saw only keys >= T carries m = MASKED and
-    // weighs 2^(MASKED - max) = 0; every row has >= 1 real key, so the max is finite.
+    // weighs 2^(MASKED - max) = 0; every row has >= 1 real key, so the max is finite.  (Band: a query row >= T of the last tile sees no
+    // key at all when span is small; its max is MASKED, which is finite too, its weights are 2^0, and the row is never stored.)
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         float mx = m[i];
@@ -151,11 +164,20 @@ __device__ __forceinline__ void attn_probs_body(
     uint32_t* const mine = patch + (DROP ? wave * 64 * MMT_PROBS_PATCH_ROW : 0);
     float* const prow = P + ((size_t)bh * T + (size_t)qt * 32) * T;       // row `query in tile` at + query * T
     const bool qfull = qt * 32 + 32 <= T;
-    kfrag(0, kf);
-    for (int kt = 0; kt < nk; ++kt) {
-        if (DROP && (kt & 63) == 0) {                   // wave-uniform: the keep bits of blocks (qt, kt + lane), one block per lane
+    if (BAND) {                                         // the key tiles below the band: zeros
+        for (int kt = 0; kt < k0; ++kt) {
+            float* const pk = prow + kt * 32 + r;
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (qt * 32 + acc32_row(i, hh) < T) pk[(size_t)acc32_row(i, hh) * T] = 0.f;
+        }
+    }
+    kfrag(k0, kf);
+    for (int kt = k0; kt < nk; ++kt) {
+        const int kb = BAND ? kt & ~63 : kt;            // first tile of the 64 whose blocks the patch holds
+        if (DROP && (BAND ? (kt == kb || kt == k0) : (kt & 63) == 0)) {       // wave-uniform: the keep bits of blocks (qt, kb + lane), one block per lane
             uint32_t W[32];
-            attn_keep_block(dc, (uint32_t)(qt * nt + min(kt + lane, nt - 1)), W);      // W[key] bit query
+            attn_keep_block(dc, (uint32_t)(qt * nt + min(kb + lane, nt - 1)), W);      // W[key] bit query
 #pragma unroll
             for (int key = 0; key < 32; ++key) mine[lane * MMT_PROBS_PATCH_ROW + key] = W[key];
         }
@@ -180,7 +202,7 @@ __device__ __forceinline__ void attn_probs_body(
 #pragma unroll
         for (int s2 = 0; s2 < KS; ++s2) kf[s2] = kn[s2];
     }
-    if (KEYS || CAUSAL) {     // the key tiles behind the length / above the diagonal: zeros (the boundary tile's masked entries were stored above, as 2^(MASKED - max) == 0)
+    if (KEYS || CAUSAL || BAND) {     // the key tiles behind the length / above the diagonal: zeros (the boundary tile's masked entries were stored above, as 2^(MASKED - max) == 0)
         for (int kt = nk; kt < nt; ++kt) {
             float* const pk = prow + kt * 32 + r;
             const bool kok = kt * 32 + r < T;
@@ -194,19 +216,26 @@ template <int DKP, bool DROP>
 __global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_kernel(
         const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
         int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop) {
-    attn_probs_body<DKP, DROP, ATTN_PLAIN>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, nullptr);
+    attn_probs_body<DKP, DROP, ATTN_PLAIN>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, nullptr, 0);
 }
 // ... with key lengths: columns >= key_lengths[b] are exact zeros
 template <int DKP, bool DROP>
 __global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_keys_kernel(
         const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
         int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop, const int* __restrict__ key_lengths) {
-    attn_probs_body<DKP, DROP, ATTN_KEYS>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, key_lengths);
+    attn_probs_body<DKP, DROP, ATTN_KEYS>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, key_lengths, 0);
 }
 // ... causal: entries above the diagonal are exact zeros
 template <int DKP, bool DROP>
 __global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_causal_kernel(
         const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
         int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop) {
-    attn_probs_body<DKP, DROP, ATTN_CAUSAL>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, nullptr);
+    attn_probs_body<DKP, DROP, ATTN_CAUSAL>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, nullptr, 0);
+}
+// ... band: entries outside keys query-span+1 .. query are exact zeros
+template <int DKP, bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_probs_band_kernel(
+        const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ rowmask, float* __restrict__ P,
+        int h, int T, int nt, int nbh, int d, int dk, float qscale, int vec, DropCfg drop, int span) {
+    attn_probs_body<DKP, DROP, ATTN_BAND>(q, k, rowmask, P, h, T, nt, nbh, d, dk, qscale, vec, drop, nullptr, span);
 }

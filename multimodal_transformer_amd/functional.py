@@ -43,13 +43,13 @@ def _seed_pair(seed):
     return (0, seed.state) if isinstance(seed, _lib.DeviceSeed) else (int(seed), None)
 
 
-def _launch_seeded(name, seed, *args, state_arg=True, key_lengths=None, causal=False):
+def _launch_seeded(name, seed, *args, state_arg=True, key_lengths=None, causal=False, span=None):
     """``name`` with the seed by value behind ``args``, or its twin ``name``_devseed with the DeviceSeed's state word there, which the
     launch reads and advances.  ``state_arg=False``: the twin takes no seed (the encoder backward finds it in its forward's workspace).
-    ``key_lengths`` / ``causal``: the ``_keys`` / ``_causal`` form of either (_lib.launch)."""
+    ``key_lengths`` / ``causal`` / ``span``: the ``_keys`` / ``_causal`` / ``_band`` form of either (_lib.launch)."""
     devseed = isinstance(seed, _lib.DeviceSeed)
     tail = (seed,) if not devseed else (seed.state,) if state_arg else ()
-    _lib.launch(name, *args, *tail, key_lengths=key_lengths, causal=causal, devseed=devseed)
+    _lib.launch(name, *args, *tail, key_lengths=key_lengths, causal=causal, devseed=devseed, span=span)
 
 
 # Key lengths: a padding mask that masks KEYS (opt-in; the reference blanks query rows only, transformer/MFT/multiTransformer.py:29-31).
@@ -91,6 +91,26 @@ def _check_causal(op, key_lengths, causal):
                          "<= t < len only, so causal attention already keeps it from the padding behind its sequence "
                          "(pass causal=True alone)" % op)
     return bool(causal)
+
+
+# Banded causal self-attention (opt-in): window t attends windows max(0, t - span + 1) .. t.
+def _check_span(op, key_lengths, causal, span, mask_keys=False):
+    """``span`` as None or an int >= 1.  It needs ``causal`` and is never combined with ``key_lengths`` (or, on a module, with
+    ``mask_keys``, which derives them): raises before any launch."""
+    if span is None:
+        return None
+    if isinstance(span, bool) or not isinstance(span, int):
+        raise ValueError("%s: span must be an int >= 1 (the number of windows a query attends, its own included) or None, got %r"
+                         % (op, span))
+    if span < 1:
+        raise ValueError("%s: span = %d, but a query attends at least its own window: span must be >= 1" % (op, span))
+    if key_lengths is not None or mask_keys:
+        raise ValueError("%s: key_lengths and span cannot be combined: span needs causal=True, and causal attention already keeps a "
+                         "valid window t < len of a prefix-masked batch from the padding behind its sequence" % op)
+    if not causal:
+        raise ValueError("%s: span = %d without causal=True: the span is the lower edge of causal attention (window t attends "
+                         "windows t - span + 1 .. t); pass causal=True with it" % (op, span))
+    return span
 
 
 # Workspaces of the entries that take memory with any contents (include/mmt_hip.h: mmt_lstm_scan_*, mmt_mfn_mem_scan_*, mmt_convpool_*,
@@ -154,8 +174,9 @@ def _chunk_seed(seed, i, nsplit=1):
     return seed if i == 0 else _lib.mix64(seed, i)
 
 
-def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths=None, causal=False):
+def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths=None, causal=False, span=None):
     """The fused stack's forward, one launch per sub-batch on a stream of its own; keeps on ``ctx`` what _encoder_bwd needs."""
+    span = _check_span("encoder_stack", key_lengths, causal, span)
     causal = _check_causal("encoder_stack", key_lengths, causal)
     lib = _lib.load()
     _lib.require_hip(x, mask, flat_params)
@@ -184,14 +205,14 @@ def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, s
             ws = _lib.POOL.get(nbytes, x_.device, tag=("encoder",) + dims + (train,))
             sd = _chunk_seed(seed, i, len(chunks))
             _launch_seeded("mmt_encoder_forward", sd, x_[b0:b1], m_[b0:b1], p_, y[b0:b1], ws, nbytes, *dims, eps, dropout_p,
-                           key_lengths=None if kl_ is None else kl_[b0:b1], causal=causal)
+                           key_lengths=None if kl_ is None else kl_[b0:b1], causal=causal, span=span)
             parts.append((b0, b1, ws, sd))
     _SPLIT_STREAMS.end(main, streams)
     if _hold(ctx, *[ws for _, _, ws, _ in parts]):
         ctx.save_for_backward(x_, m_, p_)
         ctx.parts = [(b0, b1, sd) for b0, b1, _, sd in parts]
         ctx.cfg = (T, d, h, d_ff, n_layers, eps, dropout_p)
-        ctx.key_lengths, ctx.causal = kl_, causal
+        ctx.key_lengths, ctx.causal, ctx.span = kl_, causal, span
     return y
 
 
@@ -209,7 +230,7 @@ def _encoder_bwd(ctx, dy):
         with torch.cuda.stream(st):
             _launch_seeded("mmt_encoder_backward", sd, dy_[b0:b1], x_[b0:b1], m_[b0:b1], p_, dx[b0:b1], dp, ws, ws.numel(),
                            b1 - b0, T, d, h, d_ff, n_layers, eps, dropout_p, state_arg=False,
-                           key_lengths=None if kl_ is None else kl_[b0:b1], causal=ctx.causal)
+                           key_lengths=None if kl_ is None else kl_[b0:b1], causal=ctx.causal, span=ctx.span)
             _lib.POOL.put(ws)
     _SPLIT_STREAMS.end(main, streams)
     if len(dps) > 1:                                # the sub-batches' parameter gradients, summed into the first buffer
@@ -221,23 +242,25 @@ def _encoder_bwd(ctx, dy):
 
 class _EncoderStackFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths=None, causal=False):
-        return _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths, causal)
+    def forward(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths=None, causal=False, span=None):
+        return _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths, causal, span)
 
     @staticmethod
     def backward(ctx, dy):
         dx, dflat = _encoder_bwd(ctx, dy)
-        return dx, None, dflat, None, None, None, None, None, None, None, None, None
+        return dx, None, dflat, None, None, None, None, None, None, None, None, None, None
 
 
-def encoder_stack(x, mask, flat_params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, nsplit=1, key_lengths=None, causal=False):
+def encoder_stack(x, mask, flat_params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, nsplit=1, key_lengths=None, causal=False,
+                  span=None):
     """``seed``: a python int (by value) or a ``_lib.DeviceSeed`` (device-resident: fresh masks at every hipGraph replay), or one
     of either per sub-batch stream; ``nsplit``: run the batch as that many sub-batches on HIP streams of their own (see _SPLIT_STREAMS).
     ``key_lengths``: int32 (B,) (``key_lengths(mask)``): sequence b attends keys < key_lengths[b] in every layer; None: the
     reference's semantics, every key is attended.  Sub-batches take their slice of the lengths.
-    ``causal``: window t attends windows 0 .. t in every layer (see ``sdpa``); never together with ``key_lengths`` (ValueError)."""
+    ``causal``: window t attends windows 0 .. t in every layer (see ``sdpa``); never together with ``key_lengths`` (ValueError).
+    ``span`` (with ``causal``): window t attends windows t - span + 1 .. t in every layer (see ``sdpa``)."""
     return _EncoderStackFn.apply(x, mask, flat_params, int(h), int(d_ff), int(n_layers), float(eps), float(dropout_p), _seed_arg(seed),
-                                 int(nsplit), key_lengths, causal)
+                                 int(nsplit), key_lengths, causal, span)
 
 
 class _EncoderStackParamsFn(torch.autograd.Function):
@@ -247,25 +270,25 @@ class _EncoderStackParamsFn(torch.autograd.Function):
     buffer in place with one collective and no staging copies (``parallel.allreduce_gradients``)."""
 
     @staticmethod
-    def forward(ctx, x, mask, h, d_ff, n_layers, eps, dropout_p, seed, flat, nsplit, key_lengths, causal, *params):
+    def forward(ctx, x, mask, h, d_ff, n_layers, eps, dropout_p, seed, flat, nsplit, key_lengths, causal, span, *params):
         # `flat`: the parameters' own storage when they are views of one buffer (multiTransformer.Encoder keeps them that way), else
         # None and the buffer is assembled here (one concatenation kernel per step)
         if flat is None:
             flat = torch.cat([q.detach().reshape(-1) for q in params]).float()
         ctx.shapes = [tuple(q.shape) for q in params]
-        return _encoder_fwd(ctx, x, mask, flat, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths, causal)
+        return _encoder_fwd(ctx, x, mask, flat, h, d_ff, n_layers, eps, dropout_p, seed, nsplit, key_lengths, causal, span)
 
     @staticmethod
     def backward(ctx, dy):
         dx, dflat = _encoder_bwd(ctx, dy)
         grads = [g.view(shp) for g, shp in zip(dflat.split([math.prod(shp) for shp in ctx.shapes]), ctx.shapes)]
-        return (dx, None, None, None, None, None, None, None, None, None, None, None) + tuple(grads)
+        return (dx, None, None, None, None, None, None, None, None, None, None, None, None) + tuple(grads)
 
 
 def encoder_stack_params(x, mask, params, h, d_ff, n_layers, eps=1e-6, dropout_p=0.0, seed=0, flat=None, nsplit=1, key_lengths=None,
-                         causal=False):
+                         causal=False, span=None):
     return _EncoderStackParamsFn.apply(x, mask, int(h), int(d_ff), int(n_layers), float(eps), float(dropout_p), _seed_arg(seed), flat,
-                                       int(nsplit), key_lengths, causal, *params)
+                                       int(nsplit), key_lengths, causal, span, *params)
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -300,7 +323,8 @@ def layer_norm(x, a_2, b_2, eps=1e-6):
 
 class _SdpaFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, mask, h, dropout_p, seed, key_lengths=None, causal=False):
+    def forward(ctx, q, k, v, mask, h, dropout_p, seed, key_lengths=None, causal=False, span=None):
+        span = _check_span("sdpa", key_lengths, causal, span)
         causal = _check_causal("sdpa", key_lengths, causal)
         lib = _lib.load()
         _lib.require_hip(q, k, v, mask)
@@ -317,9 +341,10 @@ class _SdpaFn(torch.autograd.Function):
             _lib.launch("mmt_sdpa_forward", None, None, None, None, None, None, 0, B, T, d, h, 0.0, 0)
         ws = _lib.POOL.get(nbytes, q_.device, tag=("sdpa", B, T, d, h, train))
         out = torch.empty_like(q_)
-        _lib.launch("mmt_sdpa_forward", q_, k_, v_, m_, out, ws, nbytes, B, T, d, h, dropout_p, seed, key_lengths=kl_, causal=causal)
+        _lib.launch("mmt_sdpa_forward", q_, k_, v_, m_, out, ws, nbytes, B, T, d, h, dropout_p, seed, key_lengths=kl_, causal=causal,
+                    span=span)
         if _hold(ctx, ws):
-            ctx.cfg, ctx.mask, ctx.key_lengths, ctx.causal = (B, T, d, h, dropout_p, seed), m_, kl_, causal
+            ctx.cfg, ctx.mask, ctx.key_lengths, ctx.causal, ctx.span = (B, T, d, h, dropout_p, seed), m_, kl_, causal, span
         return out
 
     @staticmethod
@@ -329,12 +354,12 @@ class _SdpaFn(torch.autograd.Function):
         g = _f32c(dctx)
         dq, dk, dv = (torch.empty_like(g) for _ in range(3))
         _lib.launch("mmt_sdpa_backward", g, ctx.mask, dq, dk, dv, ws, ws.numel(), B, T, d, h, dropout_p, seed, key_lengths=ctx.key_lengths,
-                    causal=ctx.causal)
+                    causal=ctx.causal, span=ctx.span)
         _lib.POOL.put(ws)
-        return dq, dk, dv, None, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
-def sdpa(q, k, v, mask, h, dropout_p=0.0, seed=0, key_lengths=None, causal=False):
+def sdpa(q, k, v, mask, h, dropout_p=0.0, seed=0, key_lengths=None, causal=False, span=None):
     """q,k,v: (B,T,d) with head i in columns [i*d/h,(i+1)*d/h); mask (B,T,1) blanks query rows; -> (B,T,d).
     dropout_p / seed: train-mode dropout on the probabilities (transformer/MFT/multiTransformer.py:32-33).
     key_lengths: int32 (B,) (``key_lengths(mask)``): sequence b attends keys < key_lengths[b] only — later keys get probability 0 and
@@ -342,17 +367,25 @@ def sdpa(q, k, v, mask, h, dropout_p=0.0, seed=0, key_lengths=None, causal=False
     causal: query window t attends keys 0 .. t of its sequence only — later keys get probability exactly 0 and no dk, dv from that query,
     a blanked query row t is uniform over its t + 1 visible keys, row 0 attends one key.  Dropout bits are drawn as without the flag.
     Not combined with key_lengths (ValueError before any launch): causal attention already keeps a valid window of a prefix-masked
-    batch from the padding behind its sequence, since t < len means every visible key is < len."""
-    return _SdpaFn.apply(q, k, v, mask, int(h), float(dropout_p), int(seed), key_lengths, causal)
+    batch from the padding behind its sequence, since t < len means every visible key is < len.
+    span (an int >= 1, with causal=True only; None: off): query window t attends keys max(0, t - span + 1) .. t — the last ``span``
+    windows, its own included.  Every other key gets probability exactly 0 and no dk, dv from that query; a blanked query row t is
+    uniform over its min(t + 1, span) visible keys; span = 1 gives ctx[b, t] = bf16(v[b, t]) in eval mode; span >= T is causal
+    attention as a function, computed by the band kernels (within tolerance of causal=True alone, not bit for bit).  ValueError before
+    any launch without causal=True, with key_lengths, for span < 1 and for a bool or a non-integer."""
+    return _SdpaFn.apply(q, k, v, mask, int(h), float(dropout_p), int(seed), key_lengths, causal, span)
 
 
-def attn_probs(q, k, mask, h, dropout_p=0.0, seed=0, key_lengths=None, causal=False):
+def attn_probs(q, k, mask, h, dropout_p=0.0, seed=0, key_lengths=None, causal=False, span=None):
     """The probabilities ``sdpa(q, k, v, mask, h, dropout_p, seed)`` uses, materialised: (B,h,T,T) fp32, [b][head][query][key]
     (transformer/MFT/multiTransformer.py:22-34, the reference's ``self.attn`` of :59).  Same operand rounding as the attention core; in
     train mode the same keep decisions for the same seed, dropped = 0 and kept = P/(1-p).  A blanked query row is exactly 1/T.
     key_lengths: as for ``sdpa``; columns >= key_lengths[b] are exact zeros and a blanked query row is 1/key_lengths[b] on the others.
     causal: as for ``sdpa``; entries above the diagonal are exact zeros and a blanked query row t is 1/(t+1) on columns 0 .. t.
+    span: as for ``sdpa``; entries outside columns max(0, t - span + 1) .. t of row t are exact zeros and a blanked query row t is
+    1/min(t + 1, span) on those columns.
     No autograd graph: the reference never differentiates the map."""
+    span = _check_span("attn_probs", key_lengths, causal, span)
     causal = _check_causal("attn_probs", key_lengths, causal)
     _lib.require_hip(q, k, mask)
     _lib.load()
@@ -367,7 +400,8 @@ def attn_probs(q, k, mask, h, dropout_p=0.0, seed=0, key_lengths=None, causal=Fa
     if h <= 0 or d % h or d // h > 64 or T > 4096:         # refused by the library before anything as large as the map is allocated
         _lib.launch("mmt_attn_probs_forward", None, None, None, None, B, T, d, h, 0.0, 0)
     out = torch.empty((B, h, T, T), dtype=torch.float32, device=q_.device)
-    _lib.launch("mmt_attn_probs_forward", q_, k_, m_, out, B, T, d, h, float(dropout_p), int(seed), key_lengths=kl_, causal=causal)
+    _lib.launch("mmt_attn_probs_forward", q_, k_, m_, out, B, T, d, h, float(dropout_p), int(seed), key_lengths=kl_, causal=causal,
+                span=span)
     return out
 
 

@@ -17,6 +17,8 @@ Deviations, all documented in DESIGN.md:
   * ``causal_attention(model)`` / ``MultiHeadedAttention.causal = True`` (off by default, no counterpart in the reference): window t
     attends windows 0 .. t only, so the model can be run and trained as an online predictor.  Results then differ from the
     reference's by design.
+  * ``causal_attention(model, span=W)`` / ``MultiHeadedAttention.span = W`` (None by default, needs ``causal``): window t attends its
+    last W windows only, t - W + 1 .. t (banded / sliding-window causal attention; the ``*_band_kernel`` entries of csrc/attn.h).
   * train-mode dropout draws from a counter-based generator inside the kernels, not from torch's
     global generator: training-mode parity with the reference is statistical, eval-mode is numerical.
 """
@@ -122,11 +124,17 @@ class MultiHeadedAttention(nn.Module):
     ``causal`` (a class attribute, off; ``causal_attention`` sets it per instance): window t attends windows 0 .. t of its sequence only;
     later windows get probability exactly 0 and no gradient from that query (the reference, :27-31, lets every window attend the whole
     batch row).  ``keep_attn`` then shows the zeros above the diagonal.  Not combined with ``mask_keys`` (ValueError at the call): a valid
-    window t < len sees keys <= t < len only, so causal attention already keeps it from the padding behind its sequence."""
+    window t < len sees keys <= t < len only, so causal attention already keeps it from the padding behind its sequence.
+
+    ``span`` (a class attribute, None; ``causal_attention(model, span=W)`` sets it per instance): with ``causal``, window t attends
+    its last ``span`` windows only, t - span + 1 .. t, its own included — a fixed receptive field per layer.  ``keep_attn`` then
+    shows the zeros on both sides of the band.  ValueError at the call without ``causal``, with ``mask_keys``, for span < 1 and
+    for a bool or a non-integer."""
 
     keep_attn = False
     mask_keys = False
     causal = False
+    span = None
 
     def __init__(self, h, d_model, dropout=0.1):
         super().__init__()
@@ -145,8 +153,14 @@ class MultiHeadedAttention(nn.Module):
                              "behind its sequence (mask_padded_keys(model, False))")
         return self.mask_keys, self.causal
 
+    def attention_span(self):
+        """``span`` of this layer, None or an int >= 1, checked against (mask_keys, causal): ValueError, before any launch, otherwise."""
+        mask_keys, causal = self.attention_mode()
+        return F_hip._check_span("MultiHeadedAttention", None, causal, self.span, mask_keys=mask_keys)
+
     def forward(self, query, key, value, mask=None):
         mask_keys, causal = self.attention_mode()
+        span = self.attention_span()
         p = float(self.dropout.p) if self.training else 0.0
         B = query.size(0)
         q, k, v = (F_hip.linear(x, l.weight, l.bias) for l, x in zip(self.linears, (query, key, value)))
@@ -157,8 +171,9 @@ class MultiHeadedAttention(nn.Module):
             m = mask.reshape(B, -1, 1)
         seed = _lib.next_dropout_seed(q.device, 3) if p > 0.0 else 0
         kl = F_hip.key_lengths(m) if mask_keys and m is not None else None      # derived once, serves both kernels
-        ctx = F_hip.sdpa(q, k, v, m, self.h, dropout_p=p, seed=seed, key_lengths=kl, causal=causal)
-        self.attn = F_hip.attn_probs(q, k, m, self.h, dropout_p=p, seed=seed, key_lengths=kl, causal=causal) if self.keep_attn else None
+        ctx = F_hip.sdpa(q, k, v, m, self.h, dropout_p=p, seed=seed, key_lengths=kl, causal=causal, span=span)
+        self.attn = (F_hip.attn_probs(q, k, m, self.h, dropout_p=p, seed=seed, key_lengths=kl, causal=causal, span=span)
+                     if self.keep_attn else None)
         return F_hip.linear(ctx, self.linears[3].weight, self.linears[3].bias)
 
 
@@ -196,8 +211,8 @@ def mask_padded_keys(module, on=True):
     return found
 
 
-def causal_attention(module, on=True):
-    """Set ``causal`` on every MultiHeadedAttention below ``module`` (the SFT / MFT / B2 models, every modality's stack of
+def causal_attention(module, on=True, span=None):
+    """Set ``causal`` and ``span`` on every MultiHeadedAttention below ``module`` (the SFT / MFT / B2 models, every modality's stack of
     MultiTransformer, the MultiCNNTransformer wrappers) -> {qualified name: module}.  From the next forward on window t attends
     windows 0 .. t of its sequence only, in every layer, forward and backward: every other part of these models already runs forward in
     time (window encoder, LayerNorm, FFN and residuals are per window), so the model's output at window t no longer depends on later
@@ -206,11 +221,17 @@ def causal_attention(module, on=True):
     An Encoder keeps running as the fused stack; only layers that disagree about the flag make it run layer by layer.  Outputs then
     differ from the reference's, whose windows attend the whole recording — by design.  Not combined with ``mask_padded_keys`` (the
     next forward raises ValueError; causal attention already keeps a valid window from its batch's padding).
-    ``causal_attention(module, False)`` restores the reference's semantics and the plain kernels."""
+    ``span`` (an int >= 1; None: no lower edge): window t attends its last ``span`` windows only, t - span + 1 .. t, so every layer has
+    a fixed receptive field and the model conditions on a context of bounded length, in training and in evaluation; the band kernels
+    also sweep about span/32 + 1 key tiles per query tile instead of all tiles up to the diagonal.  ValueError here for span < 1, a
+    bool or a non-integer, and for a span with ``on=False``.  Streams do not serve a span yet (they refuse it at open).
+    ``causal_attention(module, False)`` restores the reference's semantics and the plain kernels, and clears ``span``."""
+    span = F_hip._check_span("causal_attention", None, bool(on), span)
     found = {}
     for name, m in module.named_modules():
         if isinstance(m, MultiHeadedAttention):
             m.causal = bool(on)
+            m.span = span
             found[name] = m
     return found
 
@@ -309,6 +330,8 @@ class Encoder(nn.Module):
             return False
         if any(l.self_attn.causal != l0.self_attn.causal for l in self.layers):            # and one attention mode
             return False
+        if any(l.self_attn.span != l0.self_attn.span for l in self.layers):                # with one span
+            return False
         h, f = l0.self_attn.h, l0.feed_forward.w_1.weight.shape[0]
         p = l0.sublayer[0].dropout.p
         for l in self.layers:
@@ -332,6 +355,7 @@ class Encoder(nn.Module):
             return self.norm(x)
         l0 = self.layers[0]
         mask_keys, causal = l0.self_attn.attention_mode()      # the layers agree (_fusable); both set: ValueError before any launch
+        span = l0.self_attn.attention_span()
         for l in self.layers:                    # the fused stack forms no map: one kept by an earlier layer-by-layer call is stale
             if l.self_attn.attn is not None:
                 l.self_attn.attn = None
@@ -343,7 +367,7 @@ class Encoder(nn.Module):
         return F_hip.encoder_stack_params(x, mask, ps, l0.self_attn.h, l0.feed_forward.w_1.weight.shape[0],
                                           len(self.layers), eps=self.norm.eps, dropout_p=p, seed=seed,
                                           flat=self._flat_storage(ps) if x.is_cuda else None, nsplit=k, key_lengths=kl,
-                                          causal=causal)
+                                          causal=causal, span=span)
 
     def _stream_refusals(self):
         """What ``stream`` and ``slot_stream`` refuse, before anything is allocated or launched."""
@@ -361,6 +385,10 @@ class Encoder(nn.Module):
         if not l0.causal:
             raise ValueError("%s.stream: the layers do not attend causally, so window t depends on later windows and cannot be "
                              "predicted online: call causal_attention(model) (and train the model that way)" % name)
+        if l0.span is not None:
+            raise ValueError("%s.stream: the layers attend a band of span = %r windows, but the step kernel attends every cached key and "
+                             "would be wrong from window t = span on; the ring cache that streams a span is the follow-up to the band "
+                             "kernels (DESIGN.md 10) — until then stream the model without a span" % (name, l0.span))
         if self.norm.a_2.device.type != "cuda":
             raise ValueError("%s.stream: the encoder is on %s; move it to a HIP device (there is no CPU path)" % (name, self.norm.a_2.device))
 
