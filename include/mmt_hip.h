@@ -709,6 +709,12 @@ int mmt_ccc_forward(const float* pred, const float* target, const int32_t* lengt
 int mmt_debug_dropout_mask(float p, uint64_t seed, uint32_t stream_id, uint64_t n, uint32_t attn_Tp, uint8_t* keep,
                            float* host_scale_out, mmt_stream_t stream);
 
+/* ---- Test hook: the attention-dropout generator's stored words of one layer (nbh * nt * nt blocks of 32x32 decisions, 64 uint16 per
+ * block and array), as the kernels read them: lq in the 16-bit lane-word form (lanes = 0) or the 64-bit lane-mask form (lanes = 1), lk
+ * always in the lane-word form.  The decisions are those of mmt_debug_dropout_mask(p, seed, stream_id, ..., attn_Tp = 32 nt). */
+int mmt_debug_attn_mask_words(float p, uint64_t seed, uint32_t stream_id, int nbh, int nt, int lanes,
+                              uint16_t* lq, uint16_t* lk, mmt_stream_t stream);
+
 /* ---- Test hook: fill every LDS word of every CU, and the vector registers of every SIMD, with `pattern` (e.g. 0x7FC00000, a NaN).
  * Kernels must not depend on LDS or registers they did not write; tests run a workload, poison, run it again and require identical results.  `sink4`: any 4 writable device bytes. */
 int mmt_debug_poison_lds(uint32_t pattern, void* sink4, mmt_stream_t stream);

@@ -132,6 +132,7 @@ SIGNATURES = {
     "mmt_ccc_forward": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "mmt_debug_dropout_mask": (_I, [_F, _U64, _c.c_uint32, _U64, _c.c_uint32, _P, _P, _P]),
     "mmt_debug_poison_lds": (_I, [_c.c_uint32, _P, _P]),
+    "mmt_debug_attn_mask_words": (_I, [_F, _U64, _c.c_uint32, _I, _I, _I, _P, _P, _P]),
 }
 
 

@@ -173,7 +173,9 @@ __device__ __forceinline__ AttnBlock attn_block_causal(int nx, int nbh) {
 
 // (`//@ name` comment lines mark the phase boundaries at which tools/make_diag.py inserts cycle stamps into the GENERATED stamped twin of this
 // kernel — diagnostic builds only; this file holds no diagnostic code)
-template <int DKP, bool DROP, int MODE>
+// LANES: the keep bits come as 64-bit lane masks, one per accumulator register, in scalar registers (attn_mask.h, the lane-mask form
+// of LQ) — the plain d_k = 16 train kernel only; the host gives the generator the same choice.
+template <int DKP, bool DROP, int MODE, bool LANES = false>
 __device__ __forceinline__ void attn_fwd_body(
         const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
         bf16* __restrict__ ctx, float* __restrict__ lse,
@@ -183,6 +185,7 @@ __device__ __forceinline__ void attn_fwd_body(
     constexpr int KS = DKP / 16;
     constexpr int DKB = DKP < 32 ? DKP : 32;           // feature rows of this launch's output block
     constexpr bool ONES = (DKP == 16) && !DROP;        // row sums through the MFMA
+    static_assert(!LANES || (DROP && DKP == 16 && MODE == ATTN_PLAIN), "lane masks: the plain d_k = 16 train kernel only");
     //@ entry
     // 16-byte pieces per tile: K (R layout, all DKP features) and the 32-feature block `fb` of V — ALSO in the R layout, as the QKV
     // epilogue wrote it: the PV product contracts over keys, its A fragment (8 keys of one feature per lane) comes out of LDS
@@ -212,8 +215,10 @@ __device__ __forceinline__ void attn_fwd_body(
     const bf16* Kb = Kr + (size_t)bh * fragR_elems(Tp, DKP);
     const bf16* Vb = Vr + (size_t)bh * fragR_elems(Tp, DKP) + (size_t)fb * 4 * 256;      // feature group 4 fb of tile 0
     // dropout: this lane's 16-bit words of the wave's row of mask blocks (attn_mask.h, LQ layout), one per key tile, fetched a tile ahead
+    // (LANES: no per-lane words; the wave's row of blocks starts at block mblk0, a scalar)
     const uint16_t* mrow = maskQ + ((size_t)bh * nt + qtc) * nt * 64 + lane;
-    uint32_t mw = DROP ? mrow[BAND ? (size_t)qtc * 64 : 0] : 0u;      // band: the wave's first working tile is its diagonal one
+    uint32_t mw = (DROP && !LANES) ? mrow[BAND ? (size_t)qtc * 64 : 0] : 0u;      // band: the wave's first working tile is its diagonal one
+    const uint32_t mblk0 = LANES ? __builtin_amdgcn_readfirstlane((uint32_t)((bh * nt + qtc) * nt)) : 0u;
 
     TileStager<2, (PK + PV + MMT_THREADS - 1) / MMT_THREADS> stg;
     {
@@ -263,7 +268,7 @@ __device__ __forceinline__ void attn_fwd_body(
         progress_prio(BAND ? qt - kt : kt, BAND ? qt - klo + 1 : nk);
         const uint32_t tw = mw;                          // this tile's keep bits
         if (BAND) { if (DROP && kt > klo) mw = mrow[(size_t)(kt - 1) * 64]; }
-        else if (DROP && !TAIL && !DIAG) mw = mrow[(size_t)(kt + 1) * 64];
+        else if (DROP && !LANES && !TAIL && !DIAG) mw = mrow[(size_t)(kt + 1) * 64];
         if (more) stg.load(knext);                      // next tile in flight behind this tile's arithmetic
         const bf16* sk = stage[kt & 1];
         const bf16* sv = vpad ? zeros : sk + PK * 8 + voff;
@@ -271,11 +276,23 @@ __device__ __forceinline__ void attn_fwd_body(
         // only when the reference moves (round 3 splatted -m into the accumulator before every tile: 8 v_mov_b64 of ~100 vector
         // instructions per tile)
         f32x16 s;
+        LaneMasks lm;
         if constexpr (KS == 1) {
             // written as asm because hipcc only knows the tied form (vdst = srcC) of an MFMA on VGPRs and would copy mneg into s first;
             // the trailing s_nop are the wait states between an 8-pass MFMA and a vector instruction that reads its result, which the
             // hazard recognizer cannot add for an asm statement
             const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sk + (hh * 32 + r) * 8);
+            if constexpr (LANES) {
+                // This tile's sixteen lane masks, 128 bytes at a wave-uniform address: two scalar loads, issued HERE — behind the wait
+                // for the tile's only LDS read in front of the mask phase and ahead of the score product — because scalar loads count on
+                // the LDS wait counter and return out of order: any LDS wait with one in flight waits for it too.  From here to the mask
+                // phase (product, maximum, exp, row sum) the wave waits for no LDS result.  The place is pinned from both sides: the
+                // address passes through an empty asm that needs kf, and nothing is scheduled across the barrier behind the loads.
+                uint32_t blk = mblk0 + (uint32_t)kt;
+                asm volatile("" : "+s"(blk) : "v"(kf));
+                lm = load_lane_masks(maskQ + (size_t)blk * 64);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3\n\ts_nop 11" : "=&v"(s) : "v"(kf), "v"(qf[0]), "v"(mneg));
         } else {
             s = mfma32(*reinterpret_cast<const bf16x8*>(sk + (hh * 32 + r) * 8), qf[0], mneg);
@@ -324,7 +341,10 @@ __device__ __forceinline__ void attn_fwd_body(
         }
         //@ exp_sum
         if (DROP) {                                     // zero the dropped probabilities; 1/(1-p) is applied once, to the output row
-            static_for<0, 16>([&](auto ic) { constexpr int i = decltype(ic)::value; s[i] = keep_and<i>(s[i], tw); });
+            if constexpr (LANES) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) { s[i] = keep_lanes(s[i], lm.lo[i]); s[8 + i] = keep_lanes(s[8 + i], lm.hi[i]); }
+            } else static_for<0, 16>([&](auto ic) { constexpr int i = decltype(ic)::value; s[i] = keep_and<i>(s[i], tw); });
         }
         //@ mask
 #pragma unroll
@@ -394,6 +414,14 @@ __global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_kernel(
         bf16* __restrict__ ctx, float* __restrict__ lse,
         int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
     attn_fwd_body<DKP, DROP, ATTN_PLAIN>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, nullptr, 0);
+}
+// ... at d_k = 16 in train mode with maskQ in the lane-mask form (DROP: always true — a template so that tools/make_diag.py can twin it)
+template <bool DROP>
+__global__ __launch_bounds__(MMT_THREADS, 2) void attn_fwd_lanes16_kernel(
+        const bf16* __restrict__ Qr, const bf16* __restrict__ Kr, const bf16* __restrict__ Vr,
+        bf16* __restrict__ ctx, float* __restrict__ lse,
+        int h, int T, int nt, int nbh, int ldc, const uint16_t* __restrict__ maskQ, float drop_scale, int fb) {
+    attn_fwd_body<16, DROP, ATTN_PLAIN, true>(Qr, Kr, Vr, ctx, lse, h, T, nt, nbh, ldc, maskQ, drop_scale, fb, nullptr, 0);
 }
 // ... with key lengths: sequence b attends keys < key_lengths[b]
 template <int DKP, bool DROP>

@@ -8,7 +8,9 @@
 // zero word with v_bfe_i32, which it ANDs onto accumulator register i: two full-rate instructions per register, no compare, no
 // hash, no scalar registers.  (A first version kept the masks as 64-bit lane masks in SGPRs, loaded with s_load_dwordx16 and
 // applied with one v_cndmask_b32 per register: fewer vector instructions, but scalar loads share the LDS wait counter, so every
-// tile's first LDS wait exposed the whole scalar-load latency: +5 us per forward launch over eval mode instead of +1.)
+// tile's first LDS wait exposed the whole scalar-load latency: +5 us per forward launch over eval mode instead of +1.  The plain
+// d_k = 16 forward has that form again — see "Lane-mask form" below — with the loads placed where no LDS wait follows them until the
+// masks are needed.)
 //
 // Bernoulli words.  A 32-bit word whose bits are independent drops with probability thr16 / 65536 is built from up to 16
 // uniform random words, least significant threshold bit first:  D = bit_b ? (D | R_b) : (D & R_b)   (each step halves the
@@ -23,6 +25,14 @@
 //   LK [bh][k tile][q tile][64 lanes]: for kernels that keep the KEY on the lane (dK/dV, the one-kernel backward): lane 32 hh + key,
 //      bit j = (query (j&3) + 8(j>>2) + 4hh, key).
 // LQ needs the block transposed (bits over keys): a 32x32 bit transpose in registers (5 butterfly stages), 64 blocks per wave.
+//
+// Lane-mask form of LQ (MaskGenLayer::lanes, chosen by the host per layer with the kernel that reads it; same array, same 128 bytes
+// per block, same block order, so a launch writes one form or the other):
+//   sixteen 64-bit words per block, word i = the wave's lane mask of accumulator register i: bit r + 32 hh = the decision for
+//   (query r, key (i&3) + 8(i>>2) + 4hh).  That is the key-major bit matrix W with its rows in register order — dword 2i + hh =
+//   W[acc32_row(i, hh)] — so this form needs no transpose and no lane_word.  Its reader (attn.h, the plain d_k = 16 forward) fetches the
+//   128 bytes with wave-uniform scalar loads and applies word i to register i with ONE v_cndmask_b32 (4.2 cycles of SIMD issue where
+//   v_bfe_i32 + v_and_b32 take 6.5: profiles/r10_valu_micro.txt).  LK keeps its form: every backward kernel reads the 16-bit words.
 #pragma once
 #include "common.h"
 
@@ -93,6 +103,7 @@ struct MaskGenParams {
     uint16_t* lq; uint16_t* lk;            // layer l at + l * layer_words
     size_t layer_words;
     int nbh, nt, nlayers;
+    int lanes;                             // LQ in the lane-mask form (every layer of a launch has the same consumers)
     uint32_t thr16;
     uint32_t s0[16], s1[16];               // stream keys of the layers' attention dropout (make_drop(p, seed, 4l+0))
     const uint64_t* seedword;              // non-null: device-resident seed (common.h drop_resolve); s0[l] then holds the stream id 4l+0
@@ -101,13 +112,14 @@ struct MaskGenParams {
 struct MaskGenLayer {
     uint16_t* lq; uint16_t* lk;
     int nbh, nt;
+    int lanes;                             // LQ in the lane-mask form
     uint32_t thr16, s0, s1;
     const uint64_t* seedword;
 };
 __device__ __forceinline__ MaskGenLayer mask_gen_layer(const MaskGenParams& P, int layer) {
     MaskGenLayer G;
     G.lq = P.lq + (size_t)layer * P.layer_words; G.lk = P.lk + (size_t)layer * P.layer_words;
-    G.nbh = P.nbh; G.nt = P.nt; G.thr16 = P.thr16; G.s0 = P.s0[layer]; G.s1 = P.s1[layer]; G.seedword = P.seedword;
+    G.nbh = P.nbh; G.nt = P.nt; G.lanes = P.lanes; G.thr16 = P.thr16; G.s0 = P.s0[layer]; G.s1 = P.s1[layer]; G.seedword = P.seedword;
     return G;
 }
 
@@ -122,6 +134,20 @@ __device__ __forceinline__ void park_lane_block(uint16_t* row, const uint32_t (&
         for (int e = 0; e < 4; ++e) {
             const int l0 = 8 * (c & 3) + 2 * e, hh = c >> 2;
             v[e] = lane_word(rows[l0], hh) | (lane_word(rows[l0 + 1], hh) << 16);
+        }
+        *reinterpret_cast<u32x4_t*>(row + 8 * c) = v;
+    }
+}
+
+// the lane-mask form of one block into this lane's patch row: piece c = words 2c and 2c+1, i.e. W[acc32_row(i, hh)] for i = 2c, 2c+1
+__device__ __forceinline__ void park_lane_masks(uint16_t* row, const uint32_t (&W)[32]) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        u32x4_t v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = 2 * c + (e >> 1), hh = e & 1;
+            v[e] = W[(i & 3) + 8 * (i >> 2) + 4 * hh];
         }
         *reinterpret_cast<u32x4_t*>(row + 8 * c) = v;
     }
@@ -175,9 +201,13 @@ __device__ __forceinline__ void attn_mask_gen_block(const MaskGenLayer& P, uint1
             while (kb >= P.nt) { kb -= P.nt; if (++qb == P.nt) { qb = 0; ++bb; } }
         }
     }
-    transpose32(W);                                                        // W[query] bit key
     // ---- LQ: block index == g: the wave's 64 blocks are contiguous in memory
-    park_lane_block(mine, W);              // (same wave wrote and read the patch: program order is enough, no barrier)
+    // (same wave wrote and read the patch: program order is enough, no barrier)
+    if (P.lanes) park_lane_masks(mine, W);                                 // wave-uniform: a kernel argument
+    else {
+        transpose32(W);                                                    // W[query] bit key
+        park_lane_block(mine, W);
+    }
     from = flush_from();
     {
         uint16_t* const lq = P.lq + g0 * 64;
@@ -213,6 +243,26 @@ template <int I> __device__ __forceinline__ uint32_t keep_bits(uint32_t w) {
 }
 template <int I> __device__ __forceinline__ float keep_and(float v, uint32_t w) {
     return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, v) & keep_bits<I>(w));
+}
+// the lane-mask form: +0 in the lanes whose bit of the 64-bit mask `m` (wave-uniform: a scalar register pair) is clear — the value
+// v & 0 has — by ONE v_cndmask_b32 with the pair as its condition: the inverse ballot makes the scalar the per-lane predicate itself.
+// Not asm: its operand comes straight out of v_exp_f32, and hipcc's hazard recognizer puts the wait state a transcendental's reader
+// needs on gfx950 only in front of instructions it can see (an asm v_cndmask here read registers the exponential had not written
+// yet: NaN gradients at T = 257).
+__device__ __forceinline__ float keep_lanes(float v, uint64_t m) {
+    return __builtin_amdgcn_inverse_ballot_w64(m) ? v : 0.f;
+}
+// one block of the lane-mask form: sixteen 64-bit words, fetched through the constant address space so that a wave-uniform address
+// gives scalar loads (the arrays are written by an earlier launch and never by the reading kernel).  volatile: the loads stay where
+// the caller wrote them — hipcc otherwise sinks them next to their first use, behind LDS reads whose wait then exposes their latency
+typedef uint64_t u64x8_t __attribute__((ext_vector_type(8)));
+struct LaneMasks { u64x8_t lo, hi; };                   // words 0..7, 8..15
+__device__ __forceinline__ LaneMasks load_lane_masks(const uint16_t* block) {
+    typedef const volatile u64x8_t __attribute__((address_space(4))) * cptr;
+    const cptr p = (cptr)(uintptr_t)block;
+    LaneMasks m;
+    m.lo = p[0]; m.hi = p[1];
+    return m;
 }
 
 // ---- test hook: expand the generator's decisions to one byte per (bh, query, key) ------------------------------------

@@ -2039,6 +2039,15 @@ def poison_lds(device, pattern=0x7FC00000):
     _lib.launch("mmt_debug_poison_lds", int(pattern), sink)
 
 
+def _attn_mask_words(p, seed, stream_id, nbh, nt, device, lanes=False):
+    """Test hook: the attention-dropout generator's stored words (lq, lk), each a (nbh * nt * nt, 64) int16 tensor of raw uint16 words:
+    lq in the lane-word form, or with `lanes` in the lane-mask form the plain d_k = 16 forward reads; lk in the lane-word form."""
+    lq = torch.empty(nbh * nt * nt, 64, dtype=torch.int16, device=device)
+    lk = torch.empty_like(lq)
+    _lib.launch("mmt_debug_attn_mask_words", float(p), int(seed), int(stream_id), int(nbh), int(nt), int(bool(lanes)), lq, lk)
+    return lq, lk
+
+
 def dropout_mask(p, seed, stream_id, n, device, attn_Tp=0):
     """Test hook: (keep mask as a bool tensor of n entries, scale of kept values) of one dropout stream."""
     keep = torch.empty(n, dtype=torch.uint8, device=device)

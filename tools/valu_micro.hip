@@ -16,7 +16,11 @@
 //   * converts every row to FLOP/s where that means something and refuses to print a row above the 157.3 TFLOP/s vector peak
 //     without flagging it.
 //
-//   hipcc --offload-arch=gfx950 -O2 -o tools/bin/valu_micro tools/valu_micro.hip && tools/bin/valu_micro > profiles/r05_valu_micro.txt
+// Round 10 added the rows that price a dropout decision taken from a 64-bit lane mask in a scalar register pair: a scalar write of EXEC
+// + v_mov_b32 v, 0 under it (EXEC restored once per sixteen), v_cndmask_b32 with sixteen distinct pairs, and the attention forward's
+// per-register instruction list in its three forms (v_bfe_i32 + v_and_b32, EXEC + v_mov_b32, v_cndmask_b32).
+//
+//   hipcc --offload-arch=gfx950 -O2 -o tools/bin/valu_micro tools/valu_micro.hip && tools/bin/valu_micro > profiles/r10_valu_micro.txt
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -28,7 +32,8 @@
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 
 enum Op { EMPTY, ADD, FMA, PK_FMA, PK_MUL, EXP, CVT_PK_BF16, BFE_I32, AND, MOV, CNDMASK_SGPR, BFI, MAX3, PERM32SWAP, PERM16SWAP, DPP_MOV,
-          MFMA32, MFMA16, MFMA32_FILL6, MFMA16_FILL2, MFMA32_FILL12, EXP_FMA_MIX, BWD_MIX, NOPS };
+          MFMA32, MFMA16, MFMA32_FILL6, MFMA16_FILL2, MFMA32_FILL12, EXP_FMA_MIX, BWD_MIX,
+          EXEC_MOV, EXEC_NOT_MOV, CNDMASK_SGPR16, FWD_MIX_BFE, FWD_MIX_EXEC, FWD_MIX_CNDMASK, NOPS };
 struct OpInfo { const char* name; int per_iter; double flop_per_lane; };       // flop_per_lane: FLOP per lane and instruction (0: none)
 static const OpInfo ops[NOPS] = {
     {"(empty loop)", 1, 0}, {"v_add_f32", 128, 1}, {"v_fma_f32", 128, 2}, {"v_pk_fma_f32", 128, 4}, {"v_pk_mul_f32", 128, 2},
@@ -38,7 +43,13 @@ static const OpInfo ops[NOPS] = {
     {"mfma 32x32x16 bf16 (one chain)", 8, 0}, {"mfma 16x16x32 bf16 (one chain)", 8, 0},
     {"mfma32 + 6 v_fma per gap (per MFMA)", 8, 0}, {"mfma16 + 2 v_fma per gap (per MFMA)", 8, 0}, {"mfma32 + 12 v_fma per gap (per MFMA)", 8, 0},
     {"8 v_exp + 8 v_fma interleaved", 128, 0},
-    {"bwd score mix: exp + 2 cndmask + mul + 0.5 cvt_pk (x16 = 72)", 72 * 2, 0}};
+    {"bwd score mix: exp + 2 cndmask + mul + 0.5 cvt_pk (x16 = 72)", 72 * 2, 0},
+    // round 10: the dropout decision from a 64-bit lane mask in an SGPR pair.  One "instruction" of these rows is what ONE accumulator
+    // register costs: the scalar write of EXEC and the v_mov_b32 under it count together (the restore, once per 16, is in the figure too)
+    {"s_mov_b64 exec, s[pair] + v_mov_b32 v, 0 (per pair)", 128, 0}, {"s_not_b64 exec, s[pair] + v_mov_b32 v, 0 (per pair)", 128, 0},
+    {"v_cndmask_b32 (16 distinct sgpr pairs)", 128, 0},
+    {"fwd score mix, v_bfe+v_and form (per register)", 128, 0}, {"fwd score mix, exec+v_mov form (per register)", 128, 0},
+    {"fwd score mix, v_cndmask form (per register)", 128, 0}};
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4_ __attribute__((ext_vector_type(4)));
@@ -54,6 +65,10 @@ __global__ __launch_bounds__(1024) void probe(Rec* out, int iters) {
     float k = 1.0001f, z = 0.5f;
     unsigned long long mask = 0xF0F0F0F0A5A5A5A5ull ^ (unsigned long long)blockIdx.x;
     mask = __builtin_amdgcn_readfirstlane((unsigned)mask) | ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(mask >> 32)) << 32);
+    // three more lane masks, each in its own SGPR pair (all wave-uniform: derived from the scalar `mask`)
+    unsigned long long mask1 = ~mask, mask2 = (mask << 7) | (mask >> 57), mask3 = ~mask2;
+    asm volatile("" : "+s"(mask1), "+s"(mask2), "+s"(mask3));
+    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
@@ -147,10 +162,88 @@ __global__ __launch_bounds__(1024) void probe(Rec* out, int iters) {
                     asm volatile("v_cndmask_b32 %0, %1, %0, %2\n\tv_mul_f32 %0, %0, %1" : "+v"(r[i + 1]) : "v"(z), "s"(mask));
                     asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(k) : "v"(r[i]), "v"(r[i + 1]));
                 }
+        } else if (OP == EXEC_MOV || OP == EXEC_NOT_MOV) {
+            // sixteen registers zeroed under sixteen lane masks, EXEC back to all ones inside the statement (the waves are full)
+#define XM(n, a) XOP " exec, %" #a "\n\tv_mov_b32 %" #n ", 0\n\t"
+#define X16 XM(0, 16) XM(1, 17) XM(2, 18) XM(3, 19) XM(4, 16) XM(5, 17) XM(6, 18) XM(7, 19) XM(8, 16) XM(9, 17) XM(10, 18) XM(11, 19)      \
+            XM(12, 16) XM(13, 17) XM(14, 18) XM(15, 19) "s_mov_b64 exec, -1"
+#define R16OPS "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]), "+v"(r[9]),       \
+            "+v"(r[10]), "+v"(r[11]), "+v"(r[12]), "+v"(r[13]), "+v"(r[14]), "+v"(r[15])
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                if (OP == EXEC_MOV) {
+#define XOP "s_mov_b64"
+                    asm volatile(X16 : R16OPS : "s"(mask), "s"(mask1), "s"(mask2), "s"(mask3));
+#undef XOP
+                } else {
+#define XOP "s_not_b64"
+                    asm volatile(X16 : R16OPS : "s"(mask), "s"(mask1), "s"(mask2), "s"(mask3) : "scc");
+#undef XOP
+                }
+            }
+#undef X16
+#undef XM
+        } else if (OP == CNDMASK_SGPR16) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int i = 0; i < 16; i += 4) {
+                    asm volatile("v_cndmask_b32 %0, 0, %0, %1" : "+v"(r[i]) : "s"(mask));
+                    asm volatile("v_cndmask_b32 %0, 0, %0, %1" : "+v"(r[i + 1]) : "s"(mask1));
+                    asm volatile("v_cndmask_b32 %0, 0, %0, %1" : "+v"(r[i + 2]) : "s"(mask2));
+                    asm volatile("v_cndmask_b32 %0, 0, %0, %1" : "+v"(r[i + 3]) : "s"(mask3));
+                }
+        } else if (OP == FWD_MIX_BFE) {
+            // what one accumulator register of the attention forward asks of the vector pipe: P = exp2(s); rowsum += P; P &= keep;
+            // per register PAIR one v_max3 (the running maximum of the next tile) and one pack.  Today's form: v_bfe_i32 + v_and.
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int i = 0; i < 16; i += 2) {
+                    asm volatile("v_exp_f32 %0, %0\n\tv_exp_f32 %1, %1" : "+v"(r[i]), "+v"(r[i + 1]));
+                    asm volatile("v_add_f32 %0, %0, %1\n\tv_add_f32 %0, %0, %2" : "+v"(z) : "v"(r[i]), "v"(r[i + 1]));
+                    asm volatile("v_bfe_i32 %0, %2, 3, 1\n\tv_and_b32 %1, %1, %0" : "=&v"(x0), "+v"(r[i]) : "v"(k));
+                    asm volatile("v_bfe_i32 %0, %2, 4, 1\n\tv_and_b32 %1, %1, %0" : "=&v"(x0), "+v"(r[i + 1]) : "v"(k));
+                    asm volatile("v_max3_f32 %0, %0, %1, %2" : "+v"(x1) : "v"(r[i]), "v"(r[i + 1]));
+                    asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(x2) : "v"(r[i]), "v"(r[i + 1]));
+                }
+        } else if (OP == FWD_MIX_EXEC) {
+            // the same with the keep bits as lane masks: all sixteen zeroings of a tile in one statement, as the kernel would hold them
+#define XM(n, a) "s_not_b64 exec, %" #a "\n\tv_mov_b32 %" #n ", 0\n\t"
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+#pragma unroll
+                for (int i = 0; i < 16; i += 2) {
+                    asm volatile("v_exp_f32 %0, %0\n\tv_exp_f32 %1, %1" : "+v"(r[i]), "+v"(r[i + 1]));
+                    asm volatile("v_add_f32 %0, %0, %1\n\tv_add_f32 %0, %0, %2" : "+v"(z) : "v"(r[i]), "v"(r[i + 1]));
+                }
+                asm volatile(XM(0, 16) XM(1, 17) XM(2, 18) XM(3, 19) XM(4, 16) XM(5, 17) XM(6, 18) XM(7, 19) XM(8, 16) XM(9, 17) XM(10, 18)
+                             XM(11, 19) XM(12, 16) XM(13, 17) XM(14, 18) XM(15, 19) "s_mov_b64 exec, -1"
+                             : R16OPS : "s"(mask), "s"(mask1), "s"(mask2), "s"(mask3) : "scc");
+#pragma unroll
+                for (int i = 0; i < 16; i += 2) {
+                    asm volatile("v_max3_f32 %0, %0, %1, %2" : "+v"(x1) : "v"(r[i]), "v"(r[i + 1]));
+                    asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(x2) : "v"(r[i]), "v"(r[i + 1]));
+                }
+            }
+#undef XM
+#undef R16OPS
+        } else if (OP == FWD_MIX_CNDMASK) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int i = 0; i < 16; i += 2) {
+                    asm volatile("v_exp_f32 %0, %0\n\tv_exp_f32 %1, %1" : "+v"(r[i]), "+v"(r[i + 1]));
+                    asm volatile("v_add_f32 %0, %0, %1\n\tv_add_f32 %0, %0, %2" : "+v"(z) : "v"(r[i]), "v"(r[i + 1]));
+                    asm volatile("v_cndmask_b32 %0, 0, %0, %1" : "+v"(r[i]) : "s"((i & 2) ? mask2 : mask));
+                    asm volatile("v_cndmask_b32 %0, 0, %0, %1" : "+v"(r[i + 1]) : "s"((i & 2) ? mask3 : mask1));
+                    asm volatile("v_max3_f32 %0, %0, %1, %2" : "+v"(x1) : "v"(r[i]), "v"(r[i + 1]));
+                    asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(x2) : "v"(r[i]), "v"(r[i + 1]));
+                }
         }
     }
     asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1), "=s"(q1) :: "memory");
-    float s = a4[0] + a4[1] + a4[2] + a4[3] + k + z;
+    float s = a4[0] + a4[1] + a4[2] + a4[3] + k + z + x0 + x1 + x2;
 #pragma unroll
     for (int i = 0; i < 16; ++i) s += r[i] + acc[i];
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -291,5 +384,7 @@ int main() {
     run<PERM32SWAP>(dbuf, cus, empty); run<PERM16SWAP>(dbuf, cus, empty); run<DPP_MOV>(dbuf, cus, empty);
     run<MFMA32>(dbuf, cus, empty); run<MFMA16>(dbuf, cus, empty); run<MFMA32_FILL6>(dbuf, cus, empty); run<MFMA16_FILL2>(dbuf, cus, empty);
     run<MFMA32_FILL12>(dbuf, cus, empty); run<EXP_FMA_MIX>(dbuf, cus, empty); run<BWD_MIX>(dbuf, cus, empty);
+    run<EXEC_MOV>(dbuf, cus, empty); run<EXEC_NOT_MOV>(dbuf, cus, empty); run<CNDMASK_SGPR16>(dbuf, cus, empty);
+    run<FWD_MIX_BFE>(dbuf, cus, empty); run<FWD_MIX_EXEC>(dbuf, cus, empty); run<FWD_MIX_CNDMASK>(dbuf, cus, empty);
     return 0;
 }
