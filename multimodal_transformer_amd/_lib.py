@@ -269,26 +269,52 @@ class WorkspacePool:
     (tests/test_gpu_workspace_state.py compares a call on a fresh pool with the same call on the
     buffers another user has just handed back, bit for bit).  Lanes: the side streams on which the per-modality
     encoders of the MFT run concurrently are registered in SIDE_LANES and each owns its buffers; every
-    other stream (the caller's, a hipGraph capture stream) is lane 0 with the usual in-order semantics.
-    So concurrent streams are never handed a workspace another stream's kernels may still be using, and a
-    graph capture after warm-up finds its buffers in the pool instead of allocating (and re-zeroing) them.
+    other stream (the caller's, a user's own streams, a hipGraph capture stream) is lane 0.  So the forked pieces of one call are never
+    handed a workspace another piece's kernels may still be using, and a graph capture after warm-up finds its buffers in the pool
+    instead of allocating (and re-zeroing) them.
+
+    Streams that share a lane (two user streams, both lane 0): a buffer carries the stream that used it last and an event recorded on
+    that stream, behind the first zero fill at creation and behind the holder's last launch at ``put`` (which is called while that
+    launch is only queued).  ``get`` from another stream makes that stream wait for the event before it returns the buffer, so the new
+    holder's kernels start after the old holder's have finished, and reuse still needs no clearing.  On one stream nothing waits: the
+    stream's own order is the order.  Under hipGraph capture neither is done (an event of an eager stream cannot be waited for inside a
+    capture, and ``graphs.capture_step`` synchronises the device between warm-up and capture, so the order already holds); a buffer
+    keeps the stamp of its last eager use.  What stays with the caller: handing a HELD buffer's work from one stream to another
+    (a backward launched under another stream than its forward) is ordered like any other tensor, by the caller or by autograd.
     """
 
     def __init__(self):
         self._free = {}
         self._home = {}
+        self._last = {}         # data_ptr -> (raw handle of the stream that used the buffer last, event behind that use)
         self._mutex = threading.Lock()
+
+    def _stamp(self, buf, stream):
+        """Record, on ``stream``, the event a later holder on another stream waits for (the event object is reused per buffer)."""
+        if torch.cuda.is_current_stream_capturing():
+            return
+        with self._mutex:
+            last = self._last.get(buf.data_ptr())
+        ev = last[1] if last is not None else torch.cuda.Event()
+        ev.record(stream)
+        with self._mutex:
+            self._last[buf.data_ptr()] = (int(stream.cuda_stream), ev)
 
     def get(self, nbytes, device, tag=None):
         """``tag`` names the call site AND its shape: two shapes can need the same number of bytes with a different internal
         layout (measured: (B=4,T=50) and (B=2,T=100) encoder workspaces are both 6,158,080 bytes), and the zero pads of one
         would then be live data of the other.  Every caller passes one."""
-        key = (str(device), SIDE_LANES.get(int(torch.cuda.current_stream(device).cuda_stream), 0), int(nbytes), tag)
+        stream = torch.cuda.current_stream(device)
+        key = (str(device), SIDE_LANES.get(int(stream.cuda_stream), 0), int(nbytes), tag)
         with self._mutex:
             lst = self._free.get(key)
             buf = lst.pop() if lst else None
+            last = None if buf is None else self._last.get(buf.data_ptr())
         if buf is None:
             buf = torch.zeros(int(nbytes), dtype=torch.uint8, device=device)
+            self._stamp(buf, stream)            # behind the zero fill, which runs on this stream
+        elif last is not None and last[0] != int(stream.cuda_stream) and not torch.cuda.is_current_stream_capturing():
+            stream.wait_event(last[1])          # the previous holder's launches were only queued when it handed the buffer back
         with self._mutex:
             self._home[buf.data_ptr()] = key
         return buf
@@ -296,13 +322,16 @@ class WorkspacePool:
     def put(self, buf):
         with self._mutex:
             key = self._home.get(buf.data_ptr())
-            if key is not None:
+        if key is not None:
+            self._stamp(buf, torch.cuda.current_stream(buf.device))
+            with self._mutex:
                 self._free.setdefault(key, []).append(buf)
 
     def clear(self):
         with self._mutex:
             self._free.clear()
             self._home.clear()
+            self._last.clear()
 
 
 POOL = WorkspacePool()

@@ -192,8 +192,9 @@ def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, s
     train = dropout_p > 0.0                    # eval-mode workspaces carry no dropout bit masks
     if isinstance(seed, (list, tuple)) and len(seed) < nsplit:
         raise ValueError("encoder_stack: one seed per sub-batch stream")
-    y = torch.empty_like(x_)
     chunks = _row_chunks(B, nsplit)
+    seeds = [_chunk_seed(seed, i, len(chunks)) for i in range(len(chunks))]      # one DeviceSeed for several pieces: refused here, before
+    y = torch.empty_like(x_)                                                     # a workspace is taken or a stream forked
     main, streams = _SPLIT_STREAMS.begin(x_.device, len(chunks))
     parts = []
     for i, ((b0, b1), st) in enumerate(zip(chunks, streams)):
@@ -203,7 +204,7 @@ def _encoder_fwd(ctx, x, mask, flat_params, h, d_ff, n_layers, eps, dropout_p, s
             if nbytes == 0:
                 _lib.launch("mmt_encoder_forward", None, None, None, None, None, 0, *dims, eps, 0.0, 0)
             ws = _lib.POOL.get(nbytes, x_.device, tag=("encoder",) + dims + (train,))
-            sd = _chunk_seed(seed, i, len(chunks))
+            sd = seeds[i]
             _launch_seeded("mmt_encoder_forward", sd, x_[b0:b1], m_[b0:b1], p_, y[b0:b1], ws, nbytes, *dims, eps, dropout_p,
                            key_lengths=None if kl_ is None else kl_[b0:b1], causal=causal, span=span)
             parts.append((b0, b1, ws, sd))

@@ -1,14 +1,17 @@
 """What the GPU test files share: the old-style tolerances, the `dev` fixture, the measures of the bf16-faithful tier (tests/bf16_ref.py),
 the child-process runner for tests whose environment switches are read once per process, the harvest of device kernel names, and
-the workspace-state helpers (fills for memory of any contents, the recorder of the pool's traffic: tests/test_gpu_workspace_state.py).
+the workspace-state helpers (fills for memory of any contents, the recorder of the pool's traffic: tests/test_gpu_workspace_state.py),
+and the two stream helpers of tests/test_gpu_concurrency.py (a gate that holds a stream back, and the check that two streams overlap).
 
 A plain module, not a conftest: it defines no pytest hooks, and a test file imports what it uses by name, the fixtures included.  The
 test files keep their cases, their bounds and their comparisons.  Importing this module must not initialise the GPU: the children of
 run_child import it before they set anything up.
 """
 import json
+import math
 import os
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -336,3 +339,68 @@ def same_bits(tag, a, b, failures):
         elif not torch.equal(a[n], b[n]):
             d = (a[n].double() - b[n].double()).abs()
             failures.append("%s %s: %d of %d entries differ (max %.3e)" % (tag, n, int((d > 0).sum()), d.numel(), float(d.max())))
+
+
+# ------------------------------------------------------------------------------------------------ streams
+# What tests/test_gpu_concurrency.py makes ordering edges visible with.  A kernel that races with its producer usually loses the race
+# and reads the right data; behind a gate the producer is late for certain, so a missing edge shows as wrong bits every time.
+GATE_MS = 40.0
+_GATE = {}           # str(device) -> (a, b, milliseconds of one a @ b): calibrated once per process and device
+
+
+def _gate_operands(device):
+    key = str(device)
+    if key not in _GATE:
+        a = torch.full((4096, 4096), 1.0 / 4096, dtype=torch.float32, device=device)
+        b = torch.ones(4096, 4096, dtype=torch.float32, device=device)
+        out = torch.empty_like(a)
+        torch.mm(a, b, out=out)                                # warm-up: the library picks and loads its kernel
+        torch.cuda.synchronize(device)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        torch.mm(a, b, out=out)
+        e1.record()
+        e1.synchronize()
+        _GATE[key] = (a, b, max(float(e0.elapsed_time(e1)), 1e-3))
+    return _GATE[key]
+
+
+def gate(stream, ms=GATE_MS):
+    """Enqueue ordinary torch work (4096 x 4096 fp32 matmuls) that lasts at least `ms` on `stream` -> an event recorded behind it.
+    While `not ev.query()` nothing enqueued on `stream` after the gate has started.  A test asserts that once everything under test is
+    enqueued (assert_closed): a gate that has opened by then has shown nothing, and the test fails instead of passing."""
+    a, b, t = _gate_operands(stream.device)
+    with torch.cuda.stream(stream):
+        out = torch.empty_like(a)
+        for _ in range(int(math.ceil(ms / t))):
+            torch.mm(a, b, out=out)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+    return ev
+
+
+def assert_closed(*events):
+    for ev in events:
+        assert not ev.query(), "gate too short: it opened before everything under test was enqueued, so the run shows nothing"
+
+
+def runs_beside(a, b, ms=GATE_MS):
+    """True if work on stream `b` completes while stream `a` is still behind a gate: the two overlap.  Two streams that the runtime
+    maps onto one hardware queue serialise, and a race test on them would pass for the wrong reason: a test whose meaning depends on
+    the overlap asserts this premise first.  Polls for at most 1 s; drains the gate before it returns."""
+    ev_a = gate(a, ms)
+    with torch.cuda.stream(b):
+        torch.empty(64, dtype=torch.float32, device=b.device).fill_(1.0)
+        ev_b = torch.cuda.Event()
+        ev_b.record(b)
+    end = time.monotonic() + 1.0
+    beside = False
+    while time.monotonic() < end:
+        if ev_b.query():
+            beside = not ev_a.query()
+            break
+        if ev_a.query():
+            break
+    ev_a.synchronize()
+    ev_b.synchronize()
+    return beside
