@@ -323,6 +323,14 @@ int mmt_encoder_stream_prepare(const float* params, void* state, size_t state_by
 int mmt_encoder_stream_step(const float* x_t, const float* mask_t, const float* params, float* y_t,
                             void* state, size_t state_bytes, int t, int B, int capacity, int d, int h, int f, int n_layers,
                             float eps, mmt_stream_t stream);
+/* The step of a stack with a span (mmt_encoder_forward_band: window t attends t - span + 1 .. t), against a RING cache: the state is
+ * the one above with capacity := span (mmt_encoder_stream_bytes(B, span, ...), mmt_encoder_stream_prepare(..., B, span, ...)), position
+ * j lives in cache row j mod span, and a recording has no last window.  y_t is the row mmt_encoder_forward_band gives at [:, t];
+ * while t < span it is the row of mmt_encoder_stream_step, bit for bit.  span < 1, t < 0 or t == INT_MAX returns MMT_EINVAL with a
+ * message before anything else is looked at; span > 4096 is refused as a capacity > 4096 is. */
+int mmt_encoder_stream_step_ring(const float* x_t, const float* mask_t, const float* params, float* y_t,
+                                 void* state, size_t state_bytes, int t, int B, int span, int d, int h, int f, int n_layers,
+                                 float eps, mmt_stream_t stream);
 
 /* ---- The MFN gate, one window at a time (opt-in; eval mode, forward only).
  * Replaces one iteration t of MFN.forward's loop                               transformer/MFT/multiTransformer.py:200-247
@@ -367,6 +375,11 @@ int mmt_mfn_stream_step(const float* const* x_t, const float* mask_t, float* y_t
 int mmt_encoder_stream_step_slots(const float* x_t, const float* mask_t, const float* params, float* y_t,
                                   void* state, size_t state_bytes, int* pos, int advance,
                                   int B, int capacity, int d, int h, int f, int n_layers, float eps, mmt_stream_t stream);
+/* mmt_encoder_stream_step_ring at t = pos[b].  There is no limit: only idle slots and INT_MAX are skipped, and the position stored
+ * after the step, pos[b] + 1, reaches INT_MAX at most, the value that never runs. */
+int mmt_encoder_stream_step_ring_slots(const float* x_t, const float* mask_t, const float* params, float* y_t,
+                                       void* state, size_t state_bytes, int* pos, int advance,
+                                       int B, int span, int d, int h, int f, int n_layers, float eps, mmt_stream_t stream);
 /* The MFN gate step at t = pos[b]: copy pos[b] & 1 of the carried state is read and the other written, per sequence.  limit <= 0: no
  * limit (a gate has no cache); a gate behind encoders passes their capacity.   (MFN.forward, :200-247; :310) */
 int mmt_mfn_stream_step_slots(const float* const* x_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,

@@ -68,12 +68,14 @@ SIGNATURES = {
     "mmt_encoder_stream_bytes": (_SZ, [_I] * 6),
     "mmt_encoder_stream_prepare": (_I, [_P, _P, _SZ] + [_I] * 6 + [_P]),
     "mmt_encoder_stream_step": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 7 + [_F, _P]),
+    "mmt_encoder_stream_step_ring": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 7 + [_F, _P]),           # `span` where the twin has `capacity`
     # one window of the MFN gate per launch: (B, nmods, in_dims, hidden, output_dim), the two arrays host int32; pointer lists host arrays
     "mmt_mfn_stream_bytes": (_SZ, [_I, _I, _P, _P, _I]),
     "mmt_mfn_stream_prepare": (_I, [_P, _P, _P, _SZ, _I, _I, _P, _P, _I, _P]),
     "mmt_mfn_stream_step": (_I, [_P, _P, _P, _P, _SZ, _I, _I, _I, _P, _P, _I, _P]),
     # slots: the position of each sequence in device memory, int32 (B,), and `advance` (the gate: `limit` in front of it) for the host's t
     "mmt_encoder_stream_step_slots": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _I] + [_I] * 6 + [_F, _P]),
+    "mmt_encoder_stream_step_ring_slots": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _I] + [_I] * 6 + [_F, _P]),
     "mmt_mfn_stream_step_slots": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
     # one window of the LSTM decoder and the read-out per launch: (B, d, h_dim, n_layers); lstm_params a host array of device pointers
     "mmt_decoder_stream_bytes": (_SZ, [_I] * 4),

@@ -33,11 +33,21 @@
 // above hold: nothing written in a launch is read back in it, and workgroups do not communicate.  The last sentence of the cache
 // discipline changes for this form: every address derived from pos[b] passes slot_decode first, with the limit (capacity) taken from
 // the launch arguments, so such an address is that of a row j <= t < capacity exactly as above.
+//
+// The ring forms, encoder_step_ring_kernel and encoder_step_ring_slots_kernel: the same body again (a second compile-time switch), for a
+// stack with a span (attn.h's band kernels: window t attends t - span + 1 .. t).  The cache has `span` rows, position j lives in row
+// j mod span, and the sweeps cover the last n = min(t, span - 1) positions in AGE order, oldest first, dealt to lanes as positions are
+// above (step_ring.h states the rule and why the order matters).  The cache discipline is the one above with "row t mod span" for
+// "row t": that row held position t - span, which is outside the band, so it is written and never read in step t; every other row
+// is only read or not touched.  Every cache address comes from (b, layer, head, a row < span) with the row computed from t and span by
+// step_ring.h's three functions; no position below INT_MAX is refused, so the positioned form decodes with no limit and stores
+// p + 1 <= INT_MAX, the value that never runs.
 #pragma once
 #include "common.h"
 #include "encoder_step_plan.h"
 #include "step_common.h"          // step_bf16_round, step_block_sum, step_matvec
 #include "step_slots.h"           // slot_decode
+#include "step_ring.h"            // ring_keys, ring_first_row, ring_row
 
 struct EncStepParams {
     const float* x;            // (B, d)
@@ -96,8 +106,12 @@ __device__ __forceinline__ void step_ln_stats(const float* xs, int d, float eps,
 
 #define MMT_STEP_KEYS_INFLIGHT 4       // keys a lane has in flight in an attention sweep
 
-// SLOTS false: t = P.t (pos and advance unused).  SLOTS true: t = slot_decode(pos[b], capacity), P.t unused.
-template <bool SLOTS>
+// SLOTS false: t = P.t (pos and advance unused).  SLOTS true: t = slot_decode(pos[b], limit), P.t unused.
+// RING false: the cache has `capacity` rows, position j lives in row j, the limit is the capacity.  RING true (step_ring.h): P.capacity
+// is the span, the cache is a ring of that many rows, the sweeps cover the last n = min(t, span - 1) positions in age order and there is
+// no limit.  With RING false the three ring values below are the constants (n = t, r0 = 0, row = age), so those two instances compile
+// from the source they had.
+template <bool SLOTS, bool RING>
 __device__ __forceinline__ void encoder_step_body(const EncStepParams& P, int* pos, int advance) {
     __shared__ __attribute__((aligned(16))) float xs[MMT_STEP_MAX_D];            // the residual row, fp32
     __shared__ __attribute__((aligned(16))) float ns[MMT_STEP_MAX_D];            // bf16(LayerNorm) / the merged bf16 context, as floats
@@ -115,15 +129,21 @@ __device__ __forceinline__ void encoder_step_body(const EncStepParams& P, int* p
     __shared__ int* next;
     if (SLOTS && tid == 0) next = advance != 0 ? pos + b : nullptr;
     if (SLOTS) {
-        t = slot_decode(__builtin_amdgcn_readfirstlane(pos[b]), P.capacity);     // the one read of pos[b]; uniform, so t lives in an SGPR
+        t = slot_decode(__builtin_amdgcn_readfirstlane(pos[b]), RING ? 0 : P.capacity);      // the one read of pos[b]; uniform, so t lives in an SGPR
         if (t == MMT_SLOT_SKIP) {                                                // idle or full: a zero row and nothing else
             for (int n = tid; n < P.d; n += MMT_STEP_THREADS) P.y[(size_t)b * P.d + n] = 0.f;
             return;
         }
     } else {
         t = P.t;
-        if (t < 0 || t >= P.capacity) return;                                    // the host refuses such a call; never index the cache with it
+        if (t < 0 || (RING ? t == INT_MAX : t >= P.capacity)) return;            // the host refuses such a call; never index the cache with it
     }
+    // the cached keys of this step: n of them, age i in row `at(i)`; K_t and V_t go to row wrow.  RING: one modulo, on the uniform t
+    const int span = P.capacity;
+    const int n = RING ? ring_keys(t, span) : t;
+    const int r0 = RING ? ring_first_row(t, n, span) : 0;
+    const int wrow = RING ? ring_row(r0, n, span) : t;
+    auto at = [&](int i) { return RING ? ring_row(r0, i, span) : i; };
     const int d = P.d, h = P.h, f = P.f, dk = P.dk, dkp = P.dkp, nchunk = P.nchunk, KPd = P.KPd, KPf = P.KPf;
     const bool blank = P.mask != nullptr && P.mask[b] == 0.f;
 
@@ -168,7 +188,7 @@ __device__ __forceinline__ void encoder_step_body(const EncStepParams& P, int* p
         });
         __syncthreads();
 
-        // 3. append K_t, V_t: cache row t of every head, 16 bytes per store (bf16 of a bf16-valued float is exact)
+        // 3. append K_t, V_t: cache row wrow (t; in a ring t mod span) of every head, 16 bytes per store (bf16 of a bf16-valued float is exact)
         bf16* Kc = P.cache + (size_t)layer * P.cache_layer + (size_t)b * P.cache_seq;
         bf16* Vc = Kc + P.cache_kv;
         for (int i = tid; i < 2 * h * nchunk; i += MMT_STEP_THREADS) {
@@ -177,10 +197,10 @@ __device__ __forceinline__ void encoder_step_body(const EncStepParams& P, int* p
             bf16x8 v;
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = (bf16)src[e];
-            *reinterpret_cast<bf16x8*>((kv ? Vc : Kc) + (size_t)head * P.cache_head + (size_t)t * dkp + 8 * ch) = v;
+            *reinterpret_cast<bf16x8*>((kv ? Vc : Kc) + (size_t)head * P.cache_head + (size_t)wrow * dkp + 8 * ch) = v;
         }
 
-        // 4. attention of the one query over keys 0 .. t; key t from LDS
+        // 4. attention of the one query over the n cached keys (ages 0 .. n - 1: positions t - n .. t - 1) and key t; key t from LDS
         for (int head = wave; head < h; head += 4) {
             const bf16* Kh = Kc + (size_t)head * P.cache_head;
             const bf16* Vh = Vc + (size_t)head * P.cache_head;
@@ -195,20 +215,20 @@ __device__ __forceinline__ void encoder_step_body(const EncStepParams& P, int* p
 #pragma unroll
             for (int e = 0; e < 8; ++e) st = fmaf(q[e], kt[e], st);
             for (int o = 1; o < cl; o <<= 1) st += __shfl_xor(st, o);
-            // first sweep over the cached keys j < t: the row's exact maximum.  The loads are unconditional (a lane behind t reads row 0,
-            // which is < t inside this loop) so that several are in flight; what such a lane read is dropped by a select.
+            // first sweep over the cached keys, ages j < n: the row's exact maximum.  The loads are unconditional (a lane behind n reads the
+            // row of age 0, which is cached inside this loop) so that several are in flight; what such a lane read is dropped by a select.
             float m = st;
-            for (int j0 = 0; j0 < t; j0 += MMT_STEP_KEYS_INFLIGHT * KG) {
+            for (int j0 = 0; j0 < n; j0 += MMT_STEP_KEYS_INFLIGHT * KG) {
                 bf16x8 kk[MMT_STEP_KEYS_INFLIGHT];
 #pragma unroll
                 for (int u = 0; u < MMT_STEP_KEYS_INFLIGHT; ++u) {
                     const int j = j0 + u * KG + kg;
-                    kk[u] = *reinterpret_cast<const bf16x8*>(Kh + (size_t)(j < t ? j : 0) * dkp + 8 * c);
+                    kk[u] = *reinterpret_cast<const bf16x8*>(Kh + (size_t)at(j < n ? j : 0) * dkp + 8 * c);
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < MMT_STEP_KEYS_INFLIGHT; ++u) {
-                    const bool valid = j0 + u * KG + kg < t;
+                    const bool valid = j0 + u * KG + kg < n;
                     float part = 0.f;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) part = fmaf(q[e], (float)kk[u][e], part);
@@ -222,25 +242,25 @@ __device__ __forceinline__ void encoder_step_body(const EncStepParams& P, int* p
             float l = 0.f, acc[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-            for (int j0 = 0; j0 < t; j0 += MMT_STEP_KEYS_INFLIGHT * KG) {
+            for (int j0 = 0; j0 < n; j0 += MMT_STEP_KEYS_INFLIGHT * KG) {
                 bf16x8 kk[MMT_STEP_KEYS_INFLIGHT], v8[MMT_STEP_KEYS_INFLIGHT];
 #pragma unroll
                 for (int u = 0; u < MMT_STEP_KEYS_INFLIGHT; ++u) {
                     const int j = j0 + u * KG + kg;
-                    const size_t row = (size_t)(j < t ? j : 0) * dkp + 8 * c;
+                    const size_t row = (size_t)at(j < n ? j : 0) * dkp + 8 * c;
                     kk[u] = *reinterpret_cast<const bf16x8*>(Kh + row);
                     v8[u] = *reinterpret_cast<const bf16x8*>(Vh + row);
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < MMT_STEP_KEYS_INFLIGHT; ++u) {
-                    const bool valid = j0 + u * KG + kg < t;
+                    const bool valid = j0 + u * KG + kg < n;
                     float part = 0.f;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) part = fmaf(q[e], (float)kk[u][e], part);
                     part = chunk_ok ? part : 0.f;
                     for (int o = 1; o < cl; o <<= 1) part += __shfl_xor(part, o);
-                    const float p = valid ? fast_exp2(part - m) : 0.f;           // selects: nothing behind t is ever multiplied
+                    const float p = valid ? fast_exp2(part - m) : 0.f;           // selects: nothing behind n is ever multiplied
                     const float pb = step_bf16_round(p);
                     l += p;
 #pragma unroll
@@ -292,12 +312,19 @@ __device__ __forceinline__ void encoder_step_body(const EncStepParams& P, int* p
         P.y[(size_t)b * d + n] = fa[n] * ((xs[n] - mean) * rstd) + fb[n];
     if (SLOTS && tid == 0) {
         int* const w = next;
-        if (w != nullptr) *w = t + 1;                                            // t < capacity <= 4096: no overflow.  Read by the next launch only
+        if (w != nullptr) *w = t + 1;                                            // t < INT_MAX (slot_decode): no overflow.  Read by the next launch only
     }
 }
 
-__global__ __launch_bounds__(MMT_STEP_THREADS) void encoder_step_kernel(const EncStepParams P) { encoder_step_body<false>(P, nullptr, 0); }
+__global__ __launch_bounds__(MMT_STEP_THREADS) void encoder_step_kernel(const EncStepParams P) { encoder_step_body<false, false>(P, nullptr, 0); }
 
 __global__ __launch_bounds__(MMT_STEP_THREADS) void encoder_step_slots_kernel(const EncStepParams P, int* pos, int advance) {
-    encoder_step_body<true>(P, pos, advance);
+    encoder_step_body<true, false>(P, pos, advance);
+}
+
+// The ring forms (step_ring.h): P.capacity is the span, the cache has that many rows, and no position below INT_MAX is refused.
+__global__ __launch_bounds__(MMT_STEP_THREADS) void encoder_step_ring_kernel(const EncStepParams P) { encoder_step_body<false, true>(P, nullptr, 0); }
+
+__global__ __launch_bounds__(MMT_STEP_THREADS) void encoder_step_ring_slots_kernel(const EncStepParams P, int* pos, int advance) {
+    encoder_step_body<true, true>(P, pos, advance);
 }

@@ -1672,8 +1672,9 @@ def encoder_stream_prepare(flat_params, state, B, capacity, d, h, d_ff, n_layers
     _lib.launch("mmt_encoder_stream_prepare", p_, state, state.numel(), int(B), int(capacity), int(d), int(h), int(d_ff), int(n_layers))
 
 
-def _encoder_step(op, x_t, mask_t, flat_params, state, h, d_ff, n_layers, capacity, eps, t=None, positions=None, advance=True):
-    """Both forms of the encoder step: the position is ``t``, by value, or ``positions`` on the device (the capacity is its limit)."""
+def _encoder_step(op, x_t, mask_t, flat_params, state, h, d_ff, n_layers, capacity, eps, t=None, positions=None, advance=True, _ring=False):
+    """Both forms of the encoder step: the position is ``t``, by value, or ``positions`` on the device (the capacity is its limit).
+    ``_ring`` (streaming.encoder_ring_step*): ``capacity`` is the span of a ring cache, which no position below INT_MAX is outside."""
     _forward_only(op, (x_t, mask_t))
     if not isinstance(x_t, torch.Tensor) or x_t.dim() != 2 or x_t.dtype != torch.float32:
         raise ValueError("%s: x_t must be a float32 (B,d) tensor, got %s %s"
@@ -1683,7 +1684,10 @@ def _encoder_step(op, x_t, mask_t, flat_params, state, h, d_ff, n_layers, capaci
     capacity = int(capacity)
     if t is not None:
         where = (int(t),)
-        if not 0 <= where[0] < capacity:
+        if _ring:
+            if capacity < 1 or not 0 <= where[0] < 2 ** 31 - 1:
+                raise ValueError("%s: span = %d and position t = %d: the span must be at least 1 and t in [0, INT_MAX)" % (op, capacity, where[0]))
+        elif not 0 <= where[0] < capacity:
             raise ValueError("%s: position t = %d outside [0, capacity = %d): open a stream with a larger capacity" % (op, where[0], capacity))
     else:
         _stream_positions(op, positions, B, x_t.device)
@@ -1694,7 +1698,8 @@ def _encoder_step(op, x_t, mask_t, flat_params, state, h, d_ff, n_layers, capaci
     _stream_state(op, state, nbytes, x_t.device, "encoder_stream_state")
     x_ = _f32c(x_t)
     y = torch.empty_like(x_)
-    _lib.launch("mmt_" + op, x_, m_, p_, y, state, state.numel(), *where, B, capacity, d, int(h), int(d_ff), int(n_layers), float(eps))
+    entry = "mmt_" + op if not _ring else "mmt_encoder_stream_step_ring" + ("" if t is not None else "_slots")
+    _lib.launch(entry, x_, m_, p_, y, state, state.numel(), *where, B, capacity, d, int(h), int(d_ff), int(n_layers), float(eps))
     return y
 
 

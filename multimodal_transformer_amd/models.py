@@ -116,12 +116,15 @@ class _FrontEndStream:
     The window encoder runs on a T = 1 batch (``_encode``), then the fusion layer where the model has one, then the sequence model's
     own step (``streaming._SequenceStream``; the MFT and B3-MFN take the per-modality rows as a dict: ``streaming._GateStream``).  ``reset()`` starts a new recording."""
 
-    def __init__(self, model, batch, capacity, method="stream"):
-        """``method``: the sequence model's method that opens its stream, "stream", "slot_stream" or "device_stream"."""
+    def __init__(self, model, batch, capacity, method="stream", seq=None):
+        """``method``: the sequence model's method that opens its stream, "stream", "slot_stream" or "device_stream".  ``seq``: the
+        sequence model's stream, already open (``streaming.ring_stream``)."""
         _stream_model_checks(model)
         self.model, self.batch = model, int(batch)
         seq_model = getattr(model, "Transformer", None)
-        if seq_model is None:                                 # MultiCNNLSTM: the sequence model is .LSTM, which has no cache, so no capacity
+        if seq is not None:
+            self.seq = seq
+        elif seq_model is None:                                 # MultiCNNLSTM: the sequence model is .LSTM, which has no cache, so no capacity
             self.seq = getattr(model.LSTM, method)(batch, capacity)
         else:
             self.seq = getattr(seq_model, method)(batch, capacity)

@@ -32,9 +32,9 @@ from . import _lib
 from . import functional as F_hip
 from .functional import _MOD_STREAMS            # the one object, shared with streaming; models imports it from here
 # the models as online predictors: what stream() / slot_stream() / device_stream() below open
-from .streaming import (_INT_MAX, EncoderSlotStream, EncoderStream, MFNSlotStream, MFNStream, _GateSlotStream, _GateStream,
-                        _modality_rows, _no_slot_stream, _SequenceSlotStream, _SequenceStream, _slot_positions, _Slots,
-                        _stream_model_checks)
+from .streaming import (_INT_MAX, EncoderRingSlotStream, EncoderRingStream, EncoderSlotStream, EncoderStream, MFNSlotStream, MFNStream,
+                        _GateSlotStream, _GateStream, _modality_rows, _no_slot_stream, _SequenceSlotStream, _SequenceStream,
+                        _slot_positions, _Slots, _stream_model_checks, ring_stream)
 
 
 def clones(module, N):
@@ -224,7 +224,7 @@ def causal_attention(module, on=True, span=None):
     ``span`` (an int >= 1; None: no lower edge): window t attends its last ``span`` windows only, t - span + 1 .. t, so every layer has
     a fixed receptive field and the model conditions on a context of bounded length, in training and in evaluation; the band kernels
     also sweep about span/32 + 1 key tiles per query tile instead of all tiles up to the diagonal.  ValueError here for span < 1, a
-    bool or a non-integer, and for a span with ``on=False``.  Streams do not serve a span yet (they refuse it at open).
+    bool or a non-integer, and for a span with ``on=False``.  A span streams through ``ring_stream(model, batch)`` (``stream`` refuses it at open).
     ``causal_attention(module, False)`` restores the reference's semantics and the plain kernels, and clears ``span``."""
     span = F_hip._check_span("causal_attention", None, bool(on), span)
     found = {}
@@ -369,8 +369,9 @@ class Encoder(nn.Module):
                                           flat=self._flat_storage(ps) if x.is_cuda else None, nsplit=k, key_lengths=kl,
                                           causal=causal, span=span)
 
-    def _stream_refusals(self):
-        """What ``stream`` and ``slot_stream`` refuse, before anything is allocated or launched."""
+    def _stream_refusals(self, ring=False):
+        """What ``stream`` and ``slot_stream`` refuse, before anything is allocated or launched.  ``ring`` (``ring_stream``,
+        ``ring_slot_stream``): the same, but the span must be there."""
         name = type(self).__name__
         if self.training:
             raise ValueError("%s.stream: the encoder is in train mode; streaming is eval-mode inference (call .eval())" % name)
@@ -385,10 +386,13 @@ class Encoder(nn.Module):
         if not l0.causal:
             raise ValueError("%s.stream: the layers do not attend causally, so window t depends on later windows and cannot be "
                              "predicted online: call causal_attention(model) (and train the model that way)" % name)
-        if l0.span is not None:
-            raise ValueError("%s.stream: the layers attend a band of span = %r windows, but the step kernel attends every cached key and "
-                             "would be wrong from window t = span on; the ring cache that streams a span is the follow-up to the band "
-                             "kernels (DESIGN.md 10) — until then stream the model without a span" % (name, l0.span))
+        if ring and l0.span is None:
+            raise ValueError("%s.ring_stream: the layers have no span, so a window attends its whole past and no ring of rows can hold "
+                             "it: call causal_attention(model, span=W) (and train the model that way), or open stream(batch, capacity)" % name)
+        if not ring and l0.span is not None:
+            raise ValueError("%s.stream: the layers attend a band of span = %r windows, but this step kernel attends every cached key "
+                             "and would be wrong from window t = span on; a span streams from a ring cache of span rows, which never "
+                             "fills: Encoder.ring_stream(batch) / ring_stream(model, batch) (DESIGN.md 4.11)" % (name, l0.span))
         if self.norm.a_2.device.type != "cuda":
             raise ValueError("%s.stream: the encoder is on %s; move it to a HIP device (there is no CPU path)" % (name, self.norm.a_2.device))
 
@@ -405,6 +409,19 @@ class Encoder(nn.Module):
         refusals, before any launch."""
         self._stream_refusals()
         return EncoderSlotStream(self, batch, capacity, positions)
+
+    def ring_stream(self, batch):
+        """Open an ``EncoderRingStream``: this stack, with a span (``causal_attention(model, span=W)``), as an online predictor for
+        ``batch`` recordings of ANY length, one window per ``step`` against a ring K/V cache of ``span`` rows.  The
+        refusals of ``stream``, and ValueError for a stack without a span, before any launch."""
+        self._stream_refusals(ring=True)
+        return EncoderRingStream(self, batch)
+
+    def ring_slot_stream(self, batch, positions=None):
+        """``ring_stream(batch)`` with slots (``EncoderRingSlotStream``): positions on the device, independent seats, a step that can
+        be captured into a graph, and no slot ever full.  The same refusals, before any launch."""
+        self._stream_refusals(ring=True)
+        return EncoderRingSlotStream(self, batch, positions)
 
     sub_batch_streams = 1        # set to 2: the batch runs as two halves on two HIP streams (functional._SPLIT_STREAMS); opt-in
     sub_batch_min_windows = 8192

@@ -8,12 +8,24 @@ A stream keeps its position in one of two places.  A host stream (``EncoderStrea
 int32 per sequence on the device, read and advanced by the positioned kernels, so its sequences are seated and released independently
 and a step can be captured into a graph.  Each class decides that in its ``__init__`` and nowhere else.  The models refuse what cannot
 stream (``Encoder._stream_refusals``, ``MFN._stream_refusals``, ``models._LocalAttnLSTM._stream_refusals``) before they open one of
-these."""
+these.
+
+A model with a span (``causal_attention(model, span=W)``) streams from a ring K/V cache of ``span`` rows, which never fills
+(``EncoderRingStream``, ``EncoderRingSlotStream``; csrc/step_ring.h): ``ring_stream(model, batch, slots=False)`` opens the
+form each model has, with ring encoder streams inside."""
 import torch
 
 from . import functional as F_hip
 
 _INT_MAX = 2 ** 31 - 1
+_RING = object()                 # in place of a composite stream's capacity: its encoders stream a span from a ring cache
+
+
+def _open_encoder(encoder, batch, capacity, slots, positions=None):
+    """The encoder stream of a composite stream: the encoder's own refusals pass through."""
+    if capacity is _RING:
+        return encoder.ring_slot_stream(batch, positions) if slots else encoder.ring_stream(batch)
+    return encoder.slot_stream(batch, capacity, positions) if slots else encoder.stream(batch, capacity)
 
 
 def _slot_positions(op, positions, batch, device):
@@ -159,6 +171,72 @@ class EncoderSlotStream(_Slots, EncoderStream):
         return y.view(x_t.shape)
 
 
+def encoder_ring_step(x_t, mask_t, flat_params, state, t, h, d_ff, n_layers, span, eps=1e-6):
+    """Row t of a causal encoder stack with a span: x_t (B,d), mask_t (B) or None -> y_t (B,d) = Encoder.forward(x, mask)[:, t] with
+    ``causal_attention(model, span=span)`` on, from a RING cache of ``span`` rows in ``state`` (``functional.encoder_stream_state`` and
+    ``encoder_stream_prepare`` with capacity := span; csrc/step_ring.h).  Position j lives in row j mod span, so any 0 <= t < INT_MAX is
+    served; while t < span the row is that of ``functional.encoder_stream_step``, bit for bit.  Steps of a recording run in order; t is
+    passed by value.  One launch (encoder_step_ring_kernel).  Forward only."""
+    return F_hip._encoder_step("encoder_ring_step", x_t, mask_t, flat_params, state, h, d_ff, n_layers, span, eps, t=int(t), _ring=True)
+
+
+def encoder_ring_step_slots(x_t, mask_t, flat_params, state, positions, h, d_ff, n_layers, span, eps=1e-6, advance=True):
+    """``encoder_ring_step`` with the position of every sequence in device memory (csrc/step_slots.h): ``positions`` int32 (B), read by
+    the kernel.  Row b is the row of ``encoder_ring_step`` at t = positions[b], bit for bit, and zeros, with nothing else written, where
+    the slot is idle (negative) or stands at INT_MAX.  There is no limit, so no slot becomes full.  ``advance``: the kernel adds 1 to the
+    position of every slot it ran.  One launch (encoder_step_ring_slots_kernel), which can be captured into a graph."""
+    return F_hip._encoder_step("encoder_ring_step_slots", x_t, mask_t, flat_params, state, h, d_ff, n_layers, span, eps,
+                               positions=positions, advance=advance, _ring=True)
+
+
+class EncoderRingStream(EncoderStream):
+    """A causal ``Encoder`` with a span run one window at a time (``Encoder.ring_stream``): ``EncoderStream`` against a ring cache of
+    ``span`` rows (csrc/step_ring.h).  ``step(x_t)`` returns the row that the batch forward with the span gives at position ``t``, in ONE
+    launch of encoder_step_ring_kernel, at a cost that stops growing at t = span - 1.  ``capacity`` is None: the stream never fills
+    (a host ``t`` of INT_MAX, which is no position, raises ValueError).  ``reset()`` / ``refresh()`` as ``EncoderStream``: nothing is
+    cleared.  The first ``span`` rows are those of ``Encoder.stream(batch, span)`` of the same stack without the span, bit for bit, and
+    a row's bits depend on the last windows only, not on ``t``."""
+
+    def __init__(self, encoder, batch):
+        self._shape(encoder, batch)
+        self.t = 0
+        self._allocate()
+
+    def _shape(self, encoder, batch):
+        """As ``EncoderStream._shape`` with capacity := span: the state, its size query and its preparation are those of a plain
+        stream of ``span`` windows, so a span above 4096 is refused with that limit's message."""
+        super()._shape(encoder, batch, encoder.layers[0].self_attn.span)
+        self.span, self.capacity = self.capacity, None
+
+    def step(self, x_t, mask_t=None):
+        """x_t (B,d) or (B,1,d) float32 on the encoder's device, mask_t (B), (B,1) or (B,1,1) or None -> the same shape as x_t."""
+        if self.t >= _INT_MAX:
+            raise ValueError("EncoderRingStream.step: t = %d is INT_MAX, which is no position: reset() starts a new recording" % self.t)
+        self._check_step(x_t, mask_t)
+        y = encoder_ring_step(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.t, self.h, self.d_ff, self.n_layers,
+                              self.span, self.eps)
+        self.t += 1
+        return y.view(x_t.shape)
+
+
+class EncoderRingSlotStream(_Slots, EncoderRingStream):
+    """``EncoderRingStream`` with slots (``Encoder.ring_slot_stream``; members: ``_Slots``).  ``step(x_t, mask_t)`` is ONE launch of
+    encoder_step_ring_slots_kernel: row b is what an ``EncoderRingStream`` of that recording alone gives at window ``positions[b]``, bit
+    for bit, and the kernel advances the positions of the slots it ran.  No slot becomes full: ``full()`` shows INT_MAX only."""
+
+    def __init__(self, encoder, batch, positions=None):
+        self._shape(encoder, batch)
+        self.positions = _slot_positions("Encoder.ring_slot_stream", positions, self.batch, self.device)
+        self._allocate()
+
+    def step(self, x_t, mask_t=None, advance=True):
+        """As ``EncoderRingStream.step``.  ``advance=False`` leaves the positions (a composite stream advances them once, in its last launch)."""
+        self._check_step(x_t, mask_t)
+        y = encoder_ring_step_slots(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.positions, self.h, self.d_ff,
+                                    self.n_layers, self.span, self.eps, advance=advance)
+        return y.view(x_t.shape)
+
+
 def _no_slot_stream(model):
     raise NotImplementedError("%s.slot_stream: this model's stream keeps host-side state per recording (one position t for the batch; "
                               "with an LSTM decoder also the carried (h, c) and the first row h0 W_hh, chosen on the host at t == 0), so "
@@ -186,7 +264,7 @@ class _SequenceStream:
         if dec is not None and dec.num_layers != 1:
             raise NotImplementedError("%s.stream: a decoder with n_layers = %d; the stepping state of the stacked scan is not implemented "
                                       "(n_layers == 1 streams)" % (type(model).__name__, dec.num_layers))
-        self.enc = model.encoder.stream(batch, capacity)
+        self.enc = _open_encoder(model.encoder, batch, capacity, False)
         self._embed, self._embed_act = _embed_of(model)
         self._dec = None
         if dec is not None:
@@ -214,7 +292,7 @@ class _SequenceStream:
         op = "%s stream step" % type(m).__name__
         _check_row(op, "x_t", x_t, B, self._embed.in_features, None)         # the embed is ``linear``, which converts what it is given
         _check_mask(op, mask_t, B, None)
-        if self.enc.t >= self.enc.capacity:
+        if self.enc.capacity is not None and self.enc.t >= self.enc.capacity:          # None: a ring cache, which never fills
             raise ValueError("%s: the stream is full (t = capacity = %d)" % (op, self.enc.capacity))
         with torch.no_grad():
             first = self.enc.t == 0
@@ -252,7 +330,7 @@ class _SequenceSlotStream(_Slots):
         self._dims = (self.batch, self.d, self.h_dim, self.n_layers)
         if self.batch >= 1:
             F_hip.decoder_stream_bytes(*self._dims)                              # ValueError naming the limit, before anything is opened
-        self.enc = model.encoder.slot_stream(batch, capacity)                    # the encoder's refusals pass through; it makes the positions
+        self.enc = _open_encoder(model.encoder, batch, capacity, True)           # the encoder's refusals pass through; it makes the positions
         self.device, self.positions = self.enc.device, self.enc.positions
         self.state = F_hip.decoder_stream_state(*self._dims, self.device)
         self._embed, self._embed_act = _embed_of(model)
@@ -464,7 +542,7 @@ class _GateStream:
 
     def __init__(self, model, batch, capacity):
         stacks = self._shape(model, batch, capacity)
-        self.encs = None if stacks is None else {m: stacks[m].stream(batch, capacity) for m in self.mods}      # their refusals pass through
+        self.encs = None if stacks is None else {m: _open_encoder(stacks[m], batch, capacity, False) for m in self.mods}      # their refusals pass through
         self.gate = model.mfn.stream(batch)
         self.device = self.gate.device
 
@@ -496,7 +574,7 @@ class _GateStream:
     def step(self, inputs, mask_t=None):
         op = "%s stream step" % type(self.model).__name__
         xs = _modality_rows(op, inputs, self.mods, self.widths, self.batch, self.device, mask_t)
-        if self.encs is not None and self.t >= self.capacity:
+        if self.encs is not None and self.capacity is not None and self.t >= self.capacity:       # None: ring caches, which never fill
             raise ValueError("%s: the stream is full (t = capacity = %d)" % (op, self.capacity))
         return self._step(xs, mask_t, True)
 
@@ -538,9 +616,9 @@ class _GateSlotStream(_Slots, _GateStream):
         if stacks is not None:
             self.encs = {}
             for mod in self.mods:
-                self.encs[mod] = stacks[mod].slot_stream(batch, capacity, self.positions)                      # their refusals pass through
+                self.encs[mod] = _open_encoder(stacks[mod], batch, capacity, True, self.positions)             # their refusals pass through
                 self.positions = self.encs[mod].positions
-        self.gate = model.mfn.slot_stream(batch, capacity if stacks is not None else None, self.positions)
+        self.gate = model.mfn.slot_stream(batch, capacity if stacks is not None and capacity is not _RING else None, self.positions)
         self.device, self.positions = self.gate.device, self.gate.positions
 
     def step(self, inputs, mask_t=None, advance=True):
@@ -554,3 +632,38 @@ class _GateSlotStream(_Slots, _GateStream):
 
     def _gate_step(self, rows, r, advance):
         return self.gate.step(rows, r, advance=advance)
+
+
+def ring_stream(model, batch, slots=False):
+    """Open ``model`` as an online predictor WITHOUT a length limit: a model with a span (``causal_attention(model, span=W)``) streams
+    from ring K/V caches of ``span`` rows (``EncoderRingStream``), at a cost per window that stops growing at window
+    span - 1.  Serves ``Encoder``, ``NLPTransformer``, ``UniTransformer``, ``UniFullTransformer``, ``MultiTransformer`` and the
+    ``MultiCNNTransformer`` / ``B2`` / ``MFT`` wrappers, and returns the form each has, with ring encoder streams inside:
+
+      * ``slots=False``: what ``stream`` gives, one host ``t`` for the batch (``_SequenceStream``, ``_GateStream``, ``_FrontEndStream``);
+      * ``slots=True``: the model's own slots form, positions on the device, independent seats, capturable
+        (``graphs.capture_stream``): ``_GateSlotStream`` for the MFT, ``_SequenceSlotStream`` (``device_stream``'s) for the three
+        sequence models, the same behind the window encoder for the wrappers.
+
+    ``.capacity`` is None and ``step`` never raises "full".  Before any launch or allocation: the refusals of ``stream`` (train mode, a
+    stack that is not the standard composition, ``mask_keys``, layers that are not causal, a model that is not on a HIP device;
+    NotImplementedError for ``slots=False`` with a decoder of n_layers > 1), ValueError naming ``causal_attention(model, span=W)`` for a
+    model without a span, and ValueError naming ``stream(batch)`` for a model without attention (B3-MFN, the LSTM baselines), which
+    needs no cache to run without a limit."""
+    from . import models, multiTransformer as M
+
+    slots = bool(slots)
+    if isinstance(model, M.Encoder):
+        return model.ring_slot_stream(batch) if slots else model.ring_stream(batch)
+    seq = getattr(model, "Transformer", None) if isinstance(model, models._FrontEnd) else model
+    if isinstance(seq, M.MultiTransformer):
+        form = _GateSlotStream if slots else _GateStream
+    elif isinstance(seq, (M.NLPTransformer, M.UniTransformer, M.UniFullTransformer)):
+        form = _SequenceSlotStream if slots else _SequenceStream
+    else:
+        raise ValueError("ring_stream: %s has no attention, so no K/V cache and no length limit to lift: stream(batch) already runs for "
+                         "as long as the recording does" % type(model).__name__)
+    if seq is model:
+        return form(model, batch, _RING)
+    _stream_model_checks(model, "ring_stream")
+    return models._FrontEndStream(model, batch, None, seq=form(seq, batch, _RING))
