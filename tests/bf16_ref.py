@@ -97,13 +97,15 @@ RESCALE_THR = 8.0           # attn.h MMT_RESCALE_THR
 
 _JITTER = None      # (generator, relative size): see jitter()
 _JITTER_INPUTS = True
+_JITTER_COMPUTED_ONLY = False
 
 
 def bf16(t):
     """bf16 round-to-nearest-even of an fp64 tensor, back in fp64 (no autograd)."""
     if _JITTER is not None:
         g, eps = _JITTER
-        t = t * (1 + eps * torch.randn(t.shape, generator=g, dtype=t.dtype))
+        noisy = t * (1 + eps * torch.randn(t.shape, generator=g, dtype=t.dtype))
+        t = torch.where(t.to(torch.float32).to(t.dtype) == t, t, noisy) if _JITTER_COMPUTED_ONLY else noisy
     return t.to(torch.bfloat16).to(t.dtype)
 
 
@@ -112,17 +114,21 @@ class jitter:
     fp32 accumulation order does to the kernels' values.  Two runs of the reference, with and without, measure how far apart two
     equally correct implementations land when fp32 noise tips bf16 roundings (tests/test_bf16_ref.py).
     inputs=False: ``linear`` rounds its x and W unperturbed, as for a stand-alone affine map or Highway, whose x and W are given fp32
-    data with the same bf16 value in every implementation; only computed values (the backward's operands) are perturbed."""
-    def __init__(self, eps, seed=0, inputs=True):
-        self.eps, self.seed, self.inputs = eps, seed, inputs
+    data with the same bf16 value in every implementation; only computed values (the backward's operands) are perturbed.
+    computed_only=True: in every function, an element that is exactly an fp32 number is rounded unperturbed.  Given data (fp32 weights,
+    inputs, their copies and concatenations, exact zeros) has the same bf16 value in every implementation; a value computed in fp64 is
+    an fp32 number only by a 2^-29 chance.  For compositions whose pieces round weights and inputs at many sites (the MFN gate)."""
+    def __init__(self, eps, seed=0, inputs=True, computed_only=False):
+        self.eps, self.seed, self.inputs, self.computed_only = eps, seed, inputs, computed_only
 
     def __enter__(self):
-        global _JITTER, _JITTER_INPUTS
+        global _JITTER, _JITTER_INPUTS, _JITTER_COMPUTED_ONLY
         _JITTER, _JITTER_INPUTS = (torch.Generator().manual_seed(self.seed), self.eps), self.inputs
+        _JITTER_COMPUTED_ONLY = self.computed_only
 
     def __exit__(self, *a):
-        global _JITTER, _JITTER_INPUTS
-        _JITTER, _JITTER_INPUTS = None, True
+        global _JITTER, _JITTER_INPUTS, _JITTER_COMPUTED_ONLY
+        _JITTER, _JITTER_INPUTS, _JITTER_COMPUTED_ONLY = None, True, False
 
 
 class _RoundFwd(torch.autograd.Function):

@@ -6,6 +6,25 @@ path's sites (bf16_ref.py: the affine map's x and W, the scans' h_{t-1}, mem_{t-
 operand of every product; sums, biases, activations, the softmax, the carried state and the output stay fp64.  No site depends on a
 tile, so the stepped walk and the batch composition of the existing pieces are the SAME function (tests/test_mfn_stream_cpu.py holds
 them to 1e-12), and with ``rounding=False`` it is ``oracle.mfn_gate``.  ``bf16_ref.mfn_mem_scan`` has no initial memory and is not used.
+
+The batch composition (``lstm_states``, ``gate_from_states``, ``batch_composition``) is also the reference of the gate's TRAINING path
+(tests/test_gpu_bf16_mfn_gate.py): it runs under autograd, bf16_ref's pieces place ``round_fwd`` / ``round_bwd``, and it takes the two
+dropout multipliers and the window mask.  Sites of functional._MfnGateFn and MFN._gate beyond those of the pieces, read from the sources:
+  * b_ih + b_hh is one fp32 sum (functional.add2: glue.h copy2d_kernel, src + src2) in front of the affine map, whose bias stays
+    fp32: no bf16 site.  The reference sums the two fp32 values in fp64, 2^-25 of the bias away; both biases receive the SAME
+    gradient tensor (_Add2Fn.backward returns dy twice), db = colsum(bf16(dgx));
+  * cStar, [h ; mem] and the gamma operands Wa, Wm, b1, W2, b2 are fp32 copies (copy2d): the bf16 roundings of cStar, `attended`, `last`
+    and of the weights happen inside the affine maps that read them, one rounding of the same fp32 value per reader;
+  * softmax_mul (glue.h softmax_mul_fwd_kernel / _bwd_kernel) is fp32 throughout, forward and backward: nothing is rounded, att is kept;
+  * gradients that meet are summed in fp32 by copy2d: d attended = (d apre) Wa + (d a2') W_att2_fc1 (accumulate), and
+    dc_t = (d cStar + d cStar')[new part]_t + (d cStar + d cStar')[prev part]_{t+1} with d cStar from the product and d cStar' from
+    att1_fc1's dx; autograd's fp64 sums stand for them.  Each summand is the fp32 dx of an affine map: g W with g = bf16(.);
+  * d apre leaves the memory scan in fp32 and is rounded once in each of its two readers, the affine backward (dWa, db1, d attended:
+    grad_prep_kernel) and _wgrad (dWm): the same bf16 value, as ``round_bwd`` in bf16_ref.linear and in mfn_mem_scan place it;
+  * the out-dropout multiplier sits behind out_fc1's ReLU in the forward and inside g = bf16(dy * act' * 1/(1-p)) in the backward
+    (bf16_ref.linear's out_drop); the mask multiplies the fp32 output (copy2d rowscale) and its gradient before out_fc2's g is rounded.
+None of these differs from what ``batch_composition`` assumed before it ran under autograd; the fp32 bias sum is the one site it
+does not emulate (below the fp32 noise the jitter floor measures).
 """
 import torch
 
@@ -80,32 +99,49 @@ def mfn_gate(p, prefix, inputs, mods, mask=None, rounding=True, hidden=None):
     return torch.stack(rows, dim=1)
 
 
-def batch_composition(p, prefix, inputs, mods, rounding=True, hidden=None):
-    """The same gate from the batch path's pieces, as functional._MfnGateFn composes its kernels: bf16_ref.linear -> bf16_ref.lstm_scan
-    -> shift and concatenate -> linear x2 -> softmax * cStar -> linear x2 -> linear (apre) -> bf16_ref.mfn_mem_scan -> linear x2.
-    inputs {mod: (T, B, d_mod)} -> (B, T, output_dim)."""
-    hidden = dict(hidden or HIDDEN)
+def lstm_states(p, prefix, inputs, mods, rounding=True):
+    """Phase A of the batch path (MFN._gate): per modality gx = linear(x, W_ih, b_ih + b_hh) -> bf16_ref.lstm_scan.
+    inputs {mod: (T, B, d_mod)} -> (hs, cs), lists of (T, B, H_m).  Autograd runs through it when an argument requires grad."""
     g = lambda n: p[prefix + n]                                                          # noqa: E731
-    lin = lambda name, x, act=0: E.linear(x, g(name + ".weight"), g(name + ".bias"), act=act, rounding=rounding)   # noqa: E731
-    with torch.no_grad():
-        hs, cs = [], []
-        for m in mods:
-            gx = E.linear(inputs[m], g("lstm_%s.weight_ih" % m), g("lstm_%s.bias_ih" % m) + g("lstm_%s.bias_hh" % m), rounding=rounding)
-            h_all, c_all = E.lstm_scan(gx, g("lstm_%s.weight_hh" % m), rounding=rounding)
-            hs.append(h_all); cs.append(c_all)
-        prev = [torch.cat([torch.zeros_like(c[:1]), c[:-1]], dim=0) for c in cs]
-        c_star = torch.cat(prev + cs, dim=-1)
-        att = torch.softmax(lin("att1_fc2", lin("att1_fc1", c_star, 1)), dim=-1)
-        attended = att * c_star
-        c_hat = lin("att2_fc2", lin("att2_fc1", attended, 1), 2)
-        A = c_star.shape[-1]
-        w1, w2 = g("gamma1_fc1.weight"), g("gamma2_fc1.weight")
-        Wa, Wm = torch.cat([w1[:, :A], w2[:, :A]]), torch.cat([w1[:, A:], w2[:, A:]])
-        b1 = torch.cat([g("gamma1_fc1.bias"), g("gamma2_fc1.bias")])
-        apre = E.linear(attended, Wa, b1, rounding=rounding)
-        W2 = torch.stack([g("gamma1_fc2.weight"), g("gamma2_fc2.weight")])
-        b2 = torch.stack([g("gamma1_fc2.bias"), g("gamma2_fc2.bias")])
-        mem_all = E.mfn_mem_scan(apre, c_hat, Wm, W2, b2, rounding=rounding)
-        last = torch.cat(hs + [mem_all], dim=-1)
-        out = lin("out_fc2", lin("out_fc1", last, 1))
-    return out.permute(1, 0, 2)
+    hs, cs = [], []
+    for m in mods:
+        gx = E.linear(inputs[m], g("lstm_%s.weight_ih" % m), g("lstm_%s.bias_ih" % m) + g("lstm_%s.bias_hh" % m), rounding=rounding)
+        h_all, c_all = E.lstm_scan(gx, g("lstm_%s.weight_hh" % m), rounding=rounding)
+        hs.append(h_all); cs.append(c_all)
+    return hs, cs
+
+
+def gate_from_states(p, prefix, hs, cs, gamma_drop=None, out_drop=None, rounding=True):
+    """functional.mfn_gate(hs, cs, params, ...) from bf16_ref's pieces: hs, cs lists of (T, B, H_m) (leaves of their own or the scans'
+    outputs), gamma_drop (T, B, 128) the multiplier inside the memory scan (gamma1's 64 units first), out_drop (T, B, 64) the multiplier
+    behind out_fc1's ReLU -> (T, B, output_dim), time-major as the kernel path returns it."""
+    g = lambda n: p[prefix + n]                                                          # noqa: E731
+    lin = lambda name, x, act=0, **kw: E.linear(x, g(name + ".weight"), g(name + ".bias"), act=act, rounding=rounding, **kw)   # noqa: E731
+    prev = [torch.cat([torch.zeros_like(c[:1]), c[:-1]], dim=0) for c in cs]
+    c_star = torch.cat(prev + list(cs), dim=-1)
+    att = torch.softmax(lin("att1_fc2", lin("att1_fc1", c_star, 1)), dim=-1)
+    attended = att * c_star
+    c_hat = lin("att2_fc2", lin("att2_fc1", attended, 1), 2)
+    A = c_star.shape[-1]
+    w1, w2 = g("gamma1_fc1.weight"), g("gamma2_fc1.weight")
+    Wa, Wm = torch.cat([w1[:, :A], w2[:, :A]]), torch.cat([w1[:, A:], w2[:, A:]])
+    b1 = torch.cat([g("gamma1_fc1.bias"), g("gamma2_fc1.bias")])
+    apre = E.linear(attended, Wa, b1, rounding=rounding)
+    W2 = torch.stack([g("gamma1_fc2.weight"), g("gamma2_fc2.weight")])
+    b2 = torch.stack([g("gamma1_fc2.bias"), g("gamma2_fc2.bias")])
+    mem_all = E.mfn_mem_scan(apre, c_hat, Wm, W2, b2, drop=gamma_drop, rounding=rounding)
+    last = torch.cat(list(hs) + [mem_all], dim=-1)
+    return lin("out_fc2", lin("out_fc1", last, 1, out_drop=out_drop))
+
+
+def batch_composition(p, prefix, inputs, mods, rounding=True, hidden=None, gamma_drop=None, out_drop=None, mask=None, states=None):
+    """The same gate from the batch path's pieces, as MFN._gate and functional._MfnGateFn compose their kernels: bf16_ref.linear ->
+    bf16_ref.lstm_scan (lstm_states) -> shift and concatenate -> linear x2 -> softmax * cStar -> linear x2 -> linear (apre) ->
+    bf16_ref.mfn_mem_scan -> linear x2 (gate_from_states) -> batch-major, times the window mask (B, T, 1) as F.batch_major(out, mask).
+    inputs {mod: (T, B, d_mod)} -> (B, T, output_dim), with autograd wherever an argument requires grad.  ``hidden`` is kept for the
+    callers that pass it: the hidden sizes are read from the weights.  states: a dict that receives "hs" and "cs"."""
+    hs, cs = lstm_states(p, prefix, inputs, mods, rounding)
+    if states is not None:
+        states["hs"], states["cs"] = hs, cs
+    out = gate_from_states(p, prefix, hs, cs, gamma_drop, out_drop, rounding).permute(1, 0, 2)
+    return out if mask is None else out * mask.to(out.dtype)
