@@ -23,19 +23,12 @@
 // plan's offsets alone: t is a launch argument checked by the host, and the kernel returns at once when t < 0.  No address is derived
 // from device data.
 //
-// The positioned form, decoder_step_slots_kernel: the same body (a compile-time switch), with the position of each sequence read from
-// device memory, int pos[B] (step_slots.h).  Workgroup b reads p = pos[b] once, before anything else, makes it wave-uniform
-// (readfirstlane) and decodes it against the launch argument `limit` (<= 0: none).  An idle or full slot is skipped: its row of y is
-// written as zeros and nothing else, no carried state, no pos.  Otherwise the body runs with t = p, per sequence, and if `advance` is
-// set one thread stores p + 1 to pos[b] after the last stage.  No other workgroup reads pos[b], so both contracts above hold.  The last
-// sentence of the state discipline changes for this form: every address derived from pos[b] passes slot_decode first, with the limit
-// taken from the launch arguments; what it lets through only selects the copy, p & 1.
+// The positioned form, decoder_step_slots_kernel: the same body with the position of each sequence read from device memory, as
+// step_common.h describes it for every carried-state step; both contracts above hold for it, with slot_decode in the host's place.
 #pragma once
 #include "common.h"
-#include "scan_common.h"                 // sigmoid_f, tanh_f
-#include "step_common.h"
+#include "step_common.h"                 // step_matvec and the spine: step_enter, step_state, step_lstm_cell, step_readout, step_advance
 #include "decoder_step_plan.h"
-#include "step_slots.h"                  // slot_decode
 
 static_assert(MMT_DEC_STEP_THREADS == MMT_STEP_THREADS, "step_matvec is written for one workgroup size");
 
@@ -48,7 +41,7 @@ struct DecStepParams {
     DecStepPlan pl;
 };
 
-// SLOTS false: t = P.t (pos, limit and advance unused).  SLOTS true: t = slot_decode(pos[b], limit), P.t unused.
+// SLOTS: the positioned form (step_common.h: step_enter).
 template <bool SLOTS>
 __device__ __forceinline__ void decoder_step_body(const DecStepParams& P, int* pos, int limit, int advance) {
     constexpr int KD = MMT_DEC_STEP_MAX_D, ML = MMT_DEC_STEP_MAX_L;
@@ -60,29 +53,19 @@ __device__ __forceinline__ void decoder_step_body(const DecStepParams& P, int* p
 
     const DecStepPlan& S = P.pl;
     const int tid = threadIdx.x, b = blockIdx.x;
-    int t;
-    if (SLOTS) {
-        t = slot_decode(__builtin_amdgcn_readfirstlane(pos[b]), limit);          // the one read of pos[b]; uniform, so t lives in an SGPR
-        if (t == MMT_SLOT_SKIP) {                                                // idle or full: a zero row and nothing else
-            if (tid == 0) P.y[b] = 0.f;
-            return;
-        }
-    } else {
-        t = P.t;
-        if (t < 0) return;                                                       // the host refuses such a call
+    const int t = step_enter<SLOTS>(pos, b, limit, P.t);
+    if (t == MMT_SLOT_SKIP) {                                                    // idle or full: a zero row and nothing else
+        if (SLOTS && tid == 0) P.y[b] = 0.f;
+        return;
     }
     const int d = S.d, KPd = S.KPd, L = S.L, G = 4 * d;
     const bool first = t == 0;                                                   // uniform: no word of the carried state is read
-    float* dyn = reinterpret_cast<float*>(P.state + S.dyn_off);
-    const float* st_in = dyn + ((size_t)(t & 1) * P.B + b) * S.seq_floats;
-    float* st_out = dyn + ((size_t)((t & 1) ^ 1) * P.B + b) * S.seq_floats;
-    auto W = [&](size_t off) { return reinterpret_cast<const bf16*>(P.state + off); };
-    auto Bv = [&](size_t off) { return reinterpret_cast<const float*>(P.state + off); };
+    const StepState st = step_state(P.state, S.dyn_off, S.seq_floats, t, P.B, b);
 
     // 0. stage e and, per layer, what multiplies the layer's recurrent matrix (rounded: both feed products only)
     {
         const float* er = P.e + (size_t)b * d;
-        const float* h0 = Bv(S.h0);
+        const float* h0 = st.V(S.h0);
         for (int k = tid; k < KPd; k += MMT_DEC_STEP_THREADS) {
             es[k] = k < d ? step_bf16_round(er[k]) : 0.f;
             hc[k] = 0.f;                                                         // the cells write [0, d): the pad stays zero
@@ -90,7 +73,7 @@ __device__ __forceinline__ void decoder_step_body(const DecStepParams& P, int* p
         for (int l = 0; l < L; ++l)
             for (int k = tid; k < KPd; k += MMT_DEC_STEP_THREADS) {
                 float v = 0.f;
-                if (k < d) v = step_bf16_round(first ? h0[l * d + k] : st_in[(size_t)l * 2 * d + k]);
+                if (k < d) v = step_bf16_round(first ? h0[l * d + k] : st.in[(size_t)l * 2 * d + k]);
                 hp[l * KD + k] = v;
             }
         for (int k = S.hdim + tid; k < S.KPh; k += MMT_DEC_STEP_THREADS) hid[k] = 0.f;          // the pad of the read-out's second input
@@ -99,47 +82,33 @@ __device__ __forceinline__ void decoder_step_body(const DecStepParams& P, int* p
 
     // 1. the layers, bottom up; a row of pre has the same owner in every product of a layer (step_matvec: the owner depends on nout alone)
     for (int l = 0; l < L; ++l) {
-        const float* bias = Bv(S.bl[l]);
+        const float* bias = st.V(S.bl[l]);
         if (l == 0) {
-            step_matvec(W(S.wx), es, KPd, G, [&](int n, float acc) { pre[n] = acc + bias[n]; });
+            step_matvec(st.W(S.wx), es, KPd, G, [&](int n, float acc) { pre[n] = acc + bias[n]; });
             if (L == 1) {                                                        // W_rec on h_prev; at position 0 o_prev = 0: W_hh on dec_h0
-                step_matvec(W(first ? S.wb[0] : S.wa[0]), hp, KPd, G, [&](int n, float acc) { pre[n] += acc; });
+                step_matvec(st.W(first ? S.wb[0] : S.wa[0]), hp, KPd, G, [&](int n, float acc) { pre[n] += acc; });
             } else {
-                if (!first) step_matvec(W(S.wa[0]), hp + (L - 1) * KD, KPd, G, [&](int n, float acc) { pre[n] += acc; });     // o_prev
-                step_matvec(W(S.wb[0]), hp, KPd, G, [&](int n, float acc) { pre[n] += acc; });
+                if (!first) step_matvec(st.W(S.wa[0]), hp + (L - 1) * KD, KPd, G, [&](int n, float acc) { pre[n] += acc; });     // o_prev
+                step_matvec(st.W(S.wb[0]), hp, KPd, G, [&](int n, float acc) { pre[n] += acc; });
             }
         } else {
-            step_matvec(W(S.wa[l]), hc, KPd, G, [&](int n, float acc) { pre[n] = acc + bias[n]; });                           // h^{l-1}_t
-            step_matvec(W(S.wb[l]), hp + l * KD, KPd, G, [&](int n, float acc) { pre[n] += acc; });
+            step_matvec(st.W(S.wa[l]), hc, KPd, G, [&](int n, float acc) { pre[n] = acc + bias[n]; });                           // h^{l-1}_t
+            step_matvec(st.W(S.wb[l]), hp + l * KD, KPd, G, [&](int n, float acc) { pre[n] += acc; });
         }
         __syncthreads();                                                         // pre is whole; every read of hc by this layer is over
-        const float* c0 = Bv(S.c0);
+        const float* c0 = st.V(S.c0);
         for (int j = tid; j < d; j += MMT_DEC_STEP_THREADS) {
-            const float cprev = first ? c0[l * d + j] : st_in[(size_t)l * 2 * d + d + j];
-            const float ig = sigmoid_f(pre[j]), fg = sigmoid_f(pre[d + j]), gg = tanh_f(pre[2 * d + j]), og = sigmoid_f(pre[3 * d + j]);
-            const float c = fg * cprev + ig * gg;
-            const float h = og * tanh_f(c);
-            st_out[(size_t)l * 2 * d + j] = h; st_out[(size_t)l * 2 * d + d + j] = c;
-            hc[j] = step_bf16_round(h);
+            const float cprev = first ? c0[l * d + j] : st.in[(size_t)l * 2 * d + d + j];
+            const StepCell u = step_lstm_cell(pre, d, j, cprev, false);
+            st.out[(size_t)l * 2 * d + j] = u.h; st.out[(size_t)l * 2 * d + d + j] = u.c;
+            hc[j] = step_bf16_round(u.h);
         }
         __syncthreads();                                                         // hc is whole; every read of pre is over
     }
 
     // 2. read-out (multiTransformer.py:480-483) and the window's mask
-    {
-        const float* top = L ? hc : es;
-        const float* b1 = Bv(S.b1);
-        step_matvec(W(S.w1), top, KPd, S.hdim, [&](int n, float acc) { hid[n] = step_bf16_round(fmaxf(acc + b1[n], 0.f)); });
-        __syncthreads();
-        const float* b2 = Bv(S.b2);
-        const bool masked = P.mask != nullptr;
-        const float mk = masked ? P.mask[b] : 1.f;
-        step_matvec(W(S.w2), hid, S.KPh, 1, [&](int n, float acc) {
-            const float v = acc + b2[n];
-            P.y[b + n] = masked ? v * mk : v;
-        });
-    }
-    if (SLOTS && advance != 0 && tid == 0) pos[b] = t + 1;                       // t < INT_MAX by slot_decode: no overflow.  Read by the next launch only
+    step_readout(st.W(S.w1), st.V(S.b1), st.W(S.w2), st.V(S.b2), L ? hc : es, KPd, hid, S.hdim, S.KPh, P.mask, b, P.y + b, 1);
+    step_advance<SLOTS>(pos, b, t, advance);
 }
 
 __global__ __launch_bounds__(MMT_DEC_STEP_THREADS) void decoder_step_kernel(const DecStepParams P) { decoder_step_body<false>(P, nullptr, 0, 0); }

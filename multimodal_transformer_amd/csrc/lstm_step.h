@@ -26,18 +26,13 @@
 // launch.  Every address comes from (b < B, layer, p & 1, (p - i) % L) and the plan's offsets alone: t is a launch argument checked by
 // the host, and the kernel returns at once when t < 0.  No address is derived from device data.
 //
-// The positioned form, lstm_step_slots_kernel: the same body (a compile-time switch), with the position of each sequence read from
-// device memory, int pos[B] (step_slots.h), exactly as decoder_step_slots_kernel has it: one read of pos[b], made wave-uniform, decoded
-// by slot_decode against the launch argument `limit` (<= 0: none).  An idle or full slot is skipped: its row of y is written as zeros and
-// nothing else.  If `advance` is set one thread stores p + 1 to pos[b] after the last stage.  Every address derived from pos[b] passes
-// slot_decode first; what it lets through selects the copy, p & 1, and the ring slots.
+// The positioned form, lstm_step_slots_kernel: the same body with the position of each sequence read from device memory, as
+// step_common.h describes it for every carried-state step.  What slot_decode lets through selects the copy, p & 1, and the ring slots.
 #pragma once
 #include "common.h"
-#include "scan_common.h"                 // sigmoid_f, tanh_f
-#include "step_common.h"
+#include "step_common.h"                 // step_matvec and the spine: step_enter, step_state, step_lstm_cell, step_readout, step_advance
 #include "local_attn.h"                  // la_row_softmax
 #include "lstm_step_plan.h"
-#include "step_slots.h"                  // slot_decode
 
 static_assert(MMT_LSTM_STEP_THREADS == MMT_STEP_THREADS, "step_matvec is written for one workgroup size");
 static_assert(MMT_LSTM_STEP_MAX_TAPS == MMT_LA_MAXL, "the taps of the batch path");
@@ -51,7 +46,7 @@ struct LstmStepParams {
     LstmStepPlan pl;
 };
 
-// SLOTS false: t = P.t (pos, limit and advance unused).  SLOTS true: t = slot_decode(pos[b], limit), P.t unused.
+// SLOTS: the positioned form (step_common.h: step_enter).
 template <bool SLOTS>
 __device__ __forceinline__ void lstm_step_body(const LstmStepParams& P, int* pos, int limit, int advance) {
     constexpr int KI = MMT_LSTM_STEP_MAX_IN, KE = MMT_LSTM_STEP_MAX_E, KH = MMT_LSTM_STEP_MAX_H, ML = MMT_LSTM_STEP_MAX_LAYERS;
@@ -66,25 +61,15 @@ __device__ __forceinline__ void lstm_step_body(const LstmStepParams& P, int* pos
 
     const LstmStepPlan& S = P.pl;
     const int tid = threadIdx.x, b = blockIdx.x;
-    int t;
-    if (SLOTS) {
-        t = slot_decode(__builtin_amdgcn_readfirstlane(pos[b]), limit);          // the one read of pos[b]; uniform, so t lives in an SGPR
-        if (t == MMT_SLOT_SKIP) {                                                // idle or full: a zero row and nothing else
-            if (tid == 0) P.y[b] = 0.f;
-            return;
-        }
-    } else {
-        t = P.t;
-        if (t < 0) return;                                                       // the host refuses such a call
+    const int t = step_enter<SLOTS>(pos, b, limit, P.t);
+    if (t == MMT_SLOT_SKIP) {                                                    // idle or full: a zero row and nothing else
+        if (SLOTS && tid == 0) P.y[b] = 0.f;
+        return;
     }
     const int E = S.E, H = S.H, NL = S.NL, L = S.L, G = 4 * H;
     const bool first = t == 0;                                                   // uniform: no word of the dynamic state is read
-    float* dyn = reinterpret_cast<float*>(P.state + S.dyn_off);
-    const float* st_in = dyn + ((size_t)(t & 1) * P.B + b) * S.seq_floats;
-    float* st_out = dyn + ((size_t)((t & 1) ^ 1) * P.B + b) * S.seq_floats;
+    const StepState st = step_state(P.state, S.dyn_off, S.seq_floats, t, P.B, b);
     float* ring = reinterpret_cast<float*>(P.state + S.ring_off) + (size_t)b * S.ring_seq_floats;
-    auto W = [&](size_t off) { return reinterpret_cast<const bf16*>(P.state + off); };
-    auto Bv = [&](size_t off) { return reinterpret_cast<const float*>(P.state + off); };
     const bool masked = P.mask != nullptr;
     const float mk = masked ? P.mask[b] : 1.f;
 
@@ -97,45 +82,43 @@ __device__ __forceinline__ void lstm_step_body(const LstmStepParams& P, int* pos
         if (!first)
             for (int l = 0; l < NL; ++l)
                 for (int k = tid; k < S.KPh; k += MMT_LSTM_STEP_THREADS)
-                    hp[l * KH + k] = k < H ? step_bf16_round(st_in[(size_t)l * 2 * H + k]) : 0.f;
+                    hp[l * KH + k] = k < H ? step_bf16_round(st.in[(size_t)l * 2 * H + k]) : 0.f;
         __syncthreads();
     }
 
     // 1. embed: it feeds two products and nothing else, so only its rounded value is kept
     {
-        const float* be = Bv(S.be);
-        step_matvec(W(S.we), xs, S.KPin, E, [&](int n, float acc) { emb[n] = step_bf16_round(fmaxf(acc + be[n], 0.f)); });
+        const float* be = st.V(S.be);
+        step_matvec(st.W(S.we), xs, S.KPin, E, [&](int n, float acc) { emb[n] = step_bf16_round(fmaxf(acc + be[n], 0.f)); });
         __syncthreads();
     }
 
     // 2. the attention MLP's hidden row and layer 0's input product (linear_pair on the embedding), then the logits
     {
-        const float* ba0 = Bv(S.ba0);
-        const float* b0 = Bv(S.bl[0]);
-        step_matvec(W(S.wa0), emb, S.KPe, E, [&](int n, float acc) { hid[n] = step_bf16_round(fmaxf(acc + ba0[n], 0.f)); });
-        step_matvec(W(S.wih[0]), emb, S.KPe, G, [&](int n, float acc) { pre[n] = acc + b0[n]; });
+        const float* ba0 = st.V(S.ba0);
+        const float* b0 = st.V(S.bl[0]);
+        step_matvec(st.W(S.wa0), emb, S.KPe, E, [&](int n, float acc) { hid[n] = step_bf16_round(fmaxf(acc + ba0[n], 0.f)); });
+        step_matvec(st.W(S.wih[0]), emb, S.KPe, G, [&](int n, float acc) { pre[n] = acc + b0[n]; });
         __syncthreads();
-        const float* ba2 = Bv(S.ba2);
-        step_matvec(W(S.wa2), hid, S.KPe, L, [&](int n, float acc) { zs[n] = acc + ba2[n]; });
+        const float* ba2 = st.V(S.ba2);
+        step_matvec(st.W(S.wa2), hid, S.KPe, L, [&](int n, float acc) { zs[n] = acc + ba2[n]; });
     }
 
     // 3. the layers, bottom up; a row of pre has the same owner in every product of a layer (step_matvec: the owner depends on nout alone)
     for (int l = 0; l < NL; ++l) {
         if (l > 0) {
-            const float* bias = Bv(S.bl[l]);
-            step_matvec(W(S.wih[l]), hc, S.KPh, G, [&](int n, float acc) { pre[n] = acc + bias[n]; });                         // h^{l-1}_t
+            const float* bias = st.V(S.bl[l]);
+            step_matvec(st.W(S.wih[l]), hc, S.KPh, G, [&](int n, float acc) { pre[n] = acc + bias[n]; });                         // h^{l-1}_t
         }
-        if (!first) step_matvec(W(S.whh[l]), hp + l * KH, S.KPh, G, [&](int n, float acc) { pre[n] += acc; });
+        if (!first) step_matvec(st.W(S.whh[l]), hp + l * KH, S.KPh, G, [&](int n, float acc) { pre[n] += acc; });
         __syncthreads();                                                         // pre is whole; every read of hc by this layer is over
         const bool top = l == NL - 1;
         for (int j = tid; j < H; j += MMT_LSTM_STEP_THREADS) {
-            const float cprev = first ? 0.f : st_in[(size_t)l * 2 * H + H + j];
-            const float ig = sigmoid_f(pre[j]), fg = sigmoid_f(pre[H + j]), gg = tanh_f(pre[2 * H + j]), og = sigmoid_f(pre[3 * H + j]);
-            const float c = first ? ig * gg : fg * cprev + ig * gg;
-            const float h = og * tanh_f(c);
-            st_out[(size_t)l * 2 * H + j] = h; st_out[(size_t)l * 2 * H + H + j] = c;
-            hc[j] = step_bf16_round(h);
-            if (top) htop[j] = masked ? h * mk : h;
+            const float cprev = first ? 0.f : st.in[(size_t)l * 2 * H + H + j];
+            const StepCell u = step_lstm_cell(pre, H, j, cprev, first);
+            st.out[(size_t)l * 2 * H + j] = u.h; st.out[(size_t)l * 2 * H + H + j] = u.c;
+            hc[j] = step_bf16_round(u.h);
+            if (top) htop[j] = masked ? u.h * mk : u.h;
         }
         __syncthreads();                                                         // hc (and zs, htop) whole; every read of pre is over
     }
@@ -157,17 +140,8 @@ __device__ __forceinline__ void lstm_step_body(const LstmStepParams& P, int* pos
     }
 
     // 5. read-out and the window's mask
-    {
-        const float* bd0 = Bv(S.bd0);
-        step_matvec(W(S.wd0), hc, S.KPh, E, [&](int n, float acc) { hid[n] = step_bf16_round(fmaxf(acc + bd0[n], 0.f)); });
-        __syncthreads();
-        const float* bd2 = Bv(S.bd2);
-        step_matvec(W(S.wd2), hid, S.KPe, 1, [&](int n, float acc) {
-            const float v = acc + bd2[n];
-            P.y[b + n] = masked ? v * mk : v;
-        });
-    }
-    if (SLOTS && advance != 0 && tid == 0) pos[b] = t + 1;                       // t < INT_MAX by slot_decode: no overflow.  Read by the next launch only
+    step_readout(st.W(S.wd0), st.V(S.bd0), st.W(S.wd2), st.V(S.bd2), hc, S.KPh, hid, E, S.KPe, P.mask, b, P.y + b, 1);
+    step_advance<SLOTS>(pos, b, t, advance);
 }
 
 __global__ __launch_bounds__(MMT_LSTM_STEP_THREADS) void lstm_step_kernel(const LstmStepParams P) { lstm_step_body<false>(P, nullptr, 0, 0); }

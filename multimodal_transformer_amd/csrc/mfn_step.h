@@ -17,19 +17,12 @@
 // pattern cannot reach a result and a new recording needs no launch.  Every address comes from (b < B, t & 1) and the plan's offsets
 // alone: t is a launch argument checked by the host, and the kernel returns at once when t < 0.  No address is derived from device data.
 //
-// The positioned form, mfn_step_slots_kernel: the same body (a compile-time switch), with the position of each sequence read from
-// device memory, int pos[B] (step_slots.h).  Workgroup b reads p = pos[b] once, before anything else, makes it wave-uniform
-// (readfirstlane) and decodes it against the launch argument `limit` (<= 0: none).  An idle or full slot is skipped: its row of y is
-// written as zeros and nothing else, no carried state, no pos.  Otherwise the body runs with t = p: copy p & 1 is read and the other
-// written, per sequence, and if `advance` is set one thread stores p + 1 to pos[b] after the last stage.  No other workgroup reads
-// pos[b], so both contracts above hold.  The last sentence of the state discipline changes for this form: every address derived from
-// pos[b] passes slot_decode first, with the limit taken from the launch arguments; what it lets through only selects the copy, p & 1.
+// The positioned form, mfn_step_slots_kernel: the same body with the position of each sequence read from device memory, as
+// step_common.h describes it for every carried-state step; both contracts above hold for it, with slot_decode in the host's place.
 #pragma once
 #include "common.h"
-#include "scan_common.h"                 // sigmoid_f, tanh_f
-#include "step_common.h"
+#include "step_common.h"                 // step_matvec and the spine: step_enter, step_state, step_lstm_cell, step_readout, step_advance
 #include "mfn_step_plan.h"
-#include "step_slots.h"                  // slot_decode
 
 static_assert(MMT_MFN_STEP_THREADS == MMT_STEP_THREADS, "step_matvec is written for one workgroup size");
 
@@ -52,7 +45,7 @@ __device__ __forceinline__ float step_block_max(float v, float* red) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-// SLOTS false: t = P.t (pos, limit and advance unused).  SLOTS true: t = slot_decode(pos[b], limit), P.t unused.
+// SLOTS: the positioned form (step_common.h: step_enter).
 template <bool SLOTS>
 __device__ __forceinline__ void mfn_step_body(const MfnStepParams& P, int* pos, int limit, int advance) {
     constexpr int MD = MMT_MFN_STEP_MD, HG = MMT_MFN_STEP_HG, SHM = MMT_MFN_STEP_MAX_SH;
@@ -76,24 +69,14 @@ __device__ __forceinline__ void mfn_step_body(const MfnStepParams& P, int* pos, 
 
     const MfnStepPlan& L = P.pl;
     const int tid = threadIdx.x, b = blockIdx.x;
-    int t;
-    if (SLOTS) {
-        t = slot_decode(__builtin_amdgcn_readfirstlane(pos[b]), limit);          // the one read of pos[b]; uniform, so t lives in an SGPR
-        if (t == MMT_SLOT_SKIP) {                                                // idle or full: a zero row and nothing else
-            for (int n = tid; n < L.OD; n += MMT_MFN_STEP_THREADS) P.y[(size_t)b * L.OD + n] = 0.f;
-            return;
-        }
-    } else {
-        t = P.t;
-        if (t < 0) return;                                                       // the host refuses such a call
+    const int t = step_enter<SLOTS>(pos, b, limit, P.t);
+    if (t == MMT_SLOT_SKIP) {                                                    // idle or full: a zero row and nothing else
+        if (SLOTS) for (int n = tid; n < L.OD; n += MMT_MFN_STEP_THREADS) P.y[(size_t)b * L.OD + n] = 0.f;
+        return;
     }
     const int SH = L.SH, A = L.A, nm = L.nm;
     const bool first = t == 0;                                                   // uniform: no word of the state is read
-    float* dyn = reinterpret_cast<float*>(P.state + L.dyn_off);
-    const float* st_in = dyn + ((size_t)(t & 1) * P.B + b) * L.seq_floats;
-    float* st_out = dyn + ((size_t)((t & 1) ^ 1) * P.B + b) * L.seq_floats;
-    auto W = [&](size_t off) { return reinterpret_cast<const bf16*>(P.state + off); };
-    auto Bv = [&](size_t off) { return reinterpret_cast<const float*>(P.state + off); };
+    const StepState st = step_state(P.state, L.dyn_off, L.seq_floats, t, P.B, b);
 
     // the cell unit of this thread: modality mu, unit ju of it
     int mu = 0;
@@ -103,20 +86,20 @@ __device__ __forceinline__ void mfn_step_body(const MfnStepParams& P, int* pos, 
 
     // 0. stage x_m, h_prev and mem_prev (rounded where they feed a product); c_prev of this thread's unit stays in a register
     float cprev = 0.f;
-    if (!first && unit) cprev = st_in[SH + tid];
+    if (!first && unit) cprev = st.in[SH + tid];
     for (int m = 0; m < nm; ++m) {
         const int D = L.D[m], H = L.H[m];
         const float* xr = P.x[m] + (size_t)b * D;
         for (int k = tid; k < L.KPD[m]; k += MMT_MFN_STEP_THREADS) xs[L.xoff[m] + k] = k < D ? step_bf16_round(xr[k]) : 0.f;
         for (int k = tid; k < L.KPH[m]; k += MMT_MFN_STEP_THREADS) {
             float v = 0.f;
-            if (!first && k < H) v = step_bf16_round(st_in[L.hoff[m] + k]);
+            if (!first && k < H) v = step_bf16_round(st.in[L.hoff[m] + k]);
             hs[L.hpoff[m] + k] = v;
         }
     }
     if (tid < MD) {
         float v = 0.f;
-        if (!first) v = st_in[2 * SH + tid];
+        if (!first) v = st.in[2 * SH + tid];
         memf[tid] = v; memr[tid] = step_bf16_round(v);
     }
     for (int k = L.KL + tid; k < L.KPL; k += MMT_MFN_STEP_THREADS) last[k] = 0.f;           // the pad of the read-out's input
@@ -125,17 +108,15 @@ __device__ __forceinline__ void mfn_step_body(const MfnStepParams& P, int* pos, 
     // 1. LSTM cells (:207-208): pre = bf16(x) W_ih^T + (b_ih + b_hh) + bf16(h_prev) W_hh^T; a row has the same owner in both products
     for (int m = 0; m < nm; ++m) {
         float* pm = pre + 4 * L.hoff[m];
-        const float* bias = Bv(L.blstm[m]);
-        step_matvec(W(L.wih[m]), xs + L.xoff[m], L.KPD[m], 4 * L.H[m], [&](int n, float acc) { pm[n] = acc + bias[n]; });
-        if (!first) step_matvec(W(L.whh[m]), hs + L.hpoff[m], L.KPH[m], 4 * L.H[m], [&](int n, float acc) { pm[n] += acc; });
+        const float* bias = st.V(L.blstm[m]);
+        step_matvec(st.W(L.wih[m]), xs + L.xoff[m], L.KPD[m], 4 * L.H[m], [&](int n, float acc) { pm[n] = acc + bias[n]; });
+        if (!first) step_matvec(st.W(L.whh[m]), hs + L.hpoff[m], L.KPH[m], 4 * L.H[m], [&](int n, float acc) { pm[n] += acc; });
     }
     __syncthreads();
     if (unit) {
-        const float* pm = pre + 4 * L.hoff[mu];
-        const float ig = sigmoid_f(pm[ju]), fg = sigmoid_f(pm[Hu + ju]), gg = tanh_f(pm[2 * Hu + ju]), og = sigmoid_f(pm[3 * Hu + ju]);
-        const float c = fg * cprev + ig * gg;
-        const float h = og * tanh_f(c);
-        st_out[tid] = h; st_out[SH + tid] = c;
+        const StepCell u = step_lstm_cell(pre + 4 * L.hoff[mu], Hu, ju, cprev, false);
+        const float h = u.h, c = u.c;
+        st.out[tid] = h; st.out[SH + tid] = c;
         // 2. cStar = [c_prev of every modality ; c_new of every modality] (:212-217)
         cs[tid] = cprev; cs[SH + tid] = c;
         csr[tid] = step_bf16_round(cprev); csr[SH + tid] = step_bf16_round(c);
@@ -145,11 +126,11 @@ __device__ __forceinline__ void mfn_step_body(const MfnStepParams& P, int* pos, 
 
     // 3. attention over the A features (:218-219), softmax_mul_fwd_kernel's formula
     {
-        const float* b1 = Bv(L.b[MFN_B_A11]);
-        step_matvec(W(L.w[MFN_W_A11]), csr, A, MMT_MFN_STEP_ATT1, [&](int n, float acc) { a1[n] = step_bf16_round(fmaxf(acc + b1[n], 0.f)); });
+        const float* b1 = st.V(L.b[MFN_B_A11]);
+        step_matvec(st.W(L.w[MFN_W_A11]), csr, A, MMT_MFN_STEP_ATT1, [&](int n, float acc) { a1[n] = step_bf16_round(fmaxf(acc + b1[n], 0.f)); });
         __syncthreads();
-        const float* b2 = Bv(L.b[MFN_B_A12]);
-        step_matvec(W(L.w[MFN_W_A12]), a1, MMT_MFN_STEP_ATT1, A, [&](int n, float acc) { lg[n] = acc + b2[n]; });
+        const float* b2 = st.V(L.b[MFN_B_A12]);
+        step_matvec(st.W(L.w[MFN_W_A12]), a1, MMT_MFN_STEP_ATT1, A, [&](int n, float acc) { lg[n] = acc + b2[n]; });
         __syncthreads();
         float mx = -INFINITY;
         for (int n = tid; n < A; n += MMT_MFN_STEP_THREADS) mx = fmaxf(mx, lg[n]);
@@ -164,48 +145,38 @@ __device__ __forceinline__ void mfn_step_body(const MfnStepParams& P, int* pos, 
 
     // 4. att2_fc1 and the gates' first layers (:220-223): all three read bf16(attended) or bf16(mem_prev) only
     {
-        const float* b21 = Bv(L.b[MFN_B_A21]);
-        step_matvec(W(L.w[MFN_W_A21]), at, A, MMT_MFN_STEP_ATT2, [&](int n, float acc) { a2[n] = step_bf16_round(fmaxf(acc + b21[n], 0.f)); });
-        const float* bg = Bv(L.b[MFN_B_G1]);
-        step_matvec(W(L.w[MFN_W_WA]), at, A, 2 * HG, [&](int n, float acc) {                 // apre; with mem = 0 it is already u's argument
+        const float* b21 = st.V(L.b[MFN_B_A21]);
+        step_matvec(st.W(L.w[MFN_W_A21]), at, A, MMT_MFN_STEP_ATT2, [&](int n, float acc) { a2[n] = step_bf16_round(fmaxf(acc + b21[n], 0.f)); });
+        const float* bg = st.V(L.b[MFN_B_G1]);
+        step_matvec(st.W(L.w[MFN_W_WA]), at, A, 2 * HG, [&](int n, float acc) {                 // apre; with mem = 0 it is already u's argument
             const float v = acc + bg[n];
             us[n] = first ? step_bf16_round(fmaxf(v, 0.f)) : v;
         });
         if (!first)                                                                          // the same owner per row as the product above
-            step_matvec(W(L.w[MFN_W_WM]), memr, MD, 2 * HG, [&](int n, float acc) { us[n] = step_bf16_round(fmaxf(us[n] + acc, 0.f)); });
+            step_matvec(st.W(L.w[MFN_W_WM]), memr, MD, 2 * HG, [&](int n, float acc) { us[n] = step_bf16_round(fmaxf(us[n] + acc, 0.f)); });
         __syncthreads();
     }
 
     // 5. chat (:220), the gates (:222-223) and the memory (:224)
     {
-        const float* b22 = Bv(L.b[MFN_B_A22]);
-        step_matvec(W(L.w[MFN_W_A22]), a2, MMT_MFN_STEP_ATT2, MD, [&](int n, float acc) { chat[n] = tanh_f(acc + b22[n]); });
-        const float* bz1 = Bv(L.b[MFN_B_G21]);
-        step_matvec(W(L.w[MFN_W_W21]), us, HG, MD, [&](int n, float acc) { g1[n] = sigmoid_f(acc + bz1[n]); });
+        const float* b22 = st.V(L.b[MFN_B_A22]);
+        step_matvec(st.W(L.w[MFN_W_A22]), a2, MMT_MFN_STEP_ATT2, MD, [&](int n, float acc) { chat[n] = tanh_f(acc + b22[n]); });
+        const float* bz1 = st.V(L.b[MFN_B_G21]);
+        step_matvec(st.W(L.w[MFN_W_W21]), us, HG, MD, [&](int n, float acc) { g1[n] = sigmoid_f(acc + bz1[n]); });
         __syncthreads();
-        const float* bz2 = Bv(L.b[MFN_B_G22]);
-        step_matvec(W(L.w[MFN_W_W22]), us + HG, HG, MD, [&](int n, float acc) {
+        const float* bz2 = st.V(L.b[MFN_B_G22]);
+        step_matvec(st.W(L.w[MFN_W_W22]), us + HG, HG, MD, [&](int n, float acc) {
             const float mem = g1[n] * memf[n] + sigmoid_f(acc + bz2[n]) * chat[n];
-            st_out[2 * SH + n] = mem;
+            st.out[2 * SH + n] = mem;
             last[SH + n] = step_bf16_round(mem);
         });
         __syncthreads();
     }
 
     // 6. read-out (:241-247) and the window's mask
-    {
-        const float* bo1 = Bv(L.b[MFN_B_O1]);
-        step_matvec(W(L.w[MFN_W_O1]), last, L.KPL, MMT_MFN_STEP_OUTH, [&](int n, float acc) { hid[n] = step_bf16_round(fmaxf(acc + bo1[n], 0.f)); });
-        __syncthreads();
-        const float* bo2 = Bv(L.b[MFN_B_O2]);
-        const bool masked = P.mask != nullptr;
-        const float mk = masked ? P.mask[b] : 1.f;
-        step_matvec(W(L.w[MFN_W_O2]), hid, MMT_MFN_STEP_OUTH, L.OD, [&](int n, float acc) {
-            const float v = acc + bo2[n];
-            P.y[(size_t)b * L.OD + n] = masked ? v * mk : v;
-        });
-    }
-    if (SLOTS && advance != 0 && tid == 0) pos[b] = t + 1;                       // t < INT_MAX by slot_decode: no overflow.  Read by the next launch only
+    step_readout(st.W(L.w[MFN_W_O1]), st.V(L.b[MFN_B_O1]), st.W(L.w[MFN_W_O2]), st.V(L.b[MFN_B_O2]), last, L.KPL, hid, MMT_MFN_STEP_OUTH, MMT_MFN_STEP_OUTH,
+                 P.mask, b, P.y + (size_t)b * L.OD, L.OD);
+    step_advance<SLOTS>(pos, b, t, advance);
 }
 
 __global__ __launch_bounds__(MMT_MFN_STEP_THREADS) void mfn_step_kernel(const MfnStepParams P) { mfn_step_body<false>(P, nullptr, 0, 0); }

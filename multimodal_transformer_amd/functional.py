@@ -1643,6 +1643,33 @@ def _stream_positions(op, positions, B, device):
                             tuple(getattr(positions, "shape", ())), getattr(positions, "device", None)))
 
 
+def _step_where(op, t, positions, limit, advance, B, device):
+    """Where a step runs, as the entry's arguments: ``(t,)`` for a position by value (a negative one is refused), else ``positions`` on
+    the device with their ``limit`` (None: none) and ``advance``."""
+    if t is not None:
+        if int(t) < 0:
+            raise ValueError("%s: position t = %d is negative" % (op, int(t)))
+        return (int(t),)
+    _stream_positions(op, positions, B, device)
+    return (positions, 0 if limit is None else int(limit), int(bool(advance)))
+
+
+def _run_step(op, entry, rows, mask, out_shape, state, nbytes, maker, where, dims):
+    """The launch of a carried-state step: ``rows`` the checked input (a tensor, or a list of them that goes as a table of pointers),
+    ``mask`` from _step_mask, ``where`` from _step_where, ``nbytes`` the family's size query for these ``dims`` (called after
+    require_hip, as its ValueError comes second) and ``maker`` the name of what allocates such a state -> y_t of ``out_shape``."""
+    many = not isinstance(rows, torch.Tensor)
+    rows = list(rows) if many else [rows]
+    dev = rows[0].device
+    _lib.require_hip(*rows, state)
+    _stream_state(op, state, nbytes(), dev, maker)
+    keep = [_f32c(x) for x in rows]                                        # alive until the launch is enqueued
+    first = (ctypes.c_void_p * len(keep))(*[x.data_ptr() for x in keep]) if many else keep[0]
+    y = torch.empty(*out_shape, dtype=torch.float32, device=dev)
+    _lib.launch(entry, first, mask, y, state, state.numel(), *where, out_shape[0], *dims)
+    return y
+
+
 def encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers):
     """Bytes of the stream state of this shape; ValueError, naming the limit, for a shape outside the step kernel's domain."""
     return _stream_bytes("mmt_encoder_stream_bytes", "encoder stream: %s", b"?", int(B), int(capacity), int(d), int(h), int(d_ff), int(n_layers))
@@ -1690,8 +1717,8 @@ def _encoder_step(op, x_t, mask_t, flat_params, state, h, d_ff, n_layers, capaci
         elif not 0 <= where[0] < capacity:
             raise ValueError("%s: position t = %d outside [0, capacity = %d): open a stream with a larger capacity" % (op, where[0], capacity))
     else:
-        _stream_positions(op, positions, B, x_t.device)
-        where = (positions, int(bool(advance)))
+        where = _step_where(op, None, positions, None, advance, B, x_t.device)
+        where = (where[0], where[2])                                       # the capacity is the limit: the entry takes none
     _lib.require_hip(x_t, flat_params, state)
     nbytes = encoder_stream_bytes(B, capacity, d, h, d_ff, n_layers)
     p_ = _stream_params(op, flat_params, d, d_ff, n_layers)
@@ -1789,21 +1816,9 @@ def _mfn_step(op, xs, mask_t, state, in_dims, hidden, output_dim, t=None, positi
                              % (op, d, getattr(x, "dtype", type(x).__name__), tuple(getattr(x, "shape", ())), getattr(x, "device", None)))
     B, dev = xs[0].shape[0], xs[0].device
     m_ = _step_mask(op, mask_t, B, dev)
-    if t is not None:
-        where = (int(t),)
-        if where[0] < 0:
-            raise ValueError("%s: position t = %d is negative" % (op, where[0]))
-    else:
-        _stream_positions(op, positions, B, dev)
-        where = (positions, 0 if limit is None else int(limit), int(bool(advance)))
-    _lib.require_hip(*xs, state)
-    nbytes = mfn_stream_bytes(B, D, H, output_dim)
-    _stream_state(op, state, nbytes, dev, "mfn_stream_state")
-    keep = [_f32c(x) for x in xs]
-    px = (ctypes.c_void_p * n)(*[x.data_ptr() for x in keep])
-    y = torch.empty(B, int(output_dim), dtype=torch.float32, device=dev)
-    _lib.launch("mmt_" + op, px, m_, y, state, state.numel(), *where, B, n, cd, ch, int(output_dim))
-    return y
+    where = _step_where(op, t, positions, limit, advance, B, dev)
+    return _run_step(op, "mmt_" + op, xs, m_, (B, int(output_dim)), state, lambda: mfn_stream_bytes(B, D, H, output_dim), "mfn_stream_state",
+                     where, (n, cd, ch, int(output_dim)))
 
 
 def mfn_stream_step(xs, mask_t, state, t, in_dims, hidden, output_dim):
@@ -1923,20 +1938,9 @@ def _decoder_step(op, e_t, mask_t, state, d, h_dim, n_layers, t=None, positions=
                          % (op, int(d), getattr(e_t, "dtype", type(e_t).__name__), tuple(getattr(e_t, "shape", ()))))
     B, dev = e_t.shape[0], e_t.device
     m_ = _step_mask(op, mask_t, B, dev)
-    if t is not None:
-        where = (int(t),)
-        if where[0] < 0:
-            raise ValueError("%s: position t = %d is negative" % (op, where[0]))
-    else:
-        _stream_positions(op, positions, B, dev)
-        where = (positions, 0 if limit is None else int(limit), int(bool(advance)))
-    _lib.require_hip(e_t, state)
-    nbytes = decoder_stream_bytes(B, d, h_dim, n_layers)
-    _stream_state(op, state, nbytes, dev, "decoder_stream_state")
-    e_ = _f32c(e_t)
-    y = torch.empty(B, 1, dtype=torch.float32, device=dev)
-    _lib.launch("mmt_" + op, e_, m_, y, state, state.numel(), *where, B, int(d), int(h_dim), int(n_layers))
-    return y
+    where = _step_where(op, t, positions, limit, advance, B, dev)
+    return _run_step(op, "mmt_" + op, e_t, m_, (B, 1), state, lambda: decoder_stream_bytes(B, d, h_dim, n_layers), "decoder_stream_state",
+                     where, (int(d), int(h_dim), int(n_layers)))
 
 
 def decoder_stream_step(e_t, mask_t, state, t, d, h_dim, n_layers):
@@ -2001,20 +2005,8 @@ def _lstm_step(op, x_t, mask_t, state, dims, t=None, positions=None, limit=None,
                          % (op, dims[0], getattr(x_t, "dtype", type(x_t).__name__), tuple(getattr(x_t, "shape", ()))))
     B, dev = x_t.shape[0], x_t.device
     m_ = _step_mask(op, mask_t, B, dev)
-    if t is not None:
-        where = (int(t),)
-        if where[0] < 0:
-            raise ValueError("%s: position t = %d is negative" % (op, where[0]))
-    else:
-        _stream_positions(op, positions, B, dev)
-        where = (positions, 0 if limit is None else int(limit), int(bool(advance)))
-    _lib.require_hip(x_t, state)
-    nbytes = lstm_stream_bytes(B, *dims)
-    _stream_state(op, state, nbytes, dev, "lstm_stream_state")
-    x_ = _f32c(x_t)
-    y = torch.empty(B, 1, dtype=torch.float32, device=dev)
-    _lib.launch("mmt_" + op, x_, m_, y, state, state.numel(), *where, B, *dims)
-    return y
+    where = _step_where(op, t, positions, limit, advance, B, dev)
+    return _run_step(op, "mmt_" + op, x_t, m_, (B, 1), state, lambda: lstm_stream_bytes(B, *dims), "lstm_stream_state", where, dims)
 
 
 def lstm_stream_step(x_t, mask_t, state, t, in_dim, embed_dim, h_dim, n_layers, attn_len):

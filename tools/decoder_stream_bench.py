@@ -16,7 +16,6 @@ the JSON line is written first, to stdout and --out, and rows outside the bound 
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -26,27 +25,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden")]
 
 import multimodal_transformer_amd as m  # noqa: E402
+from stream_bench_common import spread, timed_us  # noqa: E402
 from multimodal_transformer_amd import graphs  # noqa: E402
 from decoder_stream_ref import DEC_STEP_VS_STREAM as VS_STREAM, DEC_STEP_VS_STREAM_ROW as VS_STREAM_ROW  # noqa: E402
 
 STEPS_AT = (0, 100, 300, 499)
 WINDOWS = 500
 WIDTH, D, H = 512, 128, 8
-
-
-def timed_us(fn, reps):
-    """microseconds per call of fn over `reps` back-to-back calls, by device events"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps
-
-
-def spread(vals):
-    return {"median_us": round(statistics.median(vals), 2), "min_us": round(min(vals), 2), "max_us": round(max(vals), 2)}
 
 
 def bench_sft(args, dev, n_layers):

@@ -17,7 +17,6 @@ the batch forward (rel-L2, printed).  One JSON line on stdout (and in --out)."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -26,23 +25,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import multimodal_transformer_amd as m  # noqa: E402
+from stream_bench_common import spread, timed_us  # noqa: E402
 
 SHAPES = {"shared_300_E128_H256_L5": ("MultiLSTM", 300), "b1_1556_E512_H256_L5": ("MultiLSTMB1", 1556)}
-
-
-def timed_us(fn, reps):
-    """microseconds per call of fn over `reps` back-to-back calls, by device events"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps
-
-
-def spread(vals):
-    return {"median_us": round(statistics.median(vals), 2), "min_us": round(min(vals), 2), "max_us": round(max(vals), 2)}
 
 
 def bench_shape(cls, width, args, dev):

@@ -17,7 +17,6 @@ One JSON line per depth on stdout (and in --out)."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -26,25 +25,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import multimodal_transformer_amd as m  # noqa: E402
+from stream_bench_common import spread, timed_us  # noqa: E402
 
 RING_AT = (0, None, 499, 5000, 100000)          # None: span - 1
 PLAIN_CAPACITY = 512
 REPS = 300
-
-
-def timed_us(fn, reps):
-    """microseconds per call of fn over `reps` back-to-back calls, by device events"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps
-
-
-def spread(vals):
-    return {"median_us": round(statistics.median(vals), 2), "min_us": round(min(vals), 2), "max_us": round(max(vals), 2)}
 
 
 def _encoder(args, n_layers, dev, span):

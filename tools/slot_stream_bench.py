@@ -14,7 +14,6 @@ highest block beside it.  A step is timed as its caller sees it, host enqueue in
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -23,27 +22,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import multimodal_transformer_amd as m  # noqa: E402
+from stream_bench_common import spread, timed_us  # noqa: E402
 from multimodal_transformer_amd import graphs  # noqa: E402
 
 STEPS_AT = (0, 100, 300, 499)
 WINDOWS = 500
 MODS = ["acoustic", "image", "linguistic"]
 EMBED = {"acoustic": 88, "image": 256, "linguistic": 300}
-
-
-def timed_us(fn, reps):
-    """microseconds per call of fn over `reps` back-to-back calls, by device events"""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps
-
-
-def spread(vals):
-    return {"median_us": round(statistics.median(vals), 2), "min_us": round(min(vals), 2), "max_us": round(max(vals), 2)}
 
 
 def capture(z, step):
