@@ -448,6 +448,43 @@ int mmt_lstm_stream_step_slots(const float* x_t, const float* mask_t, float* y_t
                                int* pos, int limit, int advance, int B, int in, int E, int H, int n_layers, int attn_len,
                                mmt_stream_t stream);
 
+/* ---- The LSTM baselines whose read-out feeds its own prediction back, ONE WINDOW PER CALL (csrc/lstm_step.h, the same body with a
+ * tail; layout: csrc/lstm_feedback_step_plan.h), eval mode, free-running (the teacher-forced branch reads the current target, so it is
+ * no online predictor).  This project's own addition; with attend_over_taps on it steps
+ *   tail = 1: models.MultiEDLSTM, the decoder LSTM with the read-out MLP in its recurrence     (transformer/MFT/models.py:268-308),
+ *   tail = 2: models.MultiARLSTM, the autoregressive read-out of order ar_order                 (transformer/MFT/models.py:354-400).
+ * One step is ONE launch, one workgroup per sequence, no communication between workgroups.  Numerics: the rounding sites of the
+ * batch path (mmt_lstm_fb_scan_forward, mmt_ar_combine_forward); tail 1 sums the read-out's last layer in another, fixed, order.
+ * p_init stands in for the predictions before step 0 (the models' tgt_init); the UNMASKED prediction is what is fed back.
+ * Dimensions: those of mmt_lstm_stream_* with, for tail 1, n_layers == 1 (ar_order is ignored) and, for tail 2, ar_order 1..16.
+ * Anything above a limit is MMT_EUNSUPPORTED with the limit named in mmt_last_error(), at the size query (which then returns 0); an
+ * unknown tail, non-positive sizes, null pointers, t < 0, a p_init that is not finite and a state of fewer than
+ * mmt_lstm_feedback_stream_bytes() bytes: MMT_EINVAL, before any launch.
+ * `state`: ANY CONTENTS; every word a step reads was written by the prepare entry or by an earlier step of this recording.  It holds
+ * the state of mmt_lstm_stream_* and, behind it, tail 1: the decoder's weights, the four initial rows and two copies of (hd, cd, q)
+ * per sequence; tail 2: autoreg's weights and a ring of ar_order + 1 predictions per sequence (step t writes slot t % (ar_order + 1)
+ * and reads the ar_order slots below it, never the one it writes). */
+size_t mmt_lstm_feedback_stream_bytes(int tail, int ar_order, int B, int in, int E, int H, int n_layers, int attn_len);
+/* One launch: every parameter into the state; does not touch a carried block or a ring.  params: a HOST array of device pointers, first
+ * the 10 + 4 * n_layers of mmt_lstm_stream_prepare (the LSTM being the one that reads the embedding: `encoder` for tail 1; the
+ * read-out being out.0, out.2 for tail 1 and decoder.0, decoder.2 for tail 2), then
+ *   tail 1 (9): decoder.weight_ih_l0 (4H, 1 + H), its column 0 as a contiguous (4H) vector, decoder.weight_hh_l0 (4H, H),
+ *               decoder.bias_ih_l0, decoder.bias_hh_l0 (4H), enc_h0, enc_c0, dec_h0, dec_c0 (H each);
+ *   tail 2 (2): autoreg.weight (ar_order, H), autoreg.bias (ar_order).                  (__init__, :233-266 and :322-352) */
+int mmt_lstm_feedback_stream_prepare(const float* const* params, void* state, size_t state_bytes, int tail, int ar_order,
+                                     int B, int in, int E, int H, int n_layers, int attn_len, mmt_stream_t stream);
+/* x_t (B, in) -> y_t (B, 1) at position t = the row the model's eval forward(target=None, tgt_init=p_init) gives at [:, t]; mask_t as
+ * in mmt_lstm_stream_step.  t is passed by value; steps of one recording must be enqueued in order t = 0, 1, ... on one stream.
+ *                                                                                                        (forward, :268-308, :354-400) */
+int mmt_lstm_feedback_stream_step(const float* x_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,
+                                  int t, float p_init, int tail, int ar_order, int B, int in, int E, int H, int n_layers, int attn_len,
+                                  mmt_stream_t stream);
+/* The positioned form (the slots contract above): the step at t = pos[b], per sequence.  limit <= 0: no limit.  With advance == 0 the
+ * call is repeatable: no word it reads is one it writes.                                              (forward, :268-308, :354-400) */
+int mmt_lstm_feedback_stream_step_slots(const float* x_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,
+                                        int* pos, int limit, int advance, float p_init, int tail, int ar_order,
+                                        int B, int in, int E, int H, int n_layers, int attn_len, mmt_stream_t stream);
+
 /* ---- Fused affine map  y = act(x W^T + b) [* rowscale] on bf16 MFMA.
  * Replaces nn.Linear (+ F.relu) call sites of the path: PositionwiseFeedForward (:15-20), the four
  * attention projections (:43,55,65), embeds and read-out MLPs (:270,296,340-342,400-402).

@@ -87,6 +87,11 @@ SIGNATURES = {
     "mmt_lstm_stream_prepare": (_I, [_P, _P, _SZ] + [_I] * 6 + [_P]),
     "mmt_lstm_stream_step": (_I, [_P, _P, _P, _P, _SZ] + [_I] * 7 + [_P]),
     "mmt_lstm_stream_step_slots": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _I] + [_I] * 6 + [_P]),
+    # the same step with a tail that feeds its prediction back: (tail, ar_order, B, in, E, H, n_layers, attn_len); p_init by value
+    "mmt_lstm_feedback_stream_bytes": (_SZ, [_I] * 8),
+    "mmt_lstm_feedback_stream_prepare": (_I, [_P, _P, _SZ] + [_I] * 8 + [_P]),
+    "mmt_lstm_feedback_stream_step": (_I, [_P, _P, _P, _P, _SZ, _I, _F] + [_I] * 8 + [_P]),
+    "mmt_lstm_feedback_stream_step_slots": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _I, _F] + [_I] * 8 + [_P]),
     "mmt_linear_workspace_bytes": (_SZ, [_I] * 3),
     "mmt_linear_forward": (_I, [_P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),
     "mmt_linear_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ] + [_I] * 4 + [_P]),

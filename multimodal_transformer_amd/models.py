@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, functional as F_hip
-from .streaming import LSTMSlotStream, LSTMStream
+from .streaming import LSTMFeedbackSlotStream, LSTMFeedbackStream, LSTMSlotStream, LSTMStream
 from .multiTransformer import (MultiTransformer, MultiTransformerB3, NLPTransformer, UniFullTransformer, UniTransformer, _MOD_STREAMS,
                                _hip_device, _stream_model_checks)
 
@@ -458,6 +458,31 @@ class _LocalAttnLSTM(nn.Module):
         return LSTMSlotStream(self, batch, limit)
 
 
+class _FeedbackStreams:
+    """``feedback_stream`` / ``feedback_slot_stream`` of the two baselines whose read-out feeds its own prediction back (MultiEDLSTM,
+    MultiARLSTM): the model as a free-running online predictor.  ``stream`` / ``slot_stream`` keep refusing (the fed-back prediction is
+    carried state that ``LSTMStream`` does not have); these entries carry it (csrc/lstm_step.h with a tail).  There is no
+    teacher-forced stream: that branch reads the current target, so it predicts nothing online."""
+
+    def _feedback_refusals(self, method):
+        self._stream_refusals(method)
+
+    def feedback_stream(self, batch, tgt_init=0.0):
+        """This model as an online predictor (``streaming.LSTMFeedbackStream``): ``step(x_t (B, window_embed_size), mask_t)`` -> the
+        (B,1) row that the eval ``forward(inputs, mask, lengths, target=None, tgt_init=tgt_init)`` gives at that window, in ONE launch.
+        Eval mode, ``attend_over_taps(model)`` on.  h_dim and embed_dim up to 512: the default h_dim = 512, which ``forward`` refuses,
+        streams."""
+        self._feedback_refusals("feedback_stream")
+        return LSTMFeedbackStream(self, batch, tgt_init)
+
+    def feedback_slot_stream(self, batch, limit=None, tgt_init=0.0):
+        """``feedback_stream(batch, tgt_init)`` with slots (``streaming.LSTMFeedbackSlotStream``): ``.positions``, ``.seat``,
+        ``.release``, ``.full`` (streaming._Slots); a step can be captured into a graph (``graphs.capture_stream``).  ``limit``: windows
+        per recording after which a slot counts as full (None: none)."""
+        self._feedback_refusals("feedback_slot_stream")
+        return LSTMFeedbackSlotStream(self, batch, limit, tgt_init)
+
+
 class MultiLSTM(_LocalAttnLSTM):
     """The shared copy: transformer/SFT/models.py:144-225 (MFT, B2-Trans, B3-MFN, Performance-Eval identical) — embed dropout 0.1,
     decoder Linear, ReLU, Linear (keys decoder.0 / decoder.2).  The configuration of the shipped B1-LSTM-L.pth checkpoint."""
@@ -476,7 +501,7 @@ class MultiLSTMB1(_LocalAttnLSTM):
         super().__init__(window_embed_size, embed_dim, h_dim, n_layers, attn_len, device)
 
 
-class MultiEDLSTM(_LocalAttnLSTM):
+class MultiEDLSTM(_FeedbackStreams, _LocalAttnLSTM):
     """The encoder-decoder LSTM: transformer/MFT/models.py:222-308 (the SFT, B2-Trans, B3-MFN and Performance-Eval copies are the same).
 
         context = the front of the LSTM baseline (``_front``) with ``encoder`` as its LSTM, started from enc_h0 / enc_c0       (B,T,H)
@@ -509,9 +534,16 @@ class MultiEDLSTM(_LocalAttnLSTM):
 
     def stream(self, batch, capacity=None):
         raise NotImplementedError("MultiEDLSTM.stream: the decoder LSTM with the read-out in its recurrence carries state of its own "
-                                  "(its (h, c) and the fed-back prediction); its step is not implemented (MultiLSTM and MultiLSTMB1 stream)")
+                                  "(its (h, c) and the fed-back prediction), which this stream does not have: open "
+                                  "feedback_stream(batch, tgt_init) / feedback_slot_stream(batch, limit, tgt_init) instead")
 
     slot_stream = stream
+
+    def _feedback_refusals(self, method):
+        self._stream_refusals(method)
+        if self.n_layers != 1:
+            raise NotImplementedError("MultiEDLSTM.%s: n_layers = %d; the decoder step with the read-out in its recurrence takes "
+                                      "n_layers == 1, as forward" % (method, self.n_layers))
 
     def forward(self, inputs, mask, lengths, target=None, tgt_init=0.0):
         if self.n_layers != 1:
@@ -528,7 +560,7 @@ class MultiEDLSTM(_LocalAttnLSTM):
         return F_hip.batch_major(p.reshape(T, B, 1), mask.float())
 
 
-class MultiARLSTM(_LocalAttnLSTM):
+class MultiARLSTM(_FeedbackStreams, _LocalAttnLSTM):
     """The LSTM baseline with an autoregressive read-out: transformer/MFT/models.py:310-400 (the SFT, B2-Trans, B3-MFN, Performance-Eval
     and B1-LSTM copies are the same).
 
@@ -561,7 +593,8 @@ class MultiARLSTM(_LocalAttnLSTM):
 
     def stream(self, batch, capacity=None):
         raise NotImplementedError("MultiARLSTM.stream: the autoregressive read-out carries state of its own (its last ar_order "
-                                  "predictions or targets); its step is not implemented (MultiLSTM and MultiLSTMB1 stream)")
+                                  "predictions), which this stream does not have: open feedback_stream(batch, tgt_init) / "
+                                  "feedback_slot_stream(batch, limit, tgt_init) instead")
 
     slot_stream = stream
 
@@ -612,3 +645,18 @@ class MultiCNNLSTM(_FrontEnd):
         """``stream(batch)`` with slots: sequences are seated and released independently (``.positions``, ``.seat``, ``.release``,
         ``.full``: streaming._Slots), and a step can be captured into a graph (``graphs.capture_stream``)."""
         return _FrontEndStream(self, batch, limit, "slot_stream")
+
+    def _feedback_seq(self, method, *args):
+        if not isinstance(self.LSTM, _FeedbackStreams):
+            raise ValueError("MultiCNNLSTM.%s: the sequence model %s feeds no prediction back; open stream(batch) / "
+                             "slot_stream(batch, limit)" % (method, type(self.LSTM).__name__))
+        _stream_model_checks(self, method)
+        return _FrontEndStream(self, args[0], None, seq=getattr(self.LSTM, method)(*args))
+
+    def feedback_stream(self, batch, tgt_init=0.0):
+        """With ``lstm_cls`` MultiEDLSTM or MultiARLSTM: the window encoder at T = 1, then the sequence model's ``feedback_stream``."""
+        return self._feedback_seq("feedback_stream", batch, tgt_init)
+
+    def feedback_slot_stream(self, batch, limit=None, tgt_init=0.0):
+        """``feedback_stream(batch, tgt_init)`` with slots: the sequence model's ``feedback_slot_stream``."""
+        return self._feedback_seq("feedback_slot_stream", batch, limit, tgt_init)

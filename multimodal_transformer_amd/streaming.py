@@ -8,11 +8,15 @@ A stream keeps its position in one of two places.  A host stream (``EncoderStrea
 int32 per sequence on the device, read and advanced by the positioned kernels, so its sequences are seated and released independently
 and a step can be captured into a graph.  Each class decides that in its ``__init__`` and nowhere else.  The models refuse what cannot
 stream (``Encoder._stream_refusals``, ``MFN._stream_refusals``, ``models._LocalAttnLSTM._stream_refusals``) before they open one of
-these.
+these.  ``MultiEDLSTM`` and ``MultiARLSTM``, whose read-out feeds its own prediction back, stream free-running through entries of their
+own: ``feedback_stream`` / ``feedback_slot_stream`` (``LSTMFeedbackStream``, ``LSTMFeedbackSlotStream``).
 
 A model with a span (``causal_attention(model, span=W)``) streams from a ring K/V cache of ``span`` rows, which never fills
 (``EncoderRingStream``, ``EncoderRingSlotStream``; csrc/step_ring.h): ``ring_stream(model, batch, slots=False)`` opens the
 form each model has, with ring encoder streams inside."""
+import ctypes
+import math
+
 import torch
 
 from . import functional as F_hip
@@ -462,10 +466,10 @@ class LSTMStream:
         self._dims = (model.embed[1].in_features, model.embed_dim, model.h_dim, model.n_layers, model.attn_len)
         if self.batch < 1:
             raise ValueError("%s.stream: batch must be at least 1, got %d" % (type(model).__name__, self.batch))
-        F_hip.lstm_stream_bytes(self.batch, *self._dims)                        # ValueError naming the limit
+        self._nbytes = F_hip.lstm_stream_bytes(self.batch, *self._dims)         # ValueError naming the limit
 
     def _allocate(self):
-        self.state = F_hip.lstm_stream_state(self.batch, *self._dims, self.device)
+        self.state = F_hip._scratch(self._nbytes, self.device)                  # any contents (functional.lstm_stream_state)
         self.refresh()
 
     def refresh(self):
@@ -489,9 +493,15 @@ class LSTMStream:
     def step(self, x_t, mask_t=None):
         """x_t (B, window_embed_size) float32 on the model's device, mask_t (B), (B,1) or (B,1,1) or None -> (B,1)."""
         self._check_step(x_t, mask_t)
-        y = F_hip.lstm_stream_step(x_t, mask_t, self.state, self.t, *self._dims)
+        y = self._host_step(x_t, mask_t)
         self.t += 1
         return y
+
+    def _host_step(self, x_t, mask_t):
+        return F_hip.lstm_stream_step(x_t, mask_t, self.state, self.t, *self._dims)
+
+    def _slots_step(self, x_t, mask_t, advance):
+        return F_hip.lstm_stream_step_slots(x_t, mask_t, self.state, self.positions, *self._dims, limit=self.capacity, advance=advance)
 
 
 class LSTMSlotStream(_Slots, LSTMStream):
@@ -511,7 +521,159 @@ class LSTMSlotStream(_Slots, LSTMStream):
     def step(self, x_t, mask_t=None, advance=True):
         """As ``LSTMStream.step``.  ``advance=False`` leaves the positions, so the same windows can be stepped again."""
         self._check_step(x_t, mask_t)
-        return F_hip.lstm_stream_step_slots(x_t, mask_t, self.state, self.positions, *self._dims, limit=self.capacity, advance=advance)
+        return self._slots_step(x_t, mask_t, advance)
+
+
+# The functional layer of the two LSTM baselines whose read-out feeds its own prediction back, one window per call (include/mmt_hip.h
+# mmt_lstm_feedback_stream_*): the LSTM step with a tail, on the helpers of functional.lstm_stream_*.  It stands here, beside
+# encoder_ring_step, and not in functional.py.  tail: LSTM_TAIL_FB (MultiEDLSTM, the read-out in the decoder's recurrence) or
+# LSTM_TAIL_AR (MultiARLSTM, ar_order taps on its own predictions).  The state is the LSTM stream's with the tail's pieces behind it;
+# any contents: F_hip._scratch.  dims = (in, E, H, n_layers, attn_len), as above.
+LSTM_TAIL_FB, LSTM_TAIL_AR = 1, 2
+
+
+def lstm_feedback_stream_bytes(B, tail, ar_order, in_dim, embed_dim, h_dim, n_layers, attn_len):
+    """Bytes of the feedback stream state for ``B`` sequences; ValueError, naming the limit, for a shape outside the step kernel's domain."""
+    return F_hip._stream_bytes("mmt_lstm_feedback_stream_bytes", "%s", b"lstm feedback stream: ?", int(tail), int(ar_order), int(B), int(in_dim),
+                         int(embed_dim), int(h_dim), int(n_layers), int(attn_len))
+
+
+def lstm_feedback_stream_state(B, tail, ar_order, in_dim, embed_dim, h_dim, n_layers, attn_len, device):
+    """An unprepared feedback stream state on ``device`` (uint8; any contents)."""
+    return F_hip._scratch(lstm_feedback_stream_bytes(B, tail, ar_order, in_dim, embed_dim, h_dim, n_layers, attn_len), device)
+
+
+def lstm_feedback_stream_prepare(embed_params, attn_params, lstm_params, dec_params, tail_params, state, B, tail, ar_order,
+                                 in_dim, embed_dim, h_dim, n_layers, attn_len):
+    """Convert and copy every parameter into ``state`` (one launch; no carried block or ring is touched).  The first four groups are
+    those of ``lstm_stream_prepare`` (``lstm_params`` of the LSTM that reads the embedding, ``dec_params`` the read-out's W0 (E, H), b0,
+    W2 (1, E), b2).  ``tail_params``, LSTM_TAIL_FB: the decoder's weight_ih (4H, 1 + H), weight_hh (4H, H), bias_ih, bias_hh and the rows
+    enc_h0, enc_c0, dec_h0, dec_c0 (H elements each); LSTM_TAIL_AR: autoreg's weight (ar_order, H) and bias."""
+    op = "lstm_feedback_stream_prepare"
+    tail, K = int(tail), int(ar_order)
+    I, E, H, NL, L = int(in_dim), int(embed_dim), int(h_dim), int(n_layers), int(attn_len)
+    nbytes = lstm_feedback_stream_bytes(B, tail, K, I, E, H, NL, L)
+    front = list(embed_params) + list(attn_params) + [q for layer in lstm_params for q in layer] + list(dec_params)
+    tp = list(tail_params)
+    F_hip._forward_only(op, front + tp, F_hip._PARAMS_GRAD)
+    want = [(E, I), (E,), (E, E), (E,), (L, E), (L,)]
+    want += [s for l in range(NL) for s in ((4 * H, E if l == 0 else H), (4 * H, H), (4 * H,), (4 * H,))]
+    want += [(E, H), (E,), (1, E), (1,)]
+    if tail == LSTM_TAIL_FB:
+        want += [(4 * H, 1 + H), (4 * H, H), (4 * H,), (4 * H,)] + [(H,)] * 4
+        tp = tp[:4] + [q.reshape(-1) if isinstance(q, torch.Tensor) and q.numel() == H else q for q in tp[4:]]      # (n_layers, 1, H) rows
+    else:
+        want += [(K, H), (K,)]
+    if [tuple(q.shape) for q in front + tp] != want:
+        raise ValueError("%s: the parameters have the shapes %s, expected %s" % (op, [tuple(q.shape) for q in front + tp], want))
+    F_hip._lib.require_hip(state, *front, *tp)
+    F_hip._stream_state(op, state, nbytes, front[0].device, "lstm_feedback_stream_state")
+    if tail == LSTM_TAIL_FB:                                                # a vector job copies contiguous floats: column 0 on its own
+        tp = [tp[0], tp[0][:, 0].contiguous()] + tp[1:]
+    keep = [F_hip._f32c(q) for q in front + tp]                                   # alive until the launch is enqueued
+    table = (ctypes.c_void_p * len(keep))(*[q.data_ptr() for q in keep])
+    F_hip._lib.launch("mmt_lstm_feedback_stream_prepare", table, state, state.numel(), tail, K, int(B), I, E, H, NL, L)
+
+
+def _lstm_feedback_step(op, x_t, mask_t, state, p_init, tail, ar_order, dims, t=None, positions=None, limit=None, advance=True):
+    """Both forms of the step with a tail: the position is ``t``, by value, or ``positions`` on the device with their ``limit``."""
+    dims = tuple(int(v) for v in dims)
+    tail, K, p_init = int(tail), int(ar_order), float(p_init)
+    F_hip._forward_only(op, (x_t, mask_t))
+    if not isinstance(x_t, torch.Tensor) or x_t.dim() != 2 or x_t.dtype != torch.float32 or x_t.shape[1] != dims[0]:
+        raise ValueError("%s: x_t must be a float32 (B, %d) tensor, got %s %s"
+                         % (op, dims[0], getattr(x_t, "dtype", type(x_t).__name__), tuple(getattr(x_t, "shape", ()))))
+    if not math.isfinite(p_init):
+        raise ValueError("%s: p_init must be a finite float, got %r" % (op, p_init))
+    B, dev = x_t.shape[0], x_t.device
+    m_ = F_hip._step_mask(op, mask_t, B, dev)
+    where = F_hip._step_where(op, t, positions, limit, advance, B, dev) + (p_init, tail, K)
+    return F_hip._run_step(op, "mmt_" + op, x_t, m_, (B, 1), state, lambda: lstm_feedback_stream_bytes(B, tail, K, *dims),
+                     "lstm_feedback_stream_state", where, dims)
+
+
+def lstm_feedback_stream_step(x_t, mask_t, state, t, p_init, tail, ar_order, in_dim, embed_dim, h_dim, n_layers, attn_len):
+    """Window t of ``MultiEDLSTM`` (LSTM_TAIL_FB) or ``MultiARLSTM`` (LSTM_TAIL_AR), free-running: x_t (B, in); mask_t (B) or None ->
+    y_t (B, 1) = what the model's eval ``forward(..., target=None, tgt_init=p_init)`` gives at [:, t] with ``attend_over_taps`` on.  The
+    front's carried state, and the tail's (the decoder's (h, c) and its last unmasked prediction; the last ar_order unmasked
+    predictions), live in ``state`` (lstm_feedback_stream_state, prepared by lstm_feedback_stream_prepare), which this call advances.
+    Steps of a recording run in order t = 0, 1, ...; t and p_init are passed by value.  One launch.  Forward only."""
+    return _lstm_feedback_step("lstm_feedback_stream_step", x_t, mask_t, state, p_init, tail, ar_order,
+                               (in_dim, embed_dim, h_dim, n_layers, attn_len), t=int(t))
+
+
+def lstm_feedback_stream_step_slots(x_t, mask_t, state, positions, p_init, tail, ar_order, in_dim, embed_dim, h_dim, n_layers, attn_len,
+                                    limit=None, advance=True):
+    """``lstm_feedback_stream_step`` with the position of every sequence in device memory (csrc/step_slots.h): row b is its row at
+    t = positions[b], bit for bit, where the slot is seated, and zero, with nothing else written, where it is idle or full.  With
+    ``advance=False`` the call can be repeated: no word it reads is one it writes.  One launch; it can be captured into a graph."""
+    return _lstm_feedback_step("lstm_feedback_stream_step_slots", x_t, mask_t, state, p_init, tail, ar_order,
+                               (in_dim, embed_dim, h_dim, n_layers, attn_len), positions=positions, limit=limit, advance=advance)
+
+
+class _LSTMFeedback:
+    """What the streams of the two models whose read-out feeds its own prediction back put in place of ``LSTMStream``'s: the shape
+    (the tail, ``tgt_init``), the preparation and the call inside ``step``.  ``MultiEDLSTM``: the LSTM that reads the embedding is
+    ``encoder``, started from enc_h0 / enc_c0, and the decoder cell with the read-out ``out`` in its recurrence is the tail;
+    ``MultiARLSTM``: ``lstm`` from zero states, ``decoder`` and ``autoreg`` with the ring of the last ar_order predictions."""
+
+    def _shape(self, model, batch):
+        name = type(model).__name__
+        self.model, self.batch = model, int(batch)
+        self.device = model.embed[1].weight.device
+        self._dims = (model.embed[1].in_features, model.embed_dim, model.h_dim, model.n_layers, model.attn_len)
+        fb = hasattr(model, "encoder")                          # MultiEDLSTM; else MultiARLSTM
+        self._tail = (LSTM_TAIL_FB, 0) if fb else (LSTM_TAIL_AR, int(model.ar_order))
+        if self.batch < 1:
+            raise ValueError("%s.feedback_stream: batch must be at least 1, got %d" % (name, self.batch))
+        self._nbytes = lstm_feedback_stream_bytes(self.batch, *self._tail, *self._dims)     # ValueError naming the limit
+        if isinstance(self.tgt_init, bool) or not isinstance(self.tgt_init, (int, float)) or not math.isfinite(self.tgt_init):
+            raise ValueError("%s.feedback_stream: tgt_init must be a finite float, got %r" % (name, self.tgt_init))
+        self.tgt_init = float(self.tgt_init)
+
+    def refresh(self):
+        """Convert and copy the model's current parameters, the initial rows included, into the state (one launch); every carried
+        block, the rings and the position(s) stay."""
+        m = self.model
+        lin = lambda layer: [layer.weight.detach(), layer.bias.detach()]            # noqa: E731
+        names = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+        if self._tail[0] == LSTM_TAIL_FB:
+            lstm, readout = m.encoder, lin(m.out[0]) + lin(m.out[2])
+            tail = [getattr(m.decoder, n + "_l0").detach() for n in names] + [r.detach() for r in (m.enc_h0, m.enc_c0, m.dec_h0, m.dec_c0)]
+        else:
+            lstm, readout, tail = m.lstm, lin(m.decoder[0]) + lin(m.decoder[2]), lin(m.autoreg)
+        layers = [[getattr(lstm, "%s_l%d" % (n, l)).detach() for n in names] for l in range(m.n_layers)]
+        lstm_feedback_stream_prepare(lin(m.embed[1]), lin(m.attn[0]) + lin(m.attn[2]), layers, readout, tail, self.state, self.batch,
+                                           *self._tail, *self._dims)
+
+    def _host_step(self, x_t, mask_t):
+        return lstm_feedback_stream_step(x_t, mask_t, self.state, self.t, self.tgt_init, *self._tail, *self._dims)
+
+    def _slots_step(self, x_t, mask_t, advance):
+        return lstm_feedback_stream_step_slots(x_t, mask_t, self.state, self.positions, self.tgt_init, *self._tail, *self._dims,
+                                                     limit=self.capacity, advance=advance)
+
+
+class LSTMFeedbackStream(_LSTMFeedback, LSTMStream):
+    """``MultiEDLSTM`` / ``MultiARLSTM`` (``models.attend_over_taps`` on) run one window at a time, free-running
+    (``feedback_stream``): ``step(x_t (B, window_embed_size), mask_t)`` returns the (B,1) row that the model's eval
+    ``forward(inputs, mask, lengths, target=None, tgt_init=tgt_init)`` gives at position ``t``, in ONE kernel launch (csrc/lstm_step.h
+    with a tail), and advances ``t``.  The prediction that is fed back is one more carried value; ``tgt_init`` is fixed when the
+    stream is opened.  No cache and no capacity; ``reset()`` and ``refresh()`` as ``LSTMStream``'s."""
+
+    def __init__(self, model, batch, tgt_init=0.0):
+        self.tgt_init = tgt_init
+        LSTMStream.__init__(self, model, batch)
+
+
+class LSTMFeedbackSlotStream(_LSTMFeedback, LSTMSlotStream):
+    """``LSTMFeedbackStream`` with slots (``feedback_slot_stream``; members: ``_Slots``, ``capacity`` is the ``limit``): row b is what
+    a ``LSTMFeedbackStream`` of that recording alone gives at window ``positions[b]``, bit for bit.  ``step(..., advance=False)`` can be
+    repeated: no word it reads is one it writes (two copies of every carried block; the history ring has ar_order + 1 slots)."""
+
+    def __init__(self, model, batch, limit=None, tgt_init=0.0, positions=None):
+        self.tgt_init = tgt_init
+        LSTMSlotStream.__init__(self, model, batch, limit, positions)
 
 
 def _modality_rows(op, inputs, mods, widths, B, device, mask_t):

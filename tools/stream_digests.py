@@ -4,7 +4,8 @@
 
 Prints the first 32 hex digits of the SHA-256 of every prepared state, every y_t, the state after the steps and the positions, one
 line each (the format of profiles/r09_stream_digests.txt), for the functional host (t by value) and slots (positions on the device)
-forms and the stream classes of the four families: encoder (plain and ring cache), MFN gate, decoder, LSTM baseline.  Two runs of it
+forms and the stream classes of the families: encoder (plain and ring cache), MFN gate, decoder, LSTM baseline and, after those, the LSTM
+baselines that feed their prediction back (MultiEDLSTM, MultiARLSTM; a build without them stops there).  Two runs of it
 on two builds of the library agree line for line exactly when the builds compute the same bits on these shapes.
 
 Everything is fixed: parameters and inputs come from seeded CPU generators, every state is zero-filled before it is prepared.  The
@@ -173,6 +174,23 @@ def lstms(dev):
                lambda s, t: s.step(x[t], mk[t]))
 
 
+def feedback_lstms(dev):
+    """MultiEDLSTM and MultiARLSTM (two layers, ar_order 2: the history ring of 3 slots wraps), free-running from tgt_init 0.25"""
+    F, MM = m.streaming, m.models
+    width, p0 = 20, 0.25
+    x, mk = rows(140, width, dev), masks(dev)
+    ed = seeded(MM.MultiEDLSTM(width, embed_dim=32, h_dim=24, attn_len=3, device=dev), 11, dev)
+    ar = seeded(MM.MultiARLSTM(width, embed_dim=32, h_dim=24, n_layers=2, attn_len=3, ar_order=2, device=dev), 12, dev)
+    for label, model in (("lstm fb", ed), ("lstm ar", ar)):
+        MM.attend_over_taps(model)
+        name = type(model).__name__
+        family(label, (name + ".feedback_stream", name + ".feedback_slot_stream"),
+               lambda: model.feedback_stream(B, p0), lambda: model.feedback_slot_stream(B, tgt_init=p0),
+               lambda s, t: F.lstm_feedback_stream_step(x[t], mk[t], s.state, t, p0, *s._tail, *s._dims),
+               lambda s, pos, t: F.lstm_feedback_stream_step_slots(x[t], mk[t], s.state, pos, p0, *s._tail, *s._dims),
+               lambda s, t: s.step(x[t], mk[t]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -182,7 +200,7 @@ def main():
     dev = torch.device("cuda:0")
     print("# SHA-256 (first 32 hex digits) of stream states and outputs: zero-filled states, fixed shapes and seeds", flush=True)
     with torch.no_grad():
-        for run in (encoders, mfn, decoders, lstms):
+        for run in (encoders, mfn, decoders, lstms, feedback_lstms):
             run(dev)
     torch.cuda.synchronize()
     if args.out:
