@@ -419,6 +419,32 @@ int mmt_decoder_stream_step(const float* e_t, const float* mask_t, float* y_t, v
 int mmt_decoder_stream_step_slots(const float* e_t, const float* mask_t, float* y_t, void* state, size_t state_bytes,
                                   int* pos, int limit, int advance, int B, int d, int h_dim, int n_layers, mmt_stream_t stream);
 
+/* ---- Prefill: open a recording from its history in ONE batch forward (opt-in; eval mode, forward only; csrc/step_prefill.h, the index
+ * rule in csrc/step_prefill_plan.h).  This project's own addition.  Each entry is one launch that reads what a finished batch call left
+ * behind and writes a stream state; no step kernel, no forward kernel and no state layout changes.
+ * (dst, len): sequence b < B_src of the batch has len[b] windows, 1 <= len[b] <= P, and goes to sequence dst[b] < B_state of the
+ * state.  Both null: dst[b] = b and len[b] = P, by value (a host stream, which then continues at t = P).  Both given: two int arrays
+ * (B_src) in DEVICE memory (a slots stream); the kernel checks each pair against the launch arguments and skips one outside them.
+ * pos: the stream's positions (B_state ints, device) or null; where given, pos[dst[b]] = len[b] is stored.  Distinct dst[b].
+ * Nothing else of the state is written: no other sequence, no row >= len[b], no prepared weight.
+ * MMT_EINVAL / MMT_EUNSUPPORTED before any launch, the limit named: null pointers, dst without len, B_src > B_state, P > capacity
+ * (plain form), a workspace or a state smaller than its size query or not 16-byte aligned, and every refusal of the size queries. */
+/* Replaces P calls of mmt_encoder_stream_step (ring != 0: mmt_encoder_stream_step_ring) at t = 0 .. P - 1.  `workspace`: that of a
+ * finished mmt_encoder_forward_causal (ring: mmt_encoder_forward_band with the same span) of dims (B_src, P, d, h, f, n_layers) on
+ * this stream, at least mmt_encoder_workspace_bytes_eval() bytes; it is only read.  `state`: mmt_encoder_stream_bytes(B_state, rows,
+ * d, h, f, n_layers) bytes, rows = the capacity, or the span with ring != 0.  Per layer, K | V, sequence and head, the bf16 rows of
+ * positions < len[b] (ring: the last min(len[b], span)) go to cache row pos (ring: pos mod span), the pad columns as zeros. */
+int mmt_encoder_stream_prefill(const void* workspace, size_t workspace_bytes, void* state, size_t state_bytes,
+                               const int* dst, const int* len, int* pos, int B_src, int P, int B_state, int rows, int ring,
+                               int d, int h, int f, int n_layers, mmt_stream_t stream);
+/* Replaces P calls of mmt_decoder_stream_step at t = 0 .. P - 1 for n_layers == 1.  h_all, c_all: (P, B_src, d) fp32, what
+ * mmt_lstm_scan_forward returned for the decoder's scan over the history: row len[b] - 1 of sequence b goes to copy len[b] & 1 of the
+ * carried state of sequence dst[b], the copy step len[b] reads.  n_layers == 0 has no carried state: the positions alone (pos must be
+ * given).  n_layers > 1: MMT_EUNSUPPORTED (the stacked scan returns the top layer only).  limit: the encoder's capacity, <= 0: none. */
+int mmt_decoder_stream_prefill(const float* h_all, const float* c_all, void* state, size_t state_bytes,
+                               const int* dst, const int* len, int* pos, int B_src, int P, int B_state, int limit,
+                               int d, int h_dim, int n_layers, mmt_stream_t stream);
+
 /* ---- The LSTM baseline, ONE WINDOW PER CALL (csrc/lstm_step.h): embed, attention MLP, the n_layers LSTM cells from zero states, the
  * local attention over the last attn_len outputs with the softmax over the TAPS (mmt_local_attn_forward_taps) and the read-out MLP,
  * eval mode.  This project's own addition; it steps models._LocalAttnLSTM with attend_over_taps on (MultiLSTM, MultiLSTMB1).

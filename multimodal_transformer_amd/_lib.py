@@ -82,6 +82,9 @@ SIGNATURES = {
     "mmt_decoder_stream_prepare": (_I, [_P] * 8 + [_SZ] + [_I] * 4 + [_P]),
     "mmt_decoder_stream_step": (_I, [_P, _P, _P, _P, _SZ] + [_I] * 5 + [_P]),
     "mmt_decoder_stream_step_slots": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _I] + [_I] * 4 + [_P]),
+    # prefill of a stream state from a finished batch call: (dst, len, pos) device int32 arrays or null, then the dimensions
+    "mmt_encoder_stream_prefill": (_I, [_P, _SZ, _P, _SZ, _P, _P, _P] + [_I] * 9 + [_P]),
+    "mmt_decoder_stream_prefill": (_I, [_P, _P, _P, _SZ, _P, _P, _P] + [_I] * 7 + [_P]),
     # one window of the LSTM baseline per launch: (B, in, E, H, n_layers, attn_len); params a host array of device pointers
     "mmt_lstm_stream_bytes": (_SZ, [_I] * 6),
     "mmt_lstm_stream_prepare": (_I, [_P, _P, _SZ] + [_I] * 6 + [_P]),

@@ -1960,6 +1960,18 @@ def decoder_stream_step_slots(e_t, mask_t, state, positions, d, h_dim, n_layers,
     return _decoder_step("decoder_stream_step_slots", e_t, mask_t, state, d, h_dim, n_layers, positions=positions, limit=limit, advance=advance)
 
 
+# Prefill of a stream state (include/mmt_hip.h mmt_*_stream_prefill): its functional layer stands in streaming.py, beside
+# encoder_ring_step, and these names resolve there.
+_IN_STREAMING = ("encoder_stream_prefill", "decoder_stream_prefill", "prefill_table", "check_prefill_table")
+
+
+def __getattr__(name):
+    if name in _IN_STREAMING:
+        from . import streaming
+        return getattr(streaming, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 # The LSTM baseline, one window per call (include/mmt_hip.h mmt_lstm_stream_*): eval mode, forward only.  The state (prepared bf16
 # weights, fp32 vectors, two copies of the carried (h, c) of every layer, the ring of the local attention) takes memory with any
 # contents: _scratch.  dims = (in, E, H, n_layers, attn_len).

@@ -22,7 +22,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib, functional as F_hip
-from .streaming import LSTMFeedbackSlotStream, LSTMFeedbackStream, LSTMSlotStream, LSTMStream
+from .streaming import (LSTMFeedbackSlotStream, LSTMFeedbackStream, LSTMSlotStream, LSTMStream, _SequenceSlotStream, _SequenceStream,
+                        _prefill_at_zero, check_prefill_table)
 from .multiTransformer import (MultiTransformer, MultiTransformerB3, NLPTransformer, UniFullTransformer, UniTransformer, _MOD_STREAMS,
                                _hip_device, _stream_model_checks)
 
@@ -174,6 +175,45 @@ class _FrontEndStream:
             else:
                 x = outs[m.mods[0]]
             return self.seq.step(x.reshape(B, -1), mask_t)
+
+    def prefill(self, *args, mask=None):
+        """Open recordings from their histories in ONE forward (``streaming._SequenceStream.prefill`` behind the window encoder and the
+        fusion, run as ``forward`` runs them).  A host stream: ``prefill({mod: (B, P, W, d_raw)}, mask=None)`` -> (B, P, 1), requires
+        ``t == 0``.  With slots (``device_stream``): ``prefill(indices, {mod: (k, P, W, d_raw)}, lengths, mask=None)`` -> (k, P, 1).
+        The MFT, B3-MFN and the LSTM baselines behind the window encoder: NotImplementedError (their streams say why)."""
+        m, seq = self.model, self.seq
+        if not isinstance(seq, (_SequenceStream, _SequenceSlotStream)):
+            return seq.prefill()                                 # NotImplementedError, before any launch
+        op = "%s stream prefill" % type(m).__name__
+        slots = isinstance(seq, _SequenceSlotStream)
+        if len(args) != (3 if slots else 1):
+            raise ValueError("%s: %s" % (op, "a stream with slots takes (indices, inputs, lengths)" if slots else "a host stream takes (inputs)"))
+        inputs = args[1] if slots else args[0]
+        k = len(args[0]) if slots and hasattr(args[0], "__len__") else self.batch
+        if not isinstance(inputs, dict) or any(mod not in inputs for mod in m.mods):
+            raise ValueError("%s: inputs must be a dict with an entry for every modality %s" % (op, list(m.mods)))
+        P = None
+        for mod in m.mods:
+            x = inputs[mod]
+            if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[0] != k or x.shape[1] < 1 or (P is not None and x.shape[1] != P):
+                raise ValueError("%s: inputs[%r] must have the shape (%d, P, W, d_raw) with one P >= 1 for every modality, got %s"
+                                 % (op, mod, k, tuple(getattr(x, "shape", ()))))
+            P = x.shape[1]
+        if seq.capacity is not None and P > seq.capacity:
+            raise ValueError("%s: P = %d windows > capacity = %d: open a stream with a larger capacity" % (op, P, seq.capacity))
+        if slots:
+            check_prefill_table(op, args[0], args[2], P, self.batch, seq.capacity)
+        else:
+            _prefill_at_zero(op, seq.t)
+        with torch.no_grad():
+            outs = m._encode({mod: inputs[mod] for mod in m.mods})                          # {mod: (k,P,F_mod)}
+            if len(m.mods) > 1:
+                x = F_hip.cat_cols([outs[mod] for mod in m.mods])
+                if getattr(m, "fusionLayer", None) is not None:
+                    x = F_hip.linear(x, m.fusionLayer.weight.detach(), m.fusionLayer.bias.detach(), act=2)
+            else:
+                x = outs[m.mods[0]]
+            return seq.prefill(args[0], x, args[2], mask) if slots else seq.prefill(x, mask)
 
 
 class MultiCNNTransformer(_FrontEnd):

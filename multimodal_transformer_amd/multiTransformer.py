@@ -648,17 +648,24 @@ class _DecoderMixin:
         gates_0 = enc_0 W_ih[:, d:]^T + b  +  h0 W_hh^T                               (o_{-1} = 0, h_{-1} = dec_h0)
     i.e. one batched input projection plus one LSTM scan with W_rec = W_ih[:, :d] + W_hh.  More layers: _decode_stacked."""
 
-    def _decode(self, enc, mask):
+    def _decode(self, enc, mask, _state=None):
+        """``_state`` (internal; a list): the one-layer scan's (h_all, c_all), (T, B, d) each, are appended to it (a stream's prefill
+        keeps the last row as its carried state).  What is returned does not change."""
         B, T, d = enc.shape
         if self.decoder.num_layers != 1:
             return self._decode_stacked(enc, mask)
-        Wx, W_rec, Whh, bias = F_hip.decoder_pack(self.decoder.weight_ih_l0, self.decoder.weight_hh_l0,
-                                                  self.decoder.bias_ih_l0, self.decoder.bias_hh_l0)
+        # a prefill is inference: detached views, or an autograd node that sees a tensor requiring grad keeps its pool workspace for a
+        # backward that never comes (streaming._SequenceStream._affine says the same of a step)
+        p = (lambda q: q.detach()) if _state is not None else (lambda q: q)
+        dec, out = self.decoder, self.out
+        Wx, W_rec, Whh, bias = F_hip.decoder_pack(p(dec.weight_ih_l0), p(dec.weight_hh_l0), p(dec.bias_ih_l0), p(dec.bias_hh_l0))
         gx = F_hip.linear(F_hip.time_major(enc), Wx, bias)                                  # (T,B,4d)
-        gx = F_hip.add_row0(gx, F_hip.linear(self.dec_h0, Whh))                             # step 0 sees h0 W_hh^T (in place, no concat)
-        h_all, _ = F_hip.lstm_scan(gx, W_rec, None, F_hip.broadcast_rows(self.dec_c0, B))
-        hid = F_hip.linear(h_all, self.out[0].weight, self.out[0].bias, act=1)              # rows stay time-major ...
-        return F_hip.batch_major(F_hip.linear(hid, self.out[2].weight, self.out[2].bias), mask)   # ... until the mask pass
+        gx = F_hip.add_row0(gx, F_hip.linear(p(self.dec_h0), Whh))                          # step 0 sees h0 W_hh^T (in place, no concat)
+        h_all, c_all = F_hip.lstm_scan(gx, W_rec, None, F_hip.broadcast_rows(p(self.dec_c0), B))
+        if _state is not None:
+            _state.append((h_all, c_all))
+        hid = F_hip.linear(h_all, p(out[0].weight), p(out[0].bias), act=1)                  # rows stay time-major ...
+        return F_hip.batch_major(F_hip.linear(hid, p(out[2].weight), p(out[2].bias)), mask)   # ... until the mask pass
 
 
     def _decode_stacked(self, enc, mask):

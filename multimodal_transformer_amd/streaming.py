@@ -58,6 +58,36 @@ def _check_mask(op, mask_t, B, device):
         raise ValueError("%s: mask_t must hold one entry per sequence (%d)%s" % (op, B, "" if device is None else " on %s" % device))
 
 
+def _check_history(op, x, mask, B, width, device, limit, name="x"):
+    """The history of a prefill: ``x`` float32 (B, P, width) on ``device`` with 1 <= P (<= ``limit``, a plain cache's capacity; None:
+    a ring), ``mask`` (B, P, 1), (B, P) or None on the same device -> P.  Before any launch."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != device:
+        raise ValueError("%s: %s must be a float32 tensor on %s, got %s on %s"
+                         % (op, name, device, getattr(x, "dtype", type(x).__name__), getattr(x, "device", None)))
+    if x.dim() != 3 or x.shape[0] != B or x.shape[2] != width or x.shape[1] < 1:
+        raise ValueError("%s: %s must have the shape (%d, P, %d) with P >= 1 windows, got %s" % (op, name, B, width, tuple(x.shape)))
+    P = x.shape[1]
+    if limit is not None and P > limit:
+        raise ValueError("%s: P = %d windows > capacity = %d: open a stream with a larger capacity (a ring stream has no limit)"
+                         % (op, P, limit))
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.device != device
+                             or tuple(mask.shape) not in ((B, P), (B, P, 1))):
+        raise ValueError("%s: mask must have the shape (%d, %d, 1) or (%d, %d) on %s, got %s"
+                         % (op, B, P, B, P, device, tuple(getattr(mask, "shape", ()))))
+    return P
+
+
+def _prefill_at_zero(op, t):
+    if t != 0:
+        raise ValueError("%s: the stream stands at t = %d; a prefill opens a recording from its history, at t = 0 (a chunk cannot be "
+                         "appended): call reset() first" % (op, t))
+
+
+def _no_prefill(stream, why):
+    raise NotImplementedError("%s.prefill: %s; this stream opens a recording at window 0 only: reset() / seat(), then step through "
+                              "the history (DESIGN 4.13)" % (type(stream).__name__, why))
+
+
 def _stream_model_checks(model, method="stream"):
     if model.training:
         raise ValueError("%s.%s: the model is in train mode; streaming is eval-mode inference (call .eval())" % (type(model).__name__, method))
@@ -155,6 +185,35 @@ class EncoderStream:
         _check_row("EncoderStream.step", "x_t", x_t, self.batch, self.d, self.device, windowed=True)
         _check_mask("EncoderStream.step", mask_t, self.batch, self.device)
 
+    _ring = False                    # True in EncoderRingStream: the cache is a ring of ``span`` rows
+
+    def _fill(self, x, mask, table=None, positions=None):
+        """The batch forward over a history and the fill of the cache behind it (functional.encoder_stream_prefill) -> its rows."""
+        return encoder_stream_prefill(x, mask, self._flat, self.state, self.h, self.d_ff, self.n_layers,
+                                            self.span if self._ring else self.capacity, self.eps, ring=self._ring, batch=self.batch,
+                                            table=table, positions=positions)
+
+    def prefill(self, x, mask=None):
+        """Open the recording from its history in ONE forward: x (B, P, d), mask (B, P, 1), (B, P) or None -> (B, P, d), the rows of
+        ``Encoder.forward(x, mask)`` bit for bit; afterwards ``t == P`` and ``step`` continues as if the P windows had been stepped
+        (to the distance between the batch path's rounding and the step's).  Requires ``t == 0`` and, for a plain cache,
+        1 <= P <= capacity.  One fused forward plus ONE launch of encoder_prefill_kernel (csrc/step_prefill.h)."""
+        op = "%s.prefill" % type(self).__name__
+        _prefill_at_zero(op, self.t)
+        P = _check_history(op, x, mask, self.batch, self.d, self.device, self.capacity)
+        y = self._fill(x, mask)
+        self.t = P
+        return y
+
+    def _slots_prefill(self, indices, x, lengths, mask, set_positions):
+        op = "%s.prefill" % type(self).__name__
+        k = len(indices) if hasattr(indices, "__len__") else -1
+        if not 1 <= k <= self.batch:
+            raise ValueError("%s: indices must name 1 .. batch = %d slots, got %r" % (op, self.batch, indices))
+        P = _check_history(op, x, mask, k, self.d, self.device, self.capacity)
+        table, _, prefix = prefill_table(op, indices, lengths, P, self.batch, self.capacity, self.device)
+        return self._fill(x, prefix if mask is None else mask, table, self.positions if set_positions else None)
+
 
 class EncoderSlotStream(_Slots, EncoderStream):
     """``EncoderStream`` with slots (``Encoder.slot_stream``; members: ``_Slots``).  ``step(x_t, mask_t)`` is ONE launch of
@@ -173,6 +232,15 @@ class EncoderSlotStream(_Slots, EncoderStream):
         y = F_hip.encoder_stream_step_slots(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.positions, self.h,
                                             self.d_ff, self.n_layers, self.capacity, self.eps, advance=advance)
         return y.view(x_t.shape)
+
+    def prefill(self, indices, x, lengths, mask=None, advance=True):
+        """Open recordings in the slots ``indices`` (k distinct ints, k <= batch) from their histories in ONE forward: x (k, P, d),
+        ``lengths`` k host ints with 1 <= len <= P (<= capacity), mask (k, P[, 1]) or None: the prefix mask of the lengths -> (k, P, d),
+        the rows of ``Encoder.forward(x, mask)``.  The slots may be idle, seated or full; afterwards ``positions[indices[b]] ==
+        lengths[b]``, and not a byte of any other slot has changed.  One host-to-device copy (the table), no synchronisation; one fused
+        forward plus ONE launch of encoder_prefill_kernel.  ``advance=False`` leaves the positions (a composite stream sets them in its
+        last launch)."""
+        return self._slots_prefill(indices, x, lengths, mask, bool(advance))
 
 
 def encoder_ring_step(x_t, mask_t, flat_params, state, t, h, d_ff, n_layers, span, eps=1e-6):
@@ -193,6 +261,140 @@ def encoder_ring_step_slots(x_t, mask_t, flat_params, state, positions, h, d_ff,
                                positions=positions, advance=advance, _ring=True)
 
 
+# Prefill: a stream state filled from ONE batch forward over a recording's history (include/mmt_hip.h mmt_*_stream_prefill; the index
+# rule: csrc/step_prefill_plan.h).  Eval mode, forward only.  The functional layer stands here, beside encoder_ring_step, and
+# functional.py resolves these names here.
+def prefill_table(op, indices, lengths, P, batch, limit, device):
+    """The (dst, len) table of a slots prefill: ``indices`` k distinct ints in [0, batch), ``lengths`` k ints in [1, P] (and at most
+    ``limit``, a plain cache's capacity; None: a ring) -> (an int32 (2, k) tensor on ``device``: ONE host-to-device copy and no
+    synchronisation, the lengths as a list, the prefix mask of the lengths (k, P) float32 from the same copy).  ValueError before any
+    launch for anything else."""
+    idx, lens = check_prefill_table(op, indices, lengths, P, batch, limit)
+    # the table and the prefix mask of the lengths travel as ONE buffer: int32 [dst (k) | len (k)] and then k x P floats
+    k = len(idx)
+    host = torch.empty(2 * k + k * P, dtype=torch.int32)
+    host[:2 * k] = torch.tensor(idx + lens, dtype=torch.int32)
+    host[2 * k:].view(torch.float32).view(k, P).copy_(torch.arange(P).unsqueeze(0) < torch.tensor(lens).unsqueeze(1))
+    buf = host.to(device, non_blocking=True)
+    return buf[:2 * k].view(2, k), lens, buf[2 * k:].view(torch.float32).view(k, P)
+
+
+def check_prefill_table(op, indices, lengths, P, batch, limit):
+    """The host-side refusals of ``prefill_table`` alone -> (indices, lengths) as lists of ints.  Nothing is copied or launched."""
+    try:
+        idx, lens = [int(i) for i in indices], [int(n) for n in lengths]
+    except (TypeError, ValueError):
+        raise ValueError("%s: indices and lengths must be sequences of host ints (a device tensor would synchronise)" % op)
+    if not 1 <= len(idx) <= batch or len(lens) != len(idx):
+        raise ValueError("%s: %d indices and %d lengths for a stream of %d slots: 1 <= k <= batch, one length per index"
+                         % (op, len(idx), len(lens), batch))
+    if len(set(idx)) != len(idx) or min(idx) < 0 or max(idx) >= batch:
+        raise ValueError("%s: indices must be distinct and in [0, batch = %d), got %s" % (op, batch, idx))
+    top = P if limit is None else min(P, limit)
+    if min(lens) < 1 or max(lens) > top:
+        raise ValueError("%s: lengths must lie in [1, %d] (P = %d windows%s), got %s; a recording without a window is seated with seat()"
+                         % (op, top, P, "" if limit is None else ", capacity = %d" % limit, lens))
+    return idx, lens
+
+
+def _ones_mask(B, P, device):
+    """An all-ones (B, P) mask made on the host: a copy, not a launch."""
+    return torch.ones(B, P, dtype=torch.float32).to(device, non_blocking=True)
+
+
+def _prefill_where(op, table, positions, B_src, B_state, device):
+    """(dst, len, pos) of a prefill entry: null pointers for the host's form, the rows of ``table`` and ``positions`` for the slots form."""
+    if table is None:
+        if positions is not None:
+            F_hip._stream_positions(op, positions, B_state, device)
+        return None, None, positions
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (2, B_src) or not table.is_contiguous() \
+            or table.device != device:
+        raise ValueError("%s: table must be a contiguous int32 (2, %d) tensor on %s (prefill_table)" % (op, B_src, device))
+    if positions is not None:
+        F_hip._stream_positions(op, positions, B_state, device)
+    return table[0], table[1], positions
+
+
+def encoder_stream_prefill(x, mask, flat_params, state, h, d_ff, n_layers, rows, eps=1e-6, ring=False, batch=None, table=None,
+                           positions=None):
+    """Fill the K/V cache of an encoder stream from ONE batch forward over a history: x (B_src, P, d), mask (B_src, P[, 1]) or None ->
+    y (B_src, P, d), the rows of ``encoder_stack(x, mask, ..., causal=True)`` (``ring``: with ``span=rows``), bit for bit: the fused
+    stack's eval forward runs as one piece into a pool workspace, ``mmt_encoder_stream_prefill`` moves K and V of every layer from that
+    workspace into ``state`` on the same stream (one launch), and the workspace goes back to the pool.  ``rows``: the stream's capacity,
+    or its span with ``ring``; ``batch``: the state's sequences (default B_src).  ``table`` None: sequence b fills sequence b with all P
+    windows (a host stream then continues at t = P; plain form: P <= capacity).  ``table`` (``prefill_table``): row b fills sequence
+    table[0, b] with its first table[1, b] windows.  ``positions``: the stream's int32 positions, which the launch sets to the lengths.
+    Replaces P calls of ``encoder_stream_step`` / ``encoder_ring_step``.  Forward only."""
+    op = "encoder_stream_prefill"
+    F_hip._forward_only(op, (x, mask, flat_params), "an input or a parameter requires grad: call it under torch.no_grad() with detached inputs")
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != torch.float32:
+        raise ValueError("%s: x must be a float32 (B, P, d) tensor, got %s %s"
+                         % (op, getattr(x, "dtype", type(x).__name__), tuple(getattr(x, "shape", ()))))
+    B, P, d = x.shape
+    rows, B_state = int(rows), B if batch is None else int(batch)
+    if B < 1 or P < 1:
+        raise ValueError("%s: x has no windows (shape %s): a recording without a history opens with reset() / seat()" % (op, tuple(x.shape)))
+    if not ring and P > rows:
+        raise ValueError("%s: P = %d windows > capacity = %d: open a stream with a larger capacity" % (op, P, rows))
+    if B > B_state:
+        raise ValueError("%s: %d sequences do not fit a stream of %d" % (op, B, B_state))
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.numel() != B * P or mask.device != x.device):
+        raise ValueError("%s: mask must have B*P = %d elements (shape (B,P,1) or (B,P)) on %s" % (op, B * P, x.device))
+    lib = F_hip._lib.load()
+    F_hip._lib.require_hip(x, flat_params, state)
+    dst, length, pos = _prefill_where(op, table, positions, B, B_state, x.device)
+    nstate = F_hip.encoder_stream_bytes(B_state, rows, d, h, d_ff, n_layers)
+    p_ = F_hip._f32c16(F_hip._stream_params(op, flat_params, d, d_ff, n_layers))
+    F_hip._stream_state(op, state, nstate, x.device, "encoder_stream_state")
+    x_ = F_hip._f32c16(x)
+    m_ = _ones_mask(B, P, x.device) if mask is None else F_hip._f32c(mask).view(B, P)
+    dims = (B, P, d, int(h), int(d_ff), int(n_layers))
+    nbytes = lib.mmt_encoder_workspace_bytes_eval(*dims)
+    if nbytes == 0:
+        F_hip._lib.launch("mmt_encoder_forward", None, None, None, None, None, 0, *dims, eps, 0.0, 0)      # raises with the library's reason
+    y = torch.empty_like(x_)
+    ws = F_hip._lib.POOL.get(nbytes, x.device, tag=("encoder",) + dims + (False,))       # the eval forward's own workspaces: one shape, one layout
+    try:
+        F_hip._lib.launch("mmt_encoder_forward", x_, m_, p_, y, ws, nbytes, *dims, float(eps), 0.0, 0, causal=True, span=rows if ring else None)
+        F_hip._lib.launch("mmt_encoder_stream_prefill", ws, nbytes, state, state.numel(), dst, length, pos, B, P, B_state, rows, int(bool(ring)),
+                    d, int(h), int(d_ff), int(n_layers))
+    finally:
+        F_hip._lib.POOL.put(ws)
+    return y
+
+
+def decoder_stream_prefill(h_all, c_all, state, B_state, d, h_dim, n_layers, P, limit=None, table=None, positions=None):
+    """Seed the carried state of a decoder stream (``decoder_stream_state``) from the decoder's scan over a history: h_all, c_all
+    (P, B_src, d), what ``lstm_scan`` returned (None with ``n_layers == 0``, which carries nothing); row len - 1 of sequence b goes to the
+    copy of the carried state that step len reads.  ``table`` / ``positions`` as ``encoder_stream_prefill``; in a composite stream this
+    is the last launch, and it sets the positions, as the decoder's step advances them.  One launch.  Replaces P calls of
+    ``decoder_stream_step``.  ``n_layers > 1``: NotImplementedError (``lstm_stack_scan`` returns the top layer only)."""
+    op = "decoder_stream_prefill"
+    L, d, P, B_state = int(n_layers), int(d), int(P), int(B_state)
+    if L > 1:
+        raise NotImplementedError("%s: a decoder of n_layers = %d: lstm_stack_scan returns the top layer's states only, so a stacked "
+                                  "decoder opens at window 0: step through the history" % (op, L))
+    F_hip._forward_only(op, (h_all, c_all))
+    if L == 1:
+        for name, a in (("h_all", h_all), ("c_all", c_all)):
+            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 3 or a.shape[0] != P or a.shape[2] != d \
+                    or not a.is_contiguous():
+                raise ValueError("%s: %s must be a contiguous float32 (P = %d, B, d = %d) tensor, got %s %s"
+                                 % (op, name, P, d, getattr(a, "dtype", type(a).__name__), tuple(getattr(a, "shape", ()))))
+        if h_all.shape != c_all.shape:
+            raise ValueError("%s: h_all %s and c_all %s differ" % (op, tuple(h_all.shape), tuple(c_all.shape)))
+        B = h_all.shape[1]
+    else:
+        h_all = c_all = None
+        B = B_state if table is None else int(table.shape[1])
+    F_hip._lib.require_hip(state, h_all, c_all)
+    dst, length, pos = _prefill_where(op, table, positions, B, B_state, state.device)
+    F_hip._stream_state(op, state, F_hip.decoder_stream_bytes(B_state, d, h_dim, L), state.device, "decoder_stream_state")
+    F_hip._lib.launch("mmt_decoder_stream_prefill", h_all, c_all, state, state.numel(), dst, length, pos, B, P, B_state,
+                0 if limit is None else int(limit), d, int(h_dim), L)
+
+
 class EncoderRingStream(EncoderStream):
     """A causal ``Encoder`` with a span run one window at a time (``Encoder.ring_stream``): ``EncoderStream`` against a ring cache of
     ``span`` rows (csrc/step_ring.h).  ``step(x_t)`` returns the row that the batch forward with the span gives at position ``t``, in ONE
@@ -205,6 +407,8 @@ class EncoderRingStream(EncoderStream):
         self._shape(encoder, batch)
         self.t = 0
         self._allocate()
+
+    _ring = True
 
     def _shape(self, encoder, batch):
         """As ``EncoderStream._shape`` with capacity := span: the state, its size query and its preparation are those of a plain
@@ -239,6 +443,10 @@ class EncoderRingSlotStream(_Slots, EncoderRingStream):
         y = encoder_ring_step_slots(x_t.reshape(self.batch, self.d), mask_t, self._flat, self.state, self.positions, self.h, self.d_ff,
                                     self.n_layers, self.span, self.eps, advance=advance)
         return y.view(x_t.shape)
+
+    def prefill(self, indices, x, lengths, mask=None, advance=True):
+        """As ``EncoderSlotStream.prefill``, into the ring: the last min(len, span) windows of each history, with no limit on P."""
+        return self._slots_prefill(indices, x, lengths, mask, bool(advance))
 
 
 def _no_slot_stream(model):
@@ -312,6 +520,35 @@ class _SequenceStream:
                 e = self._h
             return self._affine(self._affine(e, m.out[0], act=1), m.out[2], rowscale=r)
 
+    def prefill(self, x, mask=None):
+        """Open the recording from its history in ONE forward: x (B, P, window_embed_size), mask (B, P, 1), (B, P) or None -> the
+        (B, P, 1) predictions of the model's eval forward over these windows, bit for bit; afterwards ``t == P``, the encoder's cache
+        holds the P windows and the decoder's carried (h, c) is the scan's state behind window P - 1.  Requires ``t == 0``."""
+        m, B = self.model, self.batch
+        op = "%s stream prefill" % type(m).__name__
+        _prefill_at_zero(op, self.enc.t)
+        P = _check_history(op, x, mask, B, self._embed.in_features, self.enc.device, self.enc.capacity)
+        with torch.no_grad():
+            y, state = _sequence_forward(m, self._embed, self._embed_act, x, mask, lambda e, mk: self.enc.prefill(e, mk))
+            if state is not None:
+                self._h, self._c = state[0][P - 1], state[1][P - 1]
+        return y
+
+
+def _sequence_forward(model, embed, embed_act, x, mask, encode):
+    """The eval forward of UniFullTransformer, UniTransformer and NLPTransformer over x (B, P, width) with ``encode(e, mask)`` in the
+    encoder's place: the launches of the model's own ``forward``, in its order -> (the (B, P, 1) predictions, (h_all, c_all) of the
+    decoder's scan or None).  ``mask`` None: every window counts."""
+    B, P = x.shape[0], x.shape[1]
+    mk = _ones_mask(B, P, x.device).view(B, P, 1) if mask is None else mask.float().reshape(B, P, 1)
+    e = _SequenceStream._affine(x, embed, act=embed_act)
+    enc = encode(e, mk)
+    if getattr(model, "decoder", None) is None:
+        hid = _SequenceStream._affine(enc, model.out[0], act=1)
+        return _SequenceStream._affine(hid, model.out[2], rowscale=mk.reshape(-1)), None
+    state = []
+    return model._decode(enc, mk, _state=state), state[0]
+
 
 class _SequenceSlotStream(_Slots):
     """``device_stream()`` of UniFullTransformer, UniTransformer and NLPTransformer: a stream whose whole per-recording state lives on the
@@ -367,6 +604,29 @@ class _SequenceSlotStream(_Slots):
             return F_hip.decoder_stream_step_slots(e, r, self.state, self.positions, self.d, self.h_dim, self.n_layers,
                                                    limit=self.capacity, advance=advance)
 
+    def prefill(self, indices, x, lengths, mask=None):
+        """Open recordings in the slots ``indices`` (k distinct ints, k <= batch) from their histories in ONE forward: x (k, P,
+        window_embed_size), ``lengths`` k host ints with 1 <= len <= P (<= capacity), mask (k, P[, 1]) or None: the prefix mask of the
+        lengths -> the (k, P, 1) predictions of the model's eval forward.  The slots may be idle, seated or full; afterwards
+        ``positions[indices[b]] == lengths[b]`` and no byte of another slot has changed.  The model's forward with ONE launch of
+        encoder_prefill_kernel behind the encoder and ONE of decoder_prefill_kernel behind the decoder's scan, which sets the
+        positions (a model without a decoder layer carries nothing: the encoder's fill sets them); one host-to-device copy (the table), no synchronisation.  A stacked decoder: NotImplementedError."""
+        m, op = self.model, "%s device_stream prefill" % type(self.model).__name__
+        if self.n_layers > 1:
+            _no_prefill(self, "a decoder of n_layers = %d: lstm_stack_scan returns the top layer's states only" % self.n_layers)
+        k = len(indices) if hasattr(indices, "__len__") else -1
+        if not 1 <= k <= self.batch:
+            raise ValueError("%s: indices must name 1 .. batch = %d slots, got %r" % (op, self.batch, indices))
+        P = _check_history(op, x, mask, k, self._embed.in_features, self.device, self.capacity)
+        table, _, prefix = prefill_table(op, indices, lengths, P, self.batch, self.capacity, self.device)
+        with torch.no_grad():
+            y, state = _sequence_forward(m, self._embed, self._embed_act, x, prefix if mask is None else mask,
+                                         lambda e, mk: self.enc._fill(e, mk, table, None if self.n_layers else self.positions))
+            if self.n_layers:                # else: the read-out alone carries nothing, and the encoder's fill has set the positions
+                decoder_stream_prefill(state[0], state[1], self.state, self.batch, self.d, self.h_dim, self.n_layers, P,
+                                             limit=self.capacity, table=table, positions=self.positions)
+        return y
+
 
 class MFNStream:
     """An ``MFN`` gate run one window at a time (``MFN.stream``): ``step({mod: (B, dims[mod])}, mask_t)`` returns the (B, output_dim)
@@ -418,6 +678,10 @@ class MFNStream:
         y = F_hip.mfn_stream_step(xs, mask_t, self.state, self.t, self.in_dims, self.hidden, self.output_dim)
         self.t += 1
         return y
+
+    def prefill(self, *args, **kwargs):
+        """Not implemented: NotImplementedError before any launch."""
+        _no_prefill(self, "the MFN gate's carried (h, c, mem) is not seeded from its batch scan yet")
 
 
 class MFNSlotStream(_Slots, MFNStream):
@@ -502,6 +766,11 @@ class LSTMStream:
 
     def _slots_step(self, x_t, mask_t, advance):
         return F_hip.lstm_stream_step_slots(x_t, mask_t, self.state, self.positions, *self._dims, limit=self.capacity, advance=advance)
+
+    def prefill(self, *args, **kwargs):
+        """Not implemented: NotImplementedError before any launch."""
+        _no_prefill(self, "the LSTM baselines' carried state, their ring of taps and a fed-back prediction are not seeded from the "
+                          "batch scans yet")
 
 
 class LSTMSlotStream(_Slots, LSTMStream):
@@ -761,6 +1030,10 @@ class _GateStream:
             if fork:
                 F_hip._MOD_STREAMS.end(main, streams, list(rows.values()))
             return self._gate_step(rows, r, advance)
+
+    def prefill(self, *args, **kwargs):
+        """Not implemented: NotImplementedError before any launch."""
+        _no_prefill(self, "the MFN gate behind the modalities is not seeded from its batch scan yet")
 
 
 class _GateSlotStream(_Slots, _GateStream):
