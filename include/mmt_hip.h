@@ -445,6 +445,35 @@ int mmt_decoder_stream_prefill(const float* h_all, const float* c_all, void* sta
                                const int* dst, const int* len, int* pos, int B_src, int P, int B_state, int limit,
                                int d, int h_dim, int n_layers, mmt_stream_t stream);
 
+/* ---- Extend: move an encoder stream forward by C windows from ANY position (opt-in; eval mode, forward only; csrc/encoder_extend.h,
+ * the index rule in csrc/encoder_extend_plan.h).  This project's own addition.  The state is the step's, untouched in layout
+ * (mmt_encoder_stream_bytes / _prepare; the ring forms with capacity := span), so step, prefill and extend mix freely on one stream.
+ * x (rows, C, d), mask (rows, C) float or NULL, y (rows, C, d): row i is what mmt_encoder_stream_step (ring: _step_ring) gives for
+ * window t + i after windows t .. t + i - 1, to fp32 summation order: the same rounding sites, every product on the matrix cores.
+ * A call runs as ceil(C / 16) launches in order on `stream`, each ONE kernel launch and nothing else; one workgroup per sequence and
+ * no communication between workgroups, so a sequence's rows do not depend on its batch.  The plain forms write cache rows
+ * t .. t + C - 1; the ring forms, of the c <= 16 rows of each launch, the last min(c, span) positions, position pos to row pos mod span.
+ * MMT_EINVAL / MMT_EUNSUPPORTED before any launch, the limit named: null pointers, C < 1, t < 0, t + C > capacity (plain form; ring:
+ * t + C reaching INT_MAX), a state smaller than its size query or not 16-byte aligned, every refusal of mmt_encoder_stream_bytes, and
+ * a shape whose 16-row working set exceeds 160 KB of LDS (d = 512 with f = 2048: step through it). */
+/* The host's form: all B sequences stand at t, passed by value, and get C windows; the stream then stands at t + C. */
+int mmt_encoder_stream_extend(const float* x, const float* mask, const float* params, float* y, void* state, size_t state_bytes,
+                              int t, int C, int B, int capacity, int d, int h, int f, int n_layers, float eps, mmt_stream_t stream);
+int mmt_encoder_stream_extend_ring(const float* x, const float* mask, const float* params, float* y, void* state, size_t state_bytes,
+                                   int t, int C, int B, int span, int d, int h, int f, int n_layers, float eps, mmt_stream_t stream);
+/* The positioned forms (the slots contract above).  (dst, len): two int arrays (k) in DEVICE memory; row b < k of x goes to sequence
+ * dst[b] < B_state with its first len[b] windows, 1 <= len[b] <= C, from position pos[dst[b]].  Distinct dst[b].  All or nothing, and
+ * the same decision in every launch of the call: a pair outside its ranges, an idle slot, and a slot whose position plus len[b]
+ * exceeds the capacity (ring: reaches INT_MAX) is skipped WHOLE: its rows of y are zeros, and no byte of its cache and no position
+ * changes.  A slot that runs has rows >= len[b] of y as zeros and, with advance != 0, pos[dst[b]] += len[b], stored by the call's last
+ * launch (the earlier ones read the position the call started on).  A sequence no dst names is not touched by a byte. */
+int mmt_encoder_stream_extend_slots(const float* x, const float* mask, const float* params, float* y, void* state, size_t state_bytes,
+                                    int* pos, const int* dst, const int* len, int advance, int C, int k, int B_state, int capacity,
+                                    int d, int h, int f, int n_layers, float eps, mmt_stream_t stream);
+int mmt_encoder_stream_extend_ring_slots(const float* x, const float* mask, const float* params, float* y, void* state, size_t state_bytes,
+                                         int* pos, const int* dst, const int* len, int advance, int C, int k, int B_state, int span,
+                                         int d, int h, int f, int n_layers, float eps, mmt_stream_t stream);
+
 /* ---- The LSTM baseline, ONE WINDOW PER CALL (csrc/lstm_step.h): embed, attention MLP, the n_layers LSTM cells from zero states, the
  * local attention over the last attn_len outputs with the softmax over the TAPS (mmt_local_attn_forward_taps) and the read-out MLP,
  * eval mode.  This project's own addition; it steps models._LocalAttnLSTM with attend_over_taps on (MultiLSTM, MultiLSTMB1).

@@ -85,6 +85,11 @@ SIGNATURES = {
     # prefill of a stream state from a finished batch call: (dst, len, pos) device int32 arrays or null, then the dimensions
     "mmt_encoder_stream_prefill": (_I, [_P, _SZ, _P, _SZ, _P, _P, _P] + [_I] * 9 + [_P]),
     "mmt_decoder_stream_prefill": (_I, [_P, _P, _P, _SZ, _P, _P, _P] + [_I] * 7 + [_P]),
+    # a chunk of C windows from any position: (t, C, B, capacity | span, ...); slots: (pos, dst, len) device int32, (advance, C, k, B_state, ...)
+    "mmt_encoder_stream_extend": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 8 + [_F, _P]),
+    "mmt_encoder_stream_extend_ring": (_I, [_P, _P, _P, _P, _P, _SZ] + [_I] * 8 + [_F, _P]),
+    "mmt_encoder_stream_extend_slots": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _P, _P] + [_I] * 9 + [_F, _P]),
+    "mmt_encoder_stream_extend_ring_slots": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _P, _P] + [_I] * 9 + [_F, _P]),
     # one window of the LSTM baseline per launch: (B, in, E, H, n_layers, attn_len); params a host array of device pointers
     "mmt_lstm_stream_bytes": (_SZ, [_I] * 6),
     "mmt_lstm_stream_prepare": (_I, [_P, _P, _SZ] + [_I] * 6 + [_P]),

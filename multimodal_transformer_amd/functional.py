@@ -1962,7 +1962,8 @@ def decoder_stream_step_slots(e_t, mask_t, state, positions, d, h_dim, n_layers,
 
 # Prefill of a stream state (include/mmt_hip.h mmt_*_stream_prefill): its functional layer stands in streaming.py, beside
 # encoder_ring_step, and these names resolve there.
-_IN_STREAMING = ("encoder_stream_prefill", "decoder_stream_prefill", "prefill_table", "check_prefill_table")
+_IN_STREAMING = ("encoder_stream_prefill", "decoder_stream_prefill", "prefill_table", "check_prefill_table",
+                 "encoder_stream_extend", "encoder_stream_extend_slots")
 
 
 def __getattr__(name):

@@ -215,6 +215,38 @@ class _FrontEndStream:
                 x = outs[m.mods[0]]
             return seq.prefill(args[0], x, args[2], mask) if slots else seq.prefill(x, mask)
 
+    def extend(self, inputs, mask=None):
+        """Move the recording forward by C windows from ANY ``t`` (``streaming._SequenceStream.extend`` behind the window encoder and
+        the fusion, run as ``forward`` runs them): ``extend({mod: (B, C, W, d_raw)}, mask=None)`` -> (B, C, 1); afterwards ``t += C``.
+        Every other sequence stream behind the window encoder (the MFT, B3-MFN, the LSTM baselines, ``device_stream``):
+        NotImplementedError naming ``step`` (their streams say why)."""
+        m, seq = self.model, self.seq
+        if not isinstance(seq, _SequenceStream):
+            return seq.extend()                                  # NotImplementedError, before any launch
+        op = "%s stream extend" % type(m).__name__
+        _stream_model_checks(m, "stream extend")
+        if not isinstance(inputs, dict) or any(mod not in inputs for mod in m.mods):
+            raise ValueError("%s: inputs must be a dict with an entry for every modality %s" % (op, list(m.mods)))
+        C = None
+        for mod in m.mods:
+            x = inputs[mod]
+            if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[0] != self.batch or x.shape[1] < 1 or (C is not None and x.shape[1] != C):
+                raise ValueError("%s: inputs[%r] must have the shape (%d, C, W, d_raw) with one C >= 1 for every modality, got %s"
+                                 % (op, mod, self.batch, tuple(getattr(x, "shape", ()))))
+            C = x.shape[1]
+        if seq.capacity is not None and seq.t + C > seq.capacity:
+            raise ValueError("%s: t + C = %d + %d windows > capacity = %d: open a stream with a larger capacity (a ring stream has no limit)"
+                             % (op, seq.t, C, seq.capacity))
+        with torch.no_grad():
+            outs = m._encode({mod: inputs[mod] for mod in m.mods})                          # {mod: (B,C,F_mod)}
+            if len(m.mods) > 1:
+                x = F_hip.cat_cols([outs[mod] for mod in m.mods])
+                if getattr(m, "fusionLayer", None) is not None:
+                    x = F_hip.linear(x, m.fusionLayer.weight.detach(), m.fusionLayer.bias.detach(), act=2)
+            else:
+                x = outs[m.mods[0]]
+            return seq.extend(x, mask)
+
 
 class MultiCNNTransformer(_FrontEnd):
     """SFT: transformer/SFT/models.py:81-142."""

@@ -214,6 +214,32 @@ class EncoderStream:
         table, _, prefix = prefill_table(op, indices, lengths, P, self.batch, self.capacity, self.device)
         return self._fill(x, prefix if mask is None else mask, table, self.positions if set_positions else None)
 
+    def extend(self, x, mask=None):
+        """Move the stream forward by C windows from ANY ``t``: x (B, C, d), mask (B, C, 1), (B, C) or None -> (B, C, d), the rows
+        that C calls of ``step`` give, to fp32 summation order (the same rounding sites); afterwards ``t += C`` and
+        ``step``, ``extend`` and the cache go on as if the windows had been stepped.  A plain cache: t + C <= capacity; a ring stream
+        has no limit.  ceil(C / 16) launches of encoder_extend_kernel (csrc/encoder_extend.h), sixteen windows sharing one pass over
+        the weights.  Measured: from four windows on it is faster than stepping them; for ONE window ``step`` is the
+        better call, and at ``t == 0`` ``prefill`` is."""
+        op = "%s.extend" % type(self).__name__
+        _extend_eval(op, self.encoder)
+        C = _check_chunk(op, x, mask, self.batch, self.d, self.device, self.t, self.capacity)
+        y = encoder_stream_extend(x, mask, self._flat, self.state, self.t, self.h, self.d_ff, self.n_layers,
+                                  self.span if self._ring else self.capacity, self.eps, ring=self._ring)
+        self.t += C
+        return y
+
+    def _slots_extend(self, indices, x, lengths, mask, advance):
+        op = "%s.extend" % type(self).__name__
+        _extend_eval(op, self.encoder)
+        k = len(indices) if hasattr(indices, "__len__") else -1
+        if not 1 <= k <= self.batch:
+            raise ValueError("%s: indices must name 1 .. batch = %d slots, got %r" % (op, self.batch, indices))
+        C = _check_history(op, x, mask, k, self.d, self.device, None)
+        table, _, _ = prefill_table(op, indices, lengths, C, self.batch, self.capacity, self.device)
+        return encoder_stream_extend_slots(x, mask, self._flat, self.state, self.positions, table, self.h, self.d_ff, self.n_layers,
+                                           self.span if self._ring else self.capacity, self.eps, ring=self._ring, advance=advance)
+
 
 class EncoderSlotStream(_Slots, EncoderStream):
     """``EncoderStream`` with slots (``Encoder.slot_stream``; members: ``_Slots``).  ``step(x_t, mask_t)`` is ONE launch of
@@ -241,6 +267,15 @@ class EncoderSlotStream(_Slots, EncoderStream):
         forward plus ONE launch of encoder_prefill_kernel.  ``advance=False`` leaves the positions (a composite stream sets them in its
         last launch)."""
         return self._slots_prefill(indices, x, lengths, mask, bool(advance))
+
+    def extend(self, indices, x, lengths, mask=None, advance=True):
+        """Move the slots ``indices`` (k distinct ints, k <= batch) forward by their next windows: x (k, C, d), ``lengths`` k host ints
+        with 1 <= len <= C, mask (k, C[, 1]) or None -> (k, C, d); row b holds the ``lengths[b]`` rows that ``EncoderStream.extend`` of
+        that recording alone gives from window ``positions[indices[b]]``, bit for bit, and zeros behind them.  All or nothing, decided
+        on the device: an idle slot, and one whose position plus length exceeds the capacity, gets zero rows and nothing of it
+        changes; a slot that runs advances by its length (``advance=False`` leaves the positions).  Not a byte of any other slot
+        changes.  One host-to-device copy (the table), no synchronisation; ceil(C / 16) launches of encoder_extend_slots_kernel."""
+        return self._slots_extend(indices, x, lengths, mask, bool(advance))
 
 
 def encoder_ring_step(x_t, mask_t, flat_params, state, t, h, d_ff, n_layers, span, eps=1e-6):
@@ -395,6 +430,94 @@ def decoder_stream_prefill(h_all, c_all, state, B_state, d, h_dim, n_layers, P, 
                 0 if limit is None else int(limit), d, int(h_dim), L)
 
 
+# Extend: a stream moved forward by C windows from ANY position, sixteen windows per launch (include/mmt_hip.h mmt_encoder_stream_extend*;
+# csrc/encoder_extend.h).  Eval mode, forward only.
+EXTEND_ROWS = 16                 # windows per launch (csrc/encoder_extend_plan.h MMT_EXTEND_ROWS)
+
+
+def _extend_operands(op, x, mask, flat_params, state, B_state, h, d_ff, n_layers, rows):
+    """The checks both forms of ``encoder_stream_extend`` share, before any launch -> (x, mask, params) as the entry takes them.
+    ``B_state``: the state's sequences (None: those of x, the host form)."""
+    F_hip._forward_only(op, (x, mask, flat_params), "an input or a parameter requires grad: call it under torch.no_grad() with detached inputs")
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != torch.float32:
+        raise ValueError("%s: x must be a float32 (B, C, d) tensor, got %s %s"
+                         % (op, getattr(x, "dtype", type(x).__name__), tuple(getattr(x, "shape", ()))))
+    B, C, d = x.shape
+    if B < 1 or C < 1:
+        raise ValueError("%s: x has no windows (shape %s): C must be at least 1" % (op, tuple(x.shape)))
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.numel() != B * C or mask.device != x.device):
+        raise ValueError("%s: mask must have B*C = %d elements (shape (B,C,1) or (B,C)) on %s" % (op, B * C, x.device))
+    F_hip._lib.require_hip(x, flat_params, state)
+    nstate = F_hip.encoder_stream_bytes(B if B_state is None else B_state, rows, d, h, d_ff, n_layers)
+    p_ = F_hip._stream_params(op, flat_params, d, d_ff, n_layers)
+    F_hip._stream_state(op, state, nstate, x.device, "encoder_stream_state")
+    return F_hip._f32c(x), None if mask is None else F_hip._f32c(mask).view(B, C), p_
+
+
+def encoder_stream_extend(x, mask, flat_params, state, t, h, d_ff, n_layers, rows, eps=1e-6, ring=False):
+    """Rows t .. t + C - 1 of a causal encoder stack from the K/V cache in ``state``: x (B, C, d), mask (B, C[, 1]) or None -> y (B, C, d),
+    what C calls of ``encoder_stream_step`` (``ring``: ``encoder_ring_step``, with ``rows`` the span) give at t, t + 1, ..., to fp32
+    summation order (the same rounding sites; every product on the matrix cores), and the cache afterwards holds the C windows as
+    those calls leave it.  ``rows``: the stream's capacity, t + C <= rows; with ``ring`` its span, and no limit below INT_MAX.  t is
+    passed by value.  ceil(C / 16) launches of encoder_extend_kernel and nothing else.  Forward only."""
+    op = "encoder_stream_extend"
+    t, rows = int(t), int(rows)
+    x_, m_, p_ = _extend_operands(op, x, mask, flat_params, state, None, h, d_ff, n_layers, rows)
+    B, C, d = x_.shape
+    if t < 0 or (ring and t + C >= _INT_MAX):
+        raise ValueError("%s: position t = %d with C = %d windows: t must lie in [0, INT_MAX - C)" % (op, t, C))
+    if not ring and t + C > rows:
+        raise ValueError("%s: t + C = %d + %d > capacity = %d: open a stream with a larger capacity (a ring stream has no limit)"
+                         % (op, t, C, rows))
+    y = torch.empty_like(x_)
+    F_hip._lib.launch("mmt_encoder_stream_extend" + ("_ring" if ring else ""), x_, m_, p_, y, state, state.numel(), t, C, B, rows,
+                      d, int(h), int(d_ff), int(n_layers), float(eps))
+    return y
+
+
+def encoder_stream_extend_slots(x, mask, flat_params, state, positions, table, h, d_ff, n_layers, rows, eps=1e-6, ring=False, advance=True):
+    """``encoder_stream_extend`` with the position of every sequence in device memory (csrc/step_slots.h): x (k, C, d), ``positions`` int32
+    (B_state) and ``table`` int32 (2, k) on the device (``prefill_table``): row b goes to slot table[0, b] with its first table[1, b]
+    windows, from positions[table[0, b]].  All or nothing: an idle slot, and one whose position plus length exceeds the capacity
+    (``ring``: reaches INT_MAX), gets zero rows and not a byte of it changes; a slot that runs has zeros in its rows behind its length and,
+    with ``advance``, its position moved on by its length.  A slot the table does not name is not touched.  No position crosses the
+    host.  ceil(C / 16) launches of encoder_extend_slots_kernel and nothing else."""
+    op = "encoder_stream_extend_slots"
+    if not isinstance(positions, torch.Tensor) or positions.dim() != 1 or positions.shape[0] < 1:
+        raise ValueError("%s: positions must be the stream's int32 (B_state,) tensor" % op)
+    B_state = positions.shape[0]
+    x_, m_, p_ = _extend_operands(op, x, mask, flat_params, state, B_state, h, d_ff, n_layers, int(rows))
+    k, C, d = x_.shape
+    dst, length, pos = _prefill_where(op, table, positions, k, B_state, x_.device)
+    if dst is None or pos is None:
+        raise ValueError("%s: the table (prefill_table) and the positions are both needed" % op)
+    y = torch.empty_like(x_)
+    F_hip._lib.launch("mmt_encoder_stream_extend" + ("_ring_slots" if ring else "_slots"), x_, m_, p_, y, state, state.numel(), pos, dst, length,
+                      int(bool(advance)), C, k, B_state, int(rows), d, int(h), int(d_ff), int(n_layers), float(eps))
+    return y
+
+
+def _check_chunk(op, x, mask, B, width, device, t, limit, name="x"):
+    """The windows of an ``extend``: ``_check_history``'s checks, then t + C against a plain cache's capacity (None: a ring) -> C."""
+    C = _check_history(op, x, mask, B, width, device, None, name)
+    if limit is not None and t + C > limit:
+        raise ValueError("%s: t + C = %d + %d windows > capacity = %d: open a stream with a larger capacity (a ring stream, "
+                         "ring_stream(model, batch), has no limit)" % (op, t, C, limit))
+    if limit is None and t + C >= _INT_MAX:
+        raise ValueError("%s: t + C = %d + %d reaches INT_MAX, which is no position: reset() starts a new recording" % (op, t, C))
+    return C
+
+
+def _extend_eval(op, module):
+    if module.training:
+        raise ValueError("%s: the model is in train mode; streaming is eval-mode inference (call .eval())" % op)
+
+
+def _no_extend(stream, why):
+    raise NotImplementedError("%s.extend: %s; this stream moves one window at a time: call step once per window (DESIGN 4.14, 10)"
+                              % (type(stream).__name__, why))
+
+
 class EncoderRingStream(EncoderStream):
     """A causal ``Encoder`` with a span run one window at a time (``Encoder.ring_stream``): ``EncoderStream`` against a ring cache of
     ``span`` rows (csrc/step_ring.h).  ``step(x_t)`` returns the row that the batch forward with the span gives at position ``t``, in ONE
@@ -447,6 +570,11 @@ class EncoderRingSlotStream(_Slots, EncoderRingStream):
     def prefill(self, indices, x, lengths, mask=None, advance=True):
         """As ``EncoderSlotStream.prefill``, into the ring: the last min(len, span) windows of each history, with no limit on P."""
         return self._slots_prefill(indices, x, lengths, mask, bool(advance))
+
+    def extend(self, indices, x, lengths, mask=None, advance=True):
+        """As ``EncoderSlotStream.extend``, into the ring: no capacity, so only idle slots (and a position that would reach INT_MAX)
+        are skipped."""
+        return self._slots_extend(indices, x, lengths, mask, bool(advance))
 
 
 def _no_slot_stream(model):
@@ -533,6 +661,32 @@ class _SequenceStream:
             if state is not None:
                 self._h, self._c = state[0][P - 1], state[1][P - 1]
         return y
+
+    def extend(self, x, mask=None):
+        """Move the recording forward by C windows from ANY ``t``: x (B, C, window_embed_size), mask (B, C, 1), (B, C) or None -> the
+        (B, C, 1) predictions that C calls of ``step`` give, to fp32 summation order; afterwards ``t += C`` and the decoder's carried
+        (h, c) is the scan's state behind the last window.  The embed affine map over the C rows, ``enc.extend`` (ceil(C / 16)
+        launches), ONE scan of T = C seeded with the carried (h, c) for the LSTM decoder, and the two read-out maps.  A plain cache:
+        t + C <= capacity.  For ONE window ``step`` is the better call."""
+        m, B = self.model, self.batch
+        op = "%s stream extend" % type(m).__name__
+        _extend_eval(op, m)
+        C = _check_chunk(op, x, mask, B, self._embed.in_features, self.enc.device, self.enc.t, self.enc.capacity)
+        with torch.no_grad():
+            first = self.enc.t == 0
+            mk = None if mask is None else mask.float().reshape(B, C)
+            enc = self.enc.extend(self._affine(x, self._embed, act=self._embed_act), mk)
+            if self._dec is None:
+                hid = self._affine(enc, m.out[0], act=1)
+                return self._affine(hid, m.out[2], rowscale=None if mk is None else mk.reshape(-1))
+            Wx, W_rec, bias, row0, c0 = self._dec
+            gx = F_hip.linear(F_hip.time_major(enc), Wx, bias)                   # (C,B,4d)
+            if first:
+                gx = F_hip.add_row0(gx, row0)                                    # window 0 sees h0 W_hh^T, as _decode
+            h_all, c_all = F_hip.lstm_scan(gx, W_rec, None if first else self._h, c0 if first else self._c)
+            self._h, self._c = h_all[C - 1], c_all[C - 1]
+            hid = self._affine(h_all, m.out[0], act=1)                           # rows stay time-major ...
+            return F_hip.batch_major(self._affine(hid, m.out[2]), None if mk is None else mk.reshape(B, C, 1))     # ... until the mask pass
 
 
 def _sequence_forward(model, embed, embed_act, x, mask, encode):
@@ -627,6 +781,11 @@ class _SequenceSlotStream(_Slots):
                                              limit=self.capacity, table=table, positions=self.positions)
         return y
 
+    def extend(self, *args, **kwargs):
+        """Not implemented: NotImplementedError before any launch."""
+        _no_extend(self, "the decoder's carried state lives on the device and its step kernel has no chunked form (stream(), whose "
+                         "decoder state lives on the host, has extend)")
+
 
 class MFNStream:
     """An ``MFN`` gate run one window at a time (``MFN.stream``): ``step({mod: (B, dims[mod])}, mask_t)`` returns the (B, output_dim)
@@ -682,6 +841,10 @@ class MFNStream:
     def prefill(self, *args, **kwargs):
         """Not implemented: NotImplementedError before any launch."""
         _no_prefill(self, "the MFN gate's carried (h, c, mem) is not seeded from its batch scan yet")
+
+    def extend(self, *args, **kwargs):
+        """Not implemented: NotImplementedError before any launch."""
+        _no_extend(self, "the MFN gate's recurrence has no chunked form")
 
 
 class MFNSlotStream(_Slots, MFNStream):
@@ -771,6 +934,10 @@ class LSTMStream:
         """Not implemented: NotImplementedError before any launch."""
         _no_prefill(self, "the LSTM baselines' carried state, their ring of taps and a fed-back prediction are not seeded from the "
                           "batch scans yet")
+
+    def extend(self, *args, **kwargs):
+        """Not implemented: NotImplementedError before any launch."""
+        _no_extend(self, "the LSTM baselines' recurrence, their ring of taps and a fed-back prediction have no chunked form")
 
 
 class LSTMSlotStream(_Slots, LSTMStream):
@@ -1034,6 +1201,10 @@ class _GateStream:
     def prefill(self, *args, **kwargs):
         """Not implemented: NotImplementedError before any launch."""
         _no_prefill(self, "the MFN gate behind the modalities is not seeded from its batch scan yet")
+
+    def extend(self, *args, **kwargs):
+        """Not implemented: NotImplementedError before any launch."""
+        _no_extend(self, "the MFN gate behind the modalities has no chunked form")
 
 
 class _GateSlotStream(_Slots, _GateStream):
